@@ -20,6 +20,13 @@ BanditMFSquare table arm and a frozen 10^4-class LogregMulticlassIps arm over th
 
 Prints ONE JSON line (rank 0).  `value` counts real rows (organic + bandit; the per-user phantom row is
 excluded) over all ranks / max-over-ranks wall time.
+
+A plain run sets up, warms up, times the steps and prints the line: nothing else.  `--full` adds what takes runs of its
+own: the per-kernel rooflines (`roofline`, `kernels`: one more profiled run), the sort / decode of the whole log
+(`materialise`, `value_ordered`), the sigma_omega > 0 companion (`sigma_omega_gt0`), the other BASELINE configurations
+(`other_workloads`), at N > 1 the other scaling form and the all-reduce latency, and the CPU leg (`cpu_baseline`); the
+`--no-*` switches still drop single parts of it.  `--dump-outputs DIR` writes what the last timed step computed (see
+dump_outputs) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -52,6 +59,10 @@ HBM_PEAK_GBPS = 8000.0
 EXP_PEAK_PER_S = 1024 * 4 * 2.4e9  # v_exp_f32: quarter rate, 4 lanes per cycle and SIMD (MI355X_MICROARCH.md: transcendentals)
 VALU_WAVE_INSTR_PER_S = 1024 * 2.4e9 / 4   # a SIMD issues one full-rate vector wave-instruction per 4 cycles: 256 CUs x 4 SIMDs
 PROFILE_ROUNDS = ('r6', 'r5', 'r4', 'r3', 'r2')      # profiles/<round>/pmc_traffic.json, newest first
+DUMP_USERS = 2048                  # --dump-outputs: users (of all ranks) whose log rows are written, a seeded sample
+DUMP_SEED = 12345
+DUMP_BUDGET_BYTES = 60 << 20       # all files of one --dump-outputs call stay below 64 MB
+LOG_SAMPLE_COLUMNS = ('u', 't', 'z', 'v', 'a', 'c', 'phantom', 'ps')
 
 
 def policy_kwargs(pol):
@@ -323,6 +334,47 @@ def measured_traffic(workload, name):
     return None
 
 
+def dump_outputs(out_dir, arms, last, users, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files (prefixed `rank<R>_` at N > 1):
+      counters.npy              (arms, 4): organic, bandit, clicks, phantom of every arm's run
+      <arm>_log_sample.npy      (rows, 8): u, t, z, v, a, c, phantom, ps of the log rows (reference row order) of a fixed,
+                                seeded sample of the rank's users — the rows env.generate_logs returns for them; where the
+                                reference has no value the column holds -1 (v, a, c) or 0 (ps of non-bandit rows): every
+                                value is finite
+    The sample is the same for the same arguments, and the inputs of a run are fixed by its arguments, so two builds'
+    dumps compare row for row."""
+    import numpy as np
+    import torch
+    from recogym_amd import _abi
+    from recogym_amd.sim import decode_rows
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = '' if world == 1 else f'rank{rank}_'
+    ids = np.sort(np.random.default_rng(DUMP_SEED).choice(users, size=min(users, max(1, DUMP_USERS // world)), replace=False))
+    max_rows = DUMP_BUDGET_BYTES // (len(arms) * world * 8 * len(LOG_SAMPLE_COLUMNS))
+    for name, s in arms:
+        if s.log is None:           # --no-log: the counters are all the run returns
+            continue
+        srt, offsets = s.sorted_log()
+        dev = srt.device
+        starts = offsets[torch.from_numpy(ids).to(dev)]
+        lens = offsets[torch.from_numpy(ids + 1).to(dev)] - starts
+        keep = int((torch.cumsum(lens, 0) <= max_rows).sum().item())     # whole users only, within the size budget
+        starts, lens = starts[:keep], lens[:keep]
+        total = int(lens.sum().item())
+        before = torch.cumsum(lens, 0) - lens
+        gather = torch.arange(total, device=dev) - torch.repeat_interleave(before, lens) + torch.repeat_interleave(starts, lens)
+        ps64, _ = s.sorted_aux(offsets, srt.shape[0])
+        uniform = 1.0 / float(s.config.num_products) if s.policy in (_abi.RG_POLICY_UNIFORM_ENV, _abi.RG_POLICY_RANDOM_AGENT) else None
+        rows = decode_rows(srt[gather].cpu().numpy(), uniform, None if ps64 is None else ps64[gather].cpu().numpy())
+        rows['ps'] = np.where(rows['z'] == 1, rows['ps'], 0.0)
+        np.save(os.path.join(out_dir, f'{prefix}{name}_log_sample.npy'),
+                np.stack([rows[k].astype(np.float64) for k in LOG_SAMPLE_COLUMNS], axis=1))
+        del srt, offsets, ps64, gather
+        torch.cuda.empty_cache()
+    np.save(os.path.join(out_dir, f'{prefix}counters.npy'),
+            np.array([[c['organic'], c['bandit'], c['clicks'], c['phantom']] for c in last], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -341,10 +393,19 @@ def main():
                          'the rocprofv3 --pmc passes run, so that a counter summed over the trace belongs to one run')
     ap.add_argument('--shard', default='', help='R/W: with --gpus 1, simulate rank R\'s id range of a W-rank strongly scaled job')
     ap.add_argument('--digest', action='store_true', help='add the order-independent checksum of the last run\'s log rows')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: per-kernel rooflines, the whole-log sort / decode, the sigma_omega > 0 '
+                         'companion, the other BASELINE configurations, at N > 1 the other scaling form and the all-reduce, the CPU leg')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='write what the last timed step computed (counters, a seeded sample of the log rows) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.single_run:
         args.steps, args.warmup = 1, 0
         args.no_cpu_baseline = args.no_drift_line = args.no_materialise = args.no_other_workloads = True
+    # the per-kernel rooflines: a profiled run of their own with --full; --single-run profiles the timed run itself
+    per_kernel = args.full or args.single_run
 
     from recogym_amd import parallel
     rc = parallel.self_launch(args.gpus, os.path.abspath(__file__), sys.argv[1:])
@@ -458,6 +519,8 @@ def main():
     ranks_ms = list(per_rank_ms)
     for c in last:
         assert c['hist_overflow'] == 0 and c['log_dropped'] == 0 and c['live'] == 0 and c['exact_overflow'] == 0, c
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, arms, last, users, rank, world)
 
     def is_cached(config):
         return config.sigma_omega == 0 and os.environ.get('RECOGYM_CACHE', '1') != '0' and config.K <= 63
@@ -489,7 +552,7 @@ def main():
     # --- per-kernel rooflines, HIP events on the launch stream; `roofline` = the kernel with the most time ---
     roofline = kernels = None
     materialise = None
-    if rank == 0:
+    if rank == 0 and per_kernel:
         counters, kernels = profile(arms, cfg, already=args.single_run)
         dom = max((k for k in kernels if kernels[k]['bound'] in ('hbm', 'mfma')), key=lambda k: kernels[k]['ms'])
         roofline = dict(kernels[dom])
@@ -527,7 +590,7 @@ def main():
 
         # --- what the reference's row order costs (abstract.py:299-327 is part of generate_logs): rg_sim_sort_log on the
         # whole log of the last run; decoding into the reference's columns on a 200 k-user run of the same workload ---
-        if not args.no_materialise and not args.no_log:
+        if args.full and not args.no_materialise and not args.no_log:
             s0 = arms[0][1]
             srt, off = s0.sorted_log()              # (first call: the 16 GB result buffer comes from hipMalloc, not the cache)
             del srt, off
@@ -578,7 +641,7 @@ def main():
     # --- the sigma_omega > 0 companion of the headline workload: no per-user cache is possible there, every
     # organic draw sweeps all P products on the matrix pipe — the line that shows the sweep kernel's quality ---
     drift = None
-    if args.workload == 'c3' and not args.no_drift_line:
+    if args.full and args.workload == 'c3' and not args.no_drift_line:
         dcfg, darms = build('c3drift', users)
         d_steps = 2
         d_el, d_tot, d_last = timed(darms, d_steps, 1)
@@ -597,7 +660,7 @@ def main():
     # --- the other BASELINE configurations, three timed steps each (after one warm-up), so that the driver's clock sees them too:
     # config 2, one rank's share of config 4, config 5 (both arms) — compact entries: value, ms per step, the kernel with the most time ---
     others = None
-    if args.workload == 'c3' and world == 1 and not args.no_other_workloads and not args.shard:
+    if args.full and args.workload == 'c3' and world == 1 and not args.no_other_workloads and not args.shard:
         others = {}
         saved_fu = (first_user, users)
         for wl in ('c2', 'c4shard', 'c5'):
@@ -625,7 +688,7 @@ def main():
     # --- N > 1: the OTHER scaling form in the same run (north_star states the target as 10 M users in total over 1/2/4/8
     # GPUs: strong; the contract's `value` keeps per-GPU work fixed: weak), and the latency of the one collective the path has ---
     other = allreduce = None
-    if dist and not args.shard and not args.single_run:
+    if args.full and dist and not args.shard and not args.single_run:
         o_form = 'strong' if args.scaling == 'weak' else 'weak'
         if o_form == 'strong':
             o_total = args.users * world if args.users else total
@@ -664,7 +727,7 @@ def main():
                               'host-timed from launch to completion, after a barrier')
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:     # the CPU leg runs at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:     # the CPU leg runs at N = 1 only
         cpu = cpu_baseline(args.workload)
 
     if rank == 0:

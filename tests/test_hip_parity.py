@@ -1332,7 +1332,7 @@ def test_bench_multi_rank_line_reports_both_scaling_forms_and_the_allreduce(tmp_
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, RECOGYM_BENCH_BACKEND='gloo', RECOGYM_BENCH_ONE_DEVICE='1')
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--workload', 'tiny', '--steps', '2', '--warmup', '1',
-                          '--no-cpu-baseline', '--no-materialise'], env=env, capture_output=True, text=True, timeout=900)
+                          '--full', '--no-cpu-baseline', '--no-materialise'], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
     assert line['n_gpus'] == 2 and line['scaling'] == 'weak' and line['config']['users_total'] == 40_000

@@ -267,6 +267,60 @@ def test_bench_workloads_and_cli_are_consistent():
     assert all(shards[i][0] + shards[i][1] == shards[i + 1][0] for i in range(7))
 
 
+def test_bench_dump_outputs_writes_the_rows_of_a_seeded_user_sample(tmp_path):
+    """bench.py --dump-outputs on a stand-in for a finished Simulator (its sorted log on the CPU): the counters of every arm
+    and, per arm, every row of a fixed sample of users in the reference's order, decoded to float64 columns — the same
+    files for the same arguments, whole users only, within the size budget."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location('bench', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rs = np.random.RandomState(3)
+    users, first_user = 5000, 700
+    lens = rs.randint(1, 12, size=users)
+    offsets = np.concatenate([[0], np.cumsum(lens)])
+    u = np.repeat(np.arange(users), lens) + first_user
+    t = np.concatenate([np.arange(n) for n in lens])
+    idx = rs.randint(0, 50, size=offsets[-1])
+    bandit = rs.rand(offsets[-1]) < 0.5
+    bandit[offsets[1:] - 1] = False             # every user's last row: its phantom row
+    code = idx.astype(np.int64) | np.where(bandit, _abi.RG_EV_BANDIT, 0) | np.where(bandit & (rs.rand(offsets[-1]) < 0.2), _abi.RG_EV_CLICK, 0)
+    code[offsets[1:] - 1] |= _abi.RG_EV_PHANTOM
+    raw = np.stack([u, t, code, np.zeros_like(u)], axis=1).astype(np.int64).astype(np.uint32).view(np.int32)
+    ps = rs.rand(offsets[-1])
+
+    class Done:
+        log, policy = True, _abi.RG_POLICY_LAST_VIEW_TABLE
+        config = Configuration({**env_1_args, 'num_products': 50})
+
+        def sorted_log(self):
+            return torch.from_numpy(raw.copy()), torch.from_numpy(offsets)
+
+        def sorted_aux(self, offs, total):
+            return torch.from_numpy(ps), None
+
+    arms = [('one', Done()), ('two', Done())]
+    last = [dict(organic=10, bandit=20, clicks=3, phantom=users), dict(organic=11, bandit=21, clicks=4, phantom=users)]
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arms, last, users, 0, 1)
+    for name in ('counters', 'one_log_sample', 'two_log_sample'):
+        a, b = np.load(tmp_path / 'a' / f'{name}.npy'), np.load(tmp_path / 'b' / f'{name}.npy')
+        assert a.dtype == np.float64 and np.array_equal(a, b, equal_nan=True)
+    assert np.load(tmp_path / 'a' / 'counters.npy').tolist() == [[10, 20, 3, users], [11, 21, 4, users]]
+    got = np.load(tmp_path / 'a' / 'one_log_sample.npy')
+    ids = np.unique(got[:, 0]).astype(np.int64) - first_user
+    assert len(ids) == min(users, bench.DUMP_USERS)
+    want = np.concatenate([np.arange(offsets[i], offsets[i + 1]) for i in ids])
+    assert (got[:, 0] == u[want]).all() and (got[:, 1] == t[want]).all()
+    is_b = got[:, 2] == 1
+    assert (is_b == bandit[want]).all()
+    assert (got[~is_b, 3] == idx[want][~is_b]).all() and (got[is_b, 4] == idx[want][is_b]).all()
+    assert (got[:, 6] == ((code[want] & _abi.RG_EV_PHANTOM) != 0)).all() and got[:, 6].sum() == len(ids)
+    assert (got[is_b, 7] == ps[want][is_b]).all() and (got[~is_b, 7] == 0).all() and np.isfinite(got).all()
+    assert sum(os.path.getsize(p) for p in (tmp_path / 'a').iterdir()) < 64 << 20
+
+
 def test_gym_registration_hook(tmp_path, monkeypatch):
     """recogym_amd.register_with_gym() registers 'reco-gym-v1' with an importable `gym` (here: a stand-in with the
     registration surface the reference uses, recogym/__init__.py:35-45) and leaves an existing registration alone
