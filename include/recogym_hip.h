@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define RG_ABI_VERSION 6
+#define RG_ABI_VERSION 7
 
 /* error codes */
 #define RG_OK 0
@@ -371,6 +371,41 @@ int rg_sim_debug_click_decisions(rg_sim* sim, const int32_t* d_actions, const do
 int rg_sim_debug_set_history(rg_sim* sim, const uint32_t* d_nd, const uint32_t* d_products, const uint32_t* d_counts,
                              uint32_t stride, void* stream);
 int rg_sim_debug_ouc_acts(rg_sim* sim, const double* d_u1, int32_t* d_action, double* d_ps, uint8_t* d_flags, void* stream);
+
+/*
+ * Off-policy evaluation (evaluate_IPS / evaluate_SNIPS, reference evaluate_agent.py:753-810): replay a sorted log under a
+ * target policy.  Stateless (no rg_sim handle).  `kind`: RG_POLICY_RANDOM_AGENT (pi = 1 / P), RG_POLICY_ORGANIC_USER_COUNT
+ * (the `ps-a` vector of organic_user_count.py:45-96 over ALL the user's organic rows so far; the explore coin of
+ * exploit_explore with epsilon > 0 is the addressed policy draw of (policy_seed, u, t), words 0 and 1) or
+ * RG_POLICY_LAST_VIEW_TABLE (one-hot at table[last organic product]).
+ */
+typedef struct rg_ope_policy {
+    uint32_t kind;
+    uint32_t num_products;
+    uint64_t policy_seed;
+    uint32_t ouc_select_randomly;
+    uint32_t ouc_exploit_explore;
+    uint32_t ouc_reverse_pop;
+    uint32_t reserved;
+    double ouc_epsilon;
+    const int32_t* table;           /* RG_POLICY_LAST_VIEW_TABLE: action per last viewed product (device, P entries) */
+} rg_ope_policy;
+
+/* where the logging propensity of a bandit row comes from */
+#define RG_OPE_PS_ARRAY 0   /* d_ps[row], float64 (Simulator.sorted_aux / a DataFrame's ps column) */
+#define RG_OPE_PS_CONST 1   /* ps_const for every row (the uniform loggers' exact 1 / P) */
+#define RG_OPE_PS_ROW 2     /* the row's own float32 ps */
+
+/* rg_ope_workspace_bytes: device workspace rg_ope_replay needs for n_users users the longest of which has max_user_rows rows
+ * (0 = error, see rg_last_error).
+ * rg_ope_replay: users 0 .. n_users-1 of a sorted log (user i = rows d_offsets[i] .. d_offsets[i+1]-1, each user's first row
+ * organic); for every bandit row of them d_ratio[row] = pi(a | the user's rows before it) / ps and, when d_click is not NULL,
+ * d_click[row] = c.  Other entries of d_ratio / d_click are not written.  d_sums[0..2] = (bandit rows, sum c r, sum r),
+ * reduced in a fixed order (the same bits on every run).  Enqueued on `stream`; no synchronisation. */
+size_t rg_ope_workspace_bytes(const rg_ope_policy* pol, uint64_t n_users, uint32_t max_user_rows);
+int rg_ope_replay(const rg_ope_policy* pol, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                  uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
+                  uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -81,9 +81,10 @@ def __getattr__(name):
     if name == 'test_agent':
         from .bench_agents import test_agent
         return test_agent
-    if name == 'verify_agents':
-        from .evaluate_agent import verify_agents
-        return verify_agents
+    if name in ('verify_agents', 'verify_agents_IPS', 'verify_agents_SNIPS', 'verify_agents_recall_at_k', 'evaluate_IPS',
+                'evaluate_SNIPS', 'evaluate_recall_at_k'):
+        from . import evaluate_agent
+        return getattr(evaluate_agent, name)
     if name in ('Agent', 'RandomAgent', 'random_args', 'OrganicUserEventCounterAgent',
                 'organic_user_count_args', 'LastViewTableAgent'):
         from . import agents

@@ -7,7 +7,7 @@ infrastructure and is never imported from this package.)
 import ctypes as C
 import os
 
-RG_ABI_VERSION = 6
+RG_ABI_VERSION = 7
 
 RG_STATE_ORGANIC, RG_STATE_BANDIT, RG_STATE_STOP = 0, 1, 2
 
@@ -70,6 +70,16 @@ class RgStepResult(C.Structure):
                 ('p_click', C.c_double)]
 
 
+RG_OPE_PS_ARRAY, RG_OPE_PS_CONST, RG_OPE_PS_ROW = 0, 1, 2
+
+
+class RgOpePolicy(C.Structure):
+    """struct rg_ope_policy: the target policy of rg_ope_replay."""
+    _fields_ = [('kind', C.c_uint32), ('num_products', C.c_uint32), ('policy_seed', C.c_uint64),
+                ('ouc_select_randomly', C.c_uint32), ('ouc_exploit_explore', C.c_uint32), ('ouc_reverse_pop', C.c_uint32),
+                ('reserved', C.c_uint32), ('ouc_epsilon', C.c_double), ('table', C.c_void_p)]
+
+
 # every symbol include/recogym_hip.h declares, with its ctypes signature
 _SIM = C.c_void_p
 SYMBOLS = {
@@ -118,6 +128,9 @@ SYMBOLS = {
     'rg_sim_debug_click_decisions': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rg_sim_debug_set_history': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'rg_sim_debug_ouc_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rg_ope_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpePolicy), C.c_uint64, C.c_uint32]),
+    'rg_ope_replay': (C.c_int, [C.POINTER(RgOpePolicy), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
+                                C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 LIB_NAME = 'librecogym_hip.so'

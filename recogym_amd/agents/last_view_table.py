@@ -44,10 +44,22 @@ class LastViewTableAgent(Agent):
         return dict(policy=_abi.RG_POLICY_LAST_VIEW_TABLE, policy_seed=0, ouc=None,
                     policy_table=self.table, policy_ps=self.ps)
 
+    def ope_policy(self):
+        """The replay form of `ps-a` (evaluate_agent.evaluate_IPS on the device): one-hot at table[last viewed product]."""
+        if not getattr(self.config, 'with_ps_all', False):
+            return None
+        return dict(kind=_abi.RG_POLICY_LAST_VIEW_TABLE, num_products=int(self.config.num_products), policy_seed=0,
+                    table=self.table)
+
     def act(self, observation, reward, done):
         if observation.sessions():
             self.last_product_viewed = int(observation.sessions()[-1]['v'])
         a = int(self.table[self.last_product_viewed])
+        ps_all = ()
+        if getattr(self.config, 'with_ps_all', False):
+            # one-hot at the action, as BanditMFSquare with with_ps_all (bandit_mf.py:74-79)
+            ps_all = np.zeros(self.config.num_products)
+            ps_all[a] = 1.0
         return {**super().act(observation, reward, done), 'a': a,
                 'ps': 1.0 if self.ps is None else float(self.ps[self.last_product_viewed]),
-                'ps-a': ()}
+                'ps-a': ps_all}

@@ -54,6 +54,17 @@ class OrganicUserEventCounterAgent(Agent):
             pol['ps_all'] = self.ps_all_from_log
         return pol
 
+    def ope_policy(self):
+        """The replay form of `ps-a` (evaluate_agent.evaluate_IPS on the device): act()'s distribution over the counts of all
+        the user's organic rows so far; the explore coin is the addressed policy draw of (user, t).  None without with_ps_all
+        or with a weight_history_function."""
+        c = self.config
+        if self.history is not None or not getattr(c, 'with_ps_all', False):
+            return None
+        return dict(kind=_abi.RG_POLICY_ORGANIC_USER_COUNT, num_products=int(c.num_products), policy_seed=c.random_seed,
+                    ouc=dict(select_randomly=bool(c.select_randomly), epsilon=float(c.epsilon),
+                             exploit_explore=bool(c.exploit_explore), reverse_pop=bool(getattr(c, 'reverse_pop', False))))
+
     def ps_all_from_log(self, df):
         """`ps-a` of every bandit row of a log this agent produced (with_ps_all=True): the distribution act() sampled
         from, recomputed from the organic rows that precede the row (same arithmetic as act(); the explore flip is

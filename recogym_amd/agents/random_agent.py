@@ -22,6 +22,12 @@ class RandomAgent(Agent):
         return dict(policy=_abi.RG_POLICY_RANDOM_AGENT, policy_seed=self.config.random_seed,
                     ouc=None)
 
+    def ope_policy(self):
+        """The replay form of `ps-a` (evaluate_agent.evaluate_IPS on the device): 1 / P; None without with_ps_all."""
+        if not getattr(self.config, 'with_ps_all', False):
+            return None
+        return dict(kind=_abi.RG_POLICY_RANDOM_AGENT, num_products=int(self.config.num_products), policy_seed=0)
+
     def act(self, observation, reward, done):
         P = self.config.num_products
         ctx = observation.context()

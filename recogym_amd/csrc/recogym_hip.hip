@@ -9,3 +9,4 @@
 #include "rg_walk.hip"
 #include "rg_draw_exacthi.hip"
 #include "rg_draw_lds.hip"
+#include "rg_ope.hip"

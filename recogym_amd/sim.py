@@ -7,6 +7,7 @@ CPU fallback — constructing a Simulator without a HIP device raises.
 import ctypes as C
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -19,6 +20,11 @@ ROW_DTYPE = np.dtype([('u', np.uint32), ('t', np.uint32), ('z', np.int32), ('v',
                       ('a', np.int32), ('c', np.int32), ('phantom', np.int32),
                       ('ps', np.float64)])
 ROW_DTYPE_PCLICK = np.dtype(ROW_DTYPE.descr + [('p_click', np.float64)])
+
+# A sorted log on the device (Simulator.device_log): rows (n, 4) int32 rg_event records in the reference's order, offsets
+# (users + 1) int64, ps = float64 tensor | the exact float 1/P of the uniform loggers | None (the row's float32 value),
+# first_user = the id of user 0, num_products, time = the float64 clock of a NormalTimeGenerator (else None)
+DeviceLog = namedtuple('DeviceLog', 'rows offsets ps first_user num_products time')
 
 
 def require_device(device=None):
@@ -381,6 +387,18 @@ class Simulator:
                     self._h, offsets.data_ptr(), None if ps is None else ps.data_ptr(),
                     None if pc is None else pc.data_ptr(), total, self._stream()), 'rg_sim_sort_log_aux')
         return ps, pc
+
+    def device_log(self):
+        """The log for an off-policy evaluation on the device (evaluate_agent.evaluate_IPS & co.): a DeviceLog whose `ps` follows
+        log_columns()' rule — the exact 1/P of the uniform loggers, else the float64 side array, else the row's float32 value."""
+        rows, offsets = self.sorted_log()
+        ps64, _ = self.sorted_aux(offsets, rows.shape[0])
+        if self.policy in (_abi.RG_POLICY_UNIFORM_ENV, _abi.RG_POLICY_RANDOM_AGENT):
+            ps = 1.0 / float(self.config.num_products)
+        else:
+            ps = ps64
+        time = self.sorted_time(offsets, rows.shape[0]) if self.time_mode else None
+        return DeviceLog(rows, offsets, ps, self.first_user_id, int(self.config.num_products), time)
 
     def sorted_log_host(self):
         """-> ((n, 4) int32 host array of the log in the reference's row order, exact `ps` of the

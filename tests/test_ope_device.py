@@ -1,0 +1,195 @@
+"""Off-policy evaluation on the device (rg_ope_replay, recogym_amd/csrc/rg_ope.hip) against the host loop and the reference's
+own numbers (tests/golden/ope_*.npz), the table-overflow path, and self-evaluation at scale with exact answers."""
+import json
+
+import numpy as np
+import pandas as pd
+import pytest
+import torch
+
+import golden_util as gu
+from make_golden_ope import LOGS, OUC_VARIANTS, log_frame
+from recogym_amd import _abi
+from recogym_amd import evaluate_agent as ev
+from recogym_amd.agents import LastViewTableAgent, OrganicUserEventCounterAgent, RandomAgent
+from recogym_amd.envs.configuration import Configuration
+from recogym_amd.envs.reco_env_v1 import env_1_args, rows_to_dataframe
+from recogym_amd.sim import Simulator
+
+pytestmark = pytest.mark.gpu
+
+
+def ouc(P, seed=11, **v):
+    return OrganicUserEventCounterAgent(Configuration({'num_products': P, 'random_seed': seed, 'weight_history_function': None,
+                                                      'with_ps_all': True, **v}))
+
+
+def dense(v):
+    # the forms that sum over all P products in float64 (host: numpy's pairwise sum): relative 1e-12
+    return v.get('select_randomly') and not v.get('exploit_explore') and (v.get('epsilon') or v.get('reverse_pop'))
+
+
+def close(got, want, rel):
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape
+    if rel == 0:
+        assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), np.nonzero(got != want)[0][:8]
+    else:
+        assert np.array_equal(np.isnan(got), np.isnan(want))
+        ok = ~np.isnan(want)
+        assert np.all(np.abs(got[ok] - want[ok]) <= rel * np.abs(want[ok])), np.max(np.abs(got[ok] - want[ok]) / np.abs(want[ok]))
+
+
+def our_agent(key, P, cols):
+    if key == 'random':
+        return RandomAgent(Configuration({'num_products': P, 'random_seed': 5, 'with_ps_all': True}))
+    if key == 'bmf':
+        return LastViewTableAgent.from_bandit_mf(Configuration({'num_products': P, 'with_ps_all': True}),
+                                                 cols['bmf_product_embedding'], cols['bmf_user_embedding'])
+    return ouc(P, **OUC_VARIANTS[int(key[3:])])
+
+
+@pytest.mark.parametrize('name', LOGS)
+def test_device_equals_reference_fixture(name):
+    meta, cols = gu.load(name)
+    P = meta['env_args']['num_products']
+    want = np.load(f'{gu.GOLDEN}/ope_{name}.npz')
+    df = log_frame(cols)
+    for key, v in json.loads(str(want['meta']))['agents'].items():
+        ag = our_agent(key, P, cols)
+        assert ev.ope_policy_of(ag) is not None
+        rewards, ratio = ev.evaluate_SNIPS(ag, df)          # DataFrame in, device replay
+        close(ratio, want[f'{key}__ratio'], 1e-12 if dense(v) else 0)
+        close(rewards, want[f'{key}__c'], 0)
+
+
+def _sim_log(P, n, seed=7, **pol):
+    cfg = Configuration({**env_1_args, 'random_seed': seed, 'num_products': P, 'K': 5})
+    sim = Simulator(cfg, n, device='cuda:0', **pol)
+    sim.reset_users(0, n)
+    sim.run()
+    return sim
+
+
+@pytest.mark.parametrize('P', [10, 1000])
+def test_device_equals_host_loop_on_simulator_logs(P):
+    sim = _sim_log(P, 2000)
+    dl = sim.device_log()
+    df = rows_to_dataframe(sim.rows(), P)
+    df_small = df[df['u'] < 300].reset_index(drop=True)          # the host loop on the first 300 users (time budget)
+    n_small = int((df_small['z'] == 'bandit').sum() - (df_small[df_small['u'] == 299]['z'] == 'bandit').sum())
+    variants = [dict(select_randomly=True, exploit_explore=True, epsilon=0.0, reverse_pop=False),
+                dict(select_randomly=False, exploit_explore=True, epsilon=0.0, reverse_pop=False),
+                dict(select_randomly=True, exploit_explore=True, epsilon=0.3, reverse_pop=False),
+                dict(select_randomly=False, exploit_explore=True, epsilon=0.3, reverse_pop=False),
+                dict(select_randomly=True, exploit_explore=False, epsilon=0.1, reverse_pop=False),
+                dict(select_randomly=True, exploit_explore=False, epsilon=0.1, reverse_pop=True),
+                dict(select_randomly=False, exploit_explore=False, epsilon=0.1, reverse_pop=True)]
+    table = np.random.RandomState(3).randint(0, P, size=P)
+    targets = [('random', {}, RandomAgent(Configuration({'num_products': P, 'random_seed': 5, 'with_ps_all': True}))),
+               ('lvt', {}, LastViewTableAgent(Configuration({'num_products': P, 'with_ps_all': True}), table))]
+    targets += [(f'ouc{i}', v, ouc(P, **v)) for i, v in enumerate(variants)]
+    for key, v, ag in targets:
+        r_dev, c_dev, _ = ev.ope_replay(ag, dl)
+        r_frame, c_frame, _, _ = ev._device_or_none(ag, df)
+        assert torch.equal(r_dev, r_frame) and torch.equal(c_dev, c_frame), key        # the two inputs: identical tensors
+        _, want = ev._host_snips(ag, df_small)
+        close(r_dev[:n_small].cpu().numpy(), want, 1e-12 if dense(v) else 0)
+        ips = ev.evaluate_IPS(ag, dl)
+        assert torch.equal(ips, c_dev * r_dev)
+
+
+def test_table_overflow_path():
+    """One user with more distinct products than the LDS table holds (700 views of 700 products, 1 500 rows) goes through the
+    per-wave global table: the same ratios as the host loop."""
+    P = 1000
+    rng = np.random.RandomState(1)
+    rows = []
+    for uid, n in ((0, 1500), (1, 40), (2, 3)):
+        views = rng.permutation(P)[:700] if uid == 0 else rng.randint(0, P, size=n)
+        t = 0
+        for i in range(n):
+            if i % 2 == 0 or uid == 2:
+                rows.append((uid, t, 'organic', int(views[(i // 2) % len(views)]), None, np.nan, np.nan)); t += 1
+            rows.append((uid, t, 'bandit', None, int(rng.randint(P)), float(rng.rand() < 0.3), 1.0 / P)); t += 1
+    df = pd.DataFrame({'t': np.array([r[1] for r in rows], dtype=np.float32), 'u': [r[0] for r in rows],
+                       'z': [r[2] for r in rows], 'v': pd.array([r[3] for r in rows], dtype=pd.UInt16Dtype()),
+                       'a': pd.array([r[4] for r in rows], dtype=pd.UInt16Dtype()),
+                       'c': np.array([r[5] for r in rows], dtype=np.float32), 'ps': [r[6] for r in rows]})
+    assert (df['u'] == 0).sum() > 1024
+    for v in (dict(select_randomly=True, exploit_explore=True, epsilon=0.0, reverse_pop=False),
+              dict(select_randomly=False, exploit_explore=True, epsilon=0.0, reverse_pop=False),
+              dict(select_randomly=True, exploit_explore=False, epsilon=0.1, reverse_pop=True)):
+        ag = ouc(P, **v)
+        r, _, _, from_frame = ev._device_or_none(ag, df)
+        assert from_frame
+        _, want = ev._host_snips(ag, df)
+        close(r.cpu().numpy(), want, 1e-12 if dense(v) else 0)
+
+
+def test_self_evaluation_at_scale_is_exact_and_deterministic():
+    """OUC (select_randomly, epsilon = 0) on its own log of 10^6 users at C2's shape: every ratio is exactly 1 and sum c r is
+    the clicks of the evaluated users; RandomAgent on an agent=None log: every ratio is exactly 1; two passes: the same sums."""
+    n, P = 1_000_000, 1000
+    cfg = Configuration({**env_1_args, 'random_seed': 21, 'num_products': P, 'K': 20})
+    o = dict(select_randomly=True, exploit_explore=True, epsilon=0.0, reverse_pop=False)
+    sim = Simulator(cfg, n, device='cuda:0', policy=_abi.RG_POLICY_ORGANIC_USER_COUNT, policy_seed=11, ouc=o)
+    sim.reset_users(0, n)
+    sim.run()
+    assert sim.counters()['hist_overflow'] == 0            # the logged ps came from an uncapped history
+    dl = sim.device_log()
+    r, c, sums = ev.ope_replay(ouc(P, **o), dl)
+    assert r.numel() > n and bool((r == 1.0).all())
+    last = int(dl.offsets[n - 1].item())
+    code = dl.rows[:last, 2]
+    clicks = int((((code & _abi.RG_EV_BANDIT) != 0) & ((code & _abi.RG_EV_CLICK) != 0)).sum().item())
+    s = sums.cpu().numpy()
+    assert s[0] == r.numel() and s[1] == clicks and s[2] == r.numel()
+    _, _, sums2 = ev.ope_replay(ouc(P, **o), dl)
+    assert np.array_equal(s.view(np.uint64), sums2.cpu().numpy().view(np.uint64))
+    del sim, dl, r, c
+    sim = _sim_log(P, n, seed=22)
+    dl = sim.device_log()
+    rnd = RandomAgent(Configuration({'num_products': P, 'random_seed': 5, 'with_ps_all': True}))
+    r, _, sums = ev.ope_replay(rnd, dl)
+    assert bool((r == 1.0).all())
+    # OUC-argmax as the target on this uniform log: 2 000 sampled users against the host loop, bit for bit
+    am = dict(select_randomly=False, exploit_explore=True, epsilon=0.0, reverse_pop=False)
+    r, _, _ = ev.ope_replay(ouc(P, **am), dl)
+    users = np.sort(np.random.RandomState(4).choice(n - 1, 2000, replace=False))
+    off = dl.offsets.cpu().numpy()
+    rows = dl.rows[:int(off[n - 1])].cpu().numpy().view(np.uint32)
+    is_b = (rows[:, 2] & _abi.RG_EV_BANDIT) != 0
+    rank = np.cumsum(is_b) - 1
+    pick = np.concatenate([np.arange(off[u], off[u + 1]) for u in users])
+    sub = rows[pick].copy()
+    sub[:, 0] = np.repeat(np.arange(users.size), off[users + 1] - off[users])
+    sub = np.concatenate([sub, [[users.size, 0, 0, 0]]]).astype(np.uint32)      # + one (unevaluated) highest user
+    from recogym_amd.sim import decode_rows
+    df = rows_to_dataframe(decode_rows(sub.view(np.int32), uniform_ps=1.0 / P), P)
+    _, want = ev._host_snips(ouc(P, **am), df)
+    got = r.cpu().numpy()[rank[pick][is_b[pick]]]
+    close(got, want, 0)
+
+
+def test_ips_estimate_lies_nearer_the_target():
+    """IPS of OUC-argmax on a uniform log of 200 000 users (P = 100) against the online CTRs (verify_agents' count, disjoint
+    users).  After a click the user always goes organic, so IPS is not exactly unbiased here: the estimate must lie nearer the
+    target's online CTR than the logger's, whose CTRs differ by >= 10 standard errors."""
+    n, P = 200_000, 100
+    sim = _sim_log(P, n, seed=31)
+    ee = ev.evaluate_IPS(ouc(P, select_randomly=False, exploit_explore=True, epsilon=0.0, reverse_pop=False), sim)
+    est = float(ee.mean().item())
+    c0 = sim.counters()
+    logger = c0['clicks'] / (c0['bandit'] + c0['phantom'])
+    cfg = Configuration({**env_1_args, 'random_seed': 31, 'num_products': P, 'K': 5})
+    tsim = Simulator(cfg, n, device='cuda:0', policy=_abi.RG_POLICY_ORGANIC_USER_COUNT, policy_seed=11, log_capacity=0,
+                     ouc=dict(select_randomly=False, exploit_explore=True, epsilon=0.0, reverse_pop=False))
+    tsim.reset_users(n, n)
+    tsim.run()
+    c1 = tsim.counters()
+    target = c1['clicks'] / (c1['bandit'] + c1['phantom'])
+    se = np.sqrt(target * (1 - target) / (c1['bandit'] + c1['phantom'])) + np.sqrt(logger * (1 - logger) / (c0['bandit'] + c0['phantom']))
+    print(f'IPS {est:.6f}  target CTR {target:.6f}  logger CTR {logger:.6f}  se {se:.2e}')
+    assert abs(target - logger) >= 10 * se
+    assert abs(est - target) < abs(est - logger)
