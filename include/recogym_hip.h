@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define RG_ABI_VERSION 7
+/* v8: the entry point of the 8-bit LogReg screen (v6; opt-in, measured slower than the fp16 screen) is gone;
+ * options pipe_mode and resident_grid are gone, pipe_groups takes 0 or 1. */
+#define RG_ABI_VERSION 8
 
 /* error codes */
 #define RG_OK 0
@@ -167,8 +169,9 @@ int rg_sim_destroy(rg_sim* sim);
 /* Run-path tuning knobs by name (none changes a result or the workspace layout; the defaults are the measured optima, DESIGN.md
  * §4 / §9).  rg_sim_create takes their initial values from the RECOGYM_* environment variables of the same meaning (the A/B
  * tests' way in); after that the library never reads the environment on the run path.  Names: walk_bias, walk_refill,
- * walk_handover, walk_click_batch, walk_search_batch, walk_helpers (0 .. 7), walk_click_join, walk_line64, pipe_groups, pipe_mode, pipe_occ1, pipe_occ2, pipe_xblocks,
- * pipe_min_users, exact_mix, exact_tile, resident_grid, slices (-1 = by population), sweep_prefix_off, tail_below,
+ * walk_handover, walk_click_batch, walk_search_batch, walk_helpers (0 .. 7), walk_click_join, walk_line64, pipe_groups (1: the walked
+ * run keeps its list lengths on the device; 0: the host reads them back), pipe_occ1, pipe_occ2, pipe_xblocks,
+ * pipe_min_users, exact_mix, exact_tile, slices (-1 = by population), sweep_prefix_off, tail_below,
  * repack_every, run_ahead (events a round of a run to the end may take a user through, 0 = an event per launch), lr_part_cap (acts
  * of a step the frozen-LogReg fp16 screen takes; can only be lowered), sweep_lds (1: the unsliced sweep of a run whose draws are
  * not cached keeps its tile prefixes in LDS and searches them there, k_draw_tp; 0: k_draw_bf16p's scratch + search), debug.
@@ -230,15 +233,6 @@ int rg_sim_set_logreg_fp32(rg_sim* sim, const float* d_coef32_t, const float* d_
  * sum_p views_p (2^-11 wmax[p] + 2^-25) + (views + 3) 2^-24 (bmax + sum_p views_p wmax[p]) of the best one, and decides among
  * them by float64 scores in scipy's order (rg_sim_set_logreg's arrays): sklearn's predict() bit for bit.  NULL = off. */
 int rg_sim_set_logreg_fp16(rg_sim* sim, const uint16_t* d_coef16_t);
-
-/* Optional: the screening pass from an 8-bit copy of coef^T instead of the fp16 one (after rg_sim_set_logreg_fp16; ABI v6): the rows
- * the pass streams are a QUARTER of the float32 bytes.  d_coef8_t [num_products][n_classes] unsigned bytes q + 128 with
- * q = rint(coef^T[p][c] / d_scale8[p]) in [-127, 127], d_scale8[p] = wmax[p] / 127 (fp32, rounded up): a weight is off by at most
- * d_scale8[p] / 2, so the pass's bound is sum_p views_p wmax[p] / 254 (+ the fp32 accumulation terms) where the fp16 pass has
- * sum_p views_p wmax[p] 2^-11 — more classes survive it; they are scored once more from the fp16 rows (that pass's bound), float64
- * scores still decide among what is left.  The pass reads 20 bytes per lane and row: d_coef8_t must be readable 16 bytes past its
- * last row, and n_classes % 4 == 0.  NULL = the fp16 pass. */
-int rg_sim_set_logreg_int8(rg_sim* sim, const uint8_t* d_coef8_t, const float* d_scale8);
 
 /* Where rows go.  d_log == NULL (or capacity 0) disables logging: only counters are kept. */
 int rg_sim_set_log(rg_sim* sim, rg_event* d_log, uint64_t capacity);

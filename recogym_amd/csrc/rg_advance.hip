@@ -244,9 +244,8 @@ __device__ __forceinline__ float fma_mix_hi(float a, uint32_t w, float acc) {
     asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(w), "v"(acc));
     return r;
 }
-template <bool Q8>
 __global__ void __launch_bounds__(kBlock, RG_LR_OCC) k_logreg_screen(DevSim d, uint32_t t) {
-    constexpr uint32_t kCandCap = 64;          // candidates of a range while it streams (a lane each in the second level)
+    constexpr uint32_t kCandCap = 64;          // candidates of a range while it streams
     __shared__ uint32_t s_cand[kBlock / 64][kCandCap];
     __shared__ float s_cval[kBlock / 64][kCandCap];
     typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -292,14 +291,10 @@ __global__ void __launch_bounds__(kBlock, RG_LR_OCC) k_logreg_screen(DevSim d, u
             V += cnt;
         }
         for (int o = 32; o > 0; o >>= 1) { A += __shfl_xor(A, o); V += __shfl_xor(V, o); }
-        // (the rows' own error: 2^-11 of wmax per weight from the fp16 copy, wmax / 254 from the 8-bit one)
-        constexpr bool q8 = Q8;
-        // (8-bit: the sums are taken on q + 128 and the offset removed at the end: partial sums up to ~3 A instead of A)
+        // (the rows' own error: 2^-11 of wmax per weight from the fp16 copy)
         const float B16 = (A * 4.8828125e-4f + V * 2.98023224e-8f +
                            static_cast<float>(nd + 3) * 5.9604644775390625e-08f * (d.lr_bmax + A)) * 1.02f;
-        const float B = !q8 ? B16 : (A * 3.9764e-3f + V * 2.98023224e-8f +
-                                     static_cast<float>(nd + 3) * 5.9604644775390625e-08f * (d.lr_bmax + 3.1f * A)) * 1.02f;
-        float thr = 2.0f * B * 1.01f + 1e-30f;
+        const float thr = 2.0f * B16 * 1.01f + 1e-30f;
         const uint32_t c_lo = r * RC, c_hi = min(c_lo + RC, C);
         float rb = -INFINITY;
         uint32_t n_cand = 0;
@@ -327,184 +322,66 @@ __global__ void __launch_bounds__(kBlock, RG_LR_OCC) k_logreg_screen(DevSim d, u
                 }
             }
         };
-        if (!q8) {
-            // fp16 rows.  The first eight history rows of a batch and its intercepts are one round trip; rows beyond the eighth (long
-            // histories) four at a time.  (The next batch's rows in flight while this one is summed — 40 more registers — LOST to
-            // the waves per SIMD it costs: acts 198 ms at 3 waves with the prefetch, 173 at 4 without: ab_call28_c5.jsonl)
-            struct Batch { uint4 hv[8]; float4 b0, b1; };
-            const uint32_t p8[8] = {h_prod(h8[0]), h_prod(h8[1]), h_prod(h8[2]), h_prod(h8[3]), h_prod(h8[4]), h_prod(h8[5]), h_prod(h8[6]), h_prod(h8[7])};
-            float cn8[8];
+        // fp16 rows.  The first eight history rows of a batch and its intercepts are one round trip; rows beyond the eighth (long
+        // histories) four at a time.  (The next batch's rows in flight while this one is summed — 40 more registers — LOST to
+        // the waves per SIMD it costs: acts 198 ms at 3 waves with the prefetch, 173 at 4 without: ab_call28_c5.jsonl)
+        struct Batch { uint4 hv[8]; float4 b0, b1; };
+        const uint32_t p8[8] = {h_prod(h8[0]), h_prod(h8[1]), h_prod(h8[2]), h_prod(h8[3]), h_prod(h8[4]), h_prod(h8[5]), h_prod(h8[6]), h_prod(h8[7])};
+        float cn8[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) cn8[e] = static_cast<uint32_t>(e) < nd ? static_cast<float>(h_cnt(h8[e])) : 0.0f;
-            const unsigned short* rp[8];           // (the rows' base addresses once per act, not per batch)
+        for (int e = 0; e < 8; ++e) cn8[e] = static_cast<uint32_t>(e) < nd ? static_cast<float>(h_cnt(h8[e])) : 0.0f;
+        const unsigned short* rp[8];           // (the rows' base addresses once per act, not per batch)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) rp[e] = d.lr_coef16_t + static_cast<size_t>(p8[e]) * C;
-            auto fetch = [&](uint32_t c0, Batch& bt) {
-                const uint32_t c = c0 + 8u * static_cast<uint32_t>(lane);
-                const uint32_t cl = c < c_hi ? c : c_lo;
-                bt.b0 = *reinterpret_cast<const float4*>(d.lr_intercept32 + cl);
-                bt.b1 = *reinterpret_cast<const float4*>(d.lr_intercept32 + cl + 4);
+        for (int e = 0; e < 8; ++e) rp[e] = d.lr_coef16_t + static_cast<size_t>(p8[e]) * C;
+        auto fetch = [&](uint32_t c0, Batch& bt) {
+            const uint32_t c = c0 + 8u * static_cast<uint32_t>(lane);
+            const uint32_t cl = c < c_hi ? c : c_lo;
+            bt.b0 = *reinterpret_cast<const float4*>(d.lr_intercept32 + cl);
+            bt.b1 = *reinterpret_cast<const float4*>(d.lr_intercept32 + cl + 4);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) bt.hv[e] = *reinterpret_cast<const uint4*>(rp[e] + cl);
-            };
-            Batch cur;
-            fetch(c_lo, cur);
-            for (uint32_t c0 = c_lo; c0 < c_hi && !overflow; c0 += 512) {
-                const bool more = c0 + 512 < c_hi;
-                const uint32_t c = c0 + 8u * static_cast<uint32_t>(lane);
-                const bool in = c < c_hi;
-                const uint32_t cl = in ? c : c_lo;
-                float acc[8] = {cur.b0.x, cur.b0.y, cur.b0.z, cur.b0.w, cur.b1.x, cur.b1.y, cur.b1.z, cur.b1.w};
+            for (int e = 0; e < 8; ++e) bt.hv[e] = *reinterpret_cast<const uint4*>(rp[e] + cl);
+        };
+        Batch cur;
+        fetch(c_lo, cur);
+        for (uint32_t c0 = c_lo; c0 < c_hi && !overflow; c0 += 512) {
+            const bool more = c0 + 512 < c_hi;
+            const uint32_t c = c0 + 8u * static_cast<uint32_t>(lane);
+            const bool in = c < c_hi;
+            const uint32_t cl = in ? c : c_lo;
+            float acc[8] = {cur.b0.x, cur.b0.y, cur.b0.z, cur.b0.w, cur.b1.x, cur.b1.y, cur.b1.z, cur.b1.w};
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {                        // (rows beyond the history: count 0, no branch)
-                    const uint32_t wq[4] = {cur.hv[e].x, cur.hv[e].y, cur.hv[e].z, cur.hv[e].w};
+            for (int e = 0; e < 8; ++e) {                        // (rows beyond the history: count 0, no branch)
+                const uint32_t wq[4] = {cur.hv[e].x, cur.hv[e].y, cur.hv[e].z, cur.hv[e].w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    acc[2 * j] = fma_mix_lo(cn8[e], wq[j], acc[2 * j]);
+                    acc[2 * j + 1] = fma_mix_hi(cn8[e], wq[j], acc[2 * j + 1]);
+                }
+            }
+            for (uint32_t i0 = 8; i0 < nd; i0 += 4) {            // long histories: four more rows in flight
+                uint4 hv[4];
+                float cn[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const hent_t x = hr[min(i0 + e, nd - 1)];
+                    cn[e] = i0 + e < nd ? static_cast<float>(h_cnt(x)) : 0.0f;
+                    hv[e] = *reinterpret_cast<const uint4*>(d.lr_coef16_t + static_cast<size_t>(h_prod(x)) * C + cl);
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const uint32_t wq[4] = {hv[e].x, hv[e].y, hv[e].z, hv[e].w};
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        acc[2 * j] = fma_mix_lo(cn8[e], wq[j], acc[2 * j]);
-                        acc[2 * j + 1] = fma_mix_hi(cn8[e], wq[j], acc[2 * j + 1]);
-                    }
-                }
-                for (uint32_t i0 = 8; i0 < nd; i0 += 4) {            // long histories: four more rows in flight
-                    uint4 hv[4];
-                    float cn[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const hent_t x = hr[min(i0 + e, nd - 1)];
-                        cn[e] = i0 + e < nd ? static_cast<float>(h_cnt(x)) : 0.0f;
-                        hv[e] = *reinterpret_cast<const uint4*>(d.lr_coef16_t + static_cast<size_t>(h_prod(x)) * C + cl);
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const uint32_t wq[4] = {hv[e].x, hv[e].y, hv[e].z, hv[e].w};
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            acc[2 * j] = fma_mix_lo(cn[e], wq[j], acc[2 * j]);
-                            acc[2 * j + 1] = fma_mix_hi(cn[e], wq[j], acc[2 * j + 1]);
-                        }
-                    }
-                }
-                collect(c, in, acc);
-                if (more) fetch(c0 + 512, cur);
-            }
-        } else {
-            // 8-bit rows (q + 128: v_cvt_f32_ubyte*), count x scale folded into one factor per row, the offset 128 sum(count x scale)
-            // taken off once at the end.  A lane takes kCpl8 = 20 consecutive classes — 20 bytes per row — so that a range of
-            // <= 1 280 classes (C5: 1 256) is ONE round trip for its first eight history rows: the screen is a chain of dependent
-            // round trips (list -> history -> rows), not bytes — the 8-bit rows at 8 classes per lane took as long as the fp16 ones
-            // (profiles/r6/ab_call29_c5.jsonl).  Rows are read up to 16 bytes past a range's last class (rg_sim_set_logreg_int8: the
-            // array carries 16 bytes of padding).
-            constexpr int kCpl8 = 20;
-            struct __attribute__((packed, aligned(4))) Row8 { uint32_t w[kCpl8 / 4]; };
-            uint32_t p8[8];
-            float cs8[8];
-            float corr8 = 0.0f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                p8[e] = h_prod(h8[e]);
-                cs8[e] = static_cast<uint32_t>(e) < nd ? static_cast<float>(h_cnt(h8[e])) * d.lr_scale8[p8[e]] : 0.0f;   // (p8 is a product always)
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) corr8 = fmaf(cs8[e], 128.0f, corr8);
-            for (uint32_t c0 = c_lo; c0 < c_hi && !overflow; c0 += 64 * kCpl8) {
-                const uint32_t c = c0 + static_cast<uint32_t>(kCpl8) * static_cast<uint32_t>(lane);
-                const bool in = c < c_hi;                            // (some of the lane's classes; each is checked below)
-                const uint32_t cl = in ? c : c_lo;
-                Row8 bv[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) bv[e] = *reinterpret_cast<const Row8*>(d.lr_coef8_t + static_cast<size_t>(p8[e]) * C + cl);
-                float acc[kCpl8];
-#pragma unroll
-                for (int q = 0; q < kCpl8 / 4; ++q) {
-                    const float4 b = *reinterpret_cast<const float4*>(d.lr_intercept32 + min(cl + 4u * q, C - 4u));
-                    acc[4 * q] = b.x; acc[4 * q + 1] = b.y; acc[4 * q + 2] = b.z; acc[4 * q + 3] = b.w;
-                }
-                float corr = corr8;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-#pragma unroll
-                    for (int j = 0; j < kCpl8; ++j)
-                        acc[j] = fmaf(cs8[e], static_cast<float>((bv[e].w[j / 4] >> (8 * (j % 4))) & 0xFFu), acc[j]);
-                }
-                for (uint32_t i0 = 8; i0 < nd; i0 += 2) {            // long histories: two more rows in flight
-                    Row8 bw[2];
-                    float cs[2];
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const hent_t x = hr[min(i0 + e, nd - 1)];
-                        const uint32_t pp = h_prod(x);
-                        cs[e] = static_cast<float>(h_cnt(x)) * d.lr_scale8[pp] * (i0 + e < nd ? 1.0f : 0.0f);     // (the load unconditional)
-                        bw[e] = *reinterpret_cast<const Row8*>(d.lr_coef8_t + static_cast<size_t>(pp) * C + cl);
-                    }
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        corr = fmaf(cs[e], 128.0f, corr);
-#pragma unroll
-                        for (int j = 0; j < kCpl8; ++j)
-                            acc[j] = fmaf(cs[e], static_cast<float>((bw[e].w[j / 4] >> (8 * (j % 4))) & 0xFFu), acc[j]);
-                    }
-                }
-                float m = -INFINITY;
-#pragma unroll
-                for (int j = 0; j < kCpl8; ++j) {
-                    acc[j] -= corr;
-                    if (c + j < c_hi) m = fmaxf(m, acc[j]);
-                }
-                if (!in) m = -INFINITY;
-                rb = fmaxf(rb, wave_max_dpp(m));
-                const float cut = rb - thr;
-                // (few classes pass: one ballot over "any of mine", then the passing lanes' classes one by one)
-                bool any = false;
-#pragma unroll
-                for (int j = 0; j < kCpl8; ++j) any = any || (c + j < c_hi && acc[j] >= cut);
-                if (!in) any = false;
-                if (__ballot(any)) {
-#pragma unroll
-                    for (int j = 0; j < kCpl8; ++j) {
-                        const bool pass = in && c + j < c_hi && acc[j] >= cut;
-                        const unsigned long long pm = __ballot(pass);
-                        if (pm && !overflow) {
-                            const uint32_t np = static_cast<uint32_t>(__popcll(pm));
-                            if (n_cand + np > kCandCap) overflow = true;
-                            else {
-                                if (pass) { const uint32_t k = n_cand + prefix_in_mask(pm); s_cand[wave][k] = c + j; s_cval[wave][k] = acc[j]; }
-                                n_cand += np;
-                            }
-                        }
+                        acc[2 * j] = fma_mix_lo(cn[e], wq[j], acc[2 * j]);
+                        acc[2 * j + 1] = fma_mix_hi(cn[e], wq[j], acc[2 * j + 1]);
                     }
                 }
             }
+            collect(c, in, acc);
+            if (more) fetch(c0 + 512, cur);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         __builtin_amdgcn_wave_barrier();
-        if (q8 && !overflow) {
-            // ---- second level of the 8-bit screen: the range's true maximum is among the candidates above (within 2 B8 of the
-            // range's 8-bit maximum); their scores once more from the fp16 rows — a lane per candidate, the fp16 pass's own
-            // arithmetic (intercept32, then fma in history order), so that pass's bound B16 holds for them: from here on the
-            // range's maximum is the candidates' fp16 maximum and the band 2 B16, and k_logreg_decide works as it does on the
-            // fp16 screen (the true argmax is a candidate, its fp16 score within 2 B16 of any other candidate's) ----
-            const bool mine2 = static_cast<uint32_t>(lane) < n_cand;
-            const uint32_t cc = mine2 ? s_cand[wave][lane] : c_lo;
-            float acc = d.lr_intercept32[cc];
-            for (uint32_t i0 = 0; i0 < nd; i0 += 8) {                // eight values in flight
-                unsigned short wv[8];
-                float cn[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const hent_t x = hr[min(i0 + e, nd - 1)];
-                    cn[e] = i0 + e < nd ? static_cast<float>(h_cnt(x)) : 0.0f;
-                    wv[e] = d.lr_coef16_t[static_cast<size_t>(h_prod(x)) * C + cc];
-                }
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc = fmaf(cn[e], static_cast<float>(__builtin_bit_cast(_Float16, wv[e])), acc);
-            }
-            float m2 = mine2 ? acc : -INFINITY;
-            if (mine2) s_cval[wave][lane] = acc;
-            for (int o = 32; o > 0; o >>= 1) m2 = fmaxf(m2, __shfl_xor(m2, o));
-            rb = m2;
-            thr = 2.0f * B16 * 1.01f + 1e-30f;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-        }
         // ---- what survives the range's final maximum ----
         uint32_t* part = d.lr_part + (static_cast<size_t>(w) * kLrSplit + r) * kLrPartWords;
         const bool mine = !overflow && static_cast<uint32_t>(lane) < n_cand;
@@ -1318,7 +1195,7 @@ __global__ void __launch_bounds__(kBlock) k_tail(DevSim d, uint32_t t0) {
 }
 search_kernel_t logreg_select_kernel() { return k_logreg_select; }
 search_kernel_t logreg_acts_kernel() { return k_logreg_acts; }
-search_kernel_t logreg_screen_kernel(bool q8) { return q8 ? k_logreg_screen<true> : k_logreg_screen<false>; }
+search_kernel_t logreg_screen_kernel() { return k_logreg_screen; }
 search_kernel_t logreg_decide_kernel() { return k_logreg_decide; }
 search_kernel_t logreg_sample_kernel() { return k_logreg_sample; }
 advance_kernel_t advance_kernel() { return k_advance; }

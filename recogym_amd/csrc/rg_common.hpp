@@ -216,9 +216,8 @@ struct DevSim {
     uint32_t* park_list;      // [n_cap + 64] user indices, reserved in chunks of 64 (0xFFFFFFFF = unused entry)
     uint32_t* park_t;         // [n_cap] time of the parked draw
     uint8_t* f64_valid;       // [n_cap] exact_sums / exact_ref rows (indexed by user index in this mode) are valid
-    // The walked run as a pipeline over user groups (run_walk_pipe): every launch works on the user-index range
-    // [grp_lo, grp_lo + grp_n) and on work queues of its own, so that the launches of different groups can be in flight at once
-    // on different streams.  Outside the pipeline: the whole reset range and the two counters[] slots.
+    // The walked run: every launch works on the user-index range [grp_lo, grp_lo + grp_n) (always the whole reset range) and on
+    // work queues of its own.  run_walk_pipe: counters in walk_ctl, list lengths read on the device; run_walk: the two counters[] slots.
     uint32_t grp_lo, grp_n;
     uint32_t list_in;         // first park_list entry of the list k_exact_sums_h / k_exact_prefix read
     unsigned long long* q_ticket;        // ticket counter of the launch's work queue
@@ -264,7 +263,6 @@ struct DevSim {
     // (lr_dirty, set by history_add) and kept per user; k_logreg_select / k_logreg_acts run before k_advance
     const float* lr_coef32_t; const float* lr_intercept32; const float* lr_wmax; float lr_bmax;   // fp32 copies + max_c |coef[p][c]|, max |b|
     const unsigned short* lr_coef16_t;   // fp16 copy of coef^T (screening pass of k_logreg_acts16), or null
-    const uint8_t* lr_coef8_t; const float* lr_scale8;   // 8-bit copy (q + 128) and its per-row scale: the screening pass reads it instead, or null
     uint32_t* lr_action;      // [n_cap] by user index: action of the user's current history
     // select_randomly (rg_config.lr_select_randomly): the act is SAMPLED per event from softmax(scores) — k_logreg_sample leaves the
     // action and its probability for the step's bandit event (or, for an organic user that stops at this step, for its trailing
@@ -313,7 +311,6 @@ using namespace rgk;
 struct RunOpts {
     int exact_tile;          // RECOGYM_EXACT_TILE: the K > 64 tile kernel for every float64 resolve
     int exact_mix;           // RECOGYM_EXACT_MIX: groups of every 8 of the walk's float64 batch in the matrix form (8 = all)
-    int resident_grid;       // RECOGYM_RESIDENT_GRID: sweep grid = the resident blocks
     int slices;              // RECOGYM_SLICES: product slices of the lock-step sweep (-1 = by population)
     int sweep_prefix_off;    // RECOGYM_SWEEP_PREFIX_OFF: the sweep stores sums, k_cache_prefix converts them
     int debug;               // RECOGYM_DEBUG
@@ -338,17 +335,13 @@ struct rg_sim {
     bool walk_solo;           // its last round is k_walk_solo (RECOGYM_WALK_SOLO=0: k_walk2's)
     int n_cus;                // compute units of the device (grid of the persistent walk kernel)
     double prof_walk_ms[2];   // round 1 / round 2 of k_walk
-    // the walked run as a pipeline over user groups on two or three streams (run_walk_pipe)
-    int pipe_groups;          // user groups (1 = one group: the serial chain without host read-backs); 0 = run_walk (host-side counts)
-    int pipe_mode;            // 0: every launch on the caller's stream; 1: float64 batch + round 2 of a group on a second stream;
-                              // 2: ... and the sweeps on a third
+    // the walked run with its list lengths on the device (run_walk_pipe)
+    int pipe_groups;          // 1 = run_walk_pipe: the serial chain without host read-backs; 0 = run_walk (host-side counts)
     int pipe_occ1, pipe_occ2; // blocks per CU of the round-1 / round-2 grids (<= what the kernel is compiled for)
     int pipe_xblocks;         // blocks of the float64 batch's grid
     bool fin_in_sweep;        // the sweep of run_walk_pipe leaves the finalize / prefix kernels' output itself (RECOGYM_FIN_IN_SWEEP=0: A/B)
-    uint32_t pipe_min_users;  // users of a group (and of a pipelined run) at least: an unsliced sweep's 1024 user tiles (RECOGYM_PIPE_MIN: tests)
-    hipStream_t pipe_streams[2];
-    std::vector<hipEvent_t> pipe_events;   // ordering events (no timing), created once
-    double prof_pipe_ms;      // profiling: wall time of the pipelined runs (its kernels' own times overlap)
+    uint32_t pipe_min_users;  // users of such a run at least: an unsliced sweep's 1024 user tiles (RECOGYM_PIPE_MIN: tests)
+    double prof_pipe_ms;      // profiling: wall time of those runs
     // rg_sim_debug_walk_fate: where the last walked run left the list of its last round (null: there was none)
     uint32_t fate_base; const unsigned long long* fate_count;
     uint32_t repack_every;    // steps between repacks (RECOGYM_REPACK, 0 = never)
@@ -413,7 +406,7 @@ void (*xh_stats_kernel())(DevSim);
 search_kernel_t drift_kernel();                            // part 6
 search_kernel_t logreg_select_kernel();
 search_kernel_t logreg_acts_kernel();
-search_kernel_t logreg_screen_kernel(bool q8);
+search_kernel_t logreg_screen_kernel();
 search_kernel_t logreg_decide_kernel();
 search_kernel_t logreg_sample_kernel();
 advance_kernel_t advance_kernel();
@@ -455,15 +448,13 @@ constexpr uint32_t kHoleCode = 0xFFFFFFFFu;   // rg_event.code of an unused raw-
 constexpr int kCntTailRows = 16, kCntTailOrganic = 17, kCntTailBandit = 18, kCntTailMaxT = 19, kCntTailTicket = 20,
               kCntTailLimit = 21, kCntWalkTicket = 22, kCntParkCnt = 23;   // internal slots of counters[] (RG_CNT_N = 24)
 constexpr int kCntWalkHits = RG_CNT_MEMO_HITS;
-// the walked run as a pipeline over user groups (run_walk_pipe): at most kMaxWalkGroups groups; a park_list region per group
-// holds its users plus the 64-entry blocks its waves leave part-used (<= 2 per wave: parked users, hand-over); walk_ctl =
-// 8 counters per group {round-1 ticket, round-1 list length, float64 batch ticket, round-2 ticket, -...} and, in block
-// kMaxWalkGroups, {last round's list length, last round's ticket}.  The last round's list: kParkSlack entries per group
-// (a wave of a round 2 hands over once: <= 2 blocks).  Walk grids are capped at kMaxWalkWaves waves.
-constexpr uint32_t kMaxWalkGroups = 16;
+// the walked run: park_list holds round 1's list — the users plus the 64-entry blocks its waves leave part-used (<= 2 per wave:
+// parked users, hand-over) — and behind it the last round's list: kParkSlack entries (a wave of round 2 hands over once: <= 2
+// blocks).  run_walk_pipe's walk_ctl = 8 counters {round-1 ticket, round-1 list length, float64 batch ticket, round-2 ticket, -...}
+// and 8 more {last round's list length, last round's ticket}.  Walk grids are capped at kMaxWalkWaves waves.
 constexpr uint32_t kMaxWalkWaves = 4096;
 constexpr uint32_t kParkSlack = 2u * 64u * kMaxWalkWaves;
-constexpr uint32_t kWalkCtlWords = 8u * (kMaxWalkGroups + 1u);
+constexpr uint32_t kWalkCtlWords = 16;
 
 struct Geom { uint32_t KH, KS, TP, P_pad, n_chunks, sc_chunks, n_sc, N1, N2, N3, RS, TPB, F16, XNH, XNL, XRS; };
 
@@ -650,9 +641,8 @@ inline size_t carve_all(const rg_config& c, uint64_t n, void* base, DevSim* d) {
     // (a quarter of the organic users at the default transition matrix); what a step lists beyond the rows goes through k_logreg_acts
     const size_t lr_part_cap = lr ? (n / 2 + 4096 < n ? n / 2 + 4096 : n) : 0;
     uint32_t* lr_part = w.take<uint32_t>(lr ? lr_part_cap * static_cast<size_t>(8 * (4 + 2 * 8)) : 1);       // kLrSplit x kLrPartWords
-    // round 1's list, then round 2's hand-overs, 64-entry blocks per wave; the pipeline: a region per user group (its users +
-    // kParkSlack for the blocks its waves leave part-used) and one for the last round's list
-    uint32_t* park_list = w.take<uint32_t>(cache ? n + 128 + static_cast<size_t>(2 * kMaxWalkGroups) * kParkSlack : 1);
+    // round 1's list (the users + kParkSlack for the blocks its waves leave part-used), then round 2's hand-overs (kParkSlack)
+    uint32_t* park_list = w.take<uint32_t>(cache ? n + 128 + static_cast<size_t>(2) * kParkSlack : 1);
     unsigned long long* walk_ctl = w.take<unsigned long long>(kWalkCtlWords);
     unsigned long long* step1_buf = w.take<unsigned long long>(16);      // rg_sim_step_user: {action | result}
     uint32_t* park_t = w.take<uint32_t>(cache ? n : 1);
@@ -2072,13 +2062,6 @@ static __device__ unsigned long long g_f16w_t[8];
 #else
 #define RG_TSEC(i) do {} while (0)
 #endif
-
-
-// user groups per wave of the wide kernel (RECOGYM_F16W_UG: 1 = 8 waves x 32 users, 2 = 4 waves x 64 users)
-inline int f16w_ug() {
-    const char* e = getenv("RECOGYM_F16W_UG");
-    return (e && e[0] == '2') ? 2 : 1;
-}
 
 // RG_POLICY_LOGREG_FROZEN for one user, computed by the whole wave: lane = class (c, c + 64, ...), so the
 // coef_t rows of the viewed products are read as coalesced 512-byte runs instead of one gather per

@@ -5,8 +5,8 @@
 
 namespace rgk {
 
-template <int KH, int N1, int UG>
-__global__ void __launch_bounds__(512 / UG, 1) k_draw_f16w(DevSim d, uint32_t t, uint32_t S) {
+template <int KH, int N1>
+__global__ void __launch_bounds__(512, 1) k_draw_f16w(DevSim d, uint32_t t, uint32_t S) {
     // Nothing that lives across the tile loop may be spilled: a reload inside the loop is followed by `s_waitcnt
     // vmcnt(0)`, which also waits for the tile DMA in flight (the asm DMA is invisible to the compiler's counter
     // model) — a memory round trip per tile and wave.  The mu tile's buffer descriptor and this lane's LDS address
@@ -14,9 +14,11 @@ __global__ void __launch_bounds__(512 / UG, 1) k_draw_f16w(DevSim d, uint32_t t,
     // the kernel-argument segment.
     const __attribute__((address_space(4))) char* kargs = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
     constexpr uint32_t RSc = 32 * N1 + 16, TILE_B = 64 * RSc, NT = TILE_B / 1024;     // 1 KB per wave-wide DMA instruction
-    // UG groups of 32 users per wave, 8 / UG waves per block (256 users either way).  UG = 2: every A fragment read
-    // from LDS feeds two MFMAs (half the LDS traffic) but one wave per SIMD; UG = 1: two waves per SIMD
-    constexpr int NW = 8 / UG;
+    // One group of 32 users per wave, 8 waves per block (256 users): two waves per SIMD.  (Two groups per wave — every A fragment
+    // read from LDS feeding two MFMAs, half the LDS traffic — ran one wave per SIMD on spills and lost: DESIGN.md 3b.)  The body
+    // keeps its per-group form, arrays of length UG = 1 and loops over them: written with scalars the compiler allocates registers
+    // differently (other spills), and which of the two is faster is a measurement for a change of this kernel, not a clean-up.
+    constexpr int UG = 1, NW = 8;
     using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
     using f32x2 = __attribute__((ext_vector_type(2))) float;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -223,9 +225,8 @@ __global__ void __launch_bounds__(512 / UG, 1) k_draw_f16w(DevSim d, uint32_t t,
             }
             f32x2 x[UG][2][4];
             const bool have_p = ti > pt_lo;
-            // A operands: a ring RD k-steps deep, read RD - 1 steps ahead of the MFMAs that consume them (one wave per
-            // SIMD has nobody to hide an LDS round trip behind: deeper there)
-            constexpr int RD = UG == 2 ? 5 : 3;
+            // A operands: a ring RD k-steps deep, read RD - 1 steps ahead of the MFMAs that consume them
+            constexpr int RD = 3;
             bf16x8 A0r[RD], A1r[RD];
 #pragma unroll
             for (int s2 = 0; s2 < RD - 1 && s2 < N1; ++s2) {
@@ -319,8 +320,7 @@ __global__ void __launch_bounds__(512 / UG, 1) k_draw_f16w(DevSim d, uint32_t t,
 }
 
 draw_kernel_t f16w_kernel_for(const DevSim& d) {
-    const int ug = f16w_ug();
-#define RG_CASE(kh, a) if (d.KH == kh && d.N1 == a) return ug == 2 ? k_draw_f16w<kh, a, 2> : k_draw_f16w<kh, a, 1>;
+#define RG_CASE(kh, a) if (d.KH == kh && d.N1 == a) return k_draw_f16w<kh, a>;
     RG_CASE(16, 7) RG_CASE(32, 7) RG_CASE(32, 10) RG_CASE(32, 13)
 #undef RG_CASE
     return nullptr;

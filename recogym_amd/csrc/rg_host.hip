@@ -648,14 +648,11 @@ int device_cus(rg_sim* sim) {
     return sim->n_cus;
 }
 
-// Grid of a sweep kernel.  The per-wave scratch (chunk sums + super-chunk records, ~40 KB per wave at C3) is indexed
-// by BLOCK in the fused form.  Capping the grid at the blocks the device holds at once (RECOGYM_RESIDENT_GRID=1) keeps
-// that scratch an ~80 MB working set instead of ~650 MB, but the memory-side counters (FETCH_SIZE / WRITE_SIZE sit at
-// the L2 <-> fabric boundary and include Infinity-Cache hits) were identical and the kernel 3 % slower: not the default.
-int sweep_grid(rg_sim* sim, uint64_t work_items, uint32_t S) {
+// Grid of a sweep kernel: a block per user tile.  (Capping it at the blocks the device holds at once keeps the per-wave
+// scratch of the fused form — chunk sums + super-chunk records, ~40 KB per wave at C3 — an ~80 MB working set instead of
+// ~650 MB, but the memory-side counters were identical and the kernel 3 % slower: HISTORY.md 9.)
+int sweep_grid(rg_sim* sim, uint64_t work_items) {
     int grid = grid_for(work_items, 1);
-    const int resident = device_cus(sim) * (sim->draw_users == 256 ? 1 : 2);
-    if (S == 1 && grid > resident && sim->opt.resident_grid) grid = resident;
     if (sim->draw_users == 256 && grid > kMaxGrid / 2) grid = kMaxGrid / 2;     // 8 groups per block share the per-wave scratch
     return grid;
 }
@@ -694,7 +691,7 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         if (sim->opt.slices >= 0) S = static_cast<uint32_t>(sim->opt.slices);   // tests: force either form
         if (S > d.n_sc) S = d.n_sc;
         if (S < 1) S = 1;
-        const int grid = sweep_grid(sim, static_cast<uint64_t>(tiles_up) * S, S);
+        const int grid = sweep_grid(sim, static_cast<uint64_t>(tiles_up) * S);
         // (the search stays at the end of every user tile of the sweep: as its own kernel over the whole step — scratch slot
         // per user tile — the sweep got 15 % shorter and the step 6 % longer: profiles/r3/ab_call26_*, ab_call27_*)
         const bool tp = S == 1 && sim->tp_kernel && sim->sweep_lds && !d.use_cache;
@@ -747,7 +744,7 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
                 const int g = grid_for(waves, kBlock / 64);
                 return g < cus * blocks_per_cu ? g : cus * blocks_per_cu;
             };
-            hipLaunchKernelGGL(logreg_screen_kernel(d.lr_coef8_t != nullptr), dim3(capped((static_cast<uint64_t>(upper) / 4 + 64) * kLrSplit, 16)),
+            hipLaunchKernelGGL(logreg_screen_kernel(), dim3(capped((static_cast<uint64_t>(upper) / 4 + 64) * kLrSplit, 16)),
                                dim3(kBlock), 0, st, d, t);
             hipLaunchKernelGGL(logreg_decide_kernel(), dim3(capped(static_cast<uint64_t>(upper) / 4 + 64, 8)), dim3(kBlock), 0, st, d, t);
             if (upper > d.lr_part_cap)     // the step may list more acts than the screen's scratch has rows: the rest in fp32 / float64
@@ -817,7 +814,7 @@ int run_walk(rg_sim* sim, hipStream_t st) {
         // walk's prefix form itself (no conversion pass over the 1.3 KB of chunk sums per user)
         fused_prefix = sim->walk2 && S == 1 && sim->bf16_kernel == bf16p_kernel_for(d) && d.f16 && !d.wide && !sim->opt.sweep_prefix_off;
         ds.sweep_only = fused_prefix ? 2u : 1u;
-        const int grid = sweep_grid(sim, static_cast<uint64_t>(tiles_up) * S, S);
+        const int grid = sweep_grid(sim, static_cast<uint64_t>(tiles_up) * S);
         hipLaunchKernelGGL(sim->bf16_kernel, dim3(grid), dim3(sim->draw_threads), sim->bf16_smem, st, ds, 0u, S);
     }
     if (int rc = mark(1)) return rc;
@@ -835,6 +832,7 @@ int run_walk(rg_sim* sim, hipStream_t st) {
         const int blocks_cap = sim->n_cus * occ;
         int blocks = static_cast<int>((static_cast<uint64_t>(n_work) + kBlock - 1) / kBlock);
         if (blocks > blocks_cap) blocks = blocks_cap;
+        if (blocks > static_cast<int>(kMaxWalkWaves / 4)) blocks = kMaxWalkWaves / 4;     // (park_list's slack is sized for that many waves)
         if (blocks < 1) blocks = 1;
         // rows are reserved per wave in chunks: ~1/32 of what a wave will emit, within [256, 4096] (unused entries:
         // < 64 per chunk and the rest of every wave's last chunk — a few percent of the raw log)
@@ -930,13 +928,11 @@ walked:
     return RG_OK;
 }
 
-// The same run as a PIPELINE over user groups: the reset range is cut into G groups of equal size; per group
+// The same run as ONE CHAIN of launches whose list lengths stay on the device:
 //   sweep -> finalize -> round 1          (k_draw_bf16p sweep_only = 2, k_cache_finalize + k_cache_prefix, k_walk2)
 //   float64 batch -> prefixes -> round 2  (k_exact_sums_h, k_exact_prefix, k_walk2) on the users round 1 parked
-// and one last round (k_walk_solo) over what the rounds 2 handed over.  The second chain of group g runs on a second stream
-// while the first chain of group g + 1 runs on the caller's: the float64 batch is bound by the float64 pipes, the walk by its
-// chains of dependent loads (half of its wave cycles are waits), so they share the compute units instead of taking turns.
-// Every list length stays on the device (q_count): no host read-back between the launches, one at the end (the step limit).
+// and one last round (k_walk_solo) over what round 2 handed over.  Every list length stays on the device (q_count): no host
+// read-back between the launches, one at the end (the step limit).
 // Results are those of run_walk bit for bit: every draw is addressed by (seed, user, t), a user's events are walked by one
 // lane at a time, and the sorted log does not depend on the raw order.
 int run_walk_pipe(rg_sim* sim, hipStream_t st) {
@@ -945,38 +941,20 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
     if (d.debug_row_base)      // test hook: the walk reserves its raw rows from this counter
         HIP_TRY(hipMemcpyAsync(d.counters + kCntTailRows, &sim->d.debug_row_base, sizeof(unsigned long long), hipMemcpyHostToDevice, st));
     const uint32_t n = d.n_users;
-    // groups: equal sizes, multiples of 256 users, each large enough for the unsliced sweep (>= 1024 user tiles)
-    uint32_t G = static_cast<uint32_t>(sim->pipe_groups);
-    if (G > kMaxWalkGroups) G = kMaxWalkGroups;
-    while (G > 1 && n / G < sim->pipe_min_users) --G;
-    const uint32_t gsz = (((n + G - 1) / G) + 255u) & ~255u;
-    G = (n + gsz - 1) / gsz;
-    const int mode = G > 1 ? sim->pipe_mode : 0;
-    if (mode >= 1 && !sim->pipe_streams[0]) {
-        HIP_TRY(hipStreamCreateWithFlags(&sim->pipe_streams[0], hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&sim->pipe_streams[1], hipStreamNonBlocking));
-    }
-    const size_t n_ev = 3 * static_cast<size_t>(kMaxWalkGroups) + 2;
-    while (sim->pipe_events.size() < n_ev) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        sim->pipe_events.push_back(e);
-    }
-    hipStream_t sA = st, sB = mode >= 1 ? sim->pipe_streams[0] : st, sS = mode >= 2 ? sim->pipe_streams[1] : st;
-    // profiling: a pair of timing events around every launch group, on the stream it is launched on
+    // profiling: a pair of timing events around every launch group
     struct Span { int cls; hipEvent_t a, b; };
     std::vector<Span> spans;
-    auto span_begin = [&](int cls, hipStream_t s) -> int {
+    auto span_begin = [&](int cls) -> int {
         if (!sim->profiling) return RG_OK;
         Span sp{cls, nullptr, nullptr};
         HIP_TRY(hipEventCreate(&sp.a)); HIP_TRY(hipEventCreate(&sp.b));
-        HIP_TRY(hipEventRecord(sp.a, s));
+        HIP_TRY(hipEventRecord(sp.a, st));
         spans.push_back(sp);
         return RG_OK;
     };
-    auto span_end = [&](hipStream_t s) -> int {
+    auto span_end = [&]() -> int {
         if (!sim->profiling) return RG_OK;
-        HIP_TRY(hipEventRecord(spans.back().b, s));
+        HIP_TRY(hipEventRecord(spans.back().b, st));
         return RG_OK;
     };
     hipEvent_t wall[2] = {nullptr, nullptr};
@@ -985,12 +963,6 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         HIP_TRY(hipEventRecord(wall[0], st));
     }
     HIP_TRY(hipMemsetAsync(d.walk_ctl, 0, sizeof(unsigned long long) * kWalkCtlWords, st));
-    hipEvent_t ev_start = sim->pipe_events[3 * kMaxWalkGroups];
-    if (sB != st || sS != st) {
-        HIP_TRY(hipEventRecord(ev_start, st));
-        if (sB != st) HIP_TRY(hipStreamWaitEvent(sB, ev_start, 0));
-        if (sS != st) HIP_TRY(hipStreamWaitEvent(sS, ev_start, 0));
-    }
     const bool hist = d.policy == RG_POLICY_ORGANIC_USER_COUNT;
     const size_t smem = (kBlock / 64) * walk2_wave_lds(hist);
     const walk_kernel_t wk = walk2_kernel_for(d, sim->walk_occ);
@@ -1005,75 +977,61 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         if (chunk > 4096) chunk = 4096;
         return static_cast<uint32_t>(chunk);
     };
-    unsigned long long* ctl_last = d.walk_ctl + 8 * kMaxWalkGroups;
-    const uint32_t base_solo = ((n + 63u) & ~63u) + kMaxWalkGroups * kParkSlack;    // behind every group's region
-    for (uint32_t g = 0; g < G; ++g) {
-        DevSim dg = d;
-        dg.grp_lo = g * gsz;
-        dg.grp_n = n - dg.grp_lo < gsz ? n - dg.grp_lo : gsz;
-        unsigned long long* ctl = d.walk_ctl + 8 * g;
-        const uint32_t region = dg.grp_lo + g * kParkSlack;
-        // ---- sweep, finalize ----
-        {
-            DevSim ds = dg;
-            ds.sweep_only = 2u;
-            ds.fin_in_sweep = dg.fin_in_sweep = sim->fin_in_sweep ? 1u : 0u;
-            const uint32_t tiles_up = (dg.grp_n + sim->draw_users - 1) / sim->draw_users;
-            if (int rc = span_begin(0, sS)) return rc;
-            if (sim->xh_kernel) hipLaunchKernelGGL(sim->xh_kernel, dim3(grid_for((dg.grp_n + 32u * sim->xh_waves - 1) / (32u * sim->xh_waves), 1)), dim3(64 * sim->xh_waves), sim->xh_smem, sS, ds, 0u, 1u);
-            else
-            hipLaunchKernelGGL(sim->bf16_kernel, dim3(sweep_grid(sim, tiles_up, 1)), dim3(sim->draw_threads), sim->bf16_smem, sS, ds, 0u, 1u);
-            if (int rc = span_end(sS)) return rc;
-            if (int rc = span_begin(1, sS)) return rc;
-            hipLaunchKernelGGL(finalize_kernel_for(d), dim3(grid_for(dg.grp_n)), dim3(kBlock), 0, sS, dg);
-            hipLaunchKernelGGL(cache_prefix_kernel(), dim3(grid_for((static_cast<uint64_t>(dg.grp_n) + 7) / 8, kBlock / 64)), dim3(kBlock), 0, sS, dg, 1);
-            if (int rc = span_end(sS)) return rc;
-            if (sS != sA) {
-                HIP_TRY(hipEventRecord(sim->pipe_events[3 * g], sS));
-                HIP_TRY(hipStreamWaitEvent(sA, sim->pipe_events[3 * g], 0));
-            }
-        }
-        // ---- round 1 ----
-        {
-            DevSim dw = dg;
-            dw.q_ticket = ctl + 0; dw.q_park = ctl + 1; dw.q_count = nullptr;
-            int blocks = static_cast<int>((static_cast<uint64_t>(dg.grp_n) + kBlock - 1) / kBlock);
-            if (blocks > n_cus * sim->pipe_occ1) blocks = n_cus * sim->pipe_occ1;
-            if (blocks > static_cast<int>(kMaxWalkWaves / 4)) blocks = kMaxWalkWaves / 4;
-            if (int rc = span_begin(2, sA)) return rc;
-            hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, sA, dw, dg.grp_n, 1, walk_chunk(dg.grp_n, blocks), 0u, region);
-            if (int rc = span_end(sA)) return rc;
-            if (sB != sA) {
-                HIP_TRY(hipEventRecord(sim->pipe_events[3 * g + 1], sA));
-                HIP_TRY(hipStreamWaitEvent(sB, sim->pipe_events[3 * g + 1], 0));
-            }
-        }
-        // ---- the users it parked: float64 sums, prefixes, round 2 (what it hands over: the last round's list) ----
-        {
-            DevSim dx = dg;
-            dx.q_ticket = ctl + 2; dx.q_count = ctl + 1; dx.list_in = region;
-            const uint32_t est = dg.grp_n / 3 + 4096u;                  // launch shapes only: the lengths are read on the device
-            uint32_t xgrid = (dg.grp_n + 255u) / 256u;
-            if (xgrid > static_cast<uint32_t>(sim->pipe_xblocks)) xgrid = static_cast<uint32_t>(sim->pipe_xblocks);
-            if (int rc = span_begin(3, sB)) return rc;
-            hipLaunchKernelGGL(kh, dim3(xgrid), dim3(kBlock), exact_m_lds(d.XKB), sB, dx, dg.grp_n, mfma_of_8);
-            hipLaunchKernelGGL(exact_prefix_kernel(), dim3(grid_for(est, kBlock / 64)), dim3(kBlock), 0, sB, dx, dg.grp_n);
-            if (int rc = span_end(sB)) return rc;
-            DevSim dr = dg;
-            dr.q_ticket = ctl + 3; dr.q_park = ctl_last + 0; dr.q_count = ctl + 1;
-            int blocks = static_cast<int>((static_cast<uint64_t>(est) + kBlock - 1) / kBlock);
-            if (blocks > n_cus * sim->pipe_occ2) blocks = n_cus * sim->pipe_occ2;
-            if (blocks > static_cast<int>(kMaxWalkWaves / 4)) blocks = kMaxWalkWaves / 4;
-            if (int rc = span_begin(4, sB)) return rc;
-            hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, sB, dr, dg.grp_n, 2, walk_chunk(est, blocks), region, base_solo);
-            if (int rc = span_end(sB)) return rc;
-            if (sB != sA && g + 1 == G) {
-                HIP_TRY(hipEventRecord(sim->pipe_events[3 * g + 2], sB));
-                HIP_TRY(hipStreamWaitEvent(sA, sim->pipe_events[3 * g + 2], 0));
-            }
-        }
+    unsigned long long* ctl = d.walk_ctl;           // the rounds' queue counters; the last round's 8 words behind them
+    unsigned long long* ctl_last = d.walk_ctl + 8;
+    const uint32_t region = 0;                      // park_list: the users round 1 parked, then (behind its slack) the last round's list
+    const uint32_t base_solo = ((n + 63u) & ~63u) + kParkSlack;
+    DevSim dg = d;
+    dg.grp_lo = 0;
+    dg.grp_n = n;
+    // ---- sweep, finalize ----
+    {
+        DevSim ds = dg;
+        ds.sweep_only = 2u;
+        ds.fin_in_sweep = dg.fin_in_sweep = sim->fin_in_sweep ? 1u : 0u;
+        const uint32_t tiles_up = (n + sim->draw_users - 1) / sim->draw_users;
+        if (int rc = span_begin(0)) return rc;
+        if (sim->xh_kernel) hipLaunchKernelGGL(sim->xh_kernel, dim3(grid_for((n + 32u * sim->xh_waves - 1) / (32u * sim->xh_waves), 1)), dim3(64 * sim->xh_waves), sim->xh_smem, st, ds, 0u, 1u);
+        else
+        hipLaunchKernelGGL(sim->bf16_kernel, dim3(sweep_grid(sim, tiles_up)), dim3(sim->draw_threads), sim->bf16_smem, st, ds, 0u, 1u);
+        if (int rc = span_end()) return rc;
+        if (int rc = span_begin(1)) return rc;
+        hipLaunchKernelGGL(finalize_kernel_for(d), dim3(grid_for(n)), dim3(kBlock), 0, st, dg);
+        hipLaunchKernelGGL(cache_prefix_kernel(), dim3(grid_for((static_cast<uint64_t>(n) + 7) / 8, kBlock / 64)), dim3(kBlock), 0, st, dg, 1);
+        if (int rc = span_end()) return rc;
     }
-    // ---- last round: a wave per user (k_walk_solo) over what the rounds 2 handed over ----
+    // ---- round 1 ----
+    {
+        DevSim dw = dg;
+        dw.q_ticket = ctl + 0; dw.q_park = ctl + 1; dw.q_count = nullptr;
+        int blocks = static_cast<int>((static_cast<uint64_t>(n) + kBlock - 1) / kBlock);
+        if (blocks > n_cus * sim->pipe_occ1) blocks = n_cus * sim->pipe_occ1;
+        if (blocks > static_cast<int>(kMaxWalkWaves / 4)) blocks = kMaxWalkWaves / 4;
+        if (int rc = span_begin(2)) return rc;
+        hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, dw, n, 1, walk_chunk(n, blocks), 0u, region);
+        if (int rc = span_end()) return rc;
+    }
+    // ---- the users it parked: float64 sums, prefixes, round 2 (what it hands over: the last round's list) ----
+    {
+        DevSim dx = dg;
+        dx.q_ticket = ctl + 2; dx.q_count = ctl + 1; dx.list_in = region;
+        const uint32_t est = n / 3 + 4096u;                  // launch shapes only: the lengths are read on the device
+        uint32_t xgrid = (n + 255u) / 256u;
+        if (xgrid > static_cast<uint32_t>(sim->pipe_xblocks)) xgrid = static_cast<uint32_t>(sim->pipe_xblocks);
+        if (int rc = span_begin(3)) return rc;
+        hipLaunchKernelGGL(kh, dim3(xgrid), dim3(kBlock), exact_m_lds(d.XKB), st, dx, n, mfma_of_8);
+        hipLaunchKernelGGL(exact_prefix_kernel(), dim3(grid_for(est, kBlock / 64)), dim3(kBlock), 0, st, dx, n);
+        if (int rc = span_end()) return rc;
+        DevSim dr = dg;
+        dr.q_ticket = ctl + 3; dr.q_park = ctl_last + 0; dr.q_count = ctl + 1;
+        int blocks = static_cast<int>((static_cast<uint64_t>(est) + kBlock - 1) / kBlock);
+        if (blocks > n_cus * sim->pipe_occ2) blocks = n_cus * sim->pipe_occ2;
+        if (blocks > static_cast<int>(kMaxWalkWaves / 4)) blocks = kMaxWalkWaves / 4;
+        if (int rc = span_begin(4)) return rc;
+        hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, dr, n, 2, walk_chunk(est, blocks), region, base_solo);
+        if (int rc = span_end()) return rc;
+    }
+    // ---- last round: a wave per user (k_walk_solo) over what round 2 handed over ----
     sim->fate_base = base_solo; sim->fate_count = ctl_last + 0;
     if (d.walk_handover) {
         DevSim dl = d;
@@ -1086,9 +1044,9 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         chunk = chunk / 64 * 64;
         if (chunk < 64) chunk = 64;
         if (chunk > 1024) chunk = 1024;
-        if (int rc = span_begin(4, sA)) return rc;
-        hipLaunchKernelGGL(sk, dim3(blocks), dim3(kBlock), 0, sA, dl, n, static_cast<uint32_t>(chunk), base_solo);
-        if (int rc = span_end(sA)) return rc;
+        if (int rc = span_begin(4)) return rc;
+        hipLaunchKernelGGL(sk, dim3(blocks), dim3(kBlock), 0, st, dl, n, static_cast<uint32_t>(chunk), base_solo);
+        if (int rc = span_end()) return rc;
     }
     hipLaunchKernelGGL(k_walk_finish, dim3(1), dim3(1), 0, st, d);
     HIP_TRY(hipGetLastError());
@@ -1179,7 +1137,6 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
         o.exact_tile = getenv("RECOGYM_EXACT_TILE") ? 1 : 0;
         o.exact_mix = 5;
         if (const char* e = getenv("RECOGYM_EXACT_MIX")) o.exact_mix = atoi(e);
-        o.resident_grid = getenv("RECOGYM_RESIDENT_GRID") ? 1 : 0;
         o.slices = -1;
         if (const char* e = getenv("RECOGYM_SLICES")) o.slices = atoi(e);
         o.sweep_prefix_off = getenv("RECOGYM_SWEEP_PREFIX_OFF") ? 1 : 0;
@@ -1206,7 +1163,7 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
         if (d.wide) {
             s->bf16_kernel = static_cast<size_t>(d.P_pad) * d.RS < (1ull << 31) ? f16w_kernel_for(d) : nullptr;
             s->bf16_smem = 3 * (64 * static_cast<size_t>(d.RS) + 256) + 8 * 32 * 2 * static_cast<size_t>(d.KH) * 4;
-            s->draw_threads = 512 / f16w_ug(); s->draw_users = 256;
+            s->draw_threads = 512; s->draw_users = 256;
         }
         // the larger classes still spill registers; the fp32 kernel is faster there for now
         if (s->bf16_kernel && (d.f16 || (d.N1 <= 4 && d.KH <= 10))) d.use_mfma = 2;
@@ -1334,20 +1291,18 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
     s->walk_solo = true;
     if (const char* e = getenv("RECOGYM_WALK_SOLO")) s->walk_solo = e[0] != '0';
     s->prof_walk_ms[0] = s->prof_walk_ms[1] = 0.0;
-    // the walked run as a pipeline over user groups (run_walk_pipe).  RECOGYM_PIPE=G (0: run_walk, host-side list lengths),
-    // RECOGYM_PIPE_MODE=0|1|2, RECOGYM_PIPE_OCC1 / _OCC2 (blocks per CU of the rounds' grids), RECOGYM_PIPE_XBLOCKS: A/B tests
-    // Default: ONE group (the serial chain, every list length read on the device: no host read-back between the launches).
-    // More groups on two or three streams were measured on C3 and do not pay (profiles/r4/ab_call1_pipe_forms.jsonl, DESIGN.md
-    // 3a): the walk's three waves per SIMD fill the register file, so nothing co-resides with it, and every group adds a
-    // drain tail to both walk rounds and a partial last wave of blocks to the float64 batch.
-    s->pipe_groups = 1; s->pipe_mode = 1;
+    // the walked run as one chain with its list lengths on the device (run_walk_pipe).  RECOGYM_PIPE=0: run_walk, host-side list
+    // lengths; RECOGYM_PIPE_OCC1 / _OCC2 (blocks per CU of the rounds' grids), RECOGYM_PIPE_XBLOCKS: A/B tests.
+    // The whole reset range is ONE group on the caller's stream.  More groups on two or three streams were measured on C3 and
+    // did not pay (profiles/r4/ab_call1_pipe_forms.jsonl): the walk's three waves per SIMD fill the register file,
+    // so nothing co-resides with it, and every group adds a drain tail to both walk rounds and a partial last wave of blocks to
+    // the float64 batch.
+    s->pipe_groups = 1;
     s->pipe_occ1 = s->pipe_occ2 = s->walk_occ;
     s->pipe_xblocks = 1024;
-    s->pipe_streams[0] = s->pipe_streams[1] = nullptr;
     s->fate_base = 0; s->fate_count = nullptr;
     s->prof_pipe_ms = 0.0;
-    if (const char* e = getenv("RECOGYM_PIPE")) s->pipe_groups = atoi(e);
-    if (const char* e = getenv("RECOGYM_PIPE_MODE")) s->pipe_mode = atoi(e);
+    if (const char* e = getenv("RECOGYM_PIPE")) { const int o = atoi(e); if (o == 0 || o == 1) s->pipe_groups = o; }
     if (const char* e = getenv("RECOGYM_PIPE_OCC1")) { const int o = atoi(e); if (o >= 1 && o <= s->walk_occ) s->pipe_occ1 = o; }
     if (const char* e = getenv("RECOGYM_PIPE_OCC2")) { const int o = atoi(e); if (o >= 1 && o <= s->walk_occ) s->pipe_occ2 = o; }
     if (const char* e = getenv("RECOGYM_PIPE_XBLOCKS")) { const int o = atoi(e); if (o >= 1) s->pipe_xblocks = o; }
@@ -1396,8 +1351,6 @@ int rg_sim_destroy(rg_sim* sim) {
     if (sim->h_pinned) (void)hipHostFree(sim->h_pinned);
     if (sim->h_step) (void)hipHostFree(sim->h_step);
     for (hipEvent_t e : sim->prof_events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : sim->pipe_events) (void)hipEventDestroy(e);
-    for (hipStream_t ps : sim->pipe_streams) if (ps) (void)hipStreamDestroy(ps);
     delete sim;
     return RG_OK;
 }
@@ -1406,13 +1359,11 @@ int rg_sim_destroy(rg_sim* sim) {
 namespace {
 int* opt_int(rg_sim* s, const char* n) {
     if (!strcmp(n, "pipe_groups")) return &s->pipe_groups;
-    if (!strcmp(n, "pipe_mode")) return &s->pipe_mode;
     if (!strcmp(n, "pipe_occ1")) return &s->pipe_occ1;
     if (!strcmp(n, "pipe_occ2")) return &s->pipe_occ2;
     if (!strcmp(n, "pipe_xblocks")) return &s->pipe_xblocks;
     if (!strcmp(n, "exact_mix")) return &s->opt.exact_mix;
     if (!strcmp(n, "exact_tile")) return &s->opt.exact_tile;
-    if (!strcmp(n, "resident_grid")) return &s->opt.resident_grid;
     if (!strcmp(n, "slices")) return &s->opt.slices;
     if (!strcmp(n, "sweep_prefix_off")) return &s->opt.sweep_prefix_off;
     if (!strcmp(n, "debug")) return &s->opt.debug;
@@ -1445,10 +1396,10 @@ int rg_sim_set_option(rg_sim* sim, const char* name, int64_t value) {
         if (!strcmp(name, "pipe_xblocks") && value < 1) return fail(RG_EINVAL, "pipe_xblocks must be >= 1");
         if (!strcmp(name, "exact_mix") && (value < 0 || value > 8)) return fail(RG_EINVAL, "exact_mix must be in [0, 8]");
         if (value < -2147483647 || value > 2147483647) return fail(RG_EINVAL, "%s out of the range of an int", name);
-        if (!strcmp(name, "pipe_groups") && value < 0) return fail(RG_EINVAL, "pipe_groups must be >= 0");
-        if (!strcmp(name, "pipe_mode") && (value < 0 || value > 2)) return fail(RG_EINVAL, "pipe_mode must be 0, 1 or 2");
+        if (!strcmp(name, "pipe_groups") && (value < 0 || value > 1))
+            return fail(RG_EINVAL, "pipe_groups must be 1 (list lengths on the device) or 0 (run_walk: read back by the host)");
         if (!strcmp(name, "slices") && value < -1) return fail(RG_EINVAL, "slices must be >= -1 (-1 = by population)");
-        if ((!strcmp(name, "exact_tile") || !strcmp(name, "resident_grid") || !strcmp(name, "sweep_prefix_off") || !strcmp(name, "debug")) &&
+        if ((!strcmp(name, "exact_tile") || !strcmp(name, "sweep_prefix_off") || !strcmp(name, "debug")) &&
             (value < 0 || value > 1)) return fail(RG_EINVAL, "%s is a flag (0 or 1)", name);
         *p = static_cast<int>(value);
         return RG_OK;
@@ -1560,7 +1511,7 @@ int rg_sim_set_logreg(rg_sim* sim, const double* d_coef_t, const double* d_inter
     sim->d.lr_n = n_classes;
     // a new model invalidates the optional copies of the old one (their shapes and bounds belong to it): set them again
     sim->d.lr_coef32_t = nullptr; sim->d.lr_intercept32 = nullptr; sim->d.lr_wmax = nullptr; sim->d.lr_bmax = 0.0f;
-    sim->d.lr_coef16_t = nullptr; sim->d.lr_coef8_t = nullptr; sim->d.lr_scale8 = nullptr;
+    sim->d.lr_coef16_t = nullptr;
     return RG_OK;
 }
 
@@ -1572,7 +1523,6 @@ int rg_sim_set_logreg_fp32(rg_sim* sim, const float* d_coef32_t, const float* d_
     if (!(bmax >= 0.0f)) return fail(RG_EINVAL, "bmax must be >= 0");
     sim->d.lr_coef32_t = d_coef32_t; sim->d.lr_intercept32 = d_intercept32; sim->d.lr_wmax = d_wmax; sim->d.lr_bmax = bmax;
     sim->d.lr_coef16_t = nullptr;      // the screening pass reads intercept32 / wmax / bmax: attach it again after this call
-    sim->d.lr_coef8_t = nullptr; sim->d.lr_scale8 = nullptr;
     return RG_OK;
 }
 
@@ -1582,16 +1532,6 @@ int rg_sim_set_logreg_fp16(rg_sim* sim, const uint16_t* d_coef16_t) {
     if (d_coef16_t && !sim->d.lr_coef32_t) return fail(RG_ESTATE, "rg_sim_set_logreg_fp32 must be called first (intercept32, wmax, bmax)");
     if (d_coef16_t && sim->d.lr_n % 8u) return fail(RG_EINVAL, "the fp16 screening pass needs n_classes %% 8 == 0 (have %u)", sim->d.lr_n);
     sim->d.lr_coef16_t = d_coef16_t;
-    sim->d.lr_coef8_t = nullptr; sim->d.lr_scale8 = nullptr;
-    return RG_OK;
-}
-
-int rg_sim_set_logreg_int8(rg_sim* sim, const uint8_t* d_coef8_t, const float* d_scale8) {
-    if (!sim) return fail(RG_EINVAL, "sim is NULL");
-    if (sim->d.policy != RG_POLICY_LOGREG_FROZEN) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_FROZEN");
-    if ((d_coef8_t != nullptr) != (d_scale8 != nullptr)) return fail(RG_EINVAL, "both arrays or none");
-    if (d_coef8_t && !sim->d.lr_coef16_t) return fail(RG_ESTATE, "rg_sim_set_logreg_fp16 must be called first (the 8-bit copy replaces the rows the screening pass reads)");
-    sim->d.lr_coef8_t = d_coef8_t; sim->d.lr_scale8 = d_scale8;
     return RG_OK;
 }
 

@@ -86,6 +86,9 @@ class Simulator:
     def __init__(self, config, n_users, policy=_abi.RG_POLICY_UNIFORM_ENV, policy_seed=None,
                  ouc=None, epoch=0, log_capacity=None, device=None, tables=None, policy_table=None,
                  policy_ps=None, logreg=None, ps_float64=None, p_click=False, env0=None):
+        if policy == _abi.RG_POLICY_LOGREG_FROZEN and ((logreg or {}).get('int8') or os.environ.get('RECOGYM_LOGREG') == 'int8'):
+            # (refused, not ignored: a caller that labels the act's bytes from this switch would report 1 B per weight for an fp16 run)
+            raise ValueError("the 8-bit LogReg screen is retired (measured slower than the fp16 screen): drop logreg['int8'] / RECOGYM_LOGREG=int8")
         self.lib = _abi.load()
         self.device = require_device(device)
         self.config = config
@@ -171,23 +174,6 @@ class Simulator:
                             and float(self.logreg[0].abs().max().item()) < 6.0e4):
                         self.logreg16 = self.logreg[0].to(torch.float16).contiguous()
                         _abi.check(self.lib.rg_sim_set_logreg_fp16(self._h, self.logreg16.data_ptr()), 'rg_sim_set_logreg_fp16')
-                        # round 6, opt-in (RECOGYM_LOGREG=int8 or logreg['int8']): the screening pass from an 8-BIT copy (a quarter of the
-                        # fp32 row bytes): q = rint(w / scale) + 128, scale = wmax / 127 per product row — |w - scale q| <= scale / 2.
-                        # Its band is 8x the fp16 copy's, so the classes it keeps are scored once more from the fp16 rows (second level,
-                        # inside the screen kernel) before float64 decides
-                        if logreg.get('int8', False) or os.environ.get('RECOGYM_LOGREG', 'fp16') == 'int8':
-                            scale = (wmax.to(torch.float64) / 127.0 * (1.0 + 1e-6)).clamp_min(1e-30)
-                            q = torch.round(self.logreg[0] / scale[:, None]).clamp_(-127, 127)
-                            assert bool(((self.logreg[0] - q * scale[:, None]).abs() <= 0.5 * scale[:, None] * (1.0 + 1e-9)).all())
-                            # (16 bytes of padding behind the last row: the pass reads 20 bytes per lane and row)
-                            q8 = torch.zeros(q.numel() + 16, dtype=torch.uint8, device=q.device)
-                            q8[:q.numel()] = (q + 128.0).to(torch.uint8).reshape(-1)
-                            self.logreg8 = (q8, scale.to(torch.float32).contiguous())
-                            # (the float32 scale the kernel multiplies with must not be SMALLER than the one the weights were divided
-                            # by, or the half-step bound would be off by the rounding: compare against the float64 value)
-                            assert bool((self.logreg8[1].to(torch.float64) * (1.0 + 2e-7) >= scale).all())
-                            _abi.check(self.lib.rg_sim_set_logreg_int8(self._h, self.logreg8[0].data_ptr(), self.logreg8[1].data_ptr()),
-                                       'rg_sim_set_logreg_int8')
             if log_capacity is None:
                 log_capacity = default_log_capacity(config, self.n_users)
             self.log = None

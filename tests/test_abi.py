@@ -108,7 +108,8 @@ def test_run_options_are_set_by_name_not_by_the_environment_at_run_time(lib, mon
     assert lib.rg_sim_get_option(h, b'exact_mix', C.byref(v)) == 0 and v.value == 6
     assert lib.rg_sim_set_option(h, b'exact_mix', 4) == 0
     assert lib.rg_sim_get_option(h, b'exact_mix', C.byref(v)) == 0 and v.value == 4
-    assert lib.rg_sim_set_option(h, b'pipe_groups', 4) == 0 and lib.rg_sim_set_option(h, b'walk_bias', 6) == 0
+    assert lib.rg_sim_set_option(h, b'pipe_groups', 0) == 0 and lib.rg_sim_set_option(h, b'walk_bias', 6) == 0
+    assert lib.rg_sim_set_option(h, b'pipe_groups', 2) == -1 and b'pipe_groups' in lib.rg_last_error()
     assert lib.rg_sim_get_option(h, b'walk_bias', C.byref(v)) == 0 and v.value == 6
     assert lib.rg_sim_set_option(h, b'exact_mix', 9) == -1 and b'exact_mix' in lib.rg_last_error()
     assert lib.rg_sim_set_option(h, b'pipe_occ1', 0) == -1
