@@ -34,7 +34,9 @@ extern "C" {
 
 /* v8: the entry point of the 8-bit LogReg screen (v6; opt-in, measured slower than the fp16 screen) is gone;
  * options pipe_mode and resident_grid are gone, pipe_groups takes 0 or 1. */
-#define RG_ABI_VERSION 8
+/* v9 (additive): rg_count_train / rg_count_policy (the OrganicCount and BanditCount agents' tables from a sorted device log) and
+ * rg_sim_set_policy_table_f64 (RG_POLICY_LAST_VIEW_TABLE with a float64 `ps` table). */
+#define RG_ABI_VERSION 9
 
 /* error codes */
 #define RG_OK 0
@@ -208,6 +210,11 @@ int rg_sim_set_tables(rg_sim* sim, const double* d_gamma, const double* d_mu_org
  * d_action[p] = action taken when the user's last organic view was p, d_ps[p] = the `ps` value
  * logged with it (NULL = 1.0; BanditMFSquare logs its logit there, bandit_mf.py:84). */
 int rg_sim_set_policy_table(rg_sim* sim, const int32_t* d_action, const float* d_ps);
+
+/* The same with the `ps` table in float64 (BanditCount logs its CTR estimate (clicks + 1) / (pulls + 2) there, bandit_count.py:44,
+ * which float32 cannot hold): the float64 side array of the log (rg_sim_set_log_aux) then carries exactly d_ps[p]; the 16-byte
+ * row keeps its rounding to float32.  The two calls replace each other. */
+int rg_sim_set_policy_table_f64(rg_sim* sim, const int32_t* d_action, const double* d_ps);
 
 /* RG_POLICY_LOGREG_FROZEN: the fitted model's arrays on the device, kept by pointer: d_coef_t =
  * sklearn's coef_ TRANSPOSED, row-major [num_products][n_classes] float64; d_intercept [n_classes];
@@ -400,6 +407,48 @@ size_t rg_ope_workspace_bytes(const rg_ope_policy* pol, uint64_t n_users, uint32
 int rg_ope_replay(const rg_ope_policy* pol, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
                   uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
                   uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The count agents' training (reference agents/organic_count.py:74-82, agents/bandit_count.py:49-62 under the offline protocol
+ * of bench_agents.py:90-190): a sorted log reduced to P x P tables of 64-bit integer counters.  Stateless (no rg_sim handle).
+ * The tables are caller-owned row-major int64 device arrays; either group (co_counts | pulls + clicks) may be NULL.
+ *   co_counts[i][j] += views(i) * views(j) for every session: a maximal run of organic rows inside a user;
+ *   pulls[ix][a] += 1, clicks[ix][a] += c for every bandit row (the phantom row included), ix = the last organic view in front
+ *   of the PREVIOUS bandit row of the log, whichever user that row belongs to (the agent's last_product_viewed before the call
+ *   looks at its own session).
+ * Everything is an integer sum: the result does not depend on the order of the updates (the same bits on every run).
+ */
+typedef struct rg_count_tables {
+    uint32_t num_products;          /* P <= RG_EV_INDEX_MASK */
+    uint32_t reserved;
+    int64_t* co_counts;             /* [P][P] or NULL */
+    int64_t* pulls;                 /* [P][P] or NULL (with clicks) */
+    int64_t* clicks;                /* [P][P] or NULL (with pulls) */
+} rg_count_tables;
+
+#define RG_COUNT_ORGANIC 0
+#define RG_COUNT_BANDIT 1
+
+/* rg_count_train: ADDS users 0 .. n_users-1 of a sorted log (user i = rows d_offsets[i] .. d_offsets[i+1]-1, each user's first
+ * row organic) to the tables.  d_carry (4 int64, device): [0] in = BanditCount's last_product_viewed before the log (-1 = None),
+ * out = after it, so that a second log continues where the first ended; [1] out = the action of the one bandit row that met
+ * None (-1: there was none), [2] out = its click: NumPy's `pulls_a[None, a] += 1` adds to the WHOLE row a, and so does this
+ * call (pulls[a][:] += 1, clicks[a][:] += c) before it returns; [3] reserved.  d_workspace: rg_count_workspace_bytes() bytes;
+ * afterwards its int64 words hold [0] error bits (0), [1] cell updates the log stands for, [2] global atomics issued for them
+ * (the rest was summed in LDS first).  Synchronises `stream` twice (it reads the validation's verdict before any table is
+ * touched, and the error bits at the end).  RG_EINVAL: P out of range, a half-given pulls / clicks pair, a user whose first
+ * row is a bandit row, a row whose product is >= P (such a row is never counted), a workspace too small (RG_ENOMEM). */
+size_t rg_count_workspace_bytes(void);
+int rg_count_train(const rg_count_tables* tables, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                   int64_t* d_carry, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* rg_count_policy: the frozen policy of a trained count agent, per last viewed product l the FIRST index of the maximum of
+ * co_counts[l][:] (kind RG_COUNT_ORGANIC; d_win_* are not written) or of (clicks[l][:] + 1) / (pulls[l][:] + 2) (RG_COUNT_BANDIT),
+ * decided by exact integer cross-multiplication — the order of NumPy's rounded float64 quotients while pulls + 2 < 2^26, where
+ * distinct fractions round to distinct doubles; d_win_clicks[l] / d_win_pulls[l] receive the winning cell's counters, from which
+ * the caller takes the logged `ps` with its own float64 divide.  d_action: P int32; d_win_*: P int64.  No synchronisation. */
+int rg_count_policy(const rg_count_tables* tables, uint32_t kind, int32_t* d_action, int64_t* d_win_clicks,
+                    int64_t* d_win_pulls, void* stream);
 
 #ifdef __cplusplus
 }

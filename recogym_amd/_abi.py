@@ -7,7 +7,7 @@ infrastructure and is never imported from this package.)
 import ctypes as C
 import os
 
-RG_ABI_VERSION = 8
+RG_ABI_VERSION = 9
 
 RG_STATE_ORGANIC, RG_STATE_BANDIT, RG_STATE_STOP = 0, 1, 2
 
@@ -80,6 +80,15 @@ class RgOpePolicy(C.Structure):
                 ('reserved', C.c_uint32), ('ouc_epsilon', C.c_double), ('table', C.c_void_p)]
 
 
+RG_COUNT_ORGANIC, RG_COUNT_BANDIT = 0, 1
+
+
+class RgCountTables(C.Structure):
+    """struct rg_count_tables: the caller-owned int64 device tables of rg_count_train / rg_count_policy."""
+    _fields_ = [('num_products', C.c_uint32), ('reserved', C.c_uint32), ('co_counts', C.c_void_p), ('pulls', C.c_void_p),
+                ('clicks', C.c_void_p)]
+
+
 # every symbol include/recogym_hip.h declares, with its ctypes signature
 _SIM = C.c_void_p
 SYMBOLS = {
@@ -97,6 +106,7 @@ SYMBOLS = {
     'rg_env0_click_thresholds': (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     'rg_sim_set_env0_tables': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rg_sim_set_policy_table': (C.c_int, [_SIM, C.c_void_p, C.c_void_p]),
+    'rg_sim_set_policy_table_f64': (C.c_int, [_SIM, C.c_void_p, C.c_void_p]),
     'rg_sim_set_logreg': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     'rg_sim_set_logreg_fp32': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
     'rg_sim_set_logreg_fp16': (C.c_int, [_SIM, C.c_void_p]),
@@ -130,6 +140,10 @@ SYMBOLS = {
     'rg_ope_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpePolicy), C.c_uint64, C.c_uint32]),
     'rg_ope_replay': (C.c_int, [C.POINTER(RgOpePolicy), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
                                 C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rg_count_workspace_bytes': (C.c_size_t, []),
+    'rg_count_train': (C.c_int, [C.POINTER(RgCountTables), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
+    'rg_count_policy': (C.c_int, [C.POINTER(RgCountTables), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 LIB_NAME = 'librecogym_hip.so'

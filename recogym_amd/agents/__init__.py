@@ -6,3 +6,5 @@ from .logreg_frozen import LogregFrozenAgent
 from .logreg_ips import LogregMulticlassIpsAgent, logreg_multiclass_ips_args
 from .feature_feed import train_data_from_log
 from .bandit_mf import BanditMFSquareAgent, bandit_mf_square_args
+from .organic_count import OrganicCount, organic_count_args
+from .bandit_count import BanditCount, bandit_count_args

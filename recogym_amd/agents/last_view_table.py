@@ -10,8 +10,11 @@ from .abstract import Agent
 
 
 class LastViewTableAgent(Agent):
-    def __init__(self, config, table, ps=None):
+    def __init__(self, config, table, ps=None, ps64=False):
+        """`ps64`: the device keeps the `ps` table in float64 (BanditCount's CTR values; rg_sim_set_policy_table_f64) instead of
+        float32 (BanditMFSquare's float32 logit)."""
         super().__init__(config)
+        self.ps64 = bool(ps64)
         self.table = np.ascontiguousarray(table, dtype=np.int32)
         assert self.table.shape == (config.num_products,)
         assert self.table.min() >= 0 and self.table.max() < config.num_products
@@ -41,8 +44,11 @@ class LastViewTableAgent(Agent):
     def device_policy(self):
         if getattr(self.config, 'with_ps_all', False):
             return None
-        return dict(policy=_abi.RG_POLICY_LAST_VIEW_TABLE, policy_seed=0, ouc=None,
-                    policy_table=self.table, policy_ps=self.ps)
+        pol = dict(policy=_abi.RG_POLICY_LAST_VIEW_TABLE, policy_seed=0, ouc=None,
+                   policy_table=self.table, policy_ps=self.ps)
+        if self.ps64:
+            pol['policy_ps64'] = True
+        return pol
 
     def ope_policy(self):
         """The replay form of `ps-a` (evaluate_agent.evaluate_IPS on the device): one-hot at table[last viewed product]."""

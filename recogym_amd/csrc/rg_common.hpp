@@ -257,7 +257,7 @@ struct DevSim {
     // second copy of the slot-indexed state: k_repack_copy moves the live users' state into it, densely
     // and in list order, and the host swaps the pointers (restores the locality the lists lose over time)
     double* omega_alt; unsigned long long* hist_alt; uint32_t* lpv_alt; uint32_t* uid_alt;
-    const int32_t* pol_table; const float* pol_ps;   // caller-owned per-product tables of that policy
+    const int32_t* pol_table; const float* pol_ps; const double* pol_ps64;   // caller-owned per-product tables of that policy
     const double* lr_coef_t; const double* lr_intercept; const int32_t* lr_classes; uint32_t lr_n;   // RG_POLICY_LOGREG_FROZEN
     // the policy's act depends on the view history only: it is computed when the history has changed since the last act
     // (lr_dirty, set by history_add) and kept per user; k_logreg_select / k_logreg_acts run before k_advance
@@ -935,7 +935,7 @@ __device__ uint32_t policy_act(const DevSim& d, uint32_t slot, uint32_t user, ui
                                double* ps_out, double u1_hook = 0.0, int* flag_hook = nullptr) {
     if (d.policy == RG_POLICY_LAST_VIEW_TABLE) {
         const uint32_t p = d.lpv[slot];
-        *ps_out = d.pol_ps ? static_cast<double>(d.pol_ps[p]) : 1.0;
+        *ps_out = d.pol_ps64 ? d.pol_ps64[p] : d.pol_ps ? static_cast<double>(d.pol_ps[p]) : 1.0;
         return static_cast<uint32_t>(d.pol_table[p]);
     }
     if (d.policy == RG_POLICY_LOGREG_FROZEN) {

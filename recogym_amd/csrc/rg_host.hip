@@ -1497,6 +1497,17 @@ int rg_sim_set_policy_table(rg_sim* sim, const int32_t* d_action, const float* d
     if (!d_action) return fail(RG_EINVAL, "action table is NULL");
     sim->d.pol_table = d_action;
     sim->d.pol_ps = d_ps;
+    sim->d.pol_ps64 = nullptr;
+    return RG_OK;
+}
+
+int rg_sim_set_policy_table_f64(rg_sim* sim, const int32_t* d_action, const double* d_ps) {
+    if (!sim) return fail(RG_EINVAL, "sim is NULL");
+    if (sim->d.policy != RG_POLICY_LAST_VIEW_TABLE) return fail(RG_ESTATE, "policy is not RG_POLICY_LAST_VIEW_TABLE");
+    if (!d_action) return fail(RG_EINVAL, "action table is NULL");
+    sim->d.pol_table = d_action;
+    sim->d.pol_ps = nullptr;
+    sim->d.pol_ps64 = d_ps;
     return RG_OK;
 }
 

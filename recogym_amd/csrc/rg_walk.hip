@@ -1395,7 +1395,7 @@ __global__ void __launch_bounds__(kBlock, (KH <= 10 ? 3 : 2)) k_walk2(DevSim d_a
                     }
                 } else if (d.policy == RG_POLICY_LAST_VIEW_TABLE) {
                     const uint32_t p = d.lpv[e_slot];
-                    ps = d.pol_ps ? static_cast<double>(d.pol_ps[p]) : 1.0;
+                    ps = d.pol_ps64 ? d.pol_ps64[p] : d.pol_ps ? static_cast<double>(d.pol_ps[p]) : 1.0;
                     a = static_cast<uint32_t>(d.pol_table[p]);
                 } else {        // agent = None / RandomAgent: uniform over P from the env / the agent stream
                     const rg_u32x4 pw = rg_draw(d.policy_seed, user, e_t, 0, RG_DRAW_POLICY);
@@ -1769,7 +1769,7 @@ __global__ void __launch_bounds__(kBlock) k_walk_solo(DevSim d_arg, uint32_t n_w
                     const rg_u32x4 pw = rg_draw(d.policy_seed, user, t, 0, RG_DRAW_POLICY);
                     a = solo_ouc_act(d, hs, rg_uniform(pw.w[2], pw.w[3]), &ps);
                 } else if (d.policy == RG_POLICY_LAST_VIEW_TABLE) {
-                    ps = d.pol_ps ? static_cast<double>(d.pol_ps[lastv]) : 1.0;
+                    ps = d.pol_ps64 ? d.pol_ps64[lastv] : d.pol_ps ? static_cast<double>(d.pol_ps[lastv]) : 1.0;
                     a = static_cast<uint32_t>(d.pol_table[lastv]);
                 } else {
                     const rg_u32x4 pw = rg_draw(d.policy_seed, user, t, 0, RG_DRAW_POLICY);
@@ -1798,7 +1798,7 @@ __global__ void __launch_bounds__(kBlock) k_walk_solo(DevSim d_arg, uint32_t n_w
                     const rg_u32x4 pw = rg_draw(d.policy_seed, user, te, 0, RG_DRAW_POLICY);
                     a = solo_ouc_act(d, hs, rg_uniform(pw.w[2], pw.w[3]), &ps);
                 } else if (d.policy == RG_POLICY_LAST_VIEW_TABLE) {
-                    ps = d.pol_ps ? static_cast<double>(d.pol_ps[lastv]) : 1.0;
+                    ps = d.pol_ps64 ? d.pol_ps64[lastv] : d.pol_ps ? static_cast<double>(d.pol_ps[lastv]) : 1.0;
                     a = static_cast<uint32_t>(d.pol_table[lastv]);
                 } else {
                     const rg_u32x4 pw = rg_draw(d.policy_seed, user, te, 0, RG_DRAW_POLICY);

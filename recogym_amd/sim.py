@@ -85,7 +85,7 @@ class Simulator:
 
     def __init__(self, config, n_users, policy=_abi.RG_POLICY_UNIFORM_ENV, policy_seed=None,
                  ouc=None, epoch=0, log_capacity=None, device=None, tables=None, policy_table=None,
-                 policy_ps=None, logreg=None, ps_float64=None, p_click=False, env0=None):
+                 policy_ps=None, logreg=None, ps_float64=None, p_click=False, env0=None, policy_ps64=False):
         if policy == _abi.RG_POLICY_LOGREG_FROZEN and ((logreg or {}).get('int8') or os.environ.get('RECOGYM_LOGREG') == 'int8'):
             # (refused, not ignored: a caller that labels the act's bytes from this switch would report 1 B per weight for an fp16 run)
             raise ValueError("the 8-bit LogReg screen is retired (measured slower than the fp16 screen): drop logreg['int8'] / RECOGYM_LOGREG=int8")
@@ -134,11 +134,12 @@ class Simulator:
                                                       self._stream()), 'rg_sim_set_tables')
             if policy == _abi.RG_POLICY_LAST_VIEW_TABLE:
                 self.policy_table = torch.as_tensor(np.ascontiguousarray(policy_table, dtype=np.int32)).to(self.device)
+                # policy_ps64: the `ps` table stays float64 on the device (BanditCount's CTR values are not float32 numbers)
                 self.policy_ps = None if policy_ps is None else \
-                    torch.as_tensor(np.ascontiguousarray(policy_ps, dtype=np.float32)).to(self.device)
-                _abi.check(self.lib.rg_sim_set_policy_table(
-                    self._h, self.policy_table.data_ptr(),
-                    None if self.policy_ps is None else self.policy_ps.data_ptr()), 'rg_sim_set_policy_table')
+                    torch.as_tensor(np.ascontiguousarray(policy_ps, dtype=np.float64 if policy_ps64 else np.float32)).to(self.device)
+                set_table = self.lib.rg_sim_set_policy_table_f64 if policy_ps64 else self.lib.rg_sim_set_policy_table
+                _abi.check(set_table(self._h, self.policy_table.data_ptr(),
+                                     None if self.policy_ps is None else self.policy_ps.data_ptr()), 'rg_sim_set_policy_table')
             if policy == _abi.RG_POLICY_LOGREG_FROZEN:
                 # dict(coef_t (P, C) float64 = sklearn coef_.T, intercept (C,), classes (C,))
                 n_fit = int(np.asarray(logreg['classes']).size)
