@@ -36,7 +36,8 @@ extern "C" {
  * options pipe_mode and resident_grid are gone, pipe_groups takes 0 or 1. */
 /* v9 (additive): rg_count_train / rg_count_policy (the OrganicCount and BanditCount agents' tables from a sorted device log) and
  * rg_sim_set_policy_table_f64 (RG_POLICY_LAST_VIEW_TABLE with a float64 `ps` table). */
-#define RG_ABI_VERSION 9
+/* v10 (additive): rg_ope_logreg_workspace_bytes / rg_ope_replay_logreg (the off-policy replay of the frozen LogReg policy). */
+#define RG_ABI_VERSION 10
 
 /* error codes */
 #define RG_OK 0
@@ -407,6 +408,48 @@ size_t rg_ope_workspace_bytes(const rg_ope_policy* pol, uint64_t n_users, uint32
 int rg_ope_replay(const rg_ope_policy* pol, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
                   uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
                   uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Off-policy evaluation of the frozen LogReg policy (LogregFrozenAgent, reference agents/logreg_ips.py:60-87 with
+ * with_ps_all = True): replay a sorted log under a fitted multinomial model.  Stateless (no rg_sim handle).  The model arrays are
+ * device arrays laid out as rg_sim_set_logreg / rg_sim_set_logreg_fp32 take them.  The policy sees the user's cumulative view
+ * counts (all organic rows so far, across sessions).
+ *   select_randomly == 0: pi = [classes[argmax_c (intercept[c] + sum_p views_p coef_t[p][c])] == a] — sklearn's predict() bit for
+ *     bit: fp32 scores from the optional fp32 group decide where their margin certifies the float64 argmax (the step loop's
+ *     certificate), the float64 walk in scipy's summation order everywhere else (first maximum).  An action that is no class of
+ *     the model gets 0.
+ *   select_randomly != 0: pi = softmax(scores)[a] in float64, the step loop's arithmetic (a log it wrote under the same model
+ *     replays to ratios of exactly 1); needs classes[c] == c for c = 0 .. P-1 and P <= 1024.  No policy draw is involved.
+ */
+typedef struct rg_ope_logreg {
+    uint32_t num_products;          /* P <= RG_EV_INDEX_MASK */
+    uint32_t n_classes;             /* C >= 1 */
+    uint32_t select_randomly;
+    uint32_t reserved;
+    const double* coef_t;           /* [P][C] float64, as rg_sim_set_logreg */
+    const double* intercept;        /* [C] */
+    const int32_t* classes;         /* [C] */
+    const float* coef32_t;          /* optional [P][C]; NULL = float64 only */
+    const float* intercept32;       /* [C], with coef32_t */
+    const float* wmax;              /* [P], with coef32_t: >= max_c |coef_t[p][c]| */
+    float bmax;                     /* >= max_c |intercept[c]| */
+    uint32_t reserved2;
+} rg_ope_logreg;
+
+/* rg_ope_logreg_workspace_bytes: device workspace rg_ope_replay_logreg needs for n_users users the longest of which has
+ * max_user_rows rows (0 = error, see rg_last_error).
+ * rg_ope_replay_logreg: rows, offsets, the ps source and the outputs d_ratio / d_click / d_sums as rg_ope_replay.  The log is
+ * validated before any output is written: RG_EINVAL for a user whose first row is a bandit row or that has more than
+ * max_user_rows rows, and for a product or an action >= P (such a row never indexes the model).  RG_EINVAL also for null arrays,
+ * n_classes == 0, a half-given fp32 group, and select_randomly with n_classes != num_products, P > 1024 or classes that are not
+ * 0 .. P-1; RG_ENOMEM for a workspace too small.  Afterwards the workspace's first int64 words hold [0] error bits (0), [1] acts
+ * computed (bandit rows whose user's history changed since its previous act; the rows between reuse it), [2] acts decided by
+ * float64 scores, [3] coef_t rows read.  Synchronises `stream` once (it reads the validation's verdict), twice with
+ * select_randomly (the classes). */
+size_t rg_ope_logreg_workspace_bytes(const rg_ope_logreg* model, uint64_t n_users, uint32_t max_user_rows);
+int rg_ope_replay_logreg(const rg_ope_logreg* model, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                         uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
+                         uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /*
  * The count agents' training (reference agents/organic_count.py:74-82, agents/bandit_count.py:49-62 under the offline protocol

@@ -7,7 +7,7 @@ infrastructure and is never imported from this package.)
 import ctypes as C
 import os
 
-RG_ABI_VERSION = 9
+RG_ABI_VERSION = 10
 
 RG_STATE_ORGANIC, RG_STATE_BANDIT, RG_STATE_STOP = 0, 1, 2
 
@@ -80,6 +80,14 @@ class RgOpePolicy(C.Structure):
                 ('reserved', C.c_uint32), ('ouc_epsilon', C.c_double), ('table', C.c_void_p)]
 
 
+class RgOpeLogreg(C.Structure):
+    """struct rg_ope_logreg: the frozen LogReg model of rg_ope_replay_logreg (device arrays)."""
+    _fields_ = [('num_products', C.c_uint32), ('n_classes', C.c_uint32), ('select_randomly', C.c_uint32), ('reserved', C.c_uint32),
+                ('coef_t', C.c_void_p), ('intercept', C.c_void_p), ('classes', C.c_void_p),
+                ('coef32_t', C.c_void_p), ('intercept32', C.c_void_p), ('wmax', C.c_void_p),
+                ('bmax', C.c_float), ('reserved2', C.c_uint32)]
+
+
 RG_COUNT_ORGANIC, RG_COUNT_BANDIT = 0, 1
 
 
@@ -140,6 +148,10 @@ SYMBOLS = {
     'rg_ope_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpePolicy), C.c_uint64, C.c_uint32]),
     'rg_ope_replay': (C.c_int, [C.POINTER(RgOpePolicy), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
                                 C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rg_ope_logreg_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpeLogreg), C.c_uint64, C.c_uint32]),
+    'rg_ope_replay_logreg': (C.c_int, [C.POINTER(RgOpeLogreg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]),
     'rg_count_workspace_bytes': (C.c_size_t, []),
     'rg_count_train': (C.c_int, [C.POINTER(RgCountTables), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_void_p]),

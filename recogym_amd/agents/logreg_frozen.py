@@ -61,6 +61,19 @@ class LogregFrozenAgent(Agent):
         return dict(policy=_abi.RG_POLICY_LOGREG_FROZEN, policy_seed=0, ouc=None,
                     logreg=dict(coef_t=self.coef_t, intercept=self.intercept, classes=self.classes))
 
+    def ope_policy(self):
+        """The replay form of `ps-a` for off-policy evaluation (evaluate_agent.ope_replay -> rg_ope_replay_logreg), or None
+        (the host loop): the one-hot vector at classes[argmax] or, with select_randomly, predict_proba itself — no policy draw
+        either way.  The softmax form has the step loop's precondition (a class per product, P <= 1024)."""
+        if not getattr(self.config, 'with_ps_all', False) or self.history is not None:
+            return None
+        P = self.config.num_products
+        if self.select_randomly and (P > 1024 or len(self.classes) != P or not np.array_equal(self.classes, np.arange(P))):
+            return None
+        return dict(kind=_abi.RG_POLICY_LOGREG_FROZEN, num_products=int(P), policy_seed=0,
+                    logreg=dict(coef_t=self.coef_t, intercept=self.intercept, classes=self.classes,
+                                select_randomly=self.select_randomly))
+
     def reset(self):
         self.views = np.zeros(self.config.num_products, dtype=np.int64)
         if getattr(self, 'history', None) is not None:

@@ -98,6 +98,9 @@ class LogregMulticlassIpsAgent(Agent):
     def device_policy(self):
         return self._ready().device_policy()
 
+    def ope_policy(self):
+        return self._ready().ope_policy()
+
     def act(self, observation, reward, done):
         return self._ready().act(observation, reward, done)
 

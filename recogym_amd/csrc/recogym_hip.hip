@@ -11,3 +11,4 @@
 #include "rg_draw_lds.hip"
 #include "rg_ope.hip"
 #include "rg_count.hip"
+#include "rg_ope_logreg.hip"

@@ -1,0 +1,517 @@
+// rg_ope_logreg.hip — off-policy evaluation replay of the frozen LogReg policy (LogregFrozenAgent / LogregMulticlassIpsAgent,
+// reference agents/logreg_ips.py:60-87) over a sorted device log: pi(a | the user's views so far) / ps for every bandit row.
+//
+// The skeleton is rg_ope.hip's: one wave per user, users assigned statically (wave w takes users w, w + W, ...), rows in
+// coalesced 64-row chunks, per-wave partial sums and a fixed-order one-block reduction — the same bits on every run, no float
+// atomics.  What differs is the state a user carries and the act:
+//
+// History.  The user's views are a (product, count) list in ASCENDING PRODUCT ORDER (the float64 walk adds the terms of a class
+// in that order, as scipy's CSR x dense product does).  An organic row inserts or increments:
+//   - up to 64 entries: entry i in lane i of two registers; the position is popcount(ballot(entry < p)), the tail moves up one
+//     lane through a shuffle;
+//   - up to 512 entries: a per-wave list in LDS;
+//   - beyond: a per-wave list in global memory of max_user_rows entries (distinct products <= rows).
+// Nothing is dropped (a dropped view is a wrong pi); the views persist across the user's sessions (the reference's feature
+// provider is reset once per user).
+//
+// Act.  Computed only at a bandit row whose history changed since the user's previous act; the bandit rows up to the next
+// organic row reuse it.
+//   argmax form   fp32 scores from the fp32 copy of coef^T (lane = class, four class blocks per pass, history entries
+//                 broadcast), accepted when best - second > 2 (nd + 3) 2^-24 (bmax + sum_p views_p wmax[p]) — k_logreg_acts'
+//                 certificate; otherwise (near-ties, exact ties, no fp32 copy) the float64 walk in scipy's order, first maximum
+//                 = smallest class index among equals (logreg_act_wave's arithmetic).  pi = [classes[argmax] == a].
+//   softmax form  float64 scores in scipy's order, exp(s - max), per-lane partial sums over the classes lane, lane + 64, ...,
+//                 the xor butterfly, e / sum — k_logreg_sample's arithmetic and decomposition, so a log the step loop wrote
+//                 under the same model replays to ratios of exactly 1.  Classes 0 .. P-1, P <= 1024: the scores of a lane's
+//                 (at most 16) classes stay in registers.
+#include "rg_common.hpp"
+
+namespace {
+
+typedef unsigned long long lr_u64;
+
+constexpr int kLrWaves = 4;                      // waves per block
+constexpr uint32_t kLrRegs = 64;                 // entries of the register list
+constexpr uint32_t kLrLds = 512;                 // entries of the per-wave LDS list (4 KiB per wave, 16 KiB per block)
+constexpr uint32_t kLrMaxWaves = 4096;           // 256 CUs x 16 waves
+constexpr uint32_t kLrSoftMax = 1024;            // classes of the softmax form
+constexpr int kLrSoftBlocks = kLrSoftMax / 64;
+constexpr uint32_t kLrNone = 0xFFFFFFFFu;
+constexpr uint32_t kLrFp32MaxTerms = 1u << 16;   // longer histories go to the float64 walk
+
+constexpr lr_u64 kLrErrFirstBandit = 1, kLrErrIndex = 2, kLrErrRows = 4;
+constexpr int kLrWsErr = 0, kLrWsActs = 1, kLrWsExact = 2, kLrWsRowsRead = 3, kLrWsWords = 32;
+
+uint32_t lr_waves(uint64_t n_users) {
+    const uint64_t w = (n_users + kLrWaves - 1) / kLrWaves * kLrWaves;
+    return static_cast<uint32_t>(w < kLrWaves ? kLrWaves : (w > kLrMaxWaves ? kLrMaxWaves : w));
+}
+// entries of a wave's global list (0: no user can outgrow the LDS list)
+uint32_t lr_global_cap(uint32_t max_user_rows) { return max_user_rows > kLrLds ? max_user_rows : 0u; }
+size_t lr_slot_bytes(uint32_t n_waves) { return (static_cast<size_t>(n_waves) * 3 * sizeof(double) + 255) & ~size_t(255); }
+size_t lr_head_bytes() { return kLrWsWords * sizeof(lr_u64); }
+
+__device__ __forceinline__ lr_u64 lr_below(uint32_t lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }
+__device__ __forceinline__ uint32_t lr_lane_value(uint32_t x, uint32_t lane) {
+    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), static_cast<int>(lane)));
+}
+__device__ __forceinline__ uint32_t lr_uniform(uint32_t x) {
+    return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(x)));
+}
+__device__ __forceinline__ double lr_wave_sum(double x) {
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+__device__ __forceinline__ double lr_wave_max(double x) {
+    for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o));
+    return x;
+}
+
+// what one lane wrote to a list is read by the others: LDS within the workgroup's scope; the global list through the agent's
+// (the wave's own stores complete and its L1 lines are dropped before the next read)
+template <bool kLds>
+__device__ __forceinline__ void lr_sync() {
+    if (kLds) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// one view of product p into the sorted list (lp, lc)[0 .. n); false = the list is full (nothing written)
+template <bool kLds>
+__device__ __forceinline__ bool lr_list_add(uint32_t* lp, uint32_t* lc, uint32_t& n, uint32_t cap, uint32_t p, uint32_t lane) {
+    uint32_t pos = 0, found = kLrNone;
+    for (uint32_t j0 = 0; j0 < n; j0 += 64) {
+        const uint32_t j = j0 + lane;
+        const uint32_t v = j < n ? lp[j] : kLrNone;                   // (p < 2^29: never the filler)
+        const lr_u64 hit = __ballot(v == p);
+        if (hit) { found = j0 + static_cast<uint32_t>(__builtin_ctzll(hit)); break; }
+        const uint32_t less = static_cast<uint32_t>(__popcll(__ballot(v < p)));
+        pos += less;
+        if (less < 64) break;                                         // ascending: nothing smaller beyond
+    }
+    if (found != kLrNone) {
+        if (lane == 0) lc[found] += 1;
+        lr_sync<kLds>();
+        return true;
+    }
+    if (n >= cap) return false;
+    // entries pos .. n-1 move up one place, 64 at a time from the top (a chunk is read whole before it is written)
+    for (uint32_t hi = n; hi > pos; hi = hi - pos > 64 ? hi - 64 : pos) {
+        const bool on = lane < hi - pos;
+        const uint32_t j = hi - 1 - lane;
+        uint32_t vp = 0, vc = 0;
+        if (on) { vp = lp[j]; vc = lc[j]; }
+        lr_sync<kLds>();
+        if (on) { lp[j + 1] = vp; lc[j + 1] = vc; }
+        lr_sync<kLds>();
+    }
+    if (lane == 0) { lp[pos] = p; lc[pos] = 1; }
+    lr_sync<kLds>();
+    n += 1;
+    return true;
+}
+
+// entry i of the history, wave-uniform (T = 0: registers, 1: LDS, 2: global)
+template <int T>
+struct LrHist {
+    uint32_t hp, hc;
+    const uint32_t* lp;
+    const uint32_t* lc;
+    __device__ __forceinline__ void get(uint32_t i, uint32_t& p, uint32_t& c) const {
+        if (T == 0) { p = lr_lane_value(hp, i); c = lr_lane_value(hc, i); }
+        else { p = lr_uniform(lp[i]); c = lr_uniform(lc[i]); }
+    }
+};
+
+// fp32 scores and k_logreg_acts' margin certificate: true = class index *best_out IS the float64 argmax
+template <int T>
+__device__ __forceinline__ bool lr_fp32(const rg_ope_logreg& m, const LrHist<T>& h, uint32_t nd, uint32_t lane, uint32_t* best_out) {
+    const uint32_t C = m.n_classes;
+    float Ahat = m.bmax;
+    for (uint32_t i = 0; i < nd; ++i) {
+        uint32_t p, c;
+        h.get(i, p, c);
+        Ahat = fmaf(static_cast<float>(c), m.wmax[p], Ahat);
+    }
+    float best = -INFINITY, second = -INFINITY;
+    uint32_t best_c = 0;
+    for (uint32_t c0 = 0; c0 < C; c0 += 256) {
+        float sc[4];
+        uint32_t cc[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            cc[q] = min(c0 + 64u * q + lane, C - 1);                  // clamped: masked below
+            sc[q] = m.intercept32[cc[q]];
+        }
+        for (uint32_t i = 0; i < nd; ++i) {
+            uint32_t p, c;
+            h.get(i, p, c);
+            const float cnt = static_cast<float>(c);
+            const float* row = m.coef32_t + static_cast<size_t>(p) * C;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) sc[q] = fmaf(cnt, row[cc[q]], sc[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t c = c0 + 64u * q + lane;
+            if (c < C) {
+                if (sc[q] > best) { second = best; best = sc[q]; best_c = c; }
+                else if (sc[q] > second) second = sc[q];
+            }
+        }
+    }
+    // wave top-2 over disjoint class sets (equal best scores leave a margin of 0: not certified)
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o), os = __shfl_xor(second, o);
+        const uint32_t oc = __shfl_xor(best_c, o);
+        const float ns = fmaxf(fminf(best, ob), fmaxf(second, os));
+        if (ob > best) best_c = oc;
+        best = fmaxf(best, ob);
+        second = ns;
+    }
+    const float bound = static_cast<float>(nd + 3) * 5.9604644775390625e-08f * Ahat * 1.01f;
+    *best_out = best_c;
+    return C == 1 || best - second > 2.0f * bound;
+}
+
+// the float64 walk: per class the viewed products ascending, multiply then add, intercept last; first maximum
+template <int T>
+__device__ __forceinline__ uint32_t lr_walk(const rg_ope_logreg& m, const LrHist<T>& h, uint32_t nd, uint32_t lane) {
+    const uint32_t C = m.n_classes;
+    double best_s = -INFINITY;
+    uint32_t best_c = kLrNone;
+    for (uint32_t c0 = 0; c0 < C; c0 += 256) {
+        double sc[4] = {0.0, 0.0, 0.0, 0.0};
+        uint32_t cc[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) cc[q] = min(c0 + 64u * q + lane, C - 1);
+        for (uint32_t i0 = 0; i0 < nd; i0 += 4) {
+            double w[4][4], cnt[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                uint32_t p, c;
+                h.get(min(i0 + e, nd - 1), p, c);
+                cnt[e] = static_cast<double>(c);
+                const double* row = m.coef_t + static_cast<size_t>(p) * C;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) w[e][q] = row[cc[q]];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (i0 + e < nd) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) sc[q] = __dadd_rn(sc[q], __dmul_rn(cnt[e], w[e][q]));
+                }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t c = c0 + 64u * q + lane;
+            if (c < C) {
+                const double v = __dadd_rn(sc[q], m.intercept[c]);
+                if (best_c == kLrNone || v > best_s) { best_s = v; best_c = c; }
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double os = __shfl_xor(best_s, o);
+        const uint32_t oc = __shfl_xor(best_c, o);
+        if (oc != kLrNone && (best_c == kLrNone || os > best_s || (os == best_s && oc < best_c))) { best_s = os; best_c = oc; }
+    }
+    return best_c;
+}
+
+// softmax numerators e[j] = exp(s - max) of the classes 64 j + lane and their sum (k_logreg_sample's arithmetic)
+template <int T>
+__device__ __forceinline__ void lr_soft(const rg_ope_logreg& m, const LrHist<T>& h, uint32_t nd, uint32_t lane,
+                                        double (&ev)[kLrSoftBlocks], double& esum) {
+    const uint32_t C = m.n_classes;
+    double mx = -INFINITY;
+#pragma unroll
+    for (int g = 0; g < kLrSoftBlocks / 4; ++g) {
+        double sc[4] = {0.0, 0.0, 0.0, 0.0};
+        if (256u * g < C) {
+            uint32_t cc[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) cc[q] = min(256u * g + 64u * q + lane, C - 1);
+            for (uint32_t i = 0; i < nd; ++i) {
+                uint32_t p, c;
+                h.get(i, p, c);
+                const double cnt = static_cast<double>(c);
+                const double* row = m.coef_t + static_cast<size_t>(p) * C;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) sc[q] = __dadd_rn(sc[q], __dmul_rn(cnt, row[cc[q]]));
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t c = 256u * g + 64u * q + lane;
+            double s = 0.0;
+            if (c < C) { s = __dadd_rn(sc[q], m.intercept[c]); mx = fmax(mx, s); }
+            ev[4 * g + q] = s;
+        }
+    }
+    mx = lr_wave_max(mx);
+    double sum = 0.0;
+#pragma unroll
+    for (int j = 0; j < kLrSoftBlocks; ++j) {
+        const uint32_t c = 64u * j + lane;
+        if (c < C) { const double e = exp(ev[j] - mx); ev[j] = e; sum += e; }
+    }
+    esum = lr_wave_sum(sum);
+}
+
+__global__ void k_lr_init(lr_u64* __restrict__ ws) {
+    if (threadIdx.x < kLrWsWords) ws[threadIdx.x] = 0;
+}
+
+// every user opens with an organic row and has at most max_user_rows rows; every product and action is < P
+__global__ __launch_bounds__(256) void k_lr_check(const rg_event* __restrict__ rows, const int64_t* __restrict__ offsets,
+                                                  uint64_t n_users, uint32_t P, uint32_t max_user_rows, lr_u64* __restrict__ ws) {
+    lr_u64 err = 0;
+    for (uint64_t u = blockIdx.x * 256ull + threadIdx.x; u < n_users; u += gridDim.x * 256ull) {
+        const int64_t b = offsets[u], e = offsets[u + 1];
+        if (e < b || e - b > static_cast<int64_t>(max_user_rows)) err |= kLrErrRows;
+        else if (b < e && (rows[b].code & RG_EV_BANDIT)) err |= kLrErrFirstBandit;
+    }
+    const int64_t r0 = offsets[0], r1 = offsets[n_users];
+    for (int64_t r = r0 + blockIdx.x * 256ll + threadIdx.x; r < r1; r += gridDim.x * 256ll)
+        if ((rows[r].code & RG_EV_INDEX_MASK) >= P) err |= kLrErrIndex;
+    if (err) (void)__hip_atomic_fetch_or(&ws[kLrWsErr], err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <bool kSoft>
+__global__ __launch_bounds__(64 * kLrWaves, kSoft ? 2 : 4) void k_ope_logreg(
+    rg_ope_logreg m, const rg_event* __restrict__ rows, const int64_t* __restrict__ offsets, uint64_t n_users, uint32_t ps_mode,
+    const double* __restrict__ ps64, double ps_const, double* __restrict__ ratio, uint8_t* __restrict__ click,
+    double* __restrict__ slots, uint32_t* __restrict__ gscr, uint32_t g_cap, lr_u64* __restrict__ ws, uint32_t n_waves) {
+    __shared__ uint32_t s_p[kLrWaves][kLrLds];
+    __shared__ uint32_t s_c[kLrWaves][kLrLds];
+    const uint32_t lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    const uint32_t wave = blockIdx.x * kLrWaves + wib;
+    uint32_t* const lp = s_p[wib];
+    uint32_t* const lc = s_c[wib];
+    uint32_t* const gp = g_cap ? gscr + static_cast<size_t>(wave) * 2 * g_cap : nullptr;
+    uint32_t* const gc = gp + g_cap;
+    const uint32_t P = m.num_products;
+    double acc_n = 0.0, acc_cr = 0.0, acc_r = 0.0;
+    lr_u64 c_acts = 0, c_exact = 0, c_rows = 0, err = 0;
+
+    for (uint64_t user = wave; user < n_users; user += n_waves) {
+        const int64_t b = offsets[user], e = offsets[user + 1];
+        uint32_t hp = kLrNone, hc = 0, n = 0, tier = 0;
+        bool dirty = true;
+        uint32_t act_class = kLrNone;                 // argmax form: classes[argmax]
+        double ev[kLrSoftBlocks], esum = 1.0;         // softmax form
+#pragma unroll
+        for (int j = 0; j < kLrSoftBlocks; ++j) ev[j] = 0.0;
+
+        for (int64_t base = b; base < e; base += 64) {
+            const int64_t row = base + lane;
+            const bool live = row < e;
+            uint4 x = make_uint4(0u, 0u, 0u, 0u);
+            if (live) x = reinterpret_cast<const uint4*>(rows)[row];
+            const uint32_t idx = x.z & RG_EV_INDEX_MASK;
+            const bool ok = live && idx < P;          // (the validation pass has refused such a log: never index the model)
+            const bool isb = ok && (x.z & RG_EV_BANDIT);
+            const bool iso = ok && !(x.z & RG_EV_BANDIT);
+            const lr_u64 omask = __ballot(iso), bmask = __ballot(isb);
+            double pi = 0.0;
+            lr_u64 rem = omask | bmask;
+            while (rem) {
+                const uint32_t k = static_cast<uint32_t>(__builtin_ctzll(rem));
+                if ((omask >> k) & 1) {
+                    const uint32_t p = lr_lane_value(idx, k);
+                    bool done = false;
+                    if (tier == 0) {
+                        const lr_u64 hit = __ballot(lane < n && hp == p);
+                        if (hit) {
+                            if (lane == static_cast<uint32_t>(__builtin_ctzll(hit))) hc += 1;
+                            done = true;
+                        } else if (n < kLrRegs) {
+                            const uint32_t pos = static_cast<uint32_t>(__popcll(__ballot(lane < n && hp < p)));
+                            const uint32_t up_p = static_cast<uint32_t>(__shfl_up(static_cast<int>(hp), 1));
+                            const uint32_t up_c = static_cast<uint32_t>(__shfl_up(static_cast<int>(hc), 1));
+                            if (lane > pos && lane <= n) { hp = up_p; hc = up_c; }
+                            if (lane == pos) { hp = p; hc = 1; }
+                            n += 1;
+                            done = true;
+                        } else {
+                            lp[lane] = hp; lc[lane] = hc;             // the 65th product: on to the LDS list
+                            lr_sync<true>();
+                            tier = 1;
+                        }
+                    }
+                    if (!done && tier == 1) {
+                        if (n < kLrLds || !gp) {
+                            done = true;
+                            if (!lr_list_add<true>(lp, lc, n, kLrLds, p, lane)) err |= kLrErrRows;
+                        } else {
+                            for (uint32_t j = lane; j < n; j += 64) { gp[j] = lp[j]; gc[j] = lc[j]; }   // on to the global list
+                            lr_sync<false>();
+                            tier = 2;
+                        }
+                    }
+                    if (!done && !lr_list_add<false>(gp, gc, n, g_cap, p, lane)) err |= kLrErrRows;
+                    dirty = true;
+                    rem &= rem - 1;
+                    continue;
+                }
+                if (dirty) {
+                    auto act = [&](auto hist) __attribute__((always_inline)) {
+                        if (kSoft) {
+                            lr_soft(m, hist, n, lane, ev, esum);
+                            c_exact += 1;
+                        } else {
+                            uint32_t bc = 0;
+                            // (the certificate's rounding-up factor covers (nd + 3) 2^-24 << 1)
+                            if (!(m.coef32_t && n <= kLrFp32MaxTerms && lr_fp32(m, hist, n, lane, &bc))) { bc = lr_walk(m, hist, n, lane); c_exact += 1; }
+                            act_class = static_cast<uint32_t>(m.classes[bc]);
+                        }
+                    };
+                    if (tier == 0) act(LrHist<0>{hp, hc, nullptr, nullptr});
+                    else if (tier == 1) act(LrHist<1>{0u, 0u, lp, lc});
+                    else act(LrHist<2>{0u, 0u, gp, gc});
+                    c_acts += 1;
+                    c_rows += n;
+                    dirty = false;
+                }
+                // the bandit rows up to the next organic row share this act
+                const lr_u64 next_o = omask & ~lr_below(k);
+                const uint32_t end = next_o ? static_cast<uint32_t>(__builtin_ctzll(next_o)) : 64u;
+                const bool mine = isb && lane >= k && lane < end;
+                if (kSoft) {
+                    const uint32_t al = idx & 63, aq = idx >> 6;      // idx < P <= 1024
+                    double v = 0.0;
+#pragma unroll
+                    for (int j = 0; j < kLrSoftBlocks; ++j) {
+                        if (64u * j < P) {
+                            const double t = __shfl(ev[j], static_cast<int>(al));
+                            if (aq == static_cast<uint32_t>(j)) v = t;
+                        }
+                    }
+                    if (mine) pi = v / esum;
+                } else if (mine) {
+                    pi = act_class == idx ? 1.0 : 0.0;
+                }
+                rem &= end < 64 ? ~lr_below(end) : 0ull;
+            }
+            if (isb) {
+                const double ps = ps_mode == RG_OPE_PS_ARRAY ? ps64[row]
+                                  : ps_mode == RG_OPE_PS_CONST ? ps_const : static_cast<double>(__uint_as_float(x.w));
+                const double r = pi / ps;
+                ratio[row] = r;
+                if (click) click[row] = (x.z & RG_EV_CLICK) ? 1 : 0;
+                acc_n += 1.0;
+                acc_cr += ((x.z & RG_EV_CLICK) ? 1.0 : 0.0) * r;
+                acc_r += r;
+            }
+        }
+    }
+    acc_n = lr_wave_sum(acc_n);
+    acc_cr = lr_wave_sum(acc_cr);
+    acc_r = lr_wave_sum(acc_r);
+    if (lane == 0) {
+        slots[3 * static_cast<size_t>(wave) + 0] = acc_n;
+        slots[3 * static_cast<size_t>(wave) + 1] = acc_cr;
+        slots[3 * static_cast<size_t>(wave) + 2] = acc_r;
+        if (c_acts) {
+            (void)__hip_atomic_fetch_add(&ws[kLrWsActs], c_acts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            (void)__hip_atomic_fetch_add(&ws[kLrWsRowsRead], c_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (c_exact) (void)__hip_atomic_fetch_add(&ws[kLrWsExact], c_exact, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (err) (void)__hip_atomic_fetch_or(&ws[kLrWsErr], err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// the per-wave slots -> (n, sum c r, sum r), one block, fixed order (k_ope_reduce's scheme)
+__global__ __launch_bounds__(256) void k_lr_reduce(const double* __restrict__ slots, uint32_t n_waves, double* __restrict__ out) {
+    __shared__ double sh[3][256];
+    double a[3] = {0.0, 0.0, 0.0};
+    for (uint32_t i = threadIdx.x; i < n_waves; i += 256)
+        for (int j = 0; j < 3; ++j) a[j] += slots[3 * static_cast<size_t>(i) + j];
+    for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] = a[j];
+    __syncthreads();
+    for (uint32_t s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s)
+            for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        for (int j = 0; j < 3; ++j) out[j] = sh[j][0];
+}
+
+int lr_model_ok(const rg_ope_logreg* m, const char* who) {
+    if (!m) return fail(RG_EINVAL, "%s: null model", who);
+    if (m->num_products == 0 || m->num_products > RG_EV_INDEX_MASK) return fail(RG_EINVAL, "%s: bad num_products %u", who, m->num_products);
+    if (m->n_classes == 0) return fail(RG_EINVAL, "%s: n_classes == 0", who);
+    if (!m->coef_t || !m->intercept || !m->classes) return fail(RG_EINVAL, "%s: null coef_t / intercept / classes", who);
+    const int n32 = (m->coef32_t != nullptr) + (m->intercept32 != nullptr) + (m->wmax != nullptr);
+    if (n32 != 0 && n32 != 3) return fail(RG_EINVAL, "%s: coef32_t, intercept32 and wmax come together", who);
+    if (m->select_randomly && (m->n_classes != m->num_products || m->num_products > kLrSoftMax))
+        return fail(RG_EINVAL, "%s: select_randomly needs the classes 0 .. P-1 and P <= %u (P = %u, %u classes)", who, kLrSoftMax,
+                    m->num_products, m->n_classes);
+    return RG_OK;
+}
+
+}  // namespace
+
+extern "C" size_t rg_ope_logreg_workspace_bytes(const rg_ope_logreg* m, uint64_t n_users, uint32_t max_user_rows) {
+    if (!m) { fail(RG_EINVAL, "rg_ope_logreg_workspace_bytes: null model"); return 0; }
+    const uint32_t W = lr_waves(n_users);
+    return lr_head_bytes() + lr_slot_bytes(W) + static_cast<size_t>(W) * 2 * lr_global_cap(max_user_rows) * sizeof(uint32_t);
+}
+
+extern "C" int rg_ope_replay_logreg(const rg_ope_logreg* m, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                                    uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
+                                    uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = lr_model_ok(m, "rg_ope_replay_logreg")) return rc;
+    if (ps_mode > RG_OPE_PS_ROW || (ps_mode == RG_OPE_PS_ARRAY && !d_ps && n_users))
+        return fail(RG_EINVAL, "rg_ope_replay_logreg: bad ps source");
+    if (n_users && (!d_rows || !d_offsets || !d_ratio)) return fail(RG_EINVAL, "rg_ope_replay_logreg: null rows / offsets / ratio");
+    if (!d_sums || !d_workspace) return fail(RG_EINVAL, "rg_ope_replay_logreg: null sums / workspace");
+    const size_t need = rg_ope_logreg_workspace_bytes(m, n_users, max_user_rows);
+    if (workspace_bytes < need) return fail(RG_ENOMEM, "rg_ope_replay_logreg: workspace %zu < %zu bytes", workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(d_rows) % 16) return fail(RG_EINVAL, "rg_ope_replay_logreg: rows not 16-byte aligned");
+    if (rg_device_count() <= 0) return fail(RG_ENODEV, "no HIP device");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (m->select_randomly) {
+        static_assert(kLrSoftMax <= 1024, "the class check reads them into a stack array");
+        int32_t cls[kLrSoftMax];
+        HIP_TRY(hipMemcpyAsync(cls, m->classes, m->n_classes * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint32_t c = 0; c < m->n_classes; ++c)
+            if (cls[c] != static_cast<int32_t>(c))
+                return fail(RG_EINVAL, "rg_ope_replay_logreg: select_randomly needs classes[c] == c (classes[%u] = %d)", c, cls[c]);
+    }
+    const uint32_t W = lr_waves(n_users);
+    const uint32_t g_cap = lr_global_cap(max_user_rows);
+    lr_u64* ws = static_cast<lr_u64*>(d_workspace);
+    double* slots = reinterpret_cast<double*>(static_cast<char*>(d_workspace) + lr_head_bytes());
+    uint32_t* gscr = g_cap ? reinterpret_cast<uint32_t*>(static_cast<char*>(d_workspace) + lr_head_bytes() + lr_slot_bytes(W)) : nullptr;
+    hipLaunchKernelGGL(k_lr_init, dim3(1), dim3(64), 0, s, ws);
+    HIP_TRY(hipGetLastError());
+    if (n_users) {
+        const uint32_t check_blocks = static_cast<uint32_t>(n_users / 256 + 1 > 2048 ? 2048 : n_users / 256 + 1);
+        hipLaunchKernelGGL(k_lr_check, dim3(check_blocks), dim3(256), 0, s, d_rows, d_offsets, n_users, m->num_products, max_user_rows, ws);
+        HIP_TRY(hipGetLastError());
+        lr_u64 verdict = 0;
+        HIP_TRY(hipMemcpyAsync(&verdict, ws + kLrWsErr, sizeof(verdict), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (verdict & kLrErrRows)
+            return fail(RG_EINVAL, "rg_ope_replay_logreg: a user has more than max_user_rows = %u rows (or its offsets descend); nothing was written", max_user_rows);
+        if (verdict & kLrErrFirstBandit)
+            return fail(RG_EINVAL, "rg_ope_replay_logreg: a user opens with a bandit row; nothing was written");
+        if (verdict & kLrErrIndex)
+            return fail(RG_EINVAL, "rg_ope_replay_logreg: the log has a product or an action >= num_products %u; nothing was written", m->num_products);
+    }
+    if (m->select_randomly)
+        hipLaunchKernelGGL(k_ope_logreg<true>, dim3(W / kLrWaves), dim3(64 * kLrWaves), 0, s, *m, d_rows, d_offsets, n_users, ps_mode,
+                           d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W);
+    else
+        hipLaunchKernelGGL(k_ope_logreg<false>, dim3(W / kLrWaves), dim3(64 * kLrWaves), 0, s, *m, d_rows, d_offsets, n_users, ps_mode,
+                           d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, s, slots, W, d_sums);
+    HIP_TRY(hipGetLastError());
+    return RG_OK;
+}

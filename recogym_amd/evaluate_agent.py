@@ -11,8 +11,9 @@ verify_agents_IPS, verify_agents_SNIPS, evaluate_recall_at_k, verify_agents_reca
 Simulator.device_log().  Users 0 .. max(u) - 1 are evaluated (the reference's range(max(reco_log.u)):
 the user with the largest id is not), each user's rows in frame order.  Where a HIP device is present,
 the agent has a replay form (ope_policy_of) and the log qualifies, the rows are replayed on the device
-by rg_ope_replay; otherwise the host loop below runs: the reference's loop made linear (one stable
-group-by instead of six frame filters per user), the same act() calls in the same order."""
+by rg_ope_replay (the frozen LogReg policy: by rg_ope_replay_logreg); otherwise the host loop below runs:
+the reference's loop made linear (one stable group-by instead of six frame filters per user), the same
+act() calls in the same order."""
 import ctypes as C
 from copy import deepcopy
 
@@ -109,7 +110,7 @@ def _host_snips(agent, reco_log):
 # the device replay
 # ------------------------------------------------------------------------------------------------
 def ope_policy_of(agent):
-    """-> dict(kind, num_products, policy_seed, ouc, table) when the agent's `ps-a` has a replay form on the device, else None.
+    """-> dict(kind, num_products, policy_seed, ouc | table | logreg) when the agent's `ps-a` has a replay form on the device, else None.
     This package's agents say so themselves (ope_policy()); the reference's own classes are duck-typed where pi does not
     depend on their MT stream: RandomAgent, and OrganicUserEventCounterAgent unless exploit_explore with epsilon > 0."""
     if hasattr(agent, 'ope_policy'):
@@ -200,11 +201,37 @@ def _masked(x, mask, step=1 << 24):
     return torch.cat([x[i:i + step][mask[i:i + step]] for i in range(0, x.shape[0], step)]) if x.shape[0] else x[:0]
 
 
-def ope_replay(agent, dl, pol=None, n_users=None):
+def _logreg_model(lr, num_products, device):
+    """A policy dict's `logreg` entry -> (RgOpeLogreg, the device tensors it points into): the model moved to the log's device,
+    with the fp32 copy and the certificate's bounds the step loop uses (sim.logreg_fp32) for the argmax form."""
+    import torch
+    from .sim import logreg_fp32
+    def put(x, np_type, t_type):            # (arrays that already are tensors, e.g. on the device, are taken as they are)
+        if torch.is_tensor(x):
+            return x.to(device=device, dtype=t_type).contiguous()
+        return torch.as_tensor(np.ascontiguousarray(x, dtype=np_type)).to(device)
+    coef_t = put(lr['coef_t'], np.float64, torch.float64)
+    intercept = put(lr['intercept'], np.float64, torch.float64)
+    classes = put(lr['classes'], np.int32, torch.int32)
+    assert coef_t.shape == (num_products, classes.numel()) and intercept.shape == (classes.numel(),)
+    keep = [coef_t, intercept, classes]
+    sr = bool(lr.get('select_randomly'))
+    m = _abi.RgOpeLogreg(num_products=int(num_products), n_classes=int(classes.numel()), select_randomly=int(sr), reserved=0,
+                         coef_t=coef_t.data_ptr(), intercept=intercept.data_ptr(), classes=classes.data_ptr(),
+                         coef32_t=None, intercept32=None, wmax=None, bmax=0.0, reserved2=0)
+    if not sr and lr.get('fp32', True):
+        w32, b32, wmax, bmax = logreg_fp32(coef_t, intercept)
+        keep += [w32, b32, wmax]
+        m.coef32_t, m.intercept32, m.wmax, m.bmax = w32.data_ptr(), b32.data_ptr(), wmax.data_ptr(), bmax
+    return m, keep
+
+
+def ope_replay(agent, dl, pol=None, n_users=None, stats=None):
     """Replay a DeviceLog under `agent` on the device -> (ratio r = pi[a] / ps, click c as float64, sums) for the bandit rows of
     the log's first `n_users` users (default: all but the last, whose id is max(u)), in log order (device tensors);
     sums = float64 tensor (n, sum c r, sum r).  None where the agent has no replay form or the log does not qualify (a user
-    that opens with a bandit row; a float clock under a policy that draws)."""
+    that opens with a bandit row; a float clock under a policy that draws).  `stats` (a dict, frozen LogReg policies only)
+    receives rg_ope_replay_logreg's workspace words: error, acts, exact (acts decided by float64 scores), rows_read."""
     import torch
     pol = ope_policy_of(agent) if pol is None else pol
     if pol is None or int(pol['num_products']) != int(dl.num_products):
@@ -221,20 +248,26 @@ def ope_replay(agent, dl, pol=None, n_users=None):
             return None
     max_rows = int(lens.max().item()) if n_eval else 0
     lib = _abi.load()
-    o = pol.get('ouc') or {}
-    table = pol.get('table')
-    table_t = None if table is None else torch.as_tensor(np.ascontiguousarray(table, dtype=np.int32)).to(device)
-    cp = _abi.RgOpePolicy(kind=int(pol['kind']), num_products=int(pol['num_products']),
-                          policy_seed=int(pol.get('policy_seed') or 0) & 0xFFFFFFFFFFFFFFFF,
-                          ouc_select_randomly=int(bool(o.get('select_randomly', True))),
-                          ouc_exploit_explore=int(bool(o.get('exploit_explore', True))),
-                          ouc_reverse_pop=int(bool(o.get('reverse_pop', False))), reserved=0,
-                          ouc_epsilon=float(o.get('epsilon', 0.0)),
-                          table=None if table_t is None else table_t.data_ptr())
+    if pol.get('logreg') is not None:
+        # the frozen LogReg policy has an entry point of its own; the model moves to the log's device once per call
+        cp, keep = _logreg_model(pol['logreg'], int(pol['num_products']), device)
+        size_fn, replay_fn, what = lib.rg_ope_logreg_workspace_bytes, lib.rg_ope_replay_logreg, 'rg_ope_replay_logreg'
+    else:
+        o = pol.get('ouc') or {}
+        table = pol.get('table')
+        keep = None if table is None else torch.as_tensor(np.ascontiguousarray(table, dtype=np.int32)).to(device)
+        cp = _abi.RgOpePolicy(kind=int(pol['kind']), num_products=int(pol['num_products']),
+                              policy_seed=int(pol.get('policy_seed') or 0) & 0xFFFFFFFFFFFFFFFF,
+                              ouc_select_randomly=int(bool(o.get('select_randomly', True))),
+                              ouc_exploit_explore=int(bool(o.get('exploit_explore', True))),
+                              ouc_reverse_pop=int(bool(o.get('reverse_pop', False))), reserved=0,
+                              ouc_epsilon=float(o.get('epsilon', 0.0)),
+                              table=None if keep is None else keep.data_ptr())
+        size_fn, replay_fn, what = lib.rg_ope_workspace_bytes, lib.rg_ope_replay, 'rg_ope_replay'
     with torch.cuda.device(device):
-        need = lib.rg_ope_workspace_bytes(C.byref(cp), n_eval, max_rows)
+        need = size_fn(C.byref(cp), n_eval, max_rows)
         if need == 0:
-            raise _abi.RecoGymHipError('rg_ope_workspace_bytes: ' + lib.rg_last_error().decode())
+            raise _abi.RecoGymHipError(what + ' workspace: ' + lib.rg_last_error().decode())
         ws = torch.empty(need, dtype=torch.uint8, device=device)
         total = int(offsets[-1].item()) if n_eval else 0
         ratio = torch.empty(max(total, 1), dtype=torch.float64, device=device)
@@ -247,9 +280,11 @@ def ope_replay(agent, dl, pol=None, n_users=None):
         else:
             mode, ps_ptr, ps_const = _abi.RG_OPE_PS_ARRAY, ps.data_ptr(), 0.0
         stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _abi.check(lib.rg_ope_replay(C.byref(cp), dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows, mode, ps_ptr,
-                                     ps_const, ratio.data_ptr(), None, sums.data_ptr(), ws.data_ptr(), need, stream),
-                   'rg_ope_replay')
+        _abi.check(replay_fn(C.byref(cp), dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows, mode, ps_ptr,
+                             ps_const, ratio.data_ptr(), None, sums.data_ptr(), ws.data_ptr(), need, stream), what)
+        if stats is not None and pol.get('logreg') is not None:
+            words = ws[:32].view(torch.int64).cpu().numpy()
+            stats.update(error=int(words[0]), acts=int(words[1]), exact=int(words[2]), rows_read=int(words[3]))
         code = dl.rows[:total, 2]
         is_b = (code & _abi.RG_EV_BANDIT) != 0
         r = _masked(ratio[:total], is_b)

@@ -70,6 +70,17 @@ def decode_rows(raw, uniform_ps=None, ps64=None, p_click=None):
     return out
 
 
+def logreg_fp32(coef_t, intercept):
+    """float64 device tensors coef_t (P, C) / intercept (C,) -> (coef32_t, intercept32, wmax, bmax): the fp32 copies of the
+    certified fast scores and the bounds of their margin certificate, wmax[p] >= max_c |coef_t[p][c]| and bmax >= max_c
+    |intercept[c]|, rounded up (the step loop's k_logreg_acts and the replay's k_ope_logreg share them)."""
+    w32 = coef_t.to(torch.float32)
+    b32 = intercept.to(torch.float32)
+    wmax = (coef_t.abs().amax(dim=1) * (1.0 + 1e-6)).to(torch.float32) * (1.0 + 1e-6)
+    bmax = float(intercept.abs().max().item()) * (1.0 + 1e-6)
+    return w32.contiguous(), b32.contiguous(), wmax.contiguous(), bmax
+
+
 class Simulator:
     """N concurrent users of one reco-gym-v1 environment on one GPU.
 
@@ -161,11 +172,8 @@ class Simulator:
                            'rg_sim_set_logreg')
                 if logreg.get('fp32', True) and not logreg.get('select_randomly'):
                     # fp32 copies for the certified fast scores (the float64 arrays stay the arbiter); bounds rounded up
-                    w32 = self.logreg[0].to(torch.float32)
-                    b32 = self.logreg[1].to(torch.float32)
-                    wmax = (self.logreg[0].abs().amax(dim=1) * (1.0 + 1e-6)).to(torch.float32) * (1.0 + 1e-6)
-                    bmax = float(self.logreg[1].abs().max().item()) * (1.0 + 1e-6)
-                    self.logreg32 = (w32.contiguous(), b32.contiguous(), wmax.contiguous())
+                    *self.logreg32, bmax = logreg_fp32(self.logreg[0], self.logreg[1])
+                    self.logreg32 = tuple(self.logreg32)
                     _abi.check(self.lib.rg_sim_set_logreg_fp32(self._h, self.logreg32[0].data_ptr(), self.logreg32[1].data_ptr(),
                                                                self.logreg32[2].data_ptr(), C.c_float(bmax)), 'rg_sim_set_logreg_fp32')
                     # screening pass from a half copy of coef^T (half the row bytes; float64 decides among the candidates):
