@@ -37,7 +37,10 @@ extern "C" {
 /* v9 (additive): rg_count_train / rg_count_policy (the OrganicCount and BanditCount agents' tables from a sorted device log) and
  * rg_sim_set_policy_table_f64 (RG_POLICY_LAST_VIEW_TABLE with a float64 `ps` table). */
 /* v10 (additive): rg_ope_logreg_workspace_bytes / rg_ope_replay_logreg (the off-policy replay of the frozen LogReg policy). */
-#define RG_ABI_VERSION 10
+/* v11 (additive): rg_sim_set_epsilon_greedy (the EpsilonGreedy overlay of the lock-step kernels), rg_eg_explore_actions (its table
+ * search on caller-supplied uniforms) and rg_ope_eg_workspace_bytes / rg_ope_replay_eg (the off-policy replay of an EpsilonGreedy
+ * target). */
+#define RG_ABI_VERSION 11
 
 /* error codes */
 #define RG_OK 0
@@ -216,6 +219,25 @@ int rg_sim_set_policy_table(rg_sim* sim, const int32_t* d_action, const float* d
  * which float32 cannot hold): the float64 side array of the log (rg_sim_set_log_aux) then carries exactly d_ps[p]; the 16-byte
  * row keeps its rounding to float32.  The two calls replace each other. */
 int rg_sim_set_policy_table_f64(rg_sim* sim, const int32_t* d_action, const double* d_ps);
+
+/* EpsilonGreedy(config, agent) over the handle's policy (agents/epsilon_greedy.py:30-71; epsilon_select_worse = False): every act
+ * flips the explore coin of the addressed draw (eg_seed, user, t) — the draw contract is in recogym_rng.h — and either keeps the
+ * inner act with ps = one_minus_eps * ps_inner or takes the explore action with ps = ps_explore.  The device computes none of the
+ * constants: d_cdf is the host's NumPy table cumsum(full(n, 1.0 / n)) / last with n = P - 1 (pure_new: the greedy action is
+ * excluded) or n = P, float64, caller-owned and kept by pointer; ps_explore = epsilon * (1.0 / n); one_minus_eps = 1.0 - epsilon.
+ * Inner policies: RG_POLICY_RANDOM_AGENT, RG_POLICY_ORGANIC_USER_COUNT, RG_POLICY_LAST_VIEW_TABLE (anything else: RG_EINVAL, as
+ * are epsilon outside [0, 1], pure_new with fewer than 2 products and a NULL table).  After rg_sim_create and before
+ * rg_sim_reset_users (afterwards: RG_ESTATE).  With the overlay on a run stays in the lock-step kernels (k_advance, k_advance_run,
+ * k_tail), as with time_mode: the user-major walk has no overlay. */
+int rg_sim_set_epsilon_greedy(rg_sim* sim, double epsilon, uint64_t eg_seed, uint32_t pure_new, const double* d_cdf,
+                              double ps_explore, double one_minus_eps);
+
+/* The overlay's explore action on caller-supplied uniforms (stateless; the part rg_sim_debug_ouc_acts plays for
+ * OrganicUserEventCounter): d_out[i] = what rng.choice(P, p = product_probas) returns for the uniform d_u1[i] in [0, 1) when the
+ * greedy action is d_greedy[i] — NumPy's searchsorted(cumsum(p) / last, u, 'right') — by the device function the step loop uses.
+ * d_cdf as above.  Enqueued on `stream`; no synchronisation. */
+int rg_eg_explore_actions(uint32_t num_products, uint32_t pure_new, const double* d_cdf, const double* d_u1, const int32_t* d_greedy,
+                          uint64_t n, int32_t* d_out, void* stream);
 
 /* RG_POLICY_LOGREG_FROZEN: the fitted model's arrays on the device, kept by pointer: d_coef_t =
  * sklearn's coef_ TRANSPOSED, row-major [num_products][n_classes] float64; d_intercept [n_classes];
@@ -450,6 +472,33 @@ size_t rg_ope_logreg_workspace_bytes(const rg_ope_logreg* model, uint64_t n_user
 int rg_ope_replay_logreg(const rg_ope_logreg* model, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
                          uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
                          uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Off-policy evaluation of an EpsilonGreedy target (agents/epsilon_greedy.py:30-71 with with_ps_all = True on the wrapper and the
+ * inner agent).  `inner` is an rg_ope_policy of kind RG_POLICY_RANDOM_AGENT (the greedy action is its bounded draw of
+ * (policy_seed, u, t)) or RG_POLICY_LAST_VIEW_TABLE (table[last organic product]).  Per bandit row: g = the inner action, the
+ * explore coin from (eg.seed, u, t), and pi = what act()['ps-a'][a] holds on that branch —
+ *   explored: epsilon * (pure_new && a == g ? 0.0 : prob_explore);   greedy: (1.0 - epsilon) * pi_inner[a]
+ * — then r = pi / ps.  prob_explore is the host's 1.0 / (P - 1) (pure_new) or 1.0 / P.
+ */
+typedef struct rg_ope_eg {
+    double epsilon;
+    uint64_t seed;                  /* the wrapper's config.random_seed */
+    uint32_t pure_new;
+    uint32_t reserved;
+    double prob_explore;
+} rg_ope_eg;
+
+/* rg_ope_replay_eg: rows, offsets, the ps source, d_ratio / d_click / d_sums and the workspace as rg_ope_replay (the same
+ * skeleton: the sums are the same bits on every run).  Optional outputs, written on bandit rows only: d_greedy[row] (uint8) = 1
+ * where the act was greedy, d_h0[row] (int32) = the inner action g (the `h0` the reference reports on explored acts).  The rows'
+ * `t` must be the event index (a log with a float clock does not qualify: the target always draws).  RG_EINVAL for another inner
+ * kind, a null table, epsilon outside [0, 1], pure_new with fewer than 2 products. */
+size_t rg_ope_eg_workspace_bytes(const rg_ope_policy* inner, uint64_t n_users, uint32_t max_user_rows);
+int rg_ope_replay_eg(const rg_ope_policy* inner, const rg_ope_eg* eg, const rg_event* d_rows, const int64_t* d_offsets,
+                     uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const,
+                     double* d_ratio, uint8_t* d_click, double* d_sums, uint8_t* d_greedy, int32_t* d_h0, void* d_workspace,
+                     size_t workspace_bytes, void* stream);
 
 /*
  * The count agents' training (reference agents/organic_count.py:74-82, agents/bandit_count.py:49-62 under the offline protocol

@@ -25,6 +25,21 @@
  *   purpose RG_DRAW_RESET  (slot j, t = 0): z[2j], z[2j+1] of omega_0 (reco_env_v1.py:80)
  *   purpose RG_DRAW_TIME   (slot 0): z0 -> the time increment after event t (NormalTimeGenerator only)
  *
+ *
+ * EpsilonGreedy (agents/epsilon_greedy.py:30-46) wraps an agent and draws from a stream of its own: its act for event (user, t)
+ * uses rg_draw(eg_seed, user, t, 0, RG_DRAW_POLICY), eg_seed the WRAPPER's config.random_seed and (user, t) exactly the key of the
+ * inner policy's act of that event (with eg_seed equal to the inner seed the two acts read the same block: both are functions of it)
+ *   words 0,1 -> u0, the explore flip rng.choice([True, False], p = [eps, 1 - eps]): explores iff !(eps / (eps + (1.0 - eps)) <= u0)
+ *   words 2,3 -> u1, the explore action rng.choice(num_products, p = product_probas): NumPy's legacy choice,
+ *                cdf = cumsum(p); cdf /= cdf[-1]; searchsorted(cdf, u1, 'right').  With epsilon_pure_new p is 1.0 / (P - 1)
+ *                except 0 at the greedy action g; adding 0.0 leaves a running float64 sum unchanged, so with
+ *                c = cumsum(full(P - 1, 1.0 / (P - 1))) / last — a table that does not depend on g — the answer is
+ *                m = #{j : c[j] <= u1}, a = m if m < g else m + 1.  Without it the table has P entries and a = m.
+ * The table is built by the host with NumPy itself and only compared on the device, like the propensities it logs:
+ * eps * (1.0 / (P - 1)) (or eps * (1.0 / P)) on an explored act, (1.0 - eps) * ps_inner — one float64 multiply — on a greedy one.
+ * This is the word layout tests/ref_harness.InjectedAgentRng serves: put in as the reference object's `rng`, it yields the
+ * reference's rows under these draws.
+ *
  * seed64 is `random_seed + epoch` (abstract.py:62) for env draws and the agent's own
  * `random_seed` for RG_DRAW_POLICY draws of an agent (with agent=None the policy draw comes
  * from the env stream, abstract.py:214, so it uses the env seed).

@@ -7,7 +7,7 @@ infrastructure and is never imported from this package.)
 import ctypes as C
 import os
 
-RG_ABI_VERSION = 10
+RG_ABI_VERSION = 11
 
 RG_STATE_ORGANIC, RG_STATE_BANDIT, RG_STATE_STOP = 0, 1, 2
 
@@ -88,6 +88,12 @@ class RgOpeLogreg(C.Structure):
                 ('bmax', C.c_float), ('reserved2', C.c_uint32)]
 
 
+class RgOpeEg(C.Structure):
+    """struct rg_ope_eg: the EpsilonGreedy wrapper of rg_ope_replay_eg."""
+    _fields_ = [('epsilon', C.c_double), ('seed', C.c_uint64), ('pure_new', C.c_uint32), ('reserved', C.c_uint32),
+                ('prob_explore', C.c_double)]
+
+
 RG_COUNT_ORGANIC, RG_COUNT_BANDIT = 0, 1
 
 
@@ -115,6 +121,8 @@ SYMBOLS = {
     'rg_sim_set_env0_tables': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rg_sim_set_policy_table': (C.c_int, [_SIM, C.c_void_p, C.c_void_p]),
     'rg_sim_set_policy_table_f64': (C.c_int, [_SIM, C.c_void_p, C.c_void_p]),
+    'rg_sim_set_epsilon_greedy': (C.c_int, [_SIM, C.c_double, C.c_uint64, C.c_uint32, C.c_void_p, C.c_double, C.c_double]),
+    'rg_eg_explore_actions': (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     'rg_sim_set_logreg': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     'rg_sim_set_logreg_fp32': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
     'rg_sim_set_logreg_fp16': (C.c_int, [_SIM, C.c_void_p]),
@@ -152,6 +160,10 @@ SYMBOLS = {
     'rg_ope_replay_logreg': (C.c_int, [C.POINTER(RgOpeLogreg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                        C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                        C.c_void_p]),
+    'rg_ope_eg_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpePolicy), C.c_uint64, C.c_uint32]),
+    'rg_ope_replay_eg': (C.c_int, [C.POINTER(RgOpePolicy), C.POINTER(RgOpeEg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                   C.c_uint32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
     'rg_count_workspace_bytes': (C.c_size_t, []),
     'rg_count_train': (C.c_int, [C.POINTER(RgCountTables), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_void_p]),

@@ -481,6 +481,7 @@ __global__ void __launch_bounds__(kBlock) k_logreg_decide(DevSim d, uint32_t t) 
     }
 }
 
+template <bool EG>       // EG: the acts carry the EpsilonGreedy overlay (policy_act_eg)
 __global__ void __launch_bounds__(kAdvBlock) k_advance(DevSim d, uint32_t t, const int32_t* actions) {
     constexpr int kSub = 1;                     // block iterations that share one reservation
     __shared__ uint32_t s_cnt_o[kSub][kAdvBlock / 64], s_cnt_b[kSub][kAdvBlock / 64], s_cnt_d[kSub][kAdvBlock / 64], s_base_o, s_base_b, s_base_d;
@@ -535,7 +536,7 @@ __global__ void __launch_bounds__(kAdvBlock) k_advance(DevSim d, uint32_t t, con
                 if (need_ctr) { touch0 = om_row[0]; touch1 = om_row[d.K - 1]; }
                 // K even and <= 24 (rows are 16-byte aligned): the whole omega row is fetched here as 16-byte
                 // loads and held across the policy, so that only beta's row is left on the critical path
-                const bool pre = d.K <= 24 && !(d.K & 1);
+                const bool pre = !EG && d.K <= 24 && !(d.K & 1);
                 double2 wpre[12];
                 if (pre && need_ctr) {
 #pragma unroll
@@ -556,7 +557,7 @@ __global__ void __launch_bounds__(kAdvBlock) k_advance(DevSim d, uint32_t t, con
                     ps = __builtin_nan("");
                 }
                 else if (d.policy == RG_POLICY_LOGREG_FROZEN) { a = lr_a; ps = d.lr_sample ? d.lr_ps[uidx] : 1.0; }
-                else a = policy_act(d, slot, user, t, &ps);
+                else a = policy_act_eg<EG>(d, slot, user, t, &ps);
                 // beta[a] . omega, k ascending (the oracle's association); loads are issued eight
                 // k at a time — a plain loop leaves one HBM round trip per k on the critical path
                 const double* b = d.beta + static_cast<size_t>(a) * d.K;
@@ -637,7 +638,7 @@ __global__ void __launch_bounds__(kAdvBlock) k_advance(DevSim d, uint32_t t, con
                     // final step_offline(done=True): one more act, reward 0 (abstract.py:223-233,311-316)
                     double ps = 1.0;
                     uint32_t a;
-                    if (d.policy != RG_POLICY_LOGREG_FROZEN) a = policy_act(d, slot, user, t + 1, &ps);
+                    if (d.policy != RG_POLICY_LOGREG_FROZEN) a = policy_act_eg<EG>(d, slot, user, t + 1, &ps);
                     else if (!d.lr_sample) a = lr_a;
                     else if (is_org) { a = lr_a; ps = d.lr_ps[uidx]; }                       // k_logreg_sample drew it for event t + 1
                     else { a = d.lr_action2[uidx]; ps = d.lr_ps2[uidx]; }
@@ -735,6 +736,7 @@ constexpr uint32_t kRunAheadMax = 64;
 // one bandit event of a user whose state does not move: act, click, row (k_advance's arithmetic) -> click
 // (may_click = false: pass 1 saw the event's uniform below kNoClickBelow — it cannot click whatever the click probability is, and
 // the event draw, a Philox block, is not taken again)
+template <bool EG>
 __device__ __forceinline__ bool run_bandit_event(const DevSim& d, uint32_t slot, uint32_t user, uint32_t te, uint32_t lr_a,
                                                  uint64_t row, double clock, bool may_click) {
     double u_click = 0.0;
@@ -747,7 +749,7 @@ __device__ __forceinline__ bool run_bandit_event(const DevSim& d, uint32_t slot,
     uint32_t a = 0;
     if (RG_ADV_ABL(25)) {}
     else if (d.policy == RG_POLICY_LOGREG_FROZEN) a = lr_a;
-    else a = policy_act(d, slot, user, te, &ps);
+    else a = policy_act_eg<EG>(d, slot, user, te, &ps);
     double ctr = 0.0;
     bool click = false;
     if (need_ctr) {
@@ -787,6 +789,7 @@ __device__ __forceinline__ bool run_bandit_event(const DevSim& d, uint32_t slot,
 #ifndef RG_ADV_RUN_WAVES
 #define RG_ADV_RUN_WAVES 2
 #endif
+template <bool EG>
 __global__ void __launch_bounds__(kAdvBlock) __attribute__((amdgpu_waves_per_eu(RG_ADV_RUN_WAVES, RG_ADV_RUN_WAVES)))
 k_advance_run(DevSim d, uint32_t t, uint32_t hops) {
     constexpr int NW = kAdvBlock / 64;
@@ -873,7 +876,7 @@ k_advance_run(DevSim d, uint32_t t, uint32_t hops) {
                 const bool o_mc = __shfl(static_cast<int>(may_click), owner) != 0;
                 if (mine) {
                     const uint32_t h = k - o_excl;
-                    const bool c = run_bandit_event(d, o_slot, o_user, o_te + h, o_lr, row_w + k, 0.0, o_mc && h + 1 == o_rows);
+                    const bool c = run_bandit_event<EG>(d, o_slot, o_user, o_te + h, o_lr, row_w + k, 0.0, o_mc && h + 1 == o_rows);
                     clicks += c;
                     if (c && h + 1 == o_rows) s_click[wave][owner] = 1;
                 }
@@ -887,7 +890,7 @@ k_advance_run(DevSim d, uint32_t t, uint32_t hops) {
             for (uint32_t h = 0; h < L; ++h) {
                 const uint32_t te = te0 + h;
                 if (h >= skip) {
-                    click = run_bandit_event(d, slot, user, te, lr_a, row, clock, may_click && h + 1 == L);
+                    click = run_bandit_event<EG>(d, slot, user, te, lr_a, row, clock, may_click && h + 1 == L);
                     clicks += click;
                     row += 1;
                 }
@@ -918,7 +921,7 @@ k_advance_run(DevSim d, uint32_t t, uint32_t hops) {
                 max_t = max(max_t, t_last + 1);
                 // final step_offline(done=True): one more act, reward 0 (abstract.py:223-233,311-316)
                 double ps = 1.0;
-                const uint32_t a = d.policy == RG_POLICY_LOGREG_FROZEN ? lr_a : policy_act(d, slot, user, t_last + 1, &ps);
+                const uint32_t a = d.policy == RG_POLICY_LOGREG_FROZEN ? lr_a : policy_act_eg<EG>(d, slot, user, t_last + 1, &ps);
                 rg_event e;
                 e.u = user; e.t = t_last + 1; e.code = RG_EV_BANDIT | RG_EV_PHANTOM | a;
                 e.ps = static_cast<float>(ps);
@@ -1001,6 +1004,7 @@ __global__ void __launch_bounds__(kBlock) k_drift(DevSim d, uint32_t t) {
 }
 search_kernel_t drift_kernel() { return k_drift; }
 
+template <bool EG>
 __global__ void __launch_bounds__(kBlock) k_tail(DevSim d, uint32_t t0) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     double* om = reinterpret_cast<double*>(smem_raw);                       // [K rounded up to 2]
@@ -1118,7 +1122,7 @@ __global__ void __launch_bounds__(kBlock) k_tail(DevSim d, uint32_t t0) {
                     if (d.hist_cap) history_add(d, slot, v);
                 } else {
                     double ps;
-                    const uint32_t a = policy_act(d, slot, user, t, &ps);
+                    const uint32_t a = policy_act_eg<EG>(d, slot, user, t, &ps);
                     double ctr = 0.0;
                     click = false;
                     if (d.aux_pclick || !(rg_uniform(w.w[0], w.w[1]) < kNoClickBelow)) {
@@ -1153,7 +1157,7 @@ __global__ void __launch_bounds__(kBlock) k_tail(DevSim d, uint32_t t0) {
                 } else if (ns == RG_STATE_STOP) {
                     d.n_events[uidx] = t + 1;
                     double ps;
-                    const uint32_t a = policy_act(d, slot, user, t + 1, &ps);
+                    const uint32_t a = policy_act_eg<EG>(d, slot, user, t + 1, &ps);
                     rg_event e;
                     e.u = user; e.t = t + 1; e.code = RG_EV_BANDIT | RG_EV_PHANTOM | a;
                     e.ps = static_cast<float>(ps);
@@ -1198,9 +1202,9 @@ search_kernel_t logreg_acts_kernel() { return k_logreg_acts; }
 search_kernel_t logreg_screen_kernel() { return k_logreg_screen; }
 search_kernel_t logreg_decide_kernel() { return k_logreg_decide; }
 search_kernel_t logreg_sample_kernel() { return k_logreg_sample; }
-advance_kernel_t advance_kernel() { return k_advance; }
-advance_run_kernel_t advance_run_kernel() { return k_advance_run; }
+advance_kernel_t advance_kernel(bool eg) { return eg ? k_advance<true> : k_advance<false>; }
+advance_run_kernel_t advance_run_kernel(bool eg) { return eg ? k_advance_run<true> : k_advance_run<false>; }
 round_rows_kernel_t round_rows_kernel() { return k_round_rows; }
-search_kernel_t tail_kernel() { return k_tail; }
+search_kernel_t tail_kernel(bool eg) { return eg ? k_tail<true> : k_tail<false>; }
 
 }  // namespace rgk

@@ -301,6 +301,12 @@ struct DevSim {
     double* utime;            // [n_cap] current time of every user (index = user index)
     double* phantom_time;     // [n_cap] time of the phantom row
     double* aux_time;         // optional side array of the log: time of every raw row
+    // EpsilonGreedy overlay (rg_sim_set_epsilon_greedy; agents/epsilon_greedy.py:30-71): the lock-step kernels' EG instantiations
+    // read these, nothing else does.  The table and the two propensity factors are the host's NumPy values.
+    uint32_t eg_on, eg_pure_new;
+    uint64_t eg_seed;
+    double eg_eps, eg_ps_explore, eg_one_minus;
+    const double* eg_cdf;     // [P - 1] (pure_new) or [P]: cumsum(full(n, 1 / n)) / last, caller-owned
 };
 
 }  // namespace rgk
@@ -409,10 +415,10 @@ search_kernel_t logreg_acts_kernel();
 search_kernel_t logreg_screen_kernel();
 search_kernel_t logreg_decide_kernel();
 search_kernel_t logreg_sample_kernel();
-advance_kernel_t advance_kernel();
-advance_run_kernel_t advance_run_kernel();
+advance_kernel_t advance_kernel(bool eg);                  // eg: the instantiation that carries the EpsilonGreedy overlay
+advance_run_kernel_t advance_run_kernel(bool eg);
 round_rows_kernel_t round_rows_kernel();
-search_kernel_t tail_kernel();
+search_kernel_t tail_kernel(bool eg);
 walk_kernel_t walk_kernel_for(const DevSim& d, int occ);   // part 7
 walk_kernel_t walk2_kernel_for(const DevSim& d, int occ);  // (nullptr: this configuration keeps k_walk)
 typedef void (*solo_kernel_t)(DevSim, uint32_t, uint32_t, uint32_t);
@@ -1124,6 +1130,44 @@ __device__ uint32_t policy_act(const DevSim& d, uint32_t slot, uint32_t user, ui
     }
     *ps_out = 1.0;
     return best;
+}
+
+// ------------------------------------------------------------------------------------------
+// EpsilonGreedy (agents/epsilon_greedy.py:30-71) over the policy above; the draw contract is in recogym_rng.h.
+// ------------------------------------------------------------------------------------------
+// The explore action, rng.choice(P, p = product_probas) given its uniform: NumPy's legacy choice is
+// searchsorted(cdf, u1, 'right') = #{j : cdf[j] <= u1} over cdf = cumsum(p) / last.  `cdf` is that table over the n non-zero
+// (equal) entries of p — n = P - 1 with pure_new, where the zero at the greedy action g adds 0.0 to the running sum and so only
+// shifts the indices behind it, else n = P.  floor(u1 n) is the guess, the table decides: the walk from the guess ends within an
+// entry or two.  The table is monotone and ends at 1.0 > u1, so the answer is at most n - 1 (enforced: nothing reads past the table,
+// and the action stays below P whatever the caller's table holds).  Out of line: eps of the lanes take it, and inlined into
+// k_advance_run it costs that kernel four spilled registers.
+__device__ __attribute__((noinline)) uint32_t eg_explore_action(uint32_t P, bool pure_new, const double* __restrict__ cdf, double u1, uint32_t g) {
+    const uint32_t n = pure_new ? P - 1u : P;
+    uint32_t m = static_cast<uint32_t>(u1 * static_cast<double>(n));
+    if (m > n - 1u) m = n - 1u;
+    while (m > 0u && !(cdf[m - 1u] <= u1)) --m;
+    while (m < n - 1u && cdf[m] <= u1) ++m;
+    return (pure_new && m >= g) ? m + 1u : m;
+}
+
+// The act of the lock-step kernels.  EG = false is policy_act and nothing else (the kernels' plain instantiations are the code they
+// were before the overlay existed); EG = true flips the explore coin of (eg_seed, user, t) on top of it: an explored act takes the
+// table's action and the host's eps * (1 / n), a greedy one the inner propensity times the host's 1 - eps.
+template <bool EG>
+__device__ __forceinline__ uint32_t policy_act_eg(const DevSim& d, uint32_t slot, uint32_t user, uint32_t t, double* ps_out) {
+    uint32_t a = policy_act(d, slot, user, t, ps_out);
+    if constexpr (EG) {
+        const rg_u32x4 w = rg_draw(d.eg_seed, user, t, 0, RG_DRAW_POLICY);
+        const double eps = d.eg_eps;
+        if (!(eps / (eps + (1.0 - eps)) <= rg_uniform(w.w[0], w.w[1]))) {
+            a = eg_explore_action(d.P, d.eg_pure_new != 0u, d.eg_cdf, rg_uniform(w.w[2], w.w[3]), a);
+            *ps_out = d.eg_ps_explore;
+        } else {
+            *ps_out = d.eg_one_minus * *ps_out;
+        }
+    }
+    return a;
 }
 
 // ViewsFeaturesProvider.observe (agents/abstract.py:347-358): count one organic view, keeping the

@@ -285,6 +285,12 @@ __global__ void __launch_bounds__(kBlock) k_debug_ouc_acts(DevSim d, const doubl
         action[i] = static_cast<int32_t>(a); ps[i] = p; flags[i] = static_cast<uint8_t>(fl);
     }
 }
+// rg_eg_explore_actions: the overlay's table search (eg_explore_action) on caller-supplied uniforms and greedy actions
+__global__ void __launch_bounds__(kBlock) k_eg_explore_actions(uint32_t P, uint32_t pure_new, const double* cdf, const double* u1,
+                                                               const int32_t* greedy, uint64_t n, int32_t* out) {
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += static_cast<uint64_t>(gridDim.x) * kBlock)
+        out[i] = static_cast<int32_t>(eg_explore_action(P, pure_new != 0u, cdf, u1[i], static_cast<uint32_t>(greedy[i])));
+}
 __global__ void __launch_bounds__(kBlock) k_debug_fate_round2(DevSim d, uint8_t* flags) {
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < d.n_users; i += gridDim.x * kBlock) flags[i] = d.f64_valid[i] ? 1 : 0;
 }
@@ -757,9 +763,9 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
     if (int rc = prof_mark(sim, st)) return rc;
     // 2. click draws, transitions, drift, next lists, bandit + phantom rows
     if (d.run_ahead)       // a round: every listed user through its bandit run (k_advance_run), then the round's raw-log books
-        hipLaunchKernelGGL(advance_run_kernel(), dim3(grid_for(upper, kAdvBlock)), dim3(kAdvBlock), 0, st, d, t, d.run_ahead);
+        hipLaunchKernelGGL(advance_run_kernel(d.eg_on != 0u), dim3(grid_for(upper, kAdvBlock)), dim3(kAdvBlock), 0, st, d, t, d.run_ahead);
     else
-        hipLaunchKernelGGL(advance_kernel(), dim3(grid_for(upper, kAdvBlock)), dim3(kAdvBlock), 0, st, d, t, d_actions);
+        hipLaunchKernelGGL(advance_kernel(d.eg_on != 0u), dim3(grid_for(upper, kAdvBlock)), dim3(kAdvBlock), 0, st, d, t, d_actions);
     if (d.sigma_omega != 0.0)
         hipLaunchKernelGGL(drift_kernel(), dim3(grid_for(static_cast<uint64_t>(upper) * ((d.K + 1) / 2))), dim3(kBlock), 0, st, d, t);
     if (d.run_ahead) hipLaunchKernelGGL(round_rows_kernel(), dim3(1), dim3(1), 0, st, d, t, 0u);
@@ -1511,6 +1517,37 @@ int rg_sim_set_policy_table_f64(rg_sim* sim, const int32_t* d_action, const doub
     return RG_OK;
 }
 
+int rg_sim_set_epsilon_greedy(rg_sim* sim, double epsilon, uint64_t eg_seed, uint32_t pure_new, const double* d_cdf,
+                              double ps_explore, double one_minus_eps) {
+    if (!sim) return fail(RG_EINVAL, "sim is NULL");
+    if (sim->users_reset) return fail(RG_ESTATE, "rg_sim_set_epsilon_greedy must be called before rg_sim_reset_users");
+    const uint32_t pol = sim->d.policy;
+    if (pol != RG_POLICY_RANDOM_AGENT && pol != RG_POLICY_ORGANIC_USER_COUNT && pol != RG_POLICY_LAST_VIEW_TABLE)
+        return fail(RG_EINVAL, "EpsilonGreedy wraps RandomAgent, OrganicUserEventCounter or a last-view table on the device (policy %u)", pol);
+    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(RG_EINVAL, "epsilon %g outside [0, 1]", epsilon);
+    if (pure_new && sim->d.P < 2u) return fail(RG_EINVAL, "epsilon_pure_new needs at least 2 products");
+    if (!d_cdf) return fail(RG_EINVAL, "the explore table is NULL");
+    DevSim& d = sim->d;
+    d.eg_on = 1u; d.eg_pure_new = pure_new ? 1u : 0u; d.eg_seed = eg_seed;
+    d.eg_eps = epsilon; d.eg_ps_explore = ps_explore; d.eg_one_minus = one_minus_eps; d.eg_cdf = d_cdf;
+    sim->walk = sim->walk2 = false;            // the overlay lives in the lock-step kernels only (as time_mode / RECOGYM_WALK=0)
+    return RG_OK;
+}
+
+int rg_eg_explore_actions(uint32_t num_products, uint32_t pure_new, const double* d_cdf, const double* d_u1, const int32_t* d_greedy,
+                          uint64_t n, int32_t* d_out, void* stream) {
+    if (num_products == 0 || num_products > RG_EV_INDEX_MASK || (pure_new && num_products < 2u))
+        return fail(RG_EINVAL, "rg_eg_explore_actions: bad num_products %u", num_products);
+    if (!d_cdf || (n && (!d_u1 || !d_greedy || !d_out))) return fail(RG_EINVAL, "rg_eg_explore_actions: null array");
+    if (rg_device_count() <= 0) return fail(RG_ENODEV, "no HIP device");
+    if (n == 0) return RG_OK;
+    const uint64_t blocks = (n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_eg_explore_actions, dim3(static_cast<uint32_t>(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0,
+                       static_cast<hipStream_t>(stream), num_products, pure_new, d_cdf, d_u1, d_greedy, n, d_out);
+    HIP_TRY(hipGetLastError());
+    return RG_OK;
+}
+
 int rg_sim_set_logreg(rg_sim* sim, const double* d_coef_t, const double* d_intercept,
                       const int32_t* d_classes, uint32_t n_classes) {
     if (!sim) return fail(RG_EINVAL, "sim is NULL");
@@ -1695,7 +1732,7 @@ int rg_sim_run(rg_sim* sim, uint32_t max_steps, void* stream) {
                 HIP_TRY(hipEventRecord(ev[0], st));
             }
             const int grid = static_cast<int>(live < 2048 ? live : 2048);
-            hipLaunchKernelGGL(tail_kernel(), dim3(grid), dim3(kBlock), tail_smem, st, sim->d, sim->t);
+            hipLaunchKernelGGL(tail_kernel(sim->d.eg_on != 0u), dim3(grid), dim3(kBlock), tail_smem, st, sim->d, sim->t);
             hipLaunchKernelGGL(k_tail_finish, dim3(1), dim3(1), 0, st, sim->d, sim->t);
             HIP_TRY(hipGetLastError());
             if (sim->profiling) HIP_TRY(hipEventRecord(ev[1], st));

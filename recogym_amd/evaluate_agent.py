@@ -11,7 +11,8 @@ verify_agents_IPS, verify_agents_SNIPS, evaluate_recall_at_k, verify_agents_reca
 Simulator.device_log().  Users 0 .. max(u) - 1 are evaluated (the reference's range(max(reco_log.u)):
 the user with the largest id is not), each user's rows in frame order.  Where a HIP device is present,
 the agent has a replay form (ope_policy_of) and the log qualifies, the rows are replayed on the device
-by rg_ope_replay (the frozen LogReg policy: by rg_ope_replay_logreg); otherwise the host loop below runs:
+by rg_ope_replay (the frozen LogReg policy: by rg_ope_replay_logreg, an EpsilonGreedy target: by rg_ope_replay_eg); otherwise the
+host loop below runs:
 the reference's loop made linear (one stable group-by instead of six frame filters per user), the same
 act() calls in the same order."""
 import ctypes as C
@@ -112,13 +113,17 @@ def _host_snips(agent, reco_log):
 def ope_policy_of(agent):
     """-> dict(kind, num_products, policy_seed, ouc | table | logreg) when the agent's `ps-a` has a replay form on the device, else None.
     This package's agents say so themselves (ope_policy()); the reference's own classes are duck-typed where pi does not
-    depend on their MT stream: RandomAgent, and OrganicUserEventCounterAgent unless exploit_explore with epsilon > 0."""
+    depend on their MT stream: RandomAgent, and OrganicUserEventCounterAgent unless exploit_explore with epsilon > 0.  A reference
+    EpsilonGreedy object never qualifies: both its explore coin and (pure_new) the greedy action its pi excludes come from MT
+    streams — it stays on the host loop, whatever it wraps."""
     if hasattr(agent, 'ope_policy'):
         return agent.ope_policy()
     cfg = getattr(agent, 'config', None)
     if cfg is None or not getattr(cfg, 'with_ps_all', False):
         return None
     name = type(agent).__name__
+    if name == 'EpsilonGreedy':
+        return None
     if name == 'RandomAgent':
         return dict(kind=_abi.RG_POLICY_RANDOM_AGENT, num_products=int(cfg.num_products), policy_seed=0)
     if name == 'OrganicUserEventCounterAgent' and getattr(cfg, 'weight_history_function', None) is None \
@@ -130,6 +135,8 @@ def ope_policy_of(agent):
 
 
 def _draws(pol):
+    if pol.get('epsilon_greedy') is not None:
+        return True                            # an EpsilonGreedy target always flips its coin, keyed by the event index
     o = pol.get('ouc')
     return bool(o and o['exploit_explore'] and o['epsilon'] != 0.0)
 
@@ -226,12 +233,13 @@ def _logreg_model(lr, num_products, device):
     return m, keep
 
 
-def ope_replay(agent, dl, pol=None, n_users=None, stats=None):
+def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
     """Replay a DeviceLog under `agent` on the device -> (ratio r = pi[a] / ps, click c as float64, sums) for the bandit rows of
     the log's first `n_users` users (default: all but the last, whose id is max(u)), in log order (device tensors);
     sums = float64 tensor (n, sum c r, sum r).  None where the agent has no replay form or the log does not qualify (a user
     that opens with a bandit row; a float clock under a policy that draws).  `stats` (a dict, frozen LogReg policies only)
-    receives rg_ope_replay_logreg's workspace words: error, acts, exact (acts decided by float64 scores), rows_read."""
+    receives rg_ope_replay_logreg's workspace words: error, acts, exact (acts decided by float64 scores), rows_read.  `eg_out` (a
+    dict, EpsilonGreedy targets only) receives `greedy` (uint8) and `h0` (int32) of the same bandit rows (device tensors)."""
     import torch
     pol = ope_policy_of(agent) if pol is None else pol
     if pol is None or int(pol['num_products']) != int(dl.num_products):
@@ -248,6 +256,9 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None):
             return None
     max_rows = int(lens.max().item()) if n_eval else 0
     lib = _abi.load()
+    eg = pol.get('epsilon_greedy')
+    if eg is not None and pol.get('kind') not in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE):
+        return None
     if pol.get('logreg') is not None:
         # the frozen LogReg policy has an entry point of its own; the model moves to the log's device once per call
         cp, keep = _logreg_model(pol['logreg'], int(pol['num_products']), device)
@@ -264,6 +275,12 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None):
                               ouc_epsilon=float(o.get('epsilon', 0.0)),
                               table=None if keep is None else keep.data_ptr())
         size_fn, replay_fn, what = lib.rg_ope_workspace_bytes, lib.rg_ope_replay, 'rg_ope_replay'
+        if eg is not None:
+            from .agents.epsilon_greedy import explore_table
+            pure_new = bool(eg.get('pure_new', True))
+            ce = _abi.RgOpeEg(epsilon=float(eg['epsilon']), seed=int(eg['seed']) & 0xFFFFFFFFFFFFFFFF, pure_new=int(pure_new),
+                              reserved=0, prob_explore=explore_table(int(pol['num_products']), pure_new)[1])
+            size_fn, what = lib.rg_ope_eg_workspace_bytes, 'rg_ope_replay_eg'
     with torch.cuda.device(device):
         need = size_fn(C.byref(cp), n_eval, max_rows)
         if need == 0:
@@ -280,8 +297,17 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None):
         else:
             mode, ps_ptr, ps_const = _abi.RG_OPE_PS_ARRAY, ps.data_ptr(), 0.0
         stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _abi.check(replay_fn(C.byref(cp), dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows, mode, ps_ptr,
-                             ps_const, ratio.data_ptr(), None, sums.data_ptr(), ws.data_ptr(), need, stream), what)
+        if eg is not None:
+            want = eg_out is not None
+            greedy = torch.zeros(max(total, 1), dtype=torch.uint8, device=device) if want else None
+            h0 = torch.zeros(max(total, 1), dtype=torch.int32, device=device) if want else None
+            _abi.check(lib.rg_ope_replay_eg(C.byref(cp), C.byref(ce), dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows,
+                                            mode, ps_ptr, ps_const, ratio.data_ptr(), None, sums.data_ptr(),
+                                            greedy.data_ptr() if want else None, h0.data_ptr() if want else None,
+                                            ws.data_ptr(), need, stream), what)
+        else:
+            _abi.check(replay_fn(C.byref(cp), dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows, mode, ps_ptr,
+                                 ps_const, ratio.data_ptr(), None, sums.data_ptr(), ws.data_ptr(), need, stream), what)
         if stats is not None and pol.get('logreg') is not None:
             words = ws[:32].view(torch.int64).cpu().numpy()
             stats.update(error=int(words[0]), acts=int(words[1]), exact=int(words[2]), rows_read=int(words[3]))
@@ -289,7 +315,24 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None):
         is_b = (code & _abi.RG_EV_BANDIT) != 0
         r = _masked(ratio[:total], is_b)
         c = _masked(((code & _abi.RG_EV_CLICK) != 0).to(torch.float64), is_b)
+        if eg is not None and eg_out is not None:
+            eg_out.update(greedy=_masked(greedy[:total], is_b), h0=_masked(h0[:total], is_b))
     return r, c, sums
+
+
+def epsilon_greedy_branches(agent, reco_log):
+    """-> (greedy uint8, h0 int32) device tensors over the bandit rows of a device log (a Simulator or its device_log()), in log
+    order: which acts of the EpsilonGreedy `agent` were greedy, and the inner agent's action at every one of them (the `h0`
+    the reference's act reports on explored acts) — rg_event has no bit for either, the replay recomputes them from the
+    addressed draws.  All users of the log are covered.  None where the agent has no replay form or the log does not qualify."""
+    dl = _as_device_log(reco_log)
+    pol = ope_policy_of(agent)
+    if dl is None or pol is None or pol.get('epsilon_greedy') is None:
+        return None
+    out = {}
+    if ope_replay(agent, dl, pol, n_users=int(dl.offsets.numel()) - 1, eg_out=out) is None:
+        return None
+    return out['greedy'], out['h0']
 
 
 def _device_or_none(agent, reco_log):

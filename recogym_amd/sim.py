@@ -92,11 +92,14 @@ class Simulator:
     ps_float64   keep the propensity of every bandit row in float64 beside the 16-byte row (the dtype of
                  the reference's `ps` column); default: on for the policies whose ps is not a constant
     p_click      also keep the click probability of every bandit row (parity checks)
+    epsilon_greedy  dict(epsilon, seed, pure_new): the EpsilonGreedy overlay over `policy` (agents/epsilon_greedy.py;
+                 rg_sim_set_epsilon_greedy) — the explore table and both propensity factors are NumPy's, built here
     """
 
     def __init__(self, config, n_users, policy=_abi.RG_POLICY_UNIFORM_ENV, policy_seed=None,
                  ouc=None, epoch=0, log_capacity=None, device=None, tables=None, policy_table=None,
-                 policy_ps=None, logreg=None, ps_float64=None, p_click=False, env0=None, policy_ps64=False):
+                 policy_ps=None, logreg=None, ps_float64=None, p_click=False, env0=None, policy_ps64=False,
+                 epsilon_greedy=None):
         if policy == _abi.RG_POLICY_LOGREG_FROZEN and ((logreg or {}).get('int8') or os.environ.get('RECOGYM_LOGREG') == 'int8'):
             # (refused, not ignored: a caller that labels the act's bytes from this switch would report 1 B per weight for an fp16 run)
             raise ValueError("the 8-bit LogReg screen is retired (measured slower than the fp16 screen): drop logreg['int8'] / RECOGYM_LOGREG=int8")
@@ -111,8 +114,11 @@ class Simulator:
                                         lr_select_randomly=bool(logreg and logreg.get('select_randomly')))
         self.policy = policy
         self.time_mode = int(self.rg_config.time_mode)
+        self.epsilon_greedy = epsilon_greedy
+        # the loggers whose propensity is the constant 1 / P (its exact float64 value is filled in at decode time)
+        self.uniform_ps = policy in (_abi.RG_POLICY_UNIFORM_ENV, _abi.RG_POLICY_RANDOM_AGENT) and epsilon_greedy is None
         self.ps_float64 = ((policy in (_abi.RG_POLICY_ORGANIC_USER_COUNT, _abi.RG_POLICY_LAST_VIEW_TABLE)
-                            or bool(logreg and logreg.get('select_randomly')))
+                            or bool(logreg and logreg.get('select_randomly')) or epsilon_greedy is not None)
                            if ps_float64 is None else bool(ps_float64))
         self.keep_p_click = bool(p_click)
         host_tables = () if env0 is not None else (tables if tables is not None else draw_tables(config))
@@ -129,6 +135,17 @@ class Simulator:
             _abi.check(self.lib.rg_sim_create(C.byref(self._h), C.byref(self.rg_config),
                                               self.n_users, self.workspace.data_ptr(), need),
                        'rg_sim_create')
+            if epsilon_greedy is not None:
+                # before the tables: the overlay keeps the run in the lock-step kernels
+                from .agents.epsilon_greedy import explore_table
+                eps, pure_new = float(epsilon_greedy['epsilon']), bool(epsilon_greedy.get('pure_new', True))
+                if pure_new and config.num_products < 2:
+                    raise _abi.RecoGymHipError('rg_sim_set_epsilon_greedy: RG_EINVAL: epsilon_pure_new needs at least 2 products')
+                cdf, prob = explore_table(config.num_products, pure_new)
+                self.eg_cdf = torch.from_numpy(cdf).to(self.device)
+                _abi.check(self.lib.rg_sim_set_epsilon_greedy(self._h, eps, int(epsilon_greedy['seed']) & 0xFFFFFFFFFFFFFFFF,
+                                                              int(pure_new), self.eg_cdf.data_ptr(), eps * prob, 1.0 - eps),
+                           'rg_sim_set_epsilon_greedy')
             if env0 is not None:
                 p = np.ascontiguousarray(env0['click_probs'], dtype=np.float64)
                 qn, px1 = np.empty_like(p), np.empty_like(p)
@@ -388,7 +405,7 @@ class Simulator:
         log_columns()' rule — the exact 1/P of the uniform loggers, else the float64 side array, else the row's float32 value."""
         rows, offsets = self.sorted_log()
         ps64, _ = self.sorted_aux(offsets, rows.shape[0])
-        if self.policy in (_abi.RG_POLICY_UNIFORM_ENV, _abi.RG_POLICY_RANDOM_AGENT):
+        if self.uniform_ps:
             ps = 1.0 / float(self.config.num_products)
         else:
             ps = ps64
@@ -400,7 +417,7 @@ class Simulator:
         uniform policies or None)."""
         out, _ = self.sorted_log()
         uniform = None
-        if self.policy in (_abi.RG_POLICY_UNIFORM_ENV, _abi.RG_POLICY_RANDOM_AGENT):
+        if self.uniform_ps:
             uniform = 1.0 / float(self.config.num_products)
         return out.cpu().numpy(), uniform
 
@@ -417,7 +434,7 @@ class Simulator:
         out, offsets = self.sorted_log()
         ps64, _ = self.sorted_aux(offsets, out.shape[0])
         n = int(out.shape[0])
-        uniform = self.policy in (_abi.RG_POLICY_UNIFORM_ENV, _abi.RG_POLICY_RANDOM_AGENT)
+        uniform = self.uniform_ps
         t_sorted = self.sorted_time(offsets, n) if self.time_mode else None
 
         def decode(lo, hi, dst=None):
@@ -564,7 +581,7 @@ class Simulator:
         out, offsets = self.sorted_log()
         ps64, pc = self.sorted_aux(offsets, out.shape[0])
         uniform = None
-        if self.policy in (_abi.RG_POLICY_UNIFORM_ENV, _abi.RG_POLICY_RANDOM_AGENT):
+        if self.uniform_ps:
             uniform = 1.0 / float(self.config.num_products)
         rows = decode_rows(out.cpu().numpy(), uniform, None if ps64 is None else ps64.cpu().numpy(),
                            None if pc is None else pc.cpu().numpy())
