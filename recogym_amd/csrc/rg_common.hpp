@@ -1,4 +1,4 @@
-// rg_common.hpp — librecogym_hip.so: the reco-gym-v1 step loop as batched CDNA4 (gfx950) kernels (shared part of its seven units).
+// rg_common.hpp — librecogym_hip.so: the reco-gym-v1 step loop as batched CDNA4 (gfx950) kernels (shared part of its thirteen units).
 //
 // What runs here (reference file:line each kernel takes over; see DESIGN.md for the data layout
 // and the roofline of each kernel):
@@ -49,12 +49,14 @@
 #include "../../include/recogym_hip.h"
 #include "../../include/recogym_rng.h"
 
-// Translation units.  The library is built from seven units, one per kernel family — rg_host.hip (host code, the C ABI, small
+// Translation units.  The library is built from thirteen units, one per kernel family — rg_host.hip (host code, the C ABI, small
 // kernels), rg_exact.hip (float64 resolve), rg_draw_fp32.hip (fp32 / lean 16-bit sweeps), rg_draw_pipelined.hip (the pipelined sweep
 // + per-user cache kernels), rg_draw_wide.hip (wide-K sweep), rg_advance.hip (advance / tail / frozen LogReg), rg_walk.hip (the
-// user-major walk) — compiled in parallel and linked by __graft_entry__.build(); recogym_hip.hip includes all seven (a one-unit
-// build).  This header holds what they share: types, the workspace layout, device helpers (namespace rgk, identical in every
-// unit); a unit hands its kernels to the host code through the *_kernel_for functions declared here.
+// user-major walk), rg_draw_exacthi.hip and rg_draw_lds.hip (the error-free and the tile-prefix sweeps), rg_ope.hip,
+// rg_ope_logreg.hip and rg_ope_eg.hip (off-policy replays), rg_count.hip (count agents' training) — compiled in parallel and
+// linked by __graft_entry__.build(); recogym_hip.hip includes all of them (a one-unit build).  This header holds what they
+// share: types, the workspace layout, device helpers (namespace rgk, identical in every unit); a unit hands its kernels to the
+// host code through the *_kernel_for functions declared here.  rg_ope_common.hpp adds what the three replay units share.
 #pragma once
 
 // RG_WALK_PRECISE_CHUNK = 1 (default): the walk behind k_sweep_xh recomputes a draw's chunk as a float64 dot (one budget delta for

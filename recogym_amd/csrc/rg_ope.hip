@@ -10,21 +10,16 @@
 //   - in a per-wave global table of 2^g_log2 >= 2 x (longest user) slots otherwise — slower, equally exact (nothing is
 //     dropped: a dropped view would be a wrong pi).
 // Dense forms (epsilon smoothing, reverse_pop, the argmax of the explore flip) take one wave-wide pass over all P products,
-// cached until the user's next organic row.  No float atomics: the sums reduce in a second one-block pass in a fixed order.
-#include "rg_common.hpp"
+// cached until the user's next organic row.  No float atomics: the sums reduce in a second one-block pass in a fixed order
+// (k_ope_reduce, here, for every replay unit: rg_ope_common.hpp).
+#include "rg_ope_common.hpp"
 
 namespace {
 
-constexpr int kOpeWaves = 4;                    // waves per block
 constexpr uint32_t kOpeLdsLog2 = 10;
 constexpr uint32_t kOpeLdsSlots = 1u << kOpeLdsLog2;
 constexpr uint32_t kOpeLdsRows = kOpeLdsSlots / 2;
 constexpr uint32_t kOpeMaxWaves = 5120;         // 256 CUs x 20 waves (LDS: 4 waves x 8 KiB per block)
-
-uint32_t ope_waves(uint64_t n_users) {
-    const uint64_t w = (n_users + kOpeWaves - 1) / kOpeWaves * kOpeWaves;
-    return static_cast<uint32_t>(w < kOpeWaves ? kOpeWaves : (w > kOpeMaxWaves ? kOpeMaxWaves : w));
-}
 
 uint32_t ope_global_log2(const rg_ope_policy* pol, uint32_t max_user_rows) {
     if (pol->kind != RG_POLICY_ORGANIC_USER_COUNT || max_user_rows <= kOpeLdsRows) return 0;
@@ -32,8 +27,6 @@ uint32_t ope_global_log2(const rg_ope_policy* pol, uint32_t max_user_rows) {
     while ((1ull << l) < 2ull * max_user_rows) ++l;
     return l;
 }
-
-size_t ope_slot_bytes(uint32_t n_waves) { return (static_cast<size_t>(n_waves) * 3 * sizeof(double) + 255) & ~size_t(255); }
 
 // (product + 1, count) open-addressing table; every lane of the wave calls the writer with the same product, so each
 // lane reads back its own (identical) writes
@@ -60,12 +53,6 @@ __device__ __forceinline__ uint32_t ope_add(uint32_t* key, uint32_t* cnt, uint32
     }
     *fresh = false;
     return 0;
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
 }
 
 struct OpeDense {
@@ -154,11 +141,8 @@ __device__ __forceinline__ double ouc_chunk(const rg_ope_policy& pol, uint32_t* 
 }
 
 template <bool kLds>
-__device__ __forceinline__ void ope_user(const rg_ope_policy& pol, const rg_event* __restrict__ rows, int64_t b, int64_t e,
-                                         uint32_t ps_mode, const double* __restrict__ ps64, double ps_const,
-                                         double* __restrict__ ratio, uint8_t* __restrict__ click,
-                                         uint32_t* key, uint32_t* cnt, uint32_t mask, uint32_t shift, uint32_t lane,
-                                         double& acc_n, double& acc_cr, double& acc_r) {
+__device__ __forceinline__ void ope_user(const rg_ope_policy& pol, const OpeLog& log, int64_t b, int64_t e, uint32_t* key,
+                                         uint32_t* cnt, uint32_t mask, uint32_t shift, uint32_t lane, OpeAcc& acc) {
     const bool ouc = pol.kind == RG_POLICY_ORGANIC_USER_COUNT;
     const bool lvt = pol.kind == RG_POLICY_LAST_VIEW_TABLE;
     const double eps = pol.ouc_epsilon;
@@ -170,45 +154,24 @@ __device__ __forceinline__ void ope_user(const rg_ope_policy& pol, const rg_even
     OucState st{0u, 0u, 0u, 0u, false, OpeDense{0.0, 0.0, 0u, 0u}};
     uint32_t lpv = 0;
     for (int64_t base = b; base < e; base += 64) {
-        const int64_t row = base + lane;
-        const bool live = row < e;
-        uint4 x = make_uint4(0u, 0u, 0u, 0u);
-        if (live) x = reinterpret_cast<const uint4*>(rows)[row];
-        const bool isb = live && (x.z & RG_EV_BANDIT);
-        const bool iso = live && !(x.z & RG_EV_BANDIT);
-        const uint32_t idx = x.z & RG_EV_INDEX_MASK;
+        const OpeRow r = ope_load(log, base, e, lane);
         double pi = 0.0;
         if (ouc) {
             bool explore = false;
-            if (draw_explore && isb) {
-                const rg_u32x4 w = rg_draw(pol.policy_seed, x.x, x.y, 0, RG_DRAW_POLICY);
+            if (draw_explore && r.isb) {
+                const rg_u32x4 w = rg_draw(pol.policy_seed, r.x.x, r.x.y, 0, RG_DRAW_POLICY);
                 explore = !(eps / (eps + (1.0 - eps)) <= rg_uniform(w.w[0], w.w[1]));
             }
-            const uint64_t omask = __ballot(iso), emask = __ballot(explore);
+            const uint64_t omask = __ballot(r.iso), emask = __ballot(explore);
             const uint32_t n = static_cast<uint32_t>(e - base < 64 ? e - base : 64);
-            pi = ouc_chunk(pol, key, cnt, mask, shift, st, omask, emask, n, idx, lane);
+            pi = ouc_chunk(pol, key, cnt, mask, shift, st, omask, emask, n, r.idx, lane);
         } else if (lvt) {
-            // the last organic row before this one (in the chunk, else carried): BanditMFSquare.update_lpv
-            const uint64_t omask = __ballot(iso);
-            const uint64_t before = omask & (lane ? (~0ull >> (64 - lane)) : 0ull);
-            const int src = before ? 63 - __clzll(static_cast<long long>(before)) : 0;
-            const uint32_t from = static_cast<uint32_t>(__shfl(static_cast<int>(idx), src));
-            const uint32_t mine = before ? from : lpv;
-            pi = mine < pol.num_products && static_cast<uint32_t>(pol.table[mine]) == idx ? 1.0 : 0.0;
-            if (omask) lpv = static_cast<uint32_t>(__shfl(static_cast<int>(idx), 63 - __clzll(static_cast<long long>(omask))));
+            const uint32_t mine = ope_last_view(r, lane, lpv);
+            pi = mine < pol.num_products && static_cast<uint32_t>(pol.table[mine]) == r.idx ? 1.0 : 0.0;
         } else {
             pi = 1.0 / static_cast<double>(pol.num_products);
         }
-        if (isb) {
-            const double ps = ps_mode == RG_OPE_PS_ARRAY ? ps64[row]
-                              : ps_mode == RG_OPE_PS_CONST ? ps_const : static_cast<double>(__uint_as_float(x.w));
-            const double r = pi / ps;
-            ratio[row] = r;
-            if (click) click[row] = (x.z & RG_EV_CLICK) ? 1 : 0;
-            acc_n += 1.0;
-            acc_cr += ((x.z & RG_EV_CLICK) ? 1.0 : 0.0) * r;
-            acc_r += r;
-        }
+        if (r.isb) acc.emit(log, r, pi);
     }
 }
 
@@ -220,27 +183,19 @@ __global__ __launch_bounds__(64 * kOpeWaves) void k_ope_replay(
     __shared__ uint32_t s_cnt[kOpeWaves][kOpeLdsSlots];
     const uint32_t lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
     const uint32_t wave = blockIdx.x * kOpeWaves + wib;
-    double acc_n = 0.0, acc_cr = 0.0, acc_r = 0.0;
+    const OpeLog log{rows, offsets, n_users, ps_mode, ps64, ps_const, ratio, click, slots, n_waves};
+    OpeAcc acc;
     for (uint64_t user = wave; user < n_users; user += n_waves) {
         const int64_t b = offsets[user], e = offsets[user + 1];
         if (pol.kind != RG_POLICY_ORGANIC_USER_COUNT || e - b <= static_cast<int64_t>(kOpeLdsRows) || g_log2 == 0) {
-            ope_user<true>(pol, rows, b, e, ps_mode, ps64, ps_const, ratio, click, s_key[wib], s_cnt[wib], kOpeLdsSlots - 1,
-                           32 - kOpeLdsLog2, lane, acc_n, acc_cr, acc_r);
+            ope_user<true>(pol, log, b, e, s_key[wib], s_cnt[wib], kOpeLdsSlots - 1, 32 - kOpeLdsLog2, lane, acc);
         } else {
             const size_t G = size_t(1) << g_log2;
             uint32_t* key = gtab + static_cast<size_t>(wave) * 2 * G;
-            ope_user<false>(pol, rows, b, e, ps_mode, ps64, ps_const, ratio, click, key, key + G, static_cast<uint32_t>(G - 1),
-                            32 - g_log2, lane, acc_n, acc_cr, acc_r);
+            ope_user<false>(pol, log, b, e, key, key + G, static_cast<uint32_t>(G - 1), 32 - g_log2, lane, acc);
         }
     }
-    acc_n = wave_sum(acc_n);
-    acc_cr = wave_sum(acc_cr);
-    acc_r = wave_sum(acc_r);
-    if (lane == 0) {
-        slots[3 * static_cast<size_t>(wave) + 0] = acc_n;
-        slots[3 * static_cast<size_t>(wave) + 1] = acc_cr;
-        slots[3 * static_cast<size_t>(wave) + 2] = acc_r;
-    }
+    acc.store(log, wave, lane);
 }
 
 // the per-wave slots -> (n, sum c r, sum r), one block, fixed order
@@ -262,9 +217,15 @@ __global__ __launch_bounds__(256) void k_ope_reduce(const double* __restrict__ s
 
 }  // namespace
 
+int rgk::ope_reduce(const double* slots, uint32_t n_waves, double* d_sums, hipStream_t stream) {
+    hipLaunchKernelGGL(k_ope_reduce, dim3(1), dim3(256), 0, stream, slots, n_waves, d_sums);
+    HIP_TRY(hipGetLastError());
+    return RG_OK;
+}
+
 extern "C" size_t rg_ope_workspace_bytes(const rg_ope_policy* pol, uint64_t n_users, uint32_t max_user_rows) {
     if (!pol) { fail(RG_EINVAL, "rg_ope_workspace_bytes: null policy"); return 0; }
-    const uint32_t W = ope_waves(n_users);
+    const uint32_t W = ope_waves(n_users, kOpeMaxWaves);
     const uint32_t l = ope_global_log2(pol, max_user_rows);
     return ope_slot_bytes(W) + (l ? static_cast<size_t>(W) * 2 * (size_t(1) << l) * sizeof(uint32_t) : 0);
 }
@@ -277,14 +238,10 @@ extern "C" int rg_ope_replay(const rg_ope_policy* pol, const rg_event* d_rows, c
         return fail(RG_EINVAL, "rg_ope_replay: policy kind %u has no replay form", pol->kind);
     if (pol->num_products == 0 || pol->num_products > RG_EV_INDEX_MASK) return fail(RG_EINVAL, "rg_ope_replay: bad num_products");
     if (pol->kind == RG_POLICY_LAST_VIEW_TABLE && !pol->table) return fail(RG_EINVAL, "rg_ope_replay: null table");
-    if (ps_mode > RG_OPE_PS_ROW || (ps_mode == RG_OPE_PS_ARRAY && !d_ps && n_users))
-        return fail(RG_EINVAL, "rg_ope_replay: bad ps source");
-    if (n_users && (!d_rows || !d_offsets || !d_ratio)) return fail(RG_EINVAL, "rg_ope_replay: null rows / offsets / ratio");
-    if (!d_sums || !d_workspace) return fail(RG_EINVAL, "rg_ope_replay: null sums / workspace");
-    const size_t need = rg_ope_workspace_bytes(pol, n_users, max_user_rows);
-    if (workspace_bytes < need) return fail(RG_ENOMEM, "rg_ope_replay: workspace %zu < %zu bytes", workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(d_rows) % 16) return fail(RG_EINVAL, "rg_ope_replay: rows not 16-byte aligned");
-    const uint32_t W = ope_waves(n_users);
+    if (int rc = ope_args_ok("rg_ope_replay", ps_mode, d_ps, n_users, d_rows, d_offsets, d_ratio, d_sums, d_workspace, workspace_bytes,
+                             rg_ope_workspace_bytes(pol, n_users, max_user_rows)))
+        return rc;
+    const uint32_t W = ope_waves(n_users, kOpeMaxWaves);
     const uint32_t l = ope_global_log2(pol, max_user_rows);
     double* slots = static_cast<double*>(d_workspace);
     uint32_t* gtab = l ? reinterpret_cast<uint32_t*>(static_cast<char*>(d_workspace) + ope_slot_bytes(W)) : nullptr;
@@ -292,7 +249,5 @@ extern "C" int rg_ope_replay(const rg_ope_policy* pol, const rg_event* d_rows, c
     hipLaunchKernelGGL(k_ope_replay, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *pol, d_rows, d_offsets, n_users, ps_mode,
                        d_ps, ps_const, d_ratio, d_click, slots, gtab, l, W);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_ope_reduce, dim3(1), dim3(256), 0, s, slots, W, d_sums);
-    HIP_TRY(hipGetLastError());
-    return RG_OK;
+    return ope_reduce(slots, W, d_sums, s);
 }

@@ -1,9 +1,8 @@
 // rg_ope_logreg.hip — off-policy evaluation replay of the frozen LogReg policy (LogregFrozenAgent / LogregMulticlassIpsAgent,
 // reference agents/logreg_ips.py:60-87) over a sorted device log: pi(a | the user's views so far) / ps for every bandit row.
 //
-// The skeleton is rg_ope.hip's: one wave per user, users assigned statically (wave w takes users w, w + W, ...), rows in
-// coalesced 64-row chunks, per-wave partial sums and a fixed-order one-block reduction — the same bits on every run, no float
-// atomics.  What differs is the state a user carries and the act:
+// The skeleton is rg_ope_common.hpp's (one wave per user, 64-row chunks, per-wave sums and the fixed-order reduction).  What is
+// this unit's own is the state a user carries and the act:
 //
 // History.  The user's views are a (product, count) list in ASCENDING PRODUCT ORDER (the float64 walk adds the terms of a class
 // in that order, as scipy's CSR x dense product does).  An organic row inserts or increments:
@@ -24,13 +23,12 @@
 //                 the xor butterfly, e / sum — k_logreg_sample's arithmetic and decomposition, so a log the step loop wrote
 //                 under the same model replays to ratios of exactly 1.  Classes 0 .. P-1, P <= 1024: the scores of a lane's
 //                 (at most 16) classes stay in registers.
-#include "rg_common.hpp"
+#include "rg_ope_common.hpp"
 
 namespace {
 
 typedef unsigned long long lr_u64;
 
-constexpr int kLrWaves = 4;                      // waves per block
 constexpr uint32_t kLrRegs = 64;                 // entries of the register list
 constexpr uint32_t kLrLds = 512;                 // entries of the per-wave LDS list (4 KiB per wave, 16 KiB per block)
 constexpr uint32_t kLrMaxWaves = 4096;           // 256 CUs x 16 waves
@@ -42,13 +40,8 @@ constexpr uint32_t kLrFp32MaxTerms = 1u << 16;   // longer histories go to the f
 constexpr lr_u64 kLrErrFirstBandit = 1, kLrErrIndex = 2, kLrErrRows = 4;
 constexpr int kLrWsErr = 0, kLrWsActs = 1, kLrWsExact = 2, kLrWsRowsRead = 3, kLrWsWords = 32;
 
-uint32_t lr_waves(uint64_t n_users) {
-    const uint64_t w = (n_users + kLrWaves - 1) / kLrWaves * kLrWaves;
-    return static_cast<uint32_t>(w < kLrWaves ? kLrWaves : (w > kLrMaxWaves ? kLrMaxWaves : w));
-}
 // entries of a wave's global list (0: no user can outgrow the LDS list)
 uint32_t lr_global_cap(uint32_t max_user_rows) { return max_user_rows > kLrLds ? max_user_rows : 0u; }
-size_t lr_slot_bytes(uint32_t n_waves) { return (static_cast<size_t>(n_waves) * 3 * sizeof(double) + 255) & ~size_t(255); }
 size_t lr_head_bytes() { return kLrWsWords * sizeof(lr_u64); }
 
 __device__ __forceinline__ lr_u64 lr_below(uint32_t lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }
@@ -57,10 +50,6 @@ __device__ __forceinline__ uint32_t lr_lane_value(uint32_t x, uint32_t lane) {
 }
 __device__ __forceinline__ uint32_t lr_uniform(uint32_t x) {
     return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(x)));
-}
-__device__ __forceinline__ double lr_wave_sum(double x) {
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
 }
 __device__ __forceinline__ double lr_wave_max(double x) {
     for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o));
@@ -257,7 +246,7 @@ __device__ __forceinline__ void lr_soft(const rg_ope_logreg& m, const LrHist<T>&
         const uint32_t c = 64u * j + lane;
         if (c < C) { const double e = exp(ev[j] - mx); ev[j] = e; sum += e; }
     }
-    esum = lr_wave_sum(sum);
+    esum = wave_sum(sum);
 }
 
 __global__ void k_lr_init(lr_u64* __restrict__ ws) {
@@ -280,20 +269,21 @@ __global__ __launch_bounds__(256) void k_lr_check(const rg_event* __restrict__ r
 }
 
 template <bool kSoft>
-__global__ __launch_bounds__(64 * kLrWaves, kSoft ? 2 : 4) void k_ope_logreg(
+__global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
     rg_ope_logreg m, const rg_event* __restrict__ rows, const int64_t* __restrict__ offsets, uint64_t n_users, uint32_t ps_mode,
     const double* __restrict__ ps64, double ps_const, double* __restrict__ ratio, uint8_t* __restrict__ click,
     double* __restrict__ slots, uint32_t* __restrict__ gscr, uint32_t g_cap, lr_u64* __restrict__ ws, uint32_t n_waves) {
-    __shared__ uint32_t s_p[kLrWaves][kLrLds];
-    __shared__ uint32_t s_c[kLrWaves][kLrLds];
+    __shared__ uint32_t s_p[kOpeWaves][kLrLds];
+    __shared__ uint32_t s_c[kOpeWaves][kLrLds];
     const uint32_t lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    const uint32_t wave = blockIdx.x * kLrWaves + wib;
+    const uint32_t wave = blockIdx.x * kOpeWaves + wib;
     uint32_t* const lp = s_p[wib];
     uint32_t* const lc = s_c[wib];
     uint32_t* const gp = g_cap ? gscr + static_cast<size_t>(wave) * 2 * g_cap : nullptr;
     uint32_t* const gc = gp + g_cap;
     const uint32_t P = m.num_products;
-    double acc_n = 0.0, acc_cr = 0.0, acc_r = 0.0;
+    const OpeLog log{rows, offsets, n_users, ps_mode, ps64, ps_const, ratio, click, slots, n_waves};
+    OpeAcc acc;
     lr_u64 c_acts = 0, c_exact = 0, c_rows = 0, err = 0;
 
     for (uint64_t user = wave; user < n_users; user += n_waves) {
@@ -306,14 +296,10 @@ __global__ __launch_bounds__(64 * kLrWaves, kSoft ? 2 : 4) void k_ope_logreg(
         for (int j = 0; j < kLrSoftBlocks; ++j) ev[j] = 0.0;
 
         for (int64_t base = b; base < e; base += 64) {
-            const int64_t row = base + lane;
-            const bool live = row < e;
-            uint4 x = make_uint4(0u, 0u, 0u, 0u);
-            if (live) x = reinterpret_cast<const uint4*>(rows)[row];
-            const uint32_t idx = x.z & RG_EV_INDEX_MASK;
-            const bool ok = live && idx < P;          // (the validation pass has refused such a log: never index the model)
-            const bool isb = ok && (x.z & RG_EV_BANDIT);
-            const bool iso = ok && !(x.z & RG_EV_BANDIT);
+            const OpeRow r = ope_load(log, base, e, lane);
+            const uint32_t idx = r.idx;
+            const bool ok = idx < P;                  // (the validation pass has refused such a log: never index the model)
+            const bool isb = ok && r.isb, iso = ok && r.iso;
             const lr_u64 omask = __ballot(iso), bmask = __ballot(isb);
             double pi = 0.0;
             lr_u64 rem = omask | bmask;
@@ -395,25 +381,11 @@ __global__ __launch_bounds__(64 * kLrWaves, kSoft ? 2 : 4) void k_ope_logreg(
                 }
                 rem &= end < 64 ? ~lr_below(end) : 0ull;
             }
-            if (isb) {
-                const double ps = ps_mode == RG_OPE_PS_ARRAY ? ps64[row]
-                                  : ps_mode == RG_OPE_PS_CONST ? ps_const : static_cast<double>(__uint_as_float(x.w));
-                const double r = pi / ps;
-                ratio[row] = r;
-                if (click) click[row] = (x.z & RG_EV_CLICK) ? 1 : 0;
-                acc_n += 1.0;
-                acc_cr += ((x.z & RG_EV_CLICK) ? 1.0 : 0.0) * r;
-                acc_r += r;
-            }
+            if (isb) acc.emit(log, r, pi);
         }
     }
-    acc_n = lr_wave_sum(acc_n);
-    acc_cr = lr_wave_sum(acc_cr);
-    acc_r = lr_wave_sum(acc_r);
+    acc.store(log, wave, lane);
     if (lane == 0) {
-        slots[3 * static_cast<size_t>(wave) + 0] = acc_n;
-        slots[3 * static_cast<size_t>(wave) + 1] = acc_cr;
-        slots[3 * static_cast<size_t>(wave) + 2] = acc_r;
         if (c_acts) {
             (void)__hip_atomic_fetch_add(&ws[kLrWsActs], c_acts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             (void)__hip_atomic_fetch_add(&ws[kLrWsRowsRead], c_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -421,23 +393,6 @@ __global__ __launch_bounds__(64 * kLrWaves, kSoft ? 2 : 4) void k_ope_logreg(
         }
         if (err) (void)__hip_atomic_fetch_or(&ws[kLrWsErr], err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-}
-
-// the per-wave slots -> (n, sum c r, sum r), one block, fixed order (k_ope_reduce's scheme)
-__global__ __launch_bounds__(256) void k_lr_reduce(const double* __restrict__ slots, uint32_t n_waves, double* __restrict__ out) {
-    __shared__ double sh[3][256];
-    double a[3] = {0.0, 0.0, 0.0};
-    for (uint32_t i = threadIdx.x; i < n_waves; i += 256)
-        for (int j = 0; j < 3; ++j) a[j] += slots[3 * static_cast<size_t>(i) + j];
-    for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] = a[j];
-    __syncthreads();
-    for (uint32_t s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s)
-            for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0)
-        for (int j = 0; j < 3; ++j) out[j] = sh[j][0];
 }
 
 int lr_model_ok(const rg_ope_logreg* m, const char* who) {
@@ -457,21 +412,17 @@ int lr_model_ok(const rg_ope_logreg* m, const char* who) {
 
 extern "C" size_t rg_ope_logreg_workspace_bytes(const rg_ope_logreg* m, uint64_t n_users, uint32_t max_user_rows) {
     if (!m) { fail(RG_EINVAL, "rg_ope_logreg_workspace_bytes: null model"); return 0; }
-    const uint32_t W = lr_waves(n_users);
-    return lr_head_bytes() + lr_slot_bytes(W) + static_cast<size_t>(W) * 2 * lr_global_cap(max_user_rows) * sizeof(uint32_t);
+    const uint32_t W = ope_waves(n_users, kLrMaxWaves);
+    return lr_head_bytes() + ope_slot_bytes(W) + static_cast<size_t>(W) * 2 * lr_global_cap(max_user_rows) * sizeof(uint32_t);
 }
 
 extern "C" int rg_ope_replay_logreg(const rg_ope_logreg* m, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
                                     uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
                                     uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream) {
     if (int rc = lr_model_ok(m, "rg_ope_replay_logreg")) return rc;
-    if (ps_mode > RG_OPE_PS_ROW || (ps_mode == RG_OPE_PS_ARRAY && !d_ps && n_users))
-        return fail(RG_EINVAL, "rg_ope_replay_logreg: bad ps source");
-    if (n_users && (!d_rows || !d_offsets || !d_ratio)) return fail(RG_EINVAL, "rg_ope_replay_logreg: null rows / offsets / ratio");
-    if (!d_sums || !d_workspace) return fail(RG_EINVAL, "rg_ope_replay_logreg: null sums / workspace");
-    const size_t need = rg_ope_logreg_workspace_bytes(m, n_users, max_user_rows);
-    if (workspace_bytes < need) return fail(RG_ENOMEM, "rg_ope_replay_logreg: workspace %zu < %zu bytes", workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(d_rows) % 16) return fail(RG_EINVAL, "rg_ope_replay_logreg: rows not 16-byte aligned");
+    if (int rc = ope_args_ok("rg_ope_replay_logreg", ps_mode, d_ps, n_users, d_rows, d_offsets, d_ratio, d_sums, d_workspace,
+                             workspace_bytes, rg_ope_logreg_workspace_bytes(m, n_users, max_user_rows)))
+        return rc;
     if (rg_device_count() <= 0) return fail(RG_ENODEV, "no HIP device");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (m->select_randomly) {
@@ -483,11 +434,11 @@ extern "C" int rg_ope_replay_logreg(const rg_ope_logreg* m, const rg_event* d_ro
             if (cls[c] != static_cast<int32_t>(c))
                 return fail(RG_EINVAL, "rg_ope_replay_logreg: select_randomly needs classes[c] == c (classes[%u] = %d)", c, cls[c]);
     }
-    const uint32_t W = lr_waves(n_users);
+    const uint32_t W = ope_waves(n_users, kLrMaxWaves);
     const uint32_t g_cap = lr_global_cap(max_user_rows);
     lr_u64* ws = static_cast<lr_u64*>(d_workspace);
     double* slots = reinterpret_cast<double*>(static_cast<char*>(d_workspace) + lr_head_bytes());
-    uint32_t* gscr = g_cap ? reinterpret_cast<uint32_t*>(static_cast<char*>(d_workspace) + lr_head_bytes() + lr_slot_bytes(W)) : nullptr;
+    uint32_t* gscr = g_cap ? reinterpret_cast<uint32_t*>(static_cast<char*>(d_workspace) + lr_head_bytes() + ope_slot_bytes(W)) : nullptr;
     hipLaunchKernelGGL(k_lr_init, dim3(1), dim3(64), 0, s, ws);
     HIP_TRY(hipGetLastError());
     if (n_users) {
@@ -505,13 +456,11 @@ extern "C" int rg_ope_replay_logreg(const rg_ope_logreg* m, const rg_event* d_ro
             return fail(RG_EINVAL, "rg_ope_replay_logreg: the log has a product or an action >= num_products %u; nothing was written", m->num_products);
     }
     if (m->select_randomly)
-        hipLaunchKernelGGL(k_ope_logreg<true>, dim3(W / kLrWaves), dim3(64 * kLrWaves), 0, s, *m, d_rows, d_offsets, n_users, ps_mode,
+        hipLaunchKernelGGL(k_ope_logreg<true>, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, d_rows, d_offsets, n_users, ps_mode,
                            d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W);
     else
-        hipLaunchKernelGGL(k_ope_logreg<false>, dim3(W / kLrWaves), dim3(64 * kLrWaves), 0, s, *m, d_rows, d_offsets, n_users, ps_mode,
+        hipLaunchKernelGGL(k_ope_logreg<false>, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, d_rows, d_offsets, n_users, ps_mode,
                            d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_lr_reduce, dim3(1), dim3(256), 0, s, slots, W, d_sums);
-    HIP_TRY(hipGetLastError());
-    return RG_OK;
+    return ope_reduce(slots, W, d_sums, s);
 }

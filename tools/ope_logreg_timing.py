@@ -7,10 +7,12 @@
      same arithmetic.
 Reported: ms per act of the replay and of the step loop.  Warm-up, then device events (profiler off).
 Kernel times: run under `rocprofv3 --kernel-trace --stats -- python tools/ope_logreg_timing.py` (no counters in the same run).
+replay_sha256: the digests of the replay's ratios and of its three sums (two builds of the library compute the same: equal digests).
 Prints one JSON line; with --out the line is appended to that file (profiles/ope/ope_logreg_timing.txt).
 
     python tools/ope_logreg_timing.py [--users N] [--products P] [--reps R] [--out FILE]"""
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -68,7 +70,10 @@ def main():
     dev = dl.rows.device
     pol['logreg'] = dict(pol['logreg'], **{k: torch.as_tensor(pol['logreg'][k]).to(dev) for k in ('coef_t', 'intercept', 'classes')})
     st = {}
-    res['replay_ms'], _ = timed(lambda: ev.ope_replay(lr, dl, pol, stats=st), args.reps)
+    res['replay_ms'], out = timed(lambda: ev.ope_replay(lr, dl, pol, stats=st), args.reps)
+    res['replay_sha256'] = dict(ratio=hashlib.sha256(out[0].cpu().numpy().tobytes()).hexdigest(),
+                                sums=hashlib.sha256(out[2].cpu().numpy().tobytes()).hexdigest())
+    del out
     res['replay_acts'], res['replay_exact'], res['replay_rows_read'] = st['acts'], st['exact'], st['rows_read']
     # (the fp32 copy and the certificate's bounds are derived per call: timed alone, subtracted below)
     res['model_prep_ms'], _ = timed(lambda: ev._logreg_model(pol['logreg'], P, dev), args.reps)
