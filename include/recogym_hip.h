@@ -182,6 +182,17 @@ int rg_sim_destroy(rg_sim* sim);
  * of a step the frozen-LogReg fp16 screen takes; can only be lowered), sweep_lds (1: the unsliced sweep of a run whose draws are
  * not cached keeps its tile prefixes in LDS and searches them there, k_draw_tp; 0: k_draw_bf16p's scratch + search), debug.
  * Read-only: sweep_lds_kernel (1 where k_draw_tp serves the configuration).
+ * Read-only, a test hook — the LAUNCH LEDGER: launched_<family> = launches of that kernel family since rg_sim_create, counted on
+ * the host next to each launch.  Families: draw_f64 (the float64 kernels as the sweep of every organic user), draw_fp32
+ * (k_draw_mfma), draw16_fused / draw16_sliced (k_draw_bf16 / k_draw_bf16p / k_draw_f16w as one sweep with the search fused in /
+ * over product slices), search (k_draw_search behind the slices), draw_tp (k_draw_tp / k_draw_tpw), pick (k_pick), draw_cached
+ * (k_draw_cached), sweep_xh (k_sweep_xh), exact_m / exact_tile / exact_h (the float64 sums: a user per lane / a product per lane /
+ * the walk's mixed batch), walk (k_walk), walk2 (k_walk2), walk_solo (k_walk_solo), advance (k_advance), advance_run
+ * (k_advance_run), tail (k_tail), repack, env0 (k_draw_env0), logreg_screen, logreg_acts, logreg_sample, sort_tiled / sort_plain
+ * (the ordered log's scatter).  What rg_sim_create chose for the fast draw: draw_kh, draw_n1 (the class: KH, k-steps N1),
+ * draw_split (0 none, 1 three-way bf16, 2 two-way fp16, 3 two-way fp16 wide), draw_kernel (0 float64 only, 1 fp32 MFMA, 2 a 16-bit
+ * sweep), draw_pipelined (1: that sweep is k_draw_bf16p), xh_class (100 KH + 10 NH + NL of k_sweep_xh where it serves the walked
+ * run, else 0) and xh_waves (its waves per block, else 0).  Setting any of them fails like an unknown name.
  * RG_EINVAL for an unknown name or a value out of range. */
 int rg_sim_set_option(rg_sim* sim, const char* name, int64_t value);
 int rg_sim_get_option(rg_sim* sim, const char* name, int64_t* value);

@@ -325,8 +325,23 @@ struct RunOpts {
     unsigned long long repack_min;   // RECOGYM_REPACK_MIN: users below which slot == user index throughout
 };
 
+// The launch ledger (a test hook, host side only): launches per kernel family since rg_sim_create, each counted next to its
+// hipLaunchKernelGGL and read through rg_sim_get_option as launched_<family>.  A test that forces a path through a switch reads it
+// to prove that the named kernel served the run (with the float64 resolve behind every draw a run on another kernel still passes).
+#define RG_LEDGER_FAMILIES(X) \
+    X(draw_f64) X(draw_fp32) X(draw16_fused) X(draw16_sliced) X(search) X(draw_tp) X(pick) X(draw_cached) \
+    X(sweep_xh) X(exact_m) X(exact_tile) X(exact_h) X(walk) X(walk2) X(walk_solo) \
+    X(advance) X(advance_run) X(tail) X(repack) X(env0) X(logreg_screen) X(logreg_acts) X(logreg_sample) \
+    X(sort_tiled) X(sort_plain)
+struct Ledger {
+#define RG_LEDGER_FIELD(f) uint64_t f = 0;
+    RG_LEDGER_FAMILIES(RG_LEDGER_FIELD)
+#undef RG_LEDGER_FIELD
+};
+
 struct rg_sim {
     rg_config cfg;
+    Ledger led;
     DevSim d;
     RunOpts opt;
     void* workspace;

@@ -620,9 +620,11 @@ void launch_exact(rg_sim* sim, uint32_t t, int from_list, uint64_t est, hipStrea
         if (exact_m_kernel_t km = (sim->opt.exact_tile ? nullptr : exact_m_kernel_for(d.XKB))) {
             if (!from_list) {
                 launch_exact_m(km, d, t, 0, 0, est, st);
+                sim->led.exact_m += 1; sim->led.draw_f64 += 1;
                 hipLaunchKernelGGL(exact_ref_kernel(), dim3(grid_for(est, kBlock / 64)), dim3(kBlock), 0, st, d, t, 1u);
             }
             launch_exact_m(km, d, t, from_list, 1, est, st);
+            sim->led.exact_m += 1;
             hipLaunchKernelGGL(exact_pick_kernel(), dim3(grid_for(est, kBlock / 64)), dim3(kBlock),
                                sizeof(double) * d.K * (kBlock / 64), st, d, t, from_list, 1u);
             continue;
@@ -635,9 +637,11 @@ void launch_exact(rg_sim* sim, uint32_t t, int from_list, uint64_t est, hipStrea
         const size_t smem = sizeof(double) * (static_cast<size_t>(d.K) * 64 + 64 + kExactUsers * d.K);
         if (!from_list) {
             hipLaunchKernelGGL(exact_tile_kernel(), dim3(grid), dim3(kBlock), smem, st, d, t, 0, 0, S);
+            sim->led.exact_tile += 1; sim->led.draw_f64 += 1;
             hipLaunchKernelGGL(exact_ref_kernel(), dim3(grid_for(est, kBlock / 64)), dim3(kBlock), 0, st, d, t, 8u);
         }
         hipLaunchKernelGGL(exact_tile_kernel(), dim3(grid), dim3(kBlock), smem, st, d, t, from_list, 1, S);
+        sim->led.exact_tile += 1;
         hipLaunchKernelGGL(exact_pick_kernel(), dim3(grid_for(est, kBlock / 64)), dim3(kBlock),
                            sizeof(double) * d.K * (kBlock / 64), st, d, t, from_list, 8u);
     }
@@ -672,6 +676,7 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         DevSim& m = sim->d;
         hipLaunchKernelGGL(k_repack_copy, dim3(grid_for(upper, kBlock / 32)), dim3(kBlock), 0, st, m, t);
         hipLaunchKernelGGL(k_repack_lists, dim3(grid_for(upper)), dim3(kBlock), 0, st, m, t);
+        sim->led.repack += 1;
         std::swap(m.omega, m.omega_alt); std::swap(m.hist, m.hist_alt); std::swap(m.uid, m.uid_alt);
         if (m.lpv) std::swap(m.lpv, m.lpv_alt);
         sim->repacked = true;
@@ -681,6 +686,7 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
     // 1. organic product draws of this step (read omega before the transition drifts it)
     if (d.env_kind) {          // reco-gym-v0: a table look-up per organic user
         hipLaunchKernelGGL(k_draw_env0, dim3(grid_for(upper)), dim3(kBlock), 0, st, d, t);
+        sim->led.env0 += 1;
         if (int rc = prof_mark(sim, st)) return rc;
         if (int rc = prof_mark(sim, st)) return rc;
     } else if (d.use_mfma == 2 && d.use_cache && t > 0) {
@@ -688,6 +694,7 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         if (int rc = prof_mark(sim, st)) return rc;
         hipLaunchKernelGGL(cached_kernel_for(d), dim3(grid_for(upper, kBlock)), dim3(kBlock),
                            sizeof(float) * (kBlock / 64) * 64 * 2 * d.KH, st, d, t);
+        sim->led.draw_cached += 1;
         if (int rc = prof_mark(sim, st)) return rc;
         launch_exact(sim, t, 1, upper / 100 + 16, st);
     } else if (d.use_mfma == 2) {
@@ -701,9 +708,11 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         // (the search stays at the end of every user tile of the sweep: as its own kernel over the whole step — scratch slot
         // per user tile — the sweep got 15 % shorter and the step 6 % longer: profiles/r3/ab_call26_*, ab_call27_*)
         const bool tp = S == 1 && sim->tp_kernel && sim->sweep_lds && !d.use_cache;
-        if (tp) hipLaunchKernelGGL(sim->tp_kernel, dim3(grid), dim3(kBlock), sim->tp_smem, st, d, t, sim->tp_nts);
-        else
+        if (tp) { hipLaunchKernelGGL(sim->tp_kernel, dim3(grid), dim3(kBlock), sim->tp_smem, st, d, t, sim->tp_nts); sim->led.draw_tp += 1; }
+        else {
         hipLaunchKernelGGL(sim->bf16_kernel, dim3(grid), dim3(sim->draw_threads), sim->bf16_smem, st, d, t, S);
+        (S > 1 ? sim->led.draw16_sliced : sim->led.draw16_fused) += 1;
+        }
         if (int rc = prof_mark(sim, st)) return rc;
         if (tp) {
             // k_pick: a wave per 32 draws of one tile (the sweep listed the draws by tile), grid-stride over the groups
@@ -713,10 +722,13 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
             const uint32_t pcap = static_cast<uint32_t>(device_cus(sim)) * 4u;
             if (pgrid > pcap) pgrid = pcap;
             hipLaunchKernelGGL(sim->pick_kernel, dim3(pgrid), dim3(kBlock), psmem, st, d, t, 0u);
+            sim->led.pick += 1;
         }
-        if (S > 1)
+        if (S > 1) {
             hipLaunchKernelGGL(search_kernel_for(d), dim3(grid_for(upper, 128)), dim3(kBlock),
                                sizeof(float) * 4 * 32 * 2 * d.KH, st, d, t);
+            sim->led.search += 1;
+        }
         if (d.use_cache)       // step 0 of a sigma_omega == 0 run: the rows every later draw starts from
             hipLaunchKernelGGL(finalize_kernel_for(d), dim3(grid_for(d.n_users)), dim3(kBlock), 0, st, d);
         if (int rc = prof_mark(sim, st)) return rc;
@@ -725,6 +737,7 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         const int grid = grid_for(upper, 128);
         const size_t smem = sim->mfma_smem;
         hipLaunchKernelGGL(mfma_kernel_for(d.KH), dim3(grid), dim3(kBlock), smem, st, d, t);
+        sim->led.draw_fp32 += 1;
         if (int rc = prof_mark(sim, st)) return rc;
         if (int rc = prof_mark(sim, st)) return rc;
         // draws the fp32 path could not certify -> float64 (a few percent of the organic users)
@@ -738,9 +751,10 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
     if (d.policy == RG_POLICY_LOGREG_FROZEN) {
         // acts of the users whose view history changed since their last one (frozen LogReg at scale)
         hipLaunchKernelGGL(logreg_select_kernel(), dim3(grid_for(upper)), dim3(kBlock), 0, st, d, t);
-        if (d.lr_sample)           // select_randomly: a softmax and a draw per act (a wave each)
+        if (d.lr_sample) {         // select_randomly: a softmax and a draw per act (a wave each)
             hipLaunchKernelGGL(logreg_sample_kernel(), dim3(grid_for(static_cast<uint64_t>(upper) + 64, kBlock / 64)), dim3(kBlock), 0, st, d, t);
-        else if (d.lr_coef16_t) {       // screen (a wave per act and class range), then decide (a wave per act)
+            sim->led.logreg_sample += 1;
+        } else if (d.lr_coef16_t) {       // screen (a wave per act and class range), then decide (a wave per act)
             // (the number of acts is only known on the device — at most a quarter of the live users, usually a fiftieth: the kernels
             // walk their lists grid-stride, and the grids are capped at a few blocks per CU.  Sized for the worst case they were
             // mostly blocks that start and leave — and k_logreg_decide's three counter atomics per WAVE, one act each, were all of
@@ -752,20 +766,27 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
             };
             hipLaunchKernelGGL(logreg_screen_kernel(), dim3(capped((static_cast<uint64_t>(upper) / 4 + 64) * kLrSplit, 16)),
                                dim3(kBlock), 0, st, d, t);
+            sim->led.logreg_screen += 1;
             hipLaunchKernelGGL(logreg_decide_kernel(), dim3(capped(static_cast<uint64_t>(upper) / 4 + 64, 8)), dim3(kBlock), 0, st, d, t);
-            if (upper > d.lr_part_cap)     // the step may list more acts than the screen's scratch has rows: the rest in fp32 / float64
+            if (upper > d.lr_part_cap) {   // the step may list more acts than the screen's scratch has rows: the rest in fp32 / float64
                 hipLaunchKernelGGL(logreg_acts_kernel(), dim3(capped(static_cast<uint64_t>(upper - d.lr_part_cap) / 4 + 64, 8)), dim3(kBlock), 0, st, d, t);
+                sim->led.logreg_acts += 1;
+            }
         } else {
             const int g = grid_for(static_cast<uint64_t>(upper) / 4 + 64, kBlock / 64), cap = device_cus(sim) * 8;
             hipLaunchKernelGGL(logreg_acts_kernel(), dim3(g < cap ? g : cap), dim3(kBlock), 0, st, d, t);
+            sim->led.logreg_acts += 1;
         }
     }
     if (int rc = prof_mark(sim, st)) return rc;
     // 2. click draws, transitions, drift, next lists, bandit + phantom rows
-    if (d.run_ahead)       // a round: every listed user through its bandit run (k_advance_run), then the round's raw-log books
+    if (d.run_ahead) {     // a round: every listed user through its bandit run (k_advance_run), then the round's raw-log books
         hipLaunchKernelGGL(advance_run_kernel(d.eg_on != 0u), dim3(grid_for(upper, kAdvBlock)), dim3(kAdvBlock), 0, st, d, t, d.run_ahead);
-    else
+        sim->led.advance_run += 1;
+    } else {
         hipLaunchKernelGGL(advance_kernel(d.eg_on != 0u), dim3(grid_for(upper, kAdvBlock)), dim3(kAdvBlock), 0, st, d, t, d_actions);
+        sim->led.advance += 1;
+    }
     if (d.sigma_omega != 0.0)
         hipLaunchKernelGGL(drift_kernel(), dim3(grid_for(static_cast<uint64_t>(upper) * ((d.K + 1) / 2))), dim3(kBlock), 0, st, d, t);
     if (d.run_ahead) hipLaunchKernelGGL(round_rows_kernel(), dim3(1), dim3(1), 0, st, d, t, 0u);
@@ -822,6 +843,7 @@ int run_walk(rg_sim* sim, hipStream_t st) {
         ds.sweep_only = fused_prefix ? 2u : 1u;
         const int grid = sweep_grid(sim, static_cast<uint64_t>(tiles_up) * S);
         hipLaunchKernelGGL(sim->bf16_kernel, dim3(grid), dim3(sim->draw_threads), sim->bf16_smem, st, ds, 0u, S);
+        (S > 1 ? sim->led.draw16_sliced : sim->led.draw16_fused) += 1;
     }
     if (int rc = mark(1)) return rc;
     hipLaunchKernelGGL(finalize_kernel_for(d), dim3(grid_for(d.n_users)), dim3(kBlock), 0, st, d);
@@ -849,6 +871,7 @@ int run_walk(rg_sim* sim, hipStream_t st) {
         if (smem > 64 * 1024)
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wk), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
         hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, d, n_work, round, static_cast<uint32_t>(chunk), in_base, out_base);
+        (sim->walk2 ? sim->led.walk2 : sim->led.walk) += 1;
     };
     launch_walk(d.n_users, 1, 0u, 0u);
     if (int rc = mark(3)) return rc;
@@ -889,6 +912,7 @@ int run_walk(rg_sim* sim, hipStream_t st) {
                 if (chunk < 64) chunk = 64;
                 if (chunk > 1024) chunk = 1024;
                 hipLaunchKernelGGL(sk, dim3(blocks), dim3(kBlock), 0, st, d, n_left, static_cast<uint32_t>(chunk), base3);
+                sim->led.walk_solo += 1;
             } else launch_walk(n_left, 3, base3, base3);
         }
         return RG_OK;
@@ -901,12 +925,14 @@ int run_walk(rg_sim* sim, hipStream_t st) {
             const uint32_t groups = (n_park + 255u) / 256u;
             const uint32_t grid = groups < 1024u ? groups : 1024u;
             hipLaunchKernelGGL(kh, dim3(grid), dim3(kBlock), exact_m_lds(d.XKB), st, d, n_park, mfma_of_8);
+            sim->led.exact_h += 1;
             if (int rc = mark(4)) return rc;
             if (int rc = later_rounds(n_park)) return rc;
             goto walked;
         }
         if (exact_m_kernel_t km = exact_m_kernel_for(d.XKB)) {
             launch_exact_m(km, d, n_park, 2, 1, n_park, st);
+            sim->led.exact_m += 1;
             if (int rc = mark(4)) return rc;
             if (int rc = later_rounds(n_park)) return rc;
             goto walked;
@@ -997,9 +1023,11 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         ds.fin_in_sweep = dg.fin_in_sweep = sim->fin_in_sweep ? 1u : 0u;
         const uint32_t tiles_up = (n + sim->draw_users - 1) / sim->draw_users;
         if (int rc = span_begin(0)) return rc;
-        if (sim->xh_kernel) hipLaunchKernelGGL(sim->xh_kernel, dim3(grid_for((n + 32u * sim->xh_waves - 1) / (32u * sim->xh_waves), 1)), dim3(64 * sim->xh_waves), sim->xh_smem, st, ds, 0u, 1u);
-        else
+        if (sim->xh_kernel) { hipLaunchKernelGGL(sim->xh_kernel, dim3(grid_for((n + 32u * sim->xh_waves - 1) / (32u * sim->xh_waves), 1)), dim3(64 * sim->xh_waves), sim->xh_smem, st, ds, 0u, 1u); sim->led.sweep_xh += 1; }
+        else {
         hipLaunchKernelGGL(sim->bf16_kernel, dim3(sweep_grid(sim, tiles_up)), dim3(sim->draw_threads), sim->bf16_smem, st, ds, 0u, 1u);
+        sim->led.draw16_fused += 1;
+        }
         if (int rc = span_end()) return rc;
         if (int rc = span_begin(1)) return rc;
         hipLaunchKernelGGL(finalize_kernel_for(d), dim3(grid_for(n)), dim3(kBlock), 0, st, dg);
@@ -1015,6 +1043,7 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         if (blocks > static_cast<int>(kMaxWalkWaves / 4)) blocks = kMaxWalkWaves / 4;
         if (int rc = span_begin(2)) return rc;
         hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, dw, n, 1, walk_chunk(n, blocks), 0u, region);
+        sim->led.walk2 += 1;
         if (int rc = span_end()) return rc;
     }
     // ---- the users it parked: float64 sums, prefixes, round 2 (what it hands over: the last round's list) ----
@@ -1026,6 +1055,7 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         if (xgrid > static_cast<uint32_t>(sim->pipe_xblocks)) xgrid = static_cast<uint32_t>(sim->pipe_xblocks);
         if (int rc = span_begin(3)) return rc;
         hipLaunchKernelGGL(kh, dim3(xgrid), dim3(kBlock), exact_m_lds(d.XKB), st, dx, n, mfma_of_8);
+        sim->led.exact_h += 1;
         hipLaunchKernelGGL(exact_prefix_kernel(), dim3(grid_for(est, kBlock / 64)), dim3(kBlock), 0, st, dx, n);
         if (int rc = span_end()) return rc;
         DevSim dr = dg;
@@ -1035,6 +1065,7 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         if (blocks > static_cast<int>(kMaxWalkWaves / 4)) blocks = kMaxWalkWaves / 4;
         if (int rc = span_begin(4)) return rc;
         hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, dr, n, 2, walk_chunk(est, blocks), region, base_solo);
+        sim->led.walk2 += 1;
         if (int rc = span_end()) return rc;
     }
     // ---- last round: a wave per user (k_walk_solo) over what round 2 handed over ----
@@ -1052,6 +1083,7 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         if (chunk > 1024) chunk = 1024;
         if (int rc = span_begin(4)) return rc;
         hipLaunchKernelGGL(sk, dim3(blocks), dim3(kBlock), 0, st, dl, n, static_cast<uint32_t>(chunk), base_solo);
+        sim->led.walk_solo += 1;
         if (int rc = span_end()) return rc;
     }
     hipLaunchKernelGGL(k_walk_finish, dim3(1), dim3(1), 0, st, d);
@@ -1430,6 +1462,17 @@ int rg_sim_set_option(rg_sim* sim, const char* name, int64_t value) {
 int rg_sim_get_option(rg_sim* sim, const char* name, int64_t* value) {
     if (!sim || !name || !value) return fail(RG_EINVAL, "NULL argument");
     if (!strcmp(name, "sweep_lds_kernel")) { *value = sim->tp_kernel ? 1 : 0; return RG_OK; }     // read-only: k_draw_tp serves the configuration
+    // read-only: the launch ledger (launched_<family>) and what rg_sim_create chose for the fast draw
+#define RG_LEDGER_GET(f) if (!strcmp(name, "launched_" #f)) { *value = static_cast<int64_t>(sim->led.f); return RG_OK; }
+    RG_LEDGER_FAMILIES(RG_LEDGER_GET)
+#undef RG_LEDGER_GET
+    if (!strcmp(name, "draw_kh")) { *value = sim->d.KH; return RG_OK; }
+    if (!strcmp(name, "draw_n1")) { *value = sim->d.N1; return RG_OK; }
+    if (!strcmp(name, "draw_split")) { *value = !sim->d.N1 ? 0 : (!sim->d.f16 ? 1 : (sim->d.wide ? 3 : 2)); return RG_OK; }
+    if (!strcmp(name, "draw_kernel")) { *value = sim->d.use_mfma; return RG_OK; }
+    if (!strcmp(name, "draw_pipelined")) { *value = (sim->bf16_kernel && sim->bf16_kernel == bf16p_kernel_for(sim->d)) ? 1 : 0; return RG_OK; }
+    if (!strcmp(name, "xh_waves")) { *value = sim->xh_kernel ? sim->xh_waves : 0; return RG_OK; }
+    if (!strcmp(name, "xh_class")) { *value = sim->xh_kernel ? static_cast<int64_t>(sim->d.KH * 100 + sim->d.XNH * 10 + sim->d.XNL) : 0; return RG_OK; }
     if (int* p = opt_int(sim, name)) { *value = *p; return RG_OK; }
     if (uint32_t* p = opt_u32(sim, name)) { *value = *p; return RG_OK; }
     return fail(RG_EINVAL, "unknown option '%s'", name);
@@ -1733,6 +1776,7 @@ int rg_sim_run(rg_sim* sim, uint32_t max_steps, void* stream) {
             }
             const int grid = static_cast<int>(live < 2048 ? live : 2048);
             hipLaunchKernelGGL(tail_kernel(sim->d.eg_on != 0u), dim3(grid), dim3(kBlock), tail_smem, st, sim->d, sim->t);
+            sim->led.tail += 1;
             hipLaunchKernelGGL(k_tail_finish, dim3(1), dim3(1), 0, st, sim->d, sim->t);
             HIP_TRY(hipGetLastError());
             if (sim->profiling) HIP_TRY(hipEventRecord(ev[1], st));
@@ -1949,9 +1993,12 @@ int rg_sim_sort_log(rg_sim* sim, int64_t* d_row_offsets, int64_t* d_scratch, rg_
         static const bool plain = getenv("RECOGYM_SORT_PLAIN") != nullptr;      // (A/B: the scatter without the LDS tiles)
         const uint64_t tiles = (n_rows + kSortTile - 1) / kSortTile;
         const uint64_t cap = static_cast<uint64_t>(device_cus(sim)) * 12u;
-        if (plain) hipLaunchKernelGGL(k_scatter_rows, dim3(grid_for(n_rows)), dim3(kBlock), 0, st, d, n_rows, d_row_offsets, d_sorted, sorted_capacity);
-        else hipLaunchKernelGGL(k_scatter_rows_tiled, dim3(static_cast<unsigned>(tiles < cap ? (tiles ? tiles : 1) : cap)), dim3(kBlock), 0, st, d, n_rows,
-                                d_row_offsets, d_sorted, sorted_capacity);
+        if (plain) { hipLaunchKernelGGL(k_scatter_rows, dim3(grid_for(n_rows)), dim3(kBlock), 0, st, d, n_rows, d_row_offsets, d_sorted, sorted_capacity); sim->led.sort_plain += 1; }
+        else {
+            hipLaunchKernelGGL(k_scatter_rows_tiled, dim3(static_cast<unsigned>(tiles < cap ? (tiles ? tiles : 1) : cap)), dim3(kBlock), 0, st, d, n_rows,
+                               d_row_offsets, d_sorted, sorted_capacity);
+            sim->led.sort_tiled += 1;
+        }
     }
     hipLaunchKernelGGL(k_scatter_phantom, dim3(grid_for(n)), dim3(kBlock), 0, st, d, d_row_offsets, d_sorted,
                        sorted_capacity);

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import adversarial_util as au
 import golden_util as gu
 from recogym_amd import _abi
 from recogym_amd.envs.configuration import Configuration
@@ -19,7 +20,8 @@ pytestmark = pytest.mark.gpu
 PCLICK_RTOL = 1e-12
 
 
-def run_sim(config, n_users, n_organic=0, first_user=0, **pol):
+def run_sim(config, n_users, n_organic=0, first_user=0, with_ledger=False, **pol):
+    """rows, counters[, the launch ledger: which kernel families served the run (adversarial_util.ledger)]"""
     from recogym_amd.sim import Simulator
     pol.setdefault('p_click', True)
     sim = Simulator(config, n_users + n_organic, device='cuda:0', **pol)
@@ -27,8 +29,16 @@ def run_sim(config, n_users, n_organic=0, first_user=0, **pol):
     sim.run()
     rows = sim.rows()
     cnt = sim.counters()
+    led = au.ledger(sim)
     sim.close()
-    return rows, cnt
+    return (rows, cnt, led) if with_ledger else (rows, cnt)
+
+
+def n_super_chunks(P):
+    """Product slices a sweep can be cut into (geom_of's n_sc): RECOGYM_SLICES above it still runs that many."""
+    n_chunks = ((P + 31) // 32 + 3) & ~3
+    sc_chunks = ((n_chunks + 31) // 32 + 3) & ~3
+    return (n_chunks + sc_chunks - 1) // sc_chunks
 
 
 @pytest.mark.parametrize('name', gu.fixtures('philox_'))
@@ -119,7 +129,8 @@ def test_env0_matches_the_oracle(shape):
            'ouc': dict(policy=_abi.RG_POLICY_ORGANIC_USER_COUNT, policy_seed=4, ouc=dict(gu.OUC_DEFAULTS))}[pk]
     want_env = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, env0=t0, **pol)
     want = want_env.generate_logs(n, n_org)
-    rows, cnt = run_sim(cfg, n, n_org, env0=t0, **pol)
+    rows, cnt, led = run_sim(cfg, n, n_org, with_ledger=True, env0=t0, **pol)
+    au.assert_draws_by(led, 'env0')
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps', 'p_click')}, ps_rtol=1e-12, what=f'env0 {shape}')
     assert (rows['phantom'] == want['phantom']).all()
     oc = want_env.counters()
@@ -132,7 +143,8 @@ def test_env0_matches_the_oracle(shape):
 def test_fp32_decided_clicks_match_the_oracle(case, lockstep, monkeypatch):
     """Without the click-probability export k_walk decides a click from an fp32 evaluation of
     ff(beta[a].omega + mu_b[a]) wherever its error margin allows and falls back to float64 inside the margin (measured
-    in k_advance too: no gain there, not kept): the logged clicks must be the oracle's, walked or in lock-step."""
+    in k_advance too: no gain there, not kept): the logged clicks must be the oracle's, walked or without the walk and the
+    tail kernel (`lockstep`: k_advance over the sum cache at sigma_omega = 0, k_advance_run's rounds otherwise)."""
     from oracle import oracle as orc
     over, n_users, n_org, pol = CASES[case]
     if lockstep:
@@ -140,7 +152,17 @@ def test_fp32_decided_clicks_match_the_oracle(case, lockstep, monkeypatch):
         monkeypatch.setenv('RECOGYM_TAIL', '0')
     cfg = Configuration({**env_1_args, **over})
     want = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol).generate_logs(n_users, n_org)
-    rows, cnt = run_sim(cfg, n_users, n_org, p_click=False, **pol)
+    rows, cnt, led = run_sim(cfg, n_users, n_org, p_click=False, with_ledger=True, **pol)
+    if lockstep:
+        # no walk, no tail kernel: sigma_omega = 0 (cases 5 and 15) keeps the per-user sum cache, which runs an event per launch
+        # (k_draw_cached + k_advance); the others go to the end in run-ahead rounds (k_advance_run, which holds the same decision)
+        assert led['walk'] == led['walk2'] == led['walk_solo'] == led['tail'] == 0, led
+        if cfg.sigma_omega == 0.0:
+            assert led['advance'] > 0 and led['draw_cached'] > 0 and led['advance_run'] == 0, led
+        else:
+            assert led['advance_run'] > 0 and led['advance'] == led['draw_cached'] == 0, led
+    elif cfg.sigma_omega == 0.0:      # (cases 5 and 15: the walked run, whose kernels hold the fp32 decision)
+        assert led['walk2'] > 0 and led['advance'] == led['advance_run'] == 0, led
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps')}, ps_rtol=1e-12,
                          what=f'fp32 clicks, case {case}, lockstep {lockstep}')
     assert cnt['clicks'] == int((want['c'] == 1).sum()) > 0
@@ -157,7 +179,8 @@ def test_repacked_state_matches_oracle(case, monkeypatch):
     over, n_users, n_org, pol = CASES[case]
     cfg = Configuration({**env_1_args, **over})
     want = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol).generate_logs(n_users, n_org)
-    rows, cnt = run_sim(cfg, n_users, n_org, **pol)
+    rows, cnt, led = run_sim(cfg, n_users, n_org, with_ledger=True, **pol)
+    assert led['repack'] > 0, led
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps')},
                          ps_rtol=1e-6, what=f'repacked case {case}')
     assert (rows['phantom'] == want['phantom']).all()
@@ -174,7 +197,14 @@ def test_lock_step_to_the_end_matches_oracle(case, monkeypatch):
     cfg = Configuration({**env_1_args, **over})
     want_env = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol)
     want = want_env.generate_logs(n_users, n_org)
-    rows, cnt = run_sim(cfg, n_users, n_org, **pol)
+    rows, cnt, led = run_sim(cfg, n_users, n_org, with_ledger=True, **pol)
+    # no tail kernel, no walk.  (Since the run-ahead rounds exist these runs go in ROUNDS to the end — k_advance_run — except case 4,
+    # whose bandit events move omega; an event per launch to the end is test_run_ahead_rounds_match_the_oracle[... hops = 0].)
+    assert led['tail'] == led['walk'] == led['walk2'] == 0, led
+    if over.get('change_omega_for_bandits'):
+        assert led['advance'] > 0 and led['advance_run'] == 0, led
+    else:
+        assert led['advance_run'] > 0 and led['advance'] == 0, led
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps')},
                          ps_rtol=1e-6, what=f'lock-step case {case}')
     oc = want_env.counters()
@@ -199,7 +229,9 @@ def test_run_ahead_rounds_match_the_oracle(case, hops, monkeypatch):
     cfg = Configuration({**env_1_args, **over})
     want_env = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol)
     want = want_env.generate_logs(n_users, n_org)
-    rows, cnt = run_sim(cfg, n_users, n_org, **pol)
+    rows, cnt, led = run_sim(cfg, n_users, n_org, with_ledger=True, **pol)
+    assert led['tail'] == led['walk'] == led['walk2'] == 0, led
+    assert (led['advance_run'] > 0 and led['advance'] == 0) if hops else (led['advance'] > 0 and led['advance_run'] == 0), led
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps', 'p_click')},
                          ps_rtol=1e-12, what=f'run-ahead {hops}, case {case}')
     assert (rows['phantom'] == want['phantom']).all()
@@ -216,12 +248,22 @@ def test_run_ahead_rounds_match_the_oracle(case, hops, monkeypatch):
 def test_run_ahead_rounds_reproduce_reference_fixtures(name, hops, tail, monkeypatch):
     """The same against logs of the unmodified reference: per-user clocks (NormalTimeGenerator: the clock and the drift's scale move
     with every event of a run), the frozen LogReg act (one act serves a whole bandit run), the last-viewed-product table, the wide
-    sweep; with the tail kernel taking over from the rounds (default) and without."""
+    sweep; with the default hand-over to the per-user tail kernel and with RECOGYM_TAIL=0.  By default k_tail takes over at the
+    first poll (16 launches) in philox_bandit_mf and philox_random_agent only: per-user clocks (both normal_time fixtures), the
+    frozen LogReg policy and a 16-bit sweep beyond P x K = 10^6 (philox_p32767_k64_drift) never hand over, so those run the
+    rounds / lock-step kernels to the end either way."""
     if tail is not None:
         monkeypatch.setenv('RECOGYM_TAIL', tail)
     monkeypatch.setenv('RECOGYM_RUN_AHEAD', str(hops))
     meta, cols = gu.load(name)
-    rows, cnt = run_sim(gu.env_config(meta), meta['n_users'], meta['n_organic'], **gu.policy_args(meta, cols))
+    cfg = gu.env_config(meta)
+    rows, cnt, led = run_sim(cfg, meta['n_users'], meta['n_organic'], with_ledger=True, **gu.policy_args(meta, cols))
+    # (philox_normal_time_ouc moves omega at bandit events: it stays an event per launch whatever the cap)
+    rounds = hops > 0 and not cfg.change_omega_for_bandits
+    assert (led['advance_run'] > 0 and led['advance'] == 0) if rounds else (led['advance'] > 0 and led['advance_run'] == 0), led
+    tail_runs = tail is None and name in ('philox_bandit_mf', 'philox_random_agent')
+    assert led['walk'] == led['walk2'] == 0 and led['tail'] == (1 if tail_runs else 0), led
+    assert not tail_runs or led['advance'] + led['advance_run'] == 16, led
     gu.assert_rows_equal(rows, cols, ps_rtol=1e-5 if meta['agent'] == 'bmf' else 1e-12, what=f'{name}, run-ahead {hops}, tail {tail}')
     assert cnt['organic'] == int((cols['z'] == 0).sum())
     assert cnt['bandit'] + cnt['phantom'] == int((cols['z'] == 1).sum())
@@ -234,8 +276,9 @@ def test_repacked_fixture_last_view_table(monkeypatch):
     monkeypatch.setenv('RECOGYM_REPACK_MIN', '1')
     monkeypatch.setenv('RECOGYM_REPACK', '2')
     meta, cols = gu.load('philox_bandit_mf')
-    rows, cnt = run_sim(gu.env_config(meta), meta['n_users'], meta['n_organic'],
-                        **gu.policy_args(meta, cols))
+    rows, cnt, led = run_sim(gu.env_config(meta), meta['n_users'], meta['n_organic'], with_ledger=True,
+                             **gu.policy_args(meta, cols))
+    assert led['repack'] > 0, led
     gu.assert_rows_equal(rows, cols, ps_rtol=1e-5, what='repacked philox_bandit_mf')
 
 
@@ -254,7 +297,11 @@ def test_omega_export_after_repack(monkeypatch):
         sim.step()
     om = sim.omega().cpu().numpy()
     st = sim.states().cpu().numpy()
+    led = au.ledger(sim)
     sim.close()
+    # nine steps of the step API (an event per launch), the lists repacked before steps 2, 4, 6 and 8: without the repack slot == user
+    # throughout and everything below holds trivially
+    assert led['repack'] == 4 and led['advance'] == 9 and led['advance_run'] == led['tail'] == 0, led
     o = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX)
     want = o.generate_logs(400, first_user_id=50)
     n_rows = np.bincount(want['u'] - 50, minlength=400)
@@ -331,6 +378,15 @@ def test_more_than_a_million_users_shard_consistently():
         assert whole_chk[i] % 2 ** 64 == sum(p[1][i] for p in parts) % 2 ** 64
 
 
+def assert_sweeps_of(led, mode):
+    """The lock-step sweeps of the run were the kernel family RECOGYM_DRAW names (a value no class serves is ignored silently)."""
+    sixteen = led['draw16_fused'] + led['draw16_sliced'] + led['draw_tp']
+    got = (led['draw_f64'] > 0, led['draw_fp32'] > 0, sixteen > 0)
+    assert got == {'f64': (True, False, False), 'fp32': (False, True, False)}.get(mode, (False, False, True)), (mode, led)
+    assert led['draw_kernel'] == {'f64': 0, 'fp32': 1}.get(mode, 2) and led['draw_split'] == {'bf16': 1}.get(mode, led['draw_split'])
+    assert led['draw_cached'] == led['sweep_xh'] == led['env0'] == 0, led
+
+
 @pytest.mark.parametrize('mode', ['f64', 'fp32', 'bf16', 'f16'])
 @pytest.mark.parametrize('shape', [(10, 5), (1000, 20), (4100, 8), (700, 33)])
 def test_every_draw_kernel_matches_the_oracle(mode, shape, monkeypatch):
@@ -342,7 +398,8 @@ def test_every_draw_kernel_matches_the_oracle(mode, shape, monkeypatch):
     P, K = shape
     cfg = Configuration({**env_1_args, 'random_seed': 100 + P, 'num_products': P, 'K': K})
     want = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX).generate_logs(600)
-    rows, cnt = run_sim(cfg, 600)
+    rows, cnt, led = run_sim(cfg, 600, with_ledger=True)
+    assert_sweeps_of(led, mode)
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps')},
                          ps_rtol=1e-6, what=f'{mode} {shape}')
     if mode == 'f64':
@@ -360,7 +417,9 @@ def test_product_per_lane_float64_kernel_matches_the_oracle(draw, monkeypatch):
     monkeypatch.setenv('RECOGYM_DRAW', draw)
     cfg = Configuration({**env_1_args, 'random_seed': 321, 'num_products': 1500, 'K': 20})
     want = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX).generate_logs(500)
-    rows, cnt = run_sim(cfg, 500)
+    rows, cnt, led = run_sim(cfg, 500, with_ledger=True)
+    assert_sweeps_of(led, draw)
+    assert led['exact_tile'] > 0 and led['exact_m'] == led['exact_h'] == 0, led
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps')},
                          ps_rtol=1e-6, what=f'tile kernel, {draw}')
 
@@ -385,6 +444,7 @@ def test_certified_draws_equal_float64_draws_at_scale(shape, monkeypatch):
         rows = sim.raw_log().to(torch.int64)
         assert rows.shape[0] == c['organic'] + c['bandit']
         chk = [(rows[:, i] * (rows[:, 1] + 7) * (rows[:, 0] + 13)).sum().item() for i in range(4)]
+        assert_sweeps_of(au.ledger(sim), mode)
         sim.close()
         return c, chk
 
@@ -438,9 +498,16 @@ def test_wide_logit_range_re_references_and_still_matches_the_oracle(mode, sigma
     cfg = Configuration({**env_1_args, 'random_seed': 77, 'num_products': 3000, 'K': 20,
                          'sigma_mu_organic': sigma_mu})
     want = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX).generate_logs(400)
-    rows, cnt = run_sim(cfg, 400)
+    rows, cnt, led = run_sim(cfg, 400, with_ledger=True)
+    assert_sweeps_of(led, mode)
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps')},
                          ps_rtol=1e-6, what=f'{mode} sigma_mu={sigma_mu}')
+
+
+def assert_walk_pipe(led):
+    """run_walk_pipe served the run: k_sweep_xh, the two k_walk2 rounds around the mixed float64 batch, k_walk_solo."""
+    au.assert_draws_by(led, 'sweep_xh')
+    assert (led['walk2'], led['exact_h'], led['walk_solo'], led['walk'], led['exact_m']) == (2, 1, 1, 0, 0) and led['xh_class'] > 0, led
 
 
 @pytest.mark.parametrize('fin', ['1', '0'])
@@ -458,7 +525,8 @@ def test_error_free_sweep_re_references_and_still_matches_the_oracle(sigma_mu, f
     cfg = Configuration({**env_1_args, 'random_seed': 78, 'num_products': 3000, 'K': 20, 'sigma_mu_organic': sigma_mu, 'sigma_omega': 0.0})
     pol = dict(policy=_abi.RG_POLICY_ORGANIC_USER_COUNT, policy_seed=31, ouc=dict(gu.OUC_DEFAULTS))
     want = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol).generate_logs(700)
-    rows, cnt = run_sim(cfg, 700, p_click=False, **pol)
+    rows, cnt, led = run_sim(cfg, 700, p_click=False, with_ledger=True, **pol)
+    assert_walk_pipe(led)
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps')}, ps_rtol=1e-12, what=f'xh sigma_mu={sigma_mu} fin={fin}')
 
 
@@ -470,7 +538,7 @@ def test_repack_and_tail_kernel_do_not_change_the_log_at_scale(monkeypatch):
     cfg = Configuration({**env_1_args, 'random_seed': 23, 'num_products': 100, 'K': 20, 'sigma_omega': 0.05})
     n = 300_000
 
-    def run(repack, tail):
+    def run(repack, tail, rounds):
         monkeypatch.setenv('RECOGYM_REPACK', repack)
         monkeypatch.setenv('RECOGYM_TAIL', tail)
         sim = Simulator(cfg, n, device='cuda:0', policy=_abi.RG_POLICY_ORGANIC_USER_COUNT, policy_seed=5,
@@ -481,18 +549,21 @@ def test_repack_and_tail_kernel_do_not_change_the_log_at_scale(monkeypatch):
         rows = sim.raw_log().to(torch.int64)
         assert rows.shape[0] == c['organic'] + c['bandit']
         chk = [(rows[:, i] * (rows[:, 1] + 7) * (rows[:, 0] + 13)).sum().item() for i in range(4)]
+        led = au.ledger(sim)
         sim.close()
+        assert (led['repack'] > 0) == (repack != '0') and (led['tail'] > 0) == (tail != '0'), led
+        assert (led['advance_run'] > 0 and led['advance'] == 0) if rounds else (led['advance'] > 0 and led['advance_run'] == 0), led
         return c, chk
 
-    a_c, a_chk = run('16', '4096')
-    b_c, b_chk = run('0', '0')
+    a_c, a_chk = run('16', '4096', rounds=True)
+    b_c, b_chk = run('0', '0', rounds=True)
     for k in ('organic', 'bandit', 'clicks', 'phantom'):
         assert a_c[k] == b_c[k], k
     assert a_chk == b_chk
     # both of these went in run-ahead rounds (k_advance_run: a user's whole bandit run per launch); an event per launch must log
     # the same rows
     monkeypatch.setenv('RECOGYM_RUN_AHEAD', '0')
-    c_c, c_chk = run('16', '4096')
+    c_c, c_chk = run('16', '4096', rounds=False)
     for k in ('organic', 'bandit', 'clicks', 'phantom', 'step'):
         assert a_c[k] == c_c[k], k
     assert a_chk == c_chk
@@ -502,13 +573,16 @@ def test_fused_and_sliced_draw_forms_agree_at_scale(monkeypatch):
     """The draw kernel runs in two forms: whole product sweeps with the search fused in (steps with
     >= 1024 user tiles) and product slices + k_draw_search (fewer).  Small oracle-checked runs only
     ever take the second; here both forms are forced on the same 150 000-user run and must produce
-    the same log (order-independent checksum of every row) and counters."""
+    the same log (order-independent checksum of every row) and counters.  (Since k_draw_tp exists, RECOGYM_SLICES=1 alone
+    selects IT for this table — the launch ledger showed this test comparing k_draw_tp with the sliced form; the fused form
+    of k_draw_bf16p needs RECOGYM_SWEEP_LDS=0 as well: all three are run now.)"""
     from recogym_amd.sim import Simulator
     cfg = Configuration({**env_1_args, 'random_seed': 9, 'num_products': 1000, 'K': 20})
     n = 150_000
 
-    def run(slices):
+    def run(slices, family, sweep_lds='1'):
         monkeypatch.setenv('RECOGYM_SLICES', slices)
+        monkeypatch.setenv('RECOGYM_SWEEP_LDS', sweep_lds)
         sim = Simulator(cfg, n, device='cuda:0', policy=_abi.RG_POLICY_ORGANIC_USER_COUNT, policy_seed=3,
                         ouc=dict(gu.OUC_DEFAULTS))
         sim.reset_users(0, n)
@@ -517,14 +591,18 @@ def test_fused_and_sliced_draw_forms_agree_at_scale(monkeypatch):
         rows = sim.raw_log().to(torch.int64)
         assert rows.shape[0] == c['organic'] + c['bandit']
         chk = [(rows[:, i] * (rows[:, 1] + 7) * (rows[:, 0] + 13)).sum().item() for i in range(4)]
+        led = au.ledger(sim)
         sim.close()
+        au.assert_draws_by(led, family)
+        assert (led['search'] > 0) == (family == 'draw16_sliced') and (led['pick'] > 0) == (family == 'draw_tp'), led
         return c, chk
 
-    fused_c, fused_chk = run('1')
-    sliced_c, sliced_chk = run('4')
+    fused_c, fused_chk = run('1', 'draw_tp')
+    sliced_c, sliced_chk = run('4', 'draw16_sliced')
+    plain_c, plain_chk = run('1', 'draw16_fused', sweep_lds='0')
     for k in ('organic', 'bandit', 'clicks', 'phantom'):
-        assert fused_c[k] == sliced_c[k], k
-    assert fused_chk == sliced_chk
+        assert fused_c[k] == sliced_c[k] == plain_c[k], k
+    assert fused_chk == sliced_chk == plain_chk
     assert fused_c['live'] == 0 and fused_c['hist_overflow'] == 0
 
 
@@ -690,7 +768,8 @@ def test_sampled_frozen_logreg_matches_the_oracle(P):
     n = 400 if P < 1024 else 150
     want_env = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol)
     want = want_env.generate_logs(n, 5)
-    rows, cnt = run_sim(cfg, n, 5, **pol)
+    rows, cnt, led = run_sim(cfg, n, 5, with_ledger=True, **pol)
+    assert led['logreg_sample'] > 0 and led['logreg_acts'] == led['logreg_screen'] == led['advance_run'] == 0, led
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps', 'p_click')}, ps_rtol=1e-12, what=f'sampled logreg P={P}')
     assert (rows['phantom'] == want['phantom']).all()
     assert len(np.unique(rows['a'][rows['z'] == 1])) > min(P, 20) // 2          # it does sample
@@ -704,6 +783,7 @@ def test_frozen_logreg_at_config_5_scale_matches_the_oracle(screen, monkeypatch)
     near-ties common; classes duplicated exactly (first maximum wins) and almost exactly (1e-9 apart: far inside the
     fp16 bound, decided by float64) must come out as the oracle's argmax."""
     from oracle import oracle as orc
+    form = screen
     if screen == 'fp16_cap3':
         # the screen's scratch holds a row per act of a step (n / 2 + 4096 of them); here only 3: every step that lists more acts
         # sends the rest through k_logreg_acts (fp32 scores, float64 inside the bound)
@@ -724,7 +804,9 @@ def test_frozen_logreg_at_config_5_scale_matches_the_oracle(screen, monkeypatch)
     cfg = Configuration({**env_1_args, 'random_seed': 55, 'num_products': P, 'K': 10})
     want_env = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol)
     want = want_env.generate_logs(120)
-    rows, cnt = run_sim(cfg, 120, **pol)
+    rows, cnt, led = run_sim(cfg, 120, with_ledger=True, **pol)
+    assert (led['logreg_screen'] > 0, led['logreg_acts'] > 0) == {'fp16': (True, False), 'fp32': (False, True), 'fp16_cap3': (True, True)}[form], led
+    assert led['logreg_sample'] == 0, led
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps', 'p_click')},
                          ps_rtol=1e-12, what=f'logreg 4096 classes, {screen} screen')
     used = set(np.unique(rows['a'][rows['z'] == 1]).tolist())
@@ -771,7 +853,11 @@ def test_lds_search_sweep_matches_the_oracle(case, run_ahead, monkeypatch):
     probe.close()
     want_env = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol)
     want = want_env.generate_logs(n_users, n_org)
-    rows, cnt = run_sim(cfg, n_users, n_org, **pol)
+    rows, cnt, led = run_sim(cfg, n_users, n_org, with_ledger=True, **pol)
+    au.assert_draws_by(led, 'draw_tp')
+    assert led['pick'] == led['draw_tp'] and led['search'] == led['tail'] == 0, led
+    rounds = run_ahead != '0' and not over.get('change_omega_for_bandits')       # (case 4 moves omega at bandit events: an event per launch)
+    assert (led['advance_run'] > 0 and led['advance'] == 0) if rounds else (led['advance'] > 0 and led['advance_run'] == 0), led
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps', 'p_click')},
                          ps_rtol=1e-12, what=f'lds case {case}')
     assert (rows['phantom'] == want['phantom']).all()
@@ -781,53 +867,13 @@ def test_lds_search_sweep_matches_the_oracle(case, run_ahead, monkeypatch):
     assert cnt['exact_draws'] < 0.2 * cnt['organic'] + 50, (cnt['exact_draws'], cnt['organic'])
 
 
-@pytest.mark.parametrize('mode', ['f16', 'f16_lds', 'bf16', 'fp32'])
-@pytest.mark.parametrize('shape', [(10000, 20), (3000, 20), (1500, 40)])
-def test_certificate_is_sound_for_uniforms_next_to_cdf_boundaries(mode, shape, monkeypatch):
-    """Adversarial check of the margin certificate (DESIGN.md §2).  The uniform of every user's draw is
-    placed next to a boundary of ITS float64 cdf: u = cdf[b] * (1 +- eps), eps from 1e-9 (closer than any
-    fp32 sum can resolve) to 3e-3, through the test hook rg_sim_debug_set_uniforms.  Then
-      * every draw the matrix-core kernel certified must equal the float64 decision (soundness);
-      * nothing within 5e-7 of a boundary may be certified (the certificate's floor is 2^-20 of the total — the fp32
-        roundings of the stored prefixes — next to delta times the masses before AND behind the boundary; the COMPUTED
-        boundary a certified draw keeps that distance from is itself off the true one by the actual roundings);
-      * draws >= 1e-3 away from both neighbouring boundaries mostly are certified (the test is not
-        vacuous), and the logged index of EVERY user equals the float64 one (uncertified draws are
-        resolved by the float64 kernels)."""
-    import ctypes as C
-    from recogym_amd.envs.static_params import draw_tables
+def adversarial_step(P, K):
+    """One lock-step step of 4096 users whose uniforms sit next to boundaries of their float64 cdfs (adversarial_util.reference,
+    through the test hooks rg_sim_debug_set_omega / rg_sim_debug_set_uniforms) under the environment the caller has set:
+    (certified by the fast kernel, logged index, float64 index, margin, launch ledger)."""
     from recogym_amd.sim import Simulator
-    if mode == 'f16_lds':          # the unsliced sweep whose search runs on tile prefixes in LDS (k_draw_tp; K <= 20)
-        if shape[1] > 20:
-            pytest.skip('k_draw_tp serves K <= 20')
-        monkeypatch.setenv('RECOGYM_SLICES', '1')
-        mode = 'f16'
-    monkeypatch.setenv('RECOGYM_DRAW', mode)
-    P, K = shape
-    n = 4096
-    cfg = Configuration({**env_1_args, 'random_seed': 1234 + P + K, 'num_products': P, 'K': K})
-    gamma, mu_o, _, _ = draw_tables(cfg)
-    rng = np.random.RandomState(99)
-    omega = rng.standard_normal((n, K))
-    # the reference's arithmetic (reco_env_v1.py:119-128) in float64
-    logits = omega @ gamma.T + mu_o.reshape(1, -1)
-    logits -= logits.max(axis=1, keepdims=True)
-    e = np.exp(logits)
-    prob = e / e.sum(axis=1, keepdims=True)
-    cdf = np.cumsum(prob, axis=1)
-    cdf /= cdf[:, -1:]
-    # a boundary per user, drawn by mass (so that heavy and light products both occur), then u beside it
-    b = np.array([np.searchsorted(cdf[i], rng.random_sample(), 'right') for i in range(n)])
-    b = np.clip(b, 0, P - 2)
-    eps = 10.0 ** rng.uniform(-9, -2.5, n)
-    sign = rng.choice([-1.0, 1.0], n)
-    u = np.clip(cdf[np.arange(n), b] * (1.0 + sign * eps), 0.0, np.nextafter(1.0, 0.0))
-    want_v = np.array([np.searchsorted(cdf[i], u[i], 'right') for i in range(n)])
-    # distance of u to its two neighbouring boundaries, relative to u
-    lo = np.where(want_v > 0, cdf[np.arange(n), np.maximum(want_v - 1, 0)], -np.inf)
-    hi = np.where(want_v < P - 1, cdf[np.arange(n), np.minimum(want_v, P - 1)], np.inf)     # (no boundary behind the last product)
-    margin = np.minimum(u - lo, hi - u) / np.maximum(u, 1e-300)
-
+    cfg, omega, u, want_v, margin = au.lockstep_reference(P, K)
+    n = au.N_USERS
     sim = Simulator(cfg, n, device='cuda:0')
     sim.reset_users(0, n)
     d_om = torch.from_numpy(omega).to('cuda:0')
@@ -843,16 +889,27 @@ def test_certificate_is_sound_for_uniforms_next_to_cdf_boundaries(mode, shape, m
     raw = sim.log[:n].cpu().numpy().view(np.uint32)
     got_v = np.zeros(n, dtype=np.int64)
     got_v[raw[:, 0]] = raw[:, 2] & _abi.RG_EV_INDEX_MASK          # step 0: one organic row per user
+    led = au.ledger(sim)
     sim.close()
-    cert = ~uncert
+    return ~uncert, got_v, want_v, margin, led
+
+
+def assert_certificate_is_sound(cert, got_v, want_v, margin, what='', band=None):
+    """`band` (per user): the class's documented certificate band where it is wider than 1e-3 — then the draws that must mostly
+    be certified are those beyond 1e-3 AND beyond the band."""
     # a uniform closer than 3e-14 (relative) to a boundary may legitimately fall either way between two
     # float64 evaluations that differ in summation order; none is placed there (eps >= 1e-9)
+    far = margin > 1e-3
+    if band is not None:
+        print(f'{what}: certified share of ALL {int(far.sum())} draws beyond 1e-3: {cert[far].mean():.4f}; documented band median {np.median(band):.3e}')
+        far = far & (margin > band)
+    print(f'{what}: certified {cert.sum()} of {cert.size}; {int((margin < 5e-7).sum())} within 5e-7 of a boundary, certified share of the '
+          f'{int(far.sum())} draws beyond 1e-3: {cert[far].mean():.4f}; least certified margin {margin[cert].min():.3e}')
     bad = np.flatnonzero(cert & (got_v != want_v))
     assert bad.size == 0, (f'{bad.size} CERTIFIED draws differ from float64; first: user {bad[0]} got {got_v[bad[0]]} '
                            f'want {want_v[bad[0]]} margin {margin[bad[0]]:.3e}')
     assert not cert[margin < 5e-7].any(), 'a draw within 5e-7 of a cdf boundary was certified'
     assert (margin < 5e-7).sum() > 200 and cert.sum() > 200
-    far = margin > 1e-3
     assert far.sum() > 20 and cert[far].mean() > 0.9
     # float64 resolve of the rest.  Where the neighbouring products' masses are below float64 resolution of the
     # running sum (margin < 1e-12) two float64 evaluations with different summation trees may differ: excluded
@@ -861,6 +918,154 @@ def test_certificate_is_sound_for_uniforms_next_to_cdf_boundaries(mode, shape, m
     assert bad.size == 0, (f'{bad.size} draws differ from float64; first: user {bad[0]} got {got_v[bad[0]]} want '
                            f'{want_v[bad[0]]} margin {margin[bad[0]]:.3e} certified {cert[bad[0]]}')
     assert clear.mean() > 0.95
+
+
+@pytest.mark.parametrize('mode', ['f16', 'f16_lds', 'bf16', 'fp32'])
+@pytest.mark.parametrize('shape', [(10000, 20), (3000, 20), (1500, 40)])
+def test_certificate_is_sound_for_uniforms_next_to_cdf_boundaries(mode, shape, monkeypatch):
+    """Adversarial check of the margin certificate (DESIGN.md §2).  The uniform of every user's draw is
+    placed next to a boundary of ITS float64 cdf: u = cdf[b] * (1 +- eps), eps from 1e-9 (closer than any
+    fp32 sum can resolve) to 3e-3, through the test hook rg_sim_debug_set_uniforms.  Then
+      * every draw the matrix-core kernel certified must equal the float64 decision (soundness);
+      * nothing within 5e-7 of a boundary may be certified (the certificate's floor is 2^-20 of the total — the fp32
+        roundings of the stored prefixes — next to delta times the masses before AND behind the boundary; the COMPUTED
+        boundary a certified draw keeps that distance from is itself off the true one by the actual roundings);
+      * draws >= 1e-3 away from both neighbouring boundaries mostly are certified (the test is not
+        vacuous), and the logged index of EVERY user equals the float64 one (uncertified draws are
+        resolved by the float64 kernels).
+    The launch ledger proves the kernel: at this population the product-sliced form of the 16-bit sweeps (f16: the two-way
+    split of K = 20, the wide one of K = 40; bf16: the pipelined three-way class of K = 20, the lean (32, 12, 8, 4) one of
+    K = 40), k_draw_tp + k_pick (f16_lds), k_draw_mfma (fp32)."""
+    lds = mode == 'f16_lds'
+    if lds:                        # the unsliced sweep whose search runs on tile prefixes in LDS (k_draw_tp; K <= 20)
+        if shape[1] > 20:
+            pytest.skip('k_draw_tp serves K <= 20')
+        monkeypatch.setenv('RECOGYM_SLICES', '1')
+        mode = 'f16'
+    monkeypatch.setenv('RECOGYM_DRAW', mode)
+    P, K = shape
+    cert, got_v, want_v, margin, led = adversarial_step(P, K)
+    if lds:
+        au.assert_draws_by(led, 'draw_tp')
+        assert led['pick'] == 1 and led['search'] == 0, led
+    elif mode == 'fp32':
+        au.assert_draws_by(led, 'draw_fp32')
+    else:
+        au.assert_draws_by(led, 'draw16_sliced')
+        assert led['search'] == 1 and led['pick'] == 0 and led['draw_split'] == ({'f16': 2, 'bf16': 1}[mode] if K <= 20 else {'f16': 3, 'bf16': 1}[mode]), led
+        assert led['draw_pipelined'] == (1 if K <= 20 else 0), led
+    assert_certificate_is_sound(cert, got_v, want_v, margin, f'{mode} {shape}')
+
+
+@pytest.mark.parametrize('form,K,P', au.lockstep_cases())
+def test_certificate_is_sound_for_every_kernel_class(form, K, P, monkeypatch):
+    """The same adversarial step for ONE K PER CLASS of every draw-kernel table (adversarial_util.lockstep_cases derives the list
+    from the K -> (KH, N1, split) table, which tests/test_adversarial_inputs.py holds against the library): a kernel whose sums are
+    off by more than its certificate assumes logs a wrong index only when a uniform lands inside the error band — one draw in 10^5
+    of an ordinary run, every draw here.  P ends in a ragged tile over several tiles (545 = 4 x 128 + 33, the smallest table
+    k_draw_tp serves; 321 = 5 x 64 + 1 for the wide classes' 64-product tiles; 2049), so padding products enter the sums.  Forms,
+    each PROVEN by the launch ledger (with the float64 resolve behind every draw a run on another kernel still passes):
+      sliced  the default at 4096 users: k_draw_bf16p / k_draw_f16w over product slices + k_draw_search
+      fused   RECOGYM_SLICES=1, RECOGYM_SWEEP_LDS=0: the same kernels, one sweep with the search fused in
+      lds     RECOGYM_SLICES=1: k_draw_tp / k_draw_tpw + k_pick
+      fp32    RECOGYM_DRAW=fp32: k_draw_mfma, a K per KH (K = 100: KH = 64)
+      bf16    RECOGYM_DRAW=bf16: the pipelined three-way classes
+      lean    RECOGYM_BF16=lean, RECOGYM_DRAW=bf16: k_draw_bf16, a K per class
+    Measured on an MI355X: every class certifies >= 0.99 of the draws beyond 1e-3 except k_draw_mfma<64> at K = 100: 0.734
+    (P = 545) and 0.774 (P = 2049).  Its sums are not off — its DOCUMENTED budget is wider: delta = (K + 5) 2^-24 Ahat + 3e-5
+    is ~8e-4 at K = 100 (Ahat ~ 125), a band of 2 delta ~ 1.7e-3 around a boundary, so a third of the draws between 1e-3 and
+    3e-3 are inside it by design.  For that class the share is asserted over the draws beyond 1e-3 AND beyond the band, which
+    adversarial_util.fp32_documented_band computes per user from the float64 quantities (120 / 116 such draws)."""
+    for k in ('RECOGYM_DRAW', 'RECOGYM_BF16', 'RECOGYM_SLICES', 'RECOGYM_SWEEP_LDS', 'RECOGYM_F16W'):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in au.FORM_ENV[form].items():
+        monkeypatch.setenv(k, v)
+    setting = {'bf16': 'bf16', 'lean': 'lean_bf16', 'fp32': 'fp32'}.get(form, 'default')
+    cert, got_v, want_v, margin, led = adversarial_step(P, K)
+    assert (led['draw_kh'], led['draw_n1'], led['draw_split']) == au.geom(K, setting), led
+    if form == 'fp32':
+        au.assert_draws_by(led, 'draw_fp32')
+        assert led['search'] == led['pick'] == 0 and led['draw_kernel'] == 1, led
+    elif form == 'lds':
+        au.assert_draws_by(led, 'draw_tp')
+        assert led['pick'] == 1 and led['search'] == 0 and led['sweep_lds_kernel'] == 1, led
+    elif form == 'fused':
+        au.assert_draws_by(led, 'draw16_fused')
+        assert led['pick'] == led['search'] == 0, led
+    else:
+        au.assert_draws_by(led, 'draw16_sliced')
+        assert led['search'] == 1 and led['pick'] == 0, led
+    if form != 'fp32':
+        assert led['draw_kernel'] == 2 and led['draw_pipelined'] == (0 if form == 'lean' or led['draw_split'] == au.SPLIT_F16_WIDE else 1), led
+    assert led['exact_m'] + led['exact_tile'] == 1 and led['advance'] == 1, led      # the float64 resolve and the step's second half
+    band = au.fp32_documented_band(P, K) if form == 'fp32' and led['draw_kh'] == 64 else None
+    assert_certificate_is_sound(cert, got_v, want_v, margin, f'{form} K={K} P={P} class {au.geom(K, setting)}', band)
+
+
+def adversarial_walk(P, K):
+    """The whole sigma_omega = 0 run of 4096 users, EVERY organic draw of a user with its uniform next to a boundary of the user's
+    float64 cdf (adversarial_util.walk_reference), under the environment the caller has set: checks the logged products and
+    returns the launch ledger."""
+    from recogym_amd.sim import Simulator
+    cfg, omega, u, want_v, margin = au.walk_reference(P, K)
+    n = au.N_USERS
+    sim = Simulator(cfg, n, device='cuda:0')
+    sim.reset_users(0, n)
+    d_om = torch.from_numpy(omega).to('cuda:0')
+    d_u = torch.from_numpy(u).to('cuda:0')
+    _abi.check(sim.lib.rg_sim_debug_set_omega(sim._h, d_om.data_ptr(), sim._stream()), 'debug_set_omega')
+    _abi.check(sim.lib.rg_sim_debug_set_uniforms(sim._h, d_u.data_ptr()), 'debug_set_uniforms')
+    sim.run()
+    torch.cuda.synchronize()
+    _abi.check(sim.lib.rg_sim_debug_set_uniforms(sim._h, None), 'debug_set_uniforms')
+    rows = sim.rows()
+    c = sim.counters()
+    led = au.ledger(sim)
+    sim.close()
+    org = rows['z'] == 0
+    uu, vv = rows['u'][org].astype(np.int64), rows['v'][org].astype(np.int64)
+    assert org.sum() == c['organic'] and np.unique(uu).size == n
+    clear = margin > 1e-12
+    print(f'walk K={K} P={P}: {int(org.sum())} organic rows, float64 draws {c["exact_draws"]}, float64 sweeps {c["exact_sweeps"]}, '
+          f'users below 3e-4: {int((margin < 3e-4).sum())}')
+    bad = np.flatnonzero(clear[uu] & (vv != want_v[uu]))
+    assert bad.size == 0, (f'{bad.size} organic rows differ from float64; first: user {uu[bad[0]]} got {vv[bad[0]]} want '
+                           f'{want_v[uu[bad[0]]]} margin {margin[uu[bad[0]]]:.3e}')
+    assert clear.mean() > 0.95
+    # not vacuous: most users' draws were decided by the fp32 certificate (float64 took fewer draws than users whose
+    # margin is below 3e-4, the widest band either form leaves)
+    assert 0 < c['exact_draws'] and c['exact_sweeps'] < (margin < 3e-4).sum() + 64
+    return led
+
+
+def set_walk_form(walk, monkeypatch):
+    for k in ('RECOGYM_DRAW', 'RECOGYM_WALK', 'RECOGYM_WALK_HANDOVER', 'RECOGYM_PIPE_MIN', 'RECOGYM_XH', 'RECOGYM_XH_WAVES', 'RECOGYM_PIPE',
+              'RECOGYM_SLICES', 'RECOGYM_BF16'):
+        monkeypatch.delenv(k, raising=False)
+    if walk in ('solo_only', 'pipe_solo'):
+        monkeypatch.setenv('RECOGYM_WALK_HANDOVER', '64')
+    if walk in ('pipe', 'pipe_solo', 'pipe_xh8'):
+        monkeypatch.setenv('RECOGYM_PIPE_MIN', '256')
+    if walk == 'pipe_xh8':
+        monkeypatch.setenv('RECOGYM_XH_WAVES', '8')
+    if walk == 'k_walk':
+        monkeypatch.setenv('RECOGYM_WALK', '1')
+
+
+def assert_walk_form(led, walk, K):
+    """The ledger of a 4096-user walked run in the form the test names."""
+    if walk.startswith('pipe'):
+        assert_walk_pipe(led)
+        assert led['xh_class'] == (412 if K <= 8 else 1025) and led['xh_waves'] == (8 if walk == 'pipe_xh8' else 4), led
+    else:
+        # run_walk: the first sweep of 32 user tiles goes in product slices, sums only (no search, no lock-step half)
+        au.assert_draws_by(led, 'draw16_sliced')
+        assert led['exact_h'] + led['exact_m'] == 1 and led['search'] == led['draw_cached'] == 0, led
+        if walk == 'k_walk':
+            assert led['walk'] >= 2 and led['walk2'] == led['walk_solo'] == 0, led
+        else:
+            assert led['walk2'] >= 2 and led['walk'] == 0 and (walk != 'solo_only' or led['walk_solo'] == 1), led
+    assert led['advance'] == led['advance_run'] == led['tail'] == 0, led
 
 
 @pytest.mark.parametrize('walk', ['default', 'solo_only', 'k_walk', 'pipe', 'pipe_solo'])
@@ -873,61 +1078,22 @@ def test_walk_certificate_is_sound_for_uniforms_next_to_cdf_boundaries(shape, wa
     pick), every logged product must be float64's.  `solo_only`: hand-over at 64 live lanes, so the wave-per-user kernel
     takes nearly all users; `k_walk`: round 2's kernel; `pipe` / `pipe_solo`: run_walk_pipe (RECOGYM_PIPE_MIN lowered), whose
     sweep is k_sweep_xh — the error-free leading accumulator, a delta ~8x smaller and rho = 2^-23: the band these uniforms are
-    placed in is the one that certificate newly ACCEPTS."""
-    import ctypes as C
-    from recogym_amd.envs.static_params import draw_tables
-    from recogym_amd.sim import Simulator
-    for k in ('RECOGYM_DRAW', 'RECOGYM_WALK', 'RECOGYM_WALK_HANDOVER', 'RECOGYM_PIPE_MIN', 'RECOGYM_XH'):
-        monkeypatch.delenv(k, raising=False)
-    if walk in ('solo_only', 'pipe_solo'):
-        monkeypatch.setenv('RECOGYM_WALK_HANDOVER', '64')
-    if walk in ('pipe', 'pipe_solo'):
-        monkeypatch.setenv('RECOGYM_PIPE_MIN', '256')
-    if walk == 'k_walk':
-        monkeypatch.setenv('RECOGYM_WALK', '1')
+    placed in is the one that certificate newly ACCEPTS.  The launch ledger proves each form."""
+    set_walk_form(walk, monkeypatch)
     P, K = shape
-    n = 4096
-    cfg = Configuration({**env_1_args, 'random_seed': 4321 + P + K, 'num_products': P, 'K': K, 'sigma_omega': 0.0})
-    gamma, mu_o, _, _ = draw_tables(cfg)
-    rng = np.random.RandomState(7)
-    omega = rng.standard_normal((n, K))
-    logits = omega @ gamma.T + mu_o.reshape(1, -1)
-    logits -= logits.max(axis=1, keepdims=True)
-    e = np.exp(logits)
-    cdf = np.cumsum(e / e.sum(axis=1, keepdims=True), axis=1)
-    cdf /= cdf[:, -1:]
-    b = np.clip(np.array([np.searchsorted(cdf[i], rng.random_sample(), 'right') for i in range(n)]), 0, P - 2)
-    eps = 10.0 ** rng.uniform(-9, -2.5, n)
-    sign = rng.choice([-1.0, 1.0], n)
-    u = np.clip(cdf[np.arange(n), b] * (1.0 + sign * eps), 0.0, np.nextafter(1.0, 0.0))
-    want_v = np.array([np.searchsorted(cdf[i], u[i], 'right') for i in range(n)])
-    lo = np.where(want_v > 0, cdf[np.arange(n), np.maximum(want_v - 1, 0)], -np.inf)
-    hi = np.where(want_v < P - 1, cdf[np.arange(n), np.minimum(want_v, P - 1)], np.inf)     # (no boundary behind the last product)
-    margin = np.minimum(u - lo, hi - u) / np.maximum(u, 1e-300)
+    assert_walk_form(adversarial_walk(P, K), walk, K)
 
-    sim = Simulator(cfg, n, device='cuda:0')
-    sim.reset_users(0, n)
-    d_om = torch.from_numpy(omega).to('cuda:0')
-    d_u = torch.from_numpy(u).to('cuda:0')
-    _abi.check(sim.lib.rg_sim_debug_set_omega(sim._h, d_om.data_ptr(), sim._stream()), 'debug_set_omega')
-    _abi.check(sim.lib.rg_sim_debug_set_uniforms(sim._h, d_u.data_ptr()), 'debug_set_uniforms')
-    sim.run()
-    torch.cuda.synchronize()
-    _abi.check(sim.lib.rg_sim_debug_set_uniforms(sim._h, None), 'debug_set_uniforms')
-    rows = sim.rows()
-    c = sim.counters()
-    sim.close()
-    org = rows['z'] == 0
-    uu, vv = rows['u'][org].astype(np.int64), rows['v'][org].astype(np.int64)
-    assert org.sum() == c['organic'] and np.unique(uu).size == n
-    clear = margin > 1e-12
-    bad = np.flatnonzero(clear[uu] & (vv != want_v[uu]))
-    assert bad.size == 0, (f'{bad.size} organic rows differ from float64; first: user {uu[bad[0]]} got {vv[bad[0]]} want '
-                           f'{want_v[uu[bad[0]]]} margin {margin[uu[bad[0]]]:.3e}')
-    assert clear.mean() > 0.95
-    # not vacuous: most users' draws were decided by the fp32 certificate (float64 took fewer draws than users whose
-    # margin is below 3e-4, the widest band either form leaves)
-    assert 0 < c['exact_draws'] and c['exact_sweeps'] < (margin < 3e-4).sum() + 64
+
+@pytest.mark.parametrize('walk,K,P', au.WALK_CASES)
+def test_walk_certificate_is_sound_for_every_kernel_class(walk, K, P, monkeypatch):
+    """The adversarial walked run for the K classes the two tests above leave out: k_walk2 behind every 16-bit sweep class of
+    KH <= 16 (K = 3, 10, 13, 21 and the wide K = 27), k_walk behind the wide sweeps of KH = 32 (K = 40, 64 — its only walk),
+    run_walk_pipe with k_sweep_xh in both of its classes ((4, 1, 2): K = 3, (10, 2, 5): K = 13) and with eight waves per block;
+    P = 640 (whole tiles) and 545 (a ragged one)."""
+    set_walk_form(walk, monkeypatch)
+    led = adversarial_walk(P, K)
+    assert (led['draw_kh'], led['draw_n1'], led['draw_split']) == au.geom(K), led
+    assert_walk_form(led, walk, K)
 
 
 @pytest.mark.parametrize('variant', ['default', 'fastclick', 'k_walk', 'sliced', 'nowalk', 'repack', 'lockstep', 'nowalk_sliced'])
@@ -958,7 +1124,17 @@ def test_sigma_omega_zero_sum_cache_matches_the_oracle(shape, variant, monkeypat
     want_env = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol)
     want = want_env.generate_logs(n, n_org)
     # 'fastclick': without the click-probability export the walk decides the clicks in fp32 wherever that is certain
-    rows, cnt = run_sim(cfg, n, n_org, **pol, **(dict(p_click=False) if variant == 'fastclick' else {}))
+    rows, cnt, led = run_sim(cfg, n, n_org, with_ledger=True, **pol, **(dict(p_click=False) if variant == 'fastclick' else {}))
+    if variant in ('default', 'fastclick', 'sliced'):        # run_walk (fewer users than run_walk_pipe takes): k_walk2
+        assert led['walk2'] > 0 and led['walk'] == led['draw_cached'] == led['advance'] == led['sweep_xh'] == 0, led
+    elif variant == 'k_walk':
+        assert led['walk'] > 0 and led['walk2'] == led['walk_solo'] == led['draw_cached'] == led['advance'] == 0, led
+    else:                                                    # lock-step over the per-user sum cache
+        assert led['draw_cached'] > 0 and led['advance'] > 0 and led['walk'] == led['walk2'] == led['advance_run'] == 0, led
+        assert (led['repack'] > 0) == (variant == 'repack') and (variant != 'lockstep' or led['tail'] == 0), led
+    if variant in ('sliced', 'nowalk_sliced'):
+        # (P = 33 is ONE super-chunk: RECOGYM_SLICES=4 still runs the fused form there; the other shapes take the sliced one)
+        au.assert_draws_by(led, *(('draw16_sliced',) if n_super_chunks(P) > 1 else ('draw16_fused',)), *(() if variant == 'sliced' else ('draw_cached',)))
     cols = ('u', 't', 'z', 'v', 'a', 'c', 'ps') + (() if variant == 'fastclick' else ('p_click',))
     gu.assert_rows_equal(rows, {k: want[k] for k in cols},
                          ps_rtol=1e-12, what=f'sigma0 cache {shape} {variant}')
@@ -984,7 +1160,13 @@ def test_sum_cache_does_not_change_the_log_at_scale(monkeypatch):
         rows = sim.raw_log().to(torch.int64)
         assert rows.shape[0] == c['organic'] + c['bandit']
         chk = [(rows[:, i] * (rows[:, 1] + 7) * (rows[:, 0] + 13)).sum().item() for i in range(4)]
+        led = au.ledger(sim)
         sim.close()
+        if cache == '1':          # 200 000 users: run_walk_pipe
+            assert_walk_pipe(led)
+        else:                     # no cache: every draw sweeps, in rounds
+            assert led['walk'] == led['walk2'] == led['draw_cached'] == led['sweep_xh'] == 0 and led['advance_run'] > 0, led
+            assert led['draw16_fused'] + led['draw16_sliced'] + led['draw_tp'] > 0, led
         return c, chk
 
     on_c, on_chk = run('1')
@@ -1018,7 +1200,13 @@ def test_user_major_walk_equals_the_lock_step_loop_at_scale(monkeypatch):
         chk = [(rows[:, i] * (rows[:, 1] + 7) * (rows[:, 0] + 13)).sum().item() for i in range(4)]
         srt, off = sim.sorted_log()
         head = srt[:int(off[2000])].cpu().numpy().copy()
+        led = au.ledger(sim)
         sim.close()
+        if walk == '1':           # RECOGYM_WALK=1 is round 2's k_walk (run_walk); k_walk2 at this size is test_memo_and_anchored_...
+            assert led['walk'] > 0 and led['walk2'] == led['walk_solo'] == led['draw_cached'] == led['advance'] == 0, led
+        else:
+            assert led['draw_cached'] > 0 and led['advance'] > 0 and led['walk'] == led['walk2'] == 0, led
+        assert led['sort_tiled'] >= 1 and led['sort_plain'] == 0, led
         return c, chk, head
 
     w_c, w_chk, w_head = run('1')
@@ -1206,7 +1394,8 @@ def test_last_round_wave_per_user_kernel_matches_the_oracle(policy, handover, mo
                          policy_ps=rng.rand(P))}[policy]
     want_env = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol)
     want = want_env.generate_logs(n, n_org)
-    rows, cnt = run_sim(cfg, n, n_org, p_click=False, **pol)
+    rows, cnt, led = run_sim(cfg, n, n_org, p_click=False, with_ledger=True, **pol)
+    assert led['walk2'] > 0 and led['walk'] == led['sweep_xh'] == 0 and (handover != '64' or led['walk_solo'] == 1), led
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps')},
                          ps_rtol=1e-5 if policy == 'table' else 1e-12, what=f'solo {policy} handover {handover}')
     assert (rows['phantom'] == want['phantom']).all()
@@ -1233,7 +1422,13 @@ def test_memo_and_anchored_certificate_carry_the_walk_at_scale(monkeypatch):
         sim.reset_users(0, n)
         sim.run()
         c, dig = sim.counters(), sim.log_digest()
+        led = au.ledger(sim)
         sim.close()
+        if env:
+            au.assert_draws_by(led, 'draw_f64')
+            assert led['walk'] == led['walk2'] == led['walk_solo'] == 0, led
+        else:
+            assert_walk_pipe(led)
         return c, dig
 
     c, dig = run({})
@@ -1268,7 +1463,8 @@ def test_pipelined_walk_matches_the_oracle(policy, form, monkeypatch):
            'ouc': dict(policy=_abi.RG_POLICY_ORGANIC_USER_COUNT, policy_seed=31, ouc=dict(gu.OUC_DEFAULTS))}[policy]
     want_env = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol)
     want = want_env.generate_logs(n, n_org)
-    rows, cnt = run_sim(cfg, n, n_org, p_click=False, **pol)
+    rows, cnt, led = run_sim(cfg, n, n_org, p_click=False, with_ledger=True, **pol)
+    assert_walk_pipe(led)
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps')}, ps_rtol=1e-12, what=f'pipe {policy} {form}')
     assert (rows['phantom'] == want['phantom']).all()
     oc = want_env.counters()
@@ -1306,7 +1502,8 @@ def test_walk_helpers_do_not_change_the_log(policy, form, monkeypatch):
                    policy_ps=rs.uniform(0.1, 1.0, size=P))
     want_env = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol)
     want = want_env.generate_logs(n, n_org)
-    rows, cnt = run_sim(cfg, n, n_org, p_click=False, **pol)
+    rows, cnt, led = run_sim(cfg, n, n_org, p_click=False, with_ledger=True, **pol)
+    assert led['walk2'] > 0 and led['walk'] == led['advance'] == led['advance_run'] == 0, led
     # (the frozen table's propensities are float32 on the device, as the BanditMF fixtures': compared at that resolution)
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps')}, ps_rtol=1e-6 if policy == 'last_view' else 1e-12,
                          what=f'helpers {policy} {form}')
@@ -1393,8 +1590,15 @@ def test_raw_log_rows_beyond_2_31_are_kept(form, monkeypatch):
     sim.run()
     cnt = sim.counters()
     rows = sim.rows()
+    led = au.ledger(sim)
     sim.close()
     torch.cuda.empty_cache()
+    ran = {k: led[k] > 0 for k in ('sweep_xh', 'walk2', 'walk_solo', 'walk', 'advance_run', 'advance', 'tail')}
+    want_ran = {'walk_pipe': ('sweep_xh', 'walk2', 'walk_solo'), 'walk_pipe_solo': ('sweep_xh', 'walk2', 'walk_solo'), 'run_walk': ('walk2', 'walk_solo'),
+                'k_walk': ('walk',), 'rounds': ('advance_run',), 'lockstep': ('advance',), 'tail': ('advance', 'tail')}[form]
+    if form == 'run_walk':
+        ran['walk_solo'] = True                      # (its last round runs only if round 2 handed users over)
+    assert ran == {k: k in want_ran for k in ran}, (form, led)
     assert cnt['log_dropped'] == 0 and cnt['log_rows'] > (1 << 31), cnt
     want = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **pol).generate_logs(n)
     gu.assert_rows_equal(rows, {k: want[k] for k in ('u', 't', 'z', 'v', 'a', 'c', 'ps')}, ps_rtol=1e-12, what=f'row base 2^31 - 4096, {form}')
