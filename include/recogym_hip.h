@@ -40,7 +40,9 @@ extern "C" {
 /* v11 (additive): rg_sim_set_epsilon_greedy (the EpsilonGreedy overlay of the lock-step kernels), rg_eg_explore_actions (its table
  * search on caller-supplied uniforms) and rg_ope_eg_workspace_bytes / rg_ope_replay_eg (the off-policy replay of an EpsilonGreedy
  * target). */
-#define RG_ABI_VERSION 11
+/* v12 (additive): rg_evolution_workspace_bytes / rg_evolution_stats (the counters of one step of the epsilon-greedy evolution study)
+ * and rg_count_online_workspace_bytes / rg_count_train_online (the count agents' train calls under a row filter). */
+#define RG_ABI_VERSION 12
 
 /* error codes */
 #define RG_OK 0
@@ -552,6 +554,45 @@ int rg_count_train(const rg_count_tables* tables, const rg_event* d_rows, const 
  * the caller takes the logged `ps` with its own float64 divide.  d_action: P int32; d_win_*: P int64.  No synchronisation. */
 int rg_count_policy(const rg_count_tables* tables, uint32_t kind, int32_t* d_action, int64_t* d_win_clicks,
                     int64_t* d_win_pulls, void* stream);
+
+/*
+ * The epsilon-greedy evolution study (reference evaluate_agent.py:51-146): one step = one run, its log's statistics, and the
+ * filtered train calls of the count agents.  Stateless (no rg_sim handle); rows / offsets as rg_count_train.
+ *
+ * rg_evolution_stats: over every bandit row that is not a phantom row (an ACT): the explore flip of (eg->seed, u, t) — the draw
+ * rg_ope_replay_eg uses; eg = NULL: the acting agent has no wrapper, no act is greedy and none explored — then
+ *   d_counts[0] += clicks, [1] += acts without a click, [2] += greedy acts with a click, [3] += greedy acts without;
+ *   d_action_clicks[a] += 1 for every clicked act of action a (P int64);
+ *   d_explored[row] (uint8, one per row of the log, optional) = 1 where the act explored, 0 on every other row.
+ * Integer adds only: the same bytes on every run.  d_workspace: rg_evolution_workspace_bytes(P) bytes; the sums are staged there
+ * and added to d_counts / d_action_clicks only when the log is valid.  Synchronises `stream` once.  RG_EINVAL: a user whose
+ * first row is a bandit row, an index >= P, epsilon outside [0, 1] (nothing is added; d_explored is then unspecified);
+ * RG_ENOMEM: a workspace too small.
+ */
+size_t rg_evolution_workspace_bytes(uint32_t num_products);
+int rg_evolution_stats(const rg_ope_eg* eg, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                       uint32_t num_products, uint8_t* d_explored, int64_t* d_counts, int64_t* d_action_clicks, void* d_workspace,
+                       size_t workspace_bytes, void* stream);
+
+/*
+ * rg_count_train_online: the train calls evaluate_agent makes, under a filter.  A row is COUNTED when it is a bandit row, not a
+ * phantom row, and d_mask (uint8 per row of the log, NULL = all ones) lets it through; session(r) = the organic rows of r's user
+ * between that user's previous bandit row (counted or not; else the user's first row) and r.
+ *   co_counts += b b^T for every counted r with a non-empty session (b = its view counts); a session no counted row closes — a
+ *   user's trailing organic rows, a session in front of a filtered-out or phantom row — is never counted;
+ *   pulls[ix][a] += 1, clicks[ix][a] += c for every counted r, ix = last_product_viewed walked over the COUNTED rows in log
+ *   order, across users: it moves to the last view of session(r) where that is non-empty, after r's own ix was taken.  Rows that
+ *   meet ix = None (-1) add to the whole table row a, as NumPy's pulls_a[None, a] += 1 does; any number of rows may.
+ * d_carry[0] (int64, device): in = last_product_viewed before the log (-1 = None), out = after it (written only when pulls is
+ * given).  d_workspace: rg_count_online_workspace_bytes(P, n_users) bytes, 8-byte aligned; afterwards its int64 words hold [0]
+ * error bits, [1] cell updates the log stands for, [2] global atomics issued for them.  Synchronises `stream` once: the whole log
+ * is validated before any table is touched.  RG_EINVAL: P out of range, a half-given pulls / clicks pair, a user whose first
+ * row is a bandit row, a row whose index is >= P, d_carry[0] >= P with pulls given (nothing is written in any of these cases);
+ * RG_ENOMEM: a workspace too small.
+ */
+size_t rg_count_online_workspace_bytes(uint32_t num_products, uint64_t n_users);
+int rg_count_train_online(const rg_count_tables* tables, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                          const uint8_t* d_mask, int64_t* d_carry, void* d_workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

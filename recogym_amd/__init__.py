@@ -85,6 +85,15 @@ def __getattr__(name):
                 'evaluate_SNIPS', 'evaluate_recall_at_k'):
         from . import evaluate_agent
         return getattr(evaluate_agent, name)
+    if name in ('evaluate_agent', 'build_agent_init', 'build_agents', 'gather_agent_stats', 'generate_epsilons', 'format_epsilon',
+                'gather_exploration_stats'):
+        # (`evaluate_agent` is the module, which is callable: evaluate_agent.py; `from . import` would ask for the attribute first)
+        import importlib
+        module = importlib.import_module(__name__ + '.evaluate_agent')
+        return module if name == 'evaluate_agent' else getattr(module, name)
+    if name in ('AgentStats', 'AgentInit', 'TrainingApproach', 'EvolutionCase', 'RoiMetrics'):
+        from . import constants
+        return getattr(constants, name)
     if name in ('Agent', 'RandomAgent', 'random_args', 'OrganicUserEventCounterAgent',
                 'organic_user_count_args', 'LastViewTableAgent'):
         from . import agents

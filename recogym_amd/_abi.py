@@ -7,7 +7,7 @@ infrastructure and is never imported from this package.)
 import ctypes as C
 import os
 
-RG_ABI_VERSION = 11
+RG_ABI_VERSION = 12
 
 RG_STATE_ORGANIC, RG_STATE_BANDIT, RG_STATE_STOP = 0, 1, 2
 
@@ -168,6 +168,12 @@ SYMBOLS = {
     'rg_count_train': (C.c_int, [C.POINTER(RgCountTables), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_void_p]),
     'rg_count_policy': (C.c_int, [C.POINTER(RgCountTables), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rg_evolution_workspace_bytes': (C.c_size_t, [C.c_uint32]),
+    'rg_evolution_stats': (C.c_int, [C.POINTER(RgOpeEg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rg_count_online_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint64]),
+    'rg_count_train_online': (C.c_int, [C.POINTER(RgCountTables), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 LIB_NAME = 'librecogym_hip.so'

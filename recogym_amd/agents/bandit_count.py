@@ -90,6 +90,33 @@ class BanditCount(Agent):
             self._clicks.add(ix[ok & clk], act[ok & clk], 1)
         self._frozen = None
 
+    def train_online_from_log(self, log, mask=None):
+        """The train calls evaluate_agent's loop makes over a log (one per bandit row that is not a phantom row), restricted to
+        the rows `mask` lets through (one entry per row of the log; None = all).  `last_product_viewed` walks over those rows
+        only; every row that meets None adds to a whole table row."""
+        P = int(self.config.num_products)
+        dl = ct.as_device_log(log)
+        if dl is not None:
+            dev = dl.rows.device
+            self.last_product_viewed, _ = ct.count_train_online(dl, P, pulls=self._pulls.device(dev), clicks=self._clicks.device(dev),
+                                                                carry=self.last_product_viewed, mask=mask)
+        else:
+            u, is_b, v, a, click, phantom = ct.online_arrays(log)
+            ix, act, clk, self.last_product_viewed = ct.online_bandit_updates(
+                u, is_b, v, a, click, P, ct.counted_rows(is_b, phantom, mask), self.last_product_viewed)
+            none = ix < 0
+            if none.any():
+                n = np.bincount(act[none], minlength=P)
+                c = np.bincount(act[none & clk], minlength=P)
+                for k in np.flatnonzero(n):
+                    self._pulls.add_row(int(k), int(n[k]))
+                    if c[k]:
+                        self._clicks.add_row(int(k), int(c[k]))
+            ok = ~none
+            self._pulls.add(ix[ok], act[ok], 1)
+            self._clicks.add(ix[ok & clk], act[ok & clk], 1)
+        self._frozen = None
+
     # -- acting -----------------------------------------------------------------------------------------
     def frozen(self):
         """The argmax table and its CTR values as a LastViewTableAgent, rebuilt only after training changed the counts."""

@@ -126,9 +126,11 @@ def log_arrays(log):
     return u, is_b, v, a, np.nan_to_num(np.asarray(c, dtype=np.float64)) != 0
 
 
-def organic_updates(u, is_b, v, P):
+def organic_updates(u, is_b, v, P, sessions=None):
     """The cells b b^T of every session touches -> (rows, cols, values): b[p] = views of p in the session; every maximal run of
-    organic rows inside a user is a session (it ends in a bandit row, or ends the user: the call without an action)."""
+    organic rows inside a user is a session (it ends in a bandit row, or ends the user: the call without an action).
+    `sessions(sid)` (optional) -> the ids of the sessions that count, given every row's session id (a bandit row carries the
+    id of the session it closes)."""
     n = len(u)
     empty = np.zeros(0, dtype=np.int64)
     if n == 0 or is_b.all():
@@ -136,6 +138,10 @@ def organic_updates(u, is_b, v, P):
     start = np.r_[True, u[1:] != u[:-1]] | np.r_[False, is_b[:-1]]
     sid = np.cumsum(start) - 1
     org = ~is_b
+    if sessions is not None:
+        org = org & np.isin(sid, sessions(sid))
+        if not org.any():
+            return empty, empty, empty
     if v[org].min() < 0 or v[org].max() >= P:
         raise ValueError(f'the log views products outside [0, {P})')
     key, cnt = np.unique(sid[org] * P + v[org], return_counts=True)          # (session, product) -> views, sessions ascending
@@ -179,6 +185,56 @@ def bandit_updates(u, is_b, v, a, click, P, carry):
 
 
 # ----------------------------------------------------------------------------------------------------------
+# the online protocol under a row filter (evaluate_agent's evolution steps)
+# ----------------------------------------------------------------------------------------------------------
+def online_arrays(log):
+    """-> (u, is_b, v, a, click, phantom): log_arrays plus the phantom flag of every row — the `phantom` entry of a column
+    dict where it has one, else no row is a phantom row (a log of evaluate_agent's own loop has none)."""
+    u, is_b, v, a, click = log_arrays(log)
+    ph = log.get('phantom') if isinstance(log, dict) else None
+    return u, is_b, v, a, click, (np.zeros(len(u), dtype=bool) if ph is None else np.asarray(ph).astype(bool))
+
+
+def counted_rows(is_b, phantom=None, mask=None):
+    """The rows that stand for a train call: bandit rows that are not phantom rows and that the mask lets through."""
+    out = np.asarray(is_b, dtype=bool).copy()
+    if phantom is not None:
+        out &= ~np.asarray(phantom, dtype=bool)
+    if mask is not None:
+        out &= np.asarray(mask) != 0
+    return out
+
+
+def online_organic_updates(u, is_b, v, P, counted):
+    """OrganicCount's train calls at the counted rows -> (rows, cols, values): b b^T of every session a counted row closes (a
+    session in front of any other bandit row, or at the end of a user, is never counted)."""
+    return organic_updates(u, is_b, v, P, sessions=lambda sid: sid[counted])
+
+
+def online_bandit_updates(u, is_b, v, a, click, P, counted, carry):
+    """BanditCount's train calls at the counted rows -> (ix, action, click) per counted row and the new carry: last_product_viewed
+    walks over the counted rows in log order, across users — ix is its value before the row, then it moves to the view directly
+    in front of the row where that row is an organic row of the same user (the last view of the row's own session).  ix = -1
+    stands for None; any number of rows can meet it."""
+    rows = np.flatnonzero(counted)
+    if rows.size == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=bool), carry
+    if a[rows].min() < 0 or a[rows].max() >= P:
+        raise ValueError(f'the log has actions outside [0, {P})')
+    prev = np.maximum(rows - 1, 0)
+    has = (rows > 0) & ~is_b[prev] & (u[prev] == u[rows])
+    sv = np.where(has, v[prev], -1).astype(np.int64)
+    if sv.max() >= P:
+        raise ValueError(f'the log views products outside [0, {P})')
+    pos = np.maximum.accumulate(np.where(sv >= 0, np.arange(rows.size), -1))
+    before = np.r_[-1, pos[:-1]]
+    c0 = -1 if carry is None else int(carry)
+    ix = np.where(before >= 0, sv[np.maximum(before, 0)], c0).astype(np.int64)
+    new_carry = carry if pos[-1] < 0 else int(sv[pos[-1]])
+    return ix, a[rows].astype(np.int64), click[rows], new_carry
+
+
+# ----------------------------------------------------------------------------------------------------------
 # the device reduction
 # ----------------------------------------------------------------------------------------------------------
 def device_present():
@@ -197,15 +253,20 @@ def as_device_log(log):
     return log if isinstance(log, DeviceLog) else None
 
 
-def columns_to_device_log(u, is_b, v, a, click, P, device):
-    """Log columns -> a DeviceLog (rows in the given order; every run of equal u is a user)."""
+def columns_to_device_log(u, is_b, v, a, click, P, device, t=None, phantom=None):
+    """Log columns -> a DeviceLog (rows in the given order; every run of equal u is a user).  `t`: the rows' event indices (0
+    where not given: enough for everything that draws nothing); `phantom`: the rows that carry the phantom flag."""
     import torch
     from ..sim import DeviceLog
     n = len(u)
     raw = np.zeros((n, 4), dtype=np.uint32)
     raw[:, 0] = u.astype(np.uint32)
+    if t is not None:
+        raw[:, 1] = np.asarray(t).astype(np.uint32)
     raw[:, 2] = (np.where(is_b, a, v).astype(np.uint32) | np.where(is_b, _abi.RG_EV_BANDIT, 0).astype(np.uint32)
                  | np.where(is_b & click, _abi.RG_EV_CLICK, 0).astype(np.uint32))
+    if phantom is not None:
+        raw[:, 2] |= np.where(np.asarray(phantom, dtype=bool), _abi.RG_EV_PHANTOM, 0).astype(np.uint32)
     start = np.flatnonzero(np.r_[True, u[1:] != u[:-1]]) if n else np.zeros(0, dtype=np.int64)
     offsets = np.r_[start, n].astype(np.int64)
     return DeviceLog(torch.from_numpy(raw.view(np.int32)).to(device), torch.from_numpy(offsets).to(device), None, 0, int(P), None)
@@ -233,6 +294,37 @@ def count_train(dl, P, co=None, pulls=None, clicks=None, carry=None):
         out = cr.cpu().numpy()
         st = ws.view(torch.int64)[:4].cpu().numpy()
     return (None if out[0] < 0 else int(out[0])), dict(updates=int(st[1]), global_atomics=int(st[2]), none_row=int(out[1]))
+
+
+def count_train_online(dl, P, co=None, pulls=None, clicks=None, carry=None, mask=None):
+    """rg_count_train_online on a DeviceLog: the train calls at the counted rows (bandit, not phantom, let through by `mask`: a
+    uint8 / bool device tensor with one entry per row of the log, or None) added to the given int64 device tables -> (new
+    carry, stats dict)."""
+    import torch
+    lib = _abi.load()
+    if int(dl.num_products) != int(P):
+        raise ValueError(f'the log has {dl.num_products} products, the agent {P}')
+    device = dl.rows.device
+    n_users = int(dl.offsets.numel()) - 1
+    if mask is not None:
+        if int(mask.numel()) != int(dl.rows.shape[0]):
+            raise ValueError(f'the mask has {int(mask.numel())} entries, the log {int(dl.rows.shape[0])} rows')
+        mask = mask.to(device=device, dtype=torch.uint8).contiguous()
+    tabs = _abi.RgCountTables(num_products=int(P), reserved=0,
+                              co_counts=None if co is None else co.data_ptr(),
+                              pulls=None if pulls is None else pulls.data_ptr(),
+                              clicks=None if clicks is None else clicks.data_ptr())
+    with torch.cuda.device(device):
+        need = lib.rg_count_online_workspace_bytes(int(P), n_users)
+        ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=device)
+        cr = torch.tensor([-1 if carry is None else int(carry)], dtype=torch.int64, device=device)
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _abi.check(lib.rg_count_train_online(C.byref(tabs), dl.rows.data_ptr(), dl.offsets.data_ptr(), n_users,
+                                             None if mask is None else mask.data_ptr(), cr.data_ptr(), ws.data_ptr(), need, stream),
+                   'rg_count_train_online')
+        out = int(cr.item())
+        st = ws[:4].cpu().numpy()
+    return (None if out < 0 else out), dict(updates=int(st[1]), global_atomics=int(st[2]))
 
 
 def count_policy(P, kind, co=None, pulls=None, clicks=None):

@@ -29,7 +29,7 @@ epsilon_greedy_args = {
 _DEVICE_INNER = (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_ORGANIC_USER_COUNT, _abi.RG_POLICY_LAST_VIEW_TABLE)
 _REPLAY_INNER = (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE)
 # what the wrapper passes on to the inner agent only where that agent has it (test_agent asks with hasattr / getattr)
-_DELEGATED = ('train_from_log', 'accepts_device_log', 'needs_training')
+_DELEGATED = ('train_from_log', 'train_online_from_log', 'accepts_device_log', 'needs_training')
 
 
 def explore_table(num_products, pure_new):

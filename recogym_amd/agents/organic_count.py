@@ -58,6 +58,20 @@ class OrganicCount(Agent):
             self._co.add(*ct.organic_updates(u, is_b, v, P))
         self._frozen = None
 
+    def train_online_from_log(self, log, mask=None):
+        """The train calls evaluate_agent's loop makes over a log (one per bandit row that is not a phantom row, with the organic
+        rows directly in front of it as its session; none for a user's trailing organic rows), restricted to the rows `mask`
+        lets through (one entry per row of the log; None = all): rg_count_train_online for a Simulator / DeviceLog, array
+        operations for a DataFrame / column dict."""
+        P = int(self.config.num_products)
+        dl = ct.as_device_log(log)
+        if dl is not None:
+            ct.count_train_online(dl, P, co=self._co.device(dl.rows.device), mask=mask)
+        else:
+            u, is_b, v, _, _, phantom = ct.online_arrays(log)
+            self._co.add(*ct.online_organic_updates(u, is_b, v, P, ct.counted_rows(is_b, phantom, mask)))
+        self._frozen = None
+
     # -- acting -----------------------------------------------------------------------------------------
     def frozen(self):
         """The argmax table as a LastViewTableAgent, rebuilt only after training changed the counts."""

@@ -67,6 +67,15 @@ __device__ __forceinline__ uint32_t ope_last_view(const OpeRow& r, uint32_t lane
     return mine;
 }
 
+// EpsilonGreedy's explore flip of the act at (user u, event t): words 0,1 of the policy block of (the wrapper's seed, u, t) against
+// the first entry of NumPy's normalised cdf of p = [eps, 1 - eps] (agents/epsilon_greedy.py: rng.choice([True, False], p)).
+// Shared by the off-policy replay (rg_ope_eg.hip) and the evolution statistics (rg_evolve.hip).
+__device__ __forceinline__ double eg_threshold(double eps) { return eps / (eps + (1.0 - eps)); }
+__device__ __forceinline__ bool eg_explored(uint64_t seed, double thr, uint32_t u, uint32_t t) {
+    const rg_u32x4 w = rg_draw(seed, u, t, 0, RG_DRAW_POLICY);
+    return !(thr <= rg_uniform(w.w[0], w.w[1]));
+}
+
 // a lane's (n, sum c r, sum r) over its bandit rows, in row order
 struct OpeAcc {
     double n = 0.0, cr = 0.0, r = 0.0;

@@ -23,7 +23,7 @@ __global__ __launch_bounds__(64 * kOpeWaves) void k_ope_eg_replay(
     const uint32_t P = inner.num_products;
     const bool lvt = inner.kind == RG_POLICY_LAST_VIEW_TABLE;
     const double eps = eg.epsilon;
-    const double thr = eps / (eps + (1.0 - eps));
+    const double thr = eg_threshold(eps);
     const double pi_uniform = 1.0 / static_cast<double>(P);
     OpeAcc acc;
     for (uint64_t user = wave; user < n_users; user += n_waves) {
@@ -45,8 +45,7 @@ __global__ __launch_bounds__(64 * kOpeWaves) void k_ope_eg_replay(
                 pi_inner = pi_uniform;
             }
             if (r.isb) {
-                const rg_u32x4 w = rg_draw(eg.seed, r.x.x, r.x.y, 0, RG_DRAW_POLICY);
-                const bool explore = !(thr <= rg_uniform(w.w[0], w.w[1]));
+                const bool explore = eg_explored(eg.seed, thr, r.x.x, r.x.y);
                 const double pi = explore ? eps * ((eg.pure_new && r.idx == g) ? 0.0 : eg.prob_explore) : (1.0 - eps) * pi_inner;
                 acc.emit(log, r, pi);
                 if (greedy_out) greedy_out[r.row] = explore ? 0 : 1;

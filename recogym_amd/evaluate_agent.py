@@ -14,7 +14,17 @@ the agent has a replay form (ope_policy_of) and the log qualifies, the rows are 
 by rg_ope_replay (the frozen LogReg policy: by rg_ope_replay_logreg, an EpsilonGreedy target: by rg_ope_replay_eg); otherwise the
 host loop below runs:
 the reference's loop made linear (one stable group-by instead of six frame filters per user), the same
-act() calls in the same order."""
+act() calls in the same order.
+
+The exploration study — reference: recogym/evaluate_agent.py:51-447 (evaluate_agent, build_agent_init, build_agents,
+gather_agent_stats, generate_epsilons, format_epsilon, gather_exploration_stats; the plot functions are not part of this package).
+`evaluate_agent` lets an agent act on a block of users, trains a copy on what the TrainingApproach lets through, swaps the copy in
+and repeats.  Over agents with a device form whose training copy can reduce a device log (`train_online_from_log`: OrganicCount,
+BanditCount, also inside EpsilonGreedy) every step is one device run, one pass over its log for the statistics
+(rg_evolution_stats) and one filtered reduction into the tables (rg_count_train_online); only the step's counters leave the
+device.  Every other agent takes the host route: the reference's loop over env.reset / step / step_offline.  Both routes are
+single-process; sharding the study over ranks is out of scope.  The module itself is callable —
+`recogym_amd.evaluate_agent(env, agent, ...)` is the function, as `recogym.evaluate_agent` is in the reference."""
 import ctypes as C
 from copy import deepcopy
 
@@ -24,6 +34,7 @@ from scipy.stats.distributions import beta
 
 from . import _abi
 from .bench_agents import evaluate_counts
+from .constants import AgentInit, AgentStats, EvolutionCase, RoiMetrics, TrainingApproach  # noqa: F401
 from .envs.context import DefaultContext
 from .envs.observation import Observation
 from .envs.session import OrganicSessions
@@ -452,3 +463,337 @@ def verify_agents_recall_at_k(reco_log, agents, k=5):
         stat['0.500'].append(mean_hits)
         stat['0.975'].append(mean_hits + 2 * se_hits)
     return pd.DataFrame().from_dict(stat)
+
+
+# ------------------------------------------------------------------------------------------------
+# the exploration study
+# ------------------------------------------------------------------------------------------------
+EpsilonDelta = .02
+EpsilonSteps = 6  # Including epsilon = 0.0.
+EpsilonPrecision = 2
+EvolutionEpsilons = (0.00, 0.01, 0.02, 0.03, 0.05, 0.08)
+
+_SLIDING = (TrainingApproach.SLIDING_WINDOW_ALL_DATA, TrainingApproach.SLIDING_WINDOW_EXPLORATION_DATA)
+_EXPLORATION = (TrainingApproach.ALL_EXPLORATION_DATA, TrainingApproach.SLIDING_WINDOW_EXPLORATION_DATA)
+
+
+def evolution_stats(u, t, is_b, a, click, num_products, phantom=None, epsilon_greedy=None, greedy=None):
+    """The statistics of one evolution step from log columns (NumPy; the host form of rg_evolution_stats) -> (counts int64 [4]:
+    successes, failures, successes_greedy, failures_greedy; clicks per action int64 [P]; explored bool per row).  An act is a bandit
+    row that is not a phantom row.  `epsilon_greedy` = dict(epsilon, seed): the wrapper's explore flip is recomputed from the
+    addressed draw of (seed, u, t); `greedy` (per row, non-zero = greedy) replaces it where the log recorded it; neither: the
+    acting agent has no wrapper, no act is greedy and none explored."""
+    from . import rng
+    is_b = np.asarray(is_b, dtype=bool)
+    act = is_b if phantom is None else is_b & ~np.asarray(phantom, dtype=bool)
+    click = np.asarray(click).astype(bool) & act
+    a = np.asarray(a, dtype=np.int64)
+    if act.any() and (a[act].min() < 0 or a[act].max() >= num_products):
+        raise ValueError(f'the log has actions outside [0, {num_products})')
+    explored = np.zeros(len(is_b), dtype=bool)
+    is_greedy = np.zeros(len(is_b), dtype=bool)
+    if greedy is not None:
+        is_greedy = act & (np.asarray(greedy) > 0)
+        explored = act & ~is_greedy
+    elif epsilon_greedy is not None:
+        eps = float(epsilon_greedy['epsilon'])
+        thr = eps / (eps + (1.0 - eps))
+        for i in np.flatnonzero(act):
+            _, u0, _ = rng.policy_uniforms(int(epsilon_greedy['seed']), int(u[i]), int(t[i]))
+            explored[i] = not (thr <= u0)
+        is_greedy = act & ~explored
+    counts = np.array([click.sum(), (act & ~click).sum(), (click & is_greedy).sum(), (act & ~click & is_greedy).sum()], dtype=np.int64)
+    return counts, np.bincount(a[click], minlength=int(num_products)).astype(np.int64), explored
+
+
+def evolution_stats_device(dl, epsilon_greedy=None, counts=None, action_clicks=None):
+    """rg_evolution_stats over a DeviceLog -> (counts int64 [4], clicks per action int64 [P], explored uint8 per row), device
+    tensors; `counts` / `action_clicks` are added to where given."""
+    import torch
+    lib = _abi.load()
+    device = dl.rows.device
+    P = int(dl.num_products)
+    n_users = int(dl.offsets.numel()) - 1
+    eg = None
+    if epsilon_greedy is not None:
+        eg = _abi.RgOpeEg(epsilon=float(epsilon_greedy['epsilon']), seed=int(epsilon_greedy['seed']) & 0xFFFFFFFFFFFFFFFF,
+                          pure_new=int(bool(epsilon_greedy.get('pure_new', True))), reserved=0, prob_explore=0.0)
+    with torch.cuda.device(device):
+        counts = torch.zeros(4, dtype=torch.int64, device=device) if counts is None else counts
+        action_clicks = torch.zeros(P, dtype=torch.int64, device=device) if action_clicks is None else action_clicks
+        explored = torch.zeros(max(int(dl.rows.shape[0]), 1), dtype=torch.uint8, device=device)
+        need = lib.rg_evolution_workspace_bytes(P)
+        ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=device)
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _abi.check(lib.rg_evolution_stats(None if eg is None else C.byref(eg), dl.rows.data_ptr(), dl.offsets.data_ptr(), n_users, P,
+                                          explored.data_ptr(), counts.data_ptr(), action_clicks.data_ptr(), ws.data_ptr(), need,
+                                          stream), 'rg_evolution_stats')
+    return counts, action_clicks, explored[:int(dl.rows.shape[0])]
+
+
+def training_mask(training_approach, is_act, explored, samples, sliding_window_samples):
+    """Which rows of a step's log train the next agent -> (mask with one entry per row, or None = every act; the running
+    `samples` after the step).  is_act / explored: NumPy arrays or torch tensors, one entry per row (explored = None: the acting
+    agent reports no `greedy`).  `samples` counts the acts of all steps so far; the sliding-window approaches keep the acts at
+    which it is a multiple of `sliding_window_samples`, tested after the increment (evaluate_agent.py:103-114)."""
+    n_acts = int(is_act.sum())
+    if training_approach in (TrainingApproach.ALL_DATA, TrainingApproach.LAST_STEP):
+        return None, samples + n_acts
+    if training_approach not in _SLIDING and training_approach not in _EXPLORATION:
+        raise AssertionError(f'Unknown Training Approach: {training_approach}')
+    if n_acts == 0:
+        return is_act, samples
+    mask = is_act
+    if training_approach in _SLIDING:
+        if isinstance(is_act, np.ndarray):
+            cum = np.cumsum(is_act, dtype=np.int64)
+        else:
+            import torch
+            cum = torch.cumsum(is_act.to(torch.int64), 0)
+        mask = mask & ((cum + int(samples)) % int(sliding_window_samples) == 0)
+    if training_approach in _EXPLORATION:
+        if explored is None:
+            raise KeyError('greedy')
+        mask = mask & (explored != 0)
+    return mask, samples + n_acts
+
+
+def _is_epsilon_greedy(agent):
+    from .agents.epsilon_greedy import EpsilonGreedy
+    return isinstance(agent, EpsilonGreedy)
+
+
+def _trainable(agent):
+    from .bench_agents import _learns
+    return _learns(agent.agent if _is_epsilon_greedy(agent) else agent)
+
+
+def _device_route(env, agent):
+    from .envs.reco_env_v1 import device_policy_of
+    if not hasattr(env, 'simulate') or getattr(env, 'agent', None) is not None or not _device_present():
+        return False
+    if _trainable(agent) and not hasattr(agent, 'train_online_from_log'):
+        return False
+    return device_policy_of(agent) is not None
+
+
+def _new_rewards(num_products):
+    rewards = {EvolutionCase.SUCCESS: [], EvolutionCase.SUCCESS_GREEDY: [], EvolutionCase.FAILURE: [],
+               EvolutionCase.FAILURE_GREEDY: [], EvolutionCase.ACTIONS: dict()}
+    for action_id in range(num_products):
+        rewards[EvolutionCase.ACTIONS][action_id] = [0]
+    return rewards
+
+
+def _evolve_device(env, agent, initial_agent, n_init, num_step_users, num_steps, training_approach, window):
+    import torch
+    from .envs.reco_env_v1 import device_policy_of
+    P = int(env.config.num_products)
+    learns = _trainable(agent)
+    if n_init and learns:
+        _, sim = env.simulate(n_init, None, first_user_id=0, log=True)
+        agent.train_online_from_log(sim.device_log(), None)
+        sim.close()
+    uid = n_init
+    rewards = _new_rewards(P)
+    training_agent = deepcopy(agent)
+    samples = 0
+    for _ in range(num_steps):
+        if device_policy_of(agent) is None:
+            raise RuntimeError(f'{type(agent).__name__} lost its device form during the study')
+        eg = agent._overlay() if _is_epsilon_greedy(agent) else None
+        if num_step_users:
+            _, sim = env.simulate(num_step_users, agent, first_user_id=uid, log=True)
+            dl = sim.device_log()
+            counts, clicks, explored = evolution_stats_device(dl, eg)
+            code = dl.rows[:, 2]
+            is_act = ((code & _abi.RG_EV_BANDIT) != 0) & ((code & _abi.RG_EV_PHANTOM) == 0)
+            mask, samples = training_mask(training_approach, is_act, explored if eg is not None else None, samples, window)
+            if learns:
+                training_agent.train_online_from_log(dl, mask)
+            host = torch.cat([counts, clicks]).cpu().numpy()         # all that leaves the device
+            sim.close()
+        else:
+            host = np.zeros(4 + P, dtype=np.int64)
+        uid += num_step_users
+        for action_id in range(P):
+            rewards[EvolutionCase.ACTIONS][action_id][-1] += int(host[4 + action_id])
+            rewards[EvolutionCase.ACTIONS][action_id].append(0)
+        agent = training_agent
+        training_agent = deepcopy(initial_agent if training_approach == TrainingApproach.LAST_STEP else agent)
+        rewards[EvolutionCase.SUCCESS].append(int(host[0]))
+        rewards[EvolutionCase.SUCCESS_GREEDY].append(int(host[2]))
+        rewards[EvolutionCase.FAILURE].append(int(host[1]))
+        rewards[EvolutionCase.FAILURE_GREEDY].append(int(host[3]))
+    return rewards, agent
+
+
+def _evolve_host(env, agent, initial_agent, n_init, num_step_users, num_steps, training_approach, window):
+    """The reference's loop (evaluate_agent.py:59-146) over the per-user path of the environment."""
+    unique_user_id = 0
+    for u in range(n_init):
+        env.reset(unique_user_id + u)
+        agent.reset()
+        new_observation, reward, done, _ = env.step(None)
+        if done:
+            continue            # the first organic session ended the episode: nothing to act on (DESIGN.md 8)
+        while True:
+            old_observation = new_observation
+            action, new_observation, reward, done, _ = env.step_offline(new_observation, reward, False)
+            agent.train(old_observation, action, reward, done)
+            if done:
+                break
+    unique_user_id += n_init
+    rewards = _new_rewards(int(env.config.num_products))
+    training_agent = deepcopy(agent)
+    samples = 0
+    for _ in range(num_steps):
+        successes = successes_greedy = failures = failures_greedy = 0
+        for u in range(num_step_users):
+            env.reset(unique_user_id + u)
+            agent.reset()
+            new_observation, reward, done, _ = env.step(None)
+            while not done:
+                old_observation = new_observation
+                action = agent.act(old_observation, reward, done)
+                new_observation, reward, done, info = env.step(action['a'])
+                samples += 1
+                if training_approach == TrainingApproach.ALL_DATA or training_approach == TrainingApproach.LAST_STEP:
+                    should_update_training_data = True
+                elif training_approach == TrainingApproach.SLIDING_WINDOW_ALL_DATA:
+                    should_update_training_data = samples % window == 0
+                elif training_approach == TrainingApproach.ALL_EXPLORATION_DATA:
+                    should_update_training_data = not action['greedy']
+                elif training_approach == TrainingApproach.SLIDING_WINDOW_EXPLORATION_DATA:
+                    should_update_training_data = (not action['greedy']) and samples % window == 0
+                else:
+                    assert False, f'Unknown Training Approach: {training_approach}'
+                if should_update_training_data:
+                    training_agent.train(old_observation, action, reward, done)
+                if reward:
+                    successes += 1
+                    if 'greedy' in action and action['greedy']:
+                        successes_greedy += 1
+                    rewards[EvolutionCase.ACTIONS][int(action['a'])][-1] += 1
+                else:
+                    if 'greedy' in action and action['greedy']:
+                        failures_greedy += 1
+                    failures += 1
+        unique_user_id += num_step_users
+        agent = training_agent
+        for action_id in range(env.config.num_products):
+            rewards[EvolutionCase.ACTIONS][action_id].append(0)
+        training_agent = deepcopy(initial_agent if training_approach == TrainingApproach.LAST_STEP else agent)
+        rewards[EvolutionCase.SUCCESS].append(successes)
+        rewards[EvolutionCase.SUCCESS_GREEDY].append(successes_greedy)
+        rewards[EvolutionCase.FAILURE].append(failures)
+        rewards[EvolutionCase.FAILURE_GREEDY].append(failures_greedy)
+    return rewards, agent
+
+
+def evolve(env, agent, num_initial_train_users=100, num_step_users=1000, num_steps=10,
+           training_approach=TrainingApproach.ALL_DATA, sliding_window_samples=10000, route=None):
+    """evaluate_agent that also hands back the agent trained last -> (rewards, agent).  `route`: 'device' / 'host' forces one
+    (None: the device route where the agents have the forms it needs)."""
+    initial_agent = deepcopy(agent)
+    device = _device_route(env, agent) if route is None else route == 'device'
+    fn = _evolve_device if device else _evolve_host
+    return fn(env, agent, initial_agent, int(num_initial_train_users), int(num_step_users), int(num_steps), training_approach,
+              sliding_window_samples)
+
+
+def evaluate_agent(env, agent, num_initial_train_users=100, num_step_users=1000, num_steps=10,
+                   training_approach=TrainingApproach.ALL_DATA, sliding_window_samples=10000):
+    """Reference evaluate_agent.py:51-146 -> {EvolutionCase.SUCCESS / SUCCESS_GREEDY / FAILURE / FAILURE_GREEDY: one count per
+    step, EvolutionCase.ACTIONS: {action: clicks per step, and a trailing 0}}.  `agent` is trained in place on the initial
+    users, as in the reference.  One deviation: an initial user whose first organic session already ended the
+    episode contributes nothing (the reference lets it act once more and can revive it)."""
+    return evolve(env, agent, num_initial_train_users, num_step_users, num_steps, training_approach, sliding_window_samples)[0]
+
+
+def build_agent_init(agent_key, ctor, def_args):
+    return {agent_key: {AgentInit.CTOR: ctor, AgentInit.DEF_ARGS: def_args}}
+
+
+def build_agents(agents_init_data, new_env_args):
+    from .envs.configuration import Configuration
+    agents = dict()
+    for agent_key in agents_init_data:
+        agent_init_data = agents_init_data[agent_key]
+        ctor = agent_init_data[AgentInit.CTOR]
+        def_args = agent_init_data[AgentInit.DEF_ARGS]
+        agents[agent_key] = ctor(Configuration({**def_args, **new_env_args}))
+    return agents
+
+
+def gather_agent_stats(env, env_args, extra_env_args, agents_init_data,
+                       user_samples=(100, 1000, 2000, 3000, 5000, 8000, 10000, 13000, 14000, 15000),
+                       num_online_users: int = 15000, num_epochs: int = 1, epoch_with_random_reset: bool = False,
+                       num_organic_offline_users: int = 100, with_cache: bool = False):
+    """Reference evaluate_agent.py:185-281 over this package's test_agent -> {AgentStats.SAMPLES: user_samples,
+    AgentStats.AGENTS: {name: {AgentStats.Q0_025 / Q0_500 / Q0_975: one value per sample size}}}.  The reference's
+    multiprocessing.Pool is an in-process loop over the sample sizes here: every worker process would open the GPU, and the
+    results do not depend on it (draws are addressed by (seed, user, t), not taken from a shared stream)."""
+    from .bench_agents import test_agent
+    new_env_args = {**env_args, **extra_env_args}
+    new_env = deepcopy(env)
+    new_env.init_gym(new_env_args)
+    agents = build_agents(agents_init_data, new_env_args)
+    agent_stats = {AgentStats.SAMPLES: user_samples, AgentStats.AGENTS: dict()}
+    for agent_key in agents:
+        stats = {AgentStats.Q0_025: [], AgentStats.Q0_500: [], AgentStats.Q0_975: []}
+        for num_offline_users in user_samples:
+            result = test_agent(deepcopy(new_env), deepcopy(agents[agent_key]), num_offline_users, num_online_users,
+                                num_organic_offline_users, num_epochs, epoch_with_random_reset, with_cache)
+            stats[AgentStats.Q0_025].append(result[1])
+            stats[AgentStats.Q0_500].append(result[0])
+            stats[AgentStats.Q0_975].append(result[2])
+        agent_stats[AgentStats.AGENTS][agent_key] = stats
+    return agent_stats
+
+
+def generate_epsilons(epsilon_step=EpsilonDelta, iterations=EpsilonSteps):
+    return [0.00, 0.01, 0.02, 0.03, 0.05, 0.08]
+
+
+def format_epsilon(epsilon):
+    return ("{0:." + f"{EpsilonPrecision}" + "f}").format(round(epsilon, EpsilonPrecision))
+
+
+def gather_exploration_stats(env, env_args, extra_env_args, agents_init_data, training_approach, num_initial_train_users=1000,
+                             num_step_users=1000, epsilons=EvolutionEpsilons, num_evolution_steps=6):
+    """Reference evaluate_agent.py:344-447 -> {agent name: {format_epsilon(eps): the rewards dict of evaluate_agent for
+    EpsilonGreedy(eps) over a copy of the agent}}.  The reference's multiprocessing.Pool is an in-process loop over the epsilon
+    values here (see gather_agent_stats)."""
+    from .agents.epsilon_greedy import EpsilonGreedy, epsilon_greedy_args
+    from .envs.configuration import Configuration
+    agent_evolution_stats = dict()
+    new_env_args = {**env_args, **extra_env_args}
+    new_env = deepcopy(env)
+    new_env.init_gym(new_env_args)
+    agents = build_agents(agents_init_data, new_env_args)
+    for agent_key in agents:
+        agent_stats = dict()
+        for epsilon in epsilons:
+            agent = EpsilonGreedy(Configuration({**epsilon_greedy_args, **new_env_args, 'epsilon': epsilon}), deepcopy(agents[agent_key]))
+            rewards = evaluate_agent(deepcopy(new_env), agent, num_initial_train_users, num_step_users, num_evolution_steps,
+                                     training_approach)
+            assert len(rewards[EvolutionCase.SUCCESS]) == len(rewards[EvolutionCase.FAILURE]) == num_evolution_steps
+            agent_stats[format_epsilon(epsilon)] = {k: rewards[k] for k in (EvolutionCase.SUCCESS, EvolutionCase.SUCCESS_GREEDY,
+                                                                             EvolutionCase.FAILURE, EvolutionCase.FAILURE_GREEDY,
+                                                                             EvolutionCase.ACTIONS)}
+        agent_evolution_stats[agent_key] = agent_stats
+    return agent_evolution_stats
+
+
+class _CallableModule(type(np)):
+    """`recogym_amd.evaluate_agent` is this module (verify_agents, evaluate_IPS, ... live in it) and, called, the function of
+    the same name — the reference's package exports the function under the module's name."""
+
+    def __call__(self, *args, **kwargs):
+        return evaluate_agent(*args, **kwargs)
+
+
+import sys as _sys  # noqa: E402
+
+_sys.modules[__name__].__class__ = _CallableModule
