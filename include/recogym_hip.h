@@ -42,7 +42,9 @@ extern "C" {
  * target). */
 /* v12 (additive): rg_evolution_workspace_bytes / rg_evolution_stats (the counters of one step of the epsilon-greedy evolution study)
  * and rg_count_online_workspace_bytes / rg_count_train_online (the count agents' train calls under a row filter). */
-#define RG_ABI_VERSION 12
+/* v13 (additive): RG_POLICY_LOGREG_POLY with rg_sim_set_logreg_poly, rg_sim_read_poly_unresolved and rg_sim_debug_poly_acts (the
+ * likelihood agent LogregPolyAgent in the step loop), and the counters RG_CNT_POLY_TABLE / RG_CNT_POLY_UNRESOLVED. */
+#define RG_ABI_VERSION 13
 
 /* error codes */
 #define RG_OK 0
@@ -68,6 +70,10 @@ extern "C" {
 #define RG_POLICY_LOGREG_FROZEN 5 /* frozen LogregMulticlassIpsAgent (select_randomly = False), agents/logreg_ips.py:60-87:
                                      a = classes[argmax_c (sum_p views[p] W[c][p] + b[c])] over the user's view counts
                                      (ViewsFeaturesProvider, agents/abstract.py:316-409), ps = 1 */
+#define RG_POLICY_LOGREG_POLY 6   /* frozen LogregPolyAgent (the likelihood agent), agents/logreg_poly.py:143-167: a = the first index of
+                                     the maximum of predict_proba[:, 1] = expit(decision) over one decision per action, on the
+                                     polynomial features of the user's view counts — rg_sim_set_logreg_poly has the contract; ps = 1.
+                                     Routed like RG_POLICY_LOGREG_FROZEN (lock-step / rounds, no tail kernel). */
 
 /*
  * Everything the step loop needs from `env.config` (a Configuration built from env_1_args,
@@ -154,6 +160,9 @@ typedef struct rg_event {
 #define RG_CNT_BAD_ACTION 25   /* RG_POLICY_EXTERNAL: events whose action was outside [0, num_products): rg_sim_step evaluates them with
                                  * product 0 (it must not index beta / mu_b with them) and LOGS a = 0 — a caller bug made visible here
                                  * (rg_sim_step_user rejects the same input with RG_EINVAL before it reaches the device) */
+#define RG_CNT_POLY_TABLE 26     /* RG_POLICY_LOGREG_POLY: acts whose best decision lies on the expit step table (decided exactly there) */
+#define RG_CNT_POLY_UNRESOLVED 27 /* ... acts below the table with a lower-index decision inside the margin W of the best one: the action
+                                   * taken is the first maximal decision; the act is listed for the host (rg_sim_read_poly_unresolved) */
 #define RG_CNT_N 32             /* out[] of rg_sim_read_counters; slots 16..23 are internal */
 
 typedef struct rg_sim rg_sim;
@@ -190,7 +199,7 @@ int rg_sim_destroy(rg_sim* sim);
  * over product slices), search (k_draw_search behind the slices), draw_tp (k_draw_tp / k_draw_tpw), pick (k_pick), draw_cached
  * (k_draw_cached), sweep_xh (k_sweep_xh), exact_m / exact_tile / exact_h (the float64 sums: a user per lane / a product per lane /
  * the walk's mixed batch), walk (k_walk), walk2 (k_walk2), walk_solo (k_walk_solo), advance (k_advance), advance_run
- * (k_advance_run), tail (k_tail), repack, env0 (k_draw_env0), logreg_screen, logreg_acts, logreg_sample, sort_tiled / sort_plain
+ * (k_advance_run), tail (k_tail), repack, env0 (k_draw_env0), logreg_screen, logreg_acts, logreg_sample, logreg_poly (k_poly_acts), sort_tiled / sort_plain
  * (the ordered log's scatter).  What rg_sim_create chose for the fast draw: draw_kh, draw_n1 (the class: KH, k-steps N1),
  * draw_split (0 none, 1 three-way bf16, 2 two-way fp16, 3 two-way fp16 wide), draw_kernel (0 float64 only, 1 fp32 MFMA, 2 a 16-bit
  * sweep), draw_pipelined (1: that sweep is k_draw_bf16p), xh_class (100 KH + 10 NH + NL of k_sweep_xh where it serves the walked
@@ -276,6 +285,29 @@ int rg_sim_set_logreg_fp32(rg_sim* sim, const float* d_coef32_t, const float* d_
  * sum_p views_p (2^-11 wmax[p] + 2^-25) + (views + 3) 2^-24 (bmax + sum_p views_p wmax[p]) of the best one, and decides among
  * them by float64 scores in scipy's order (rg_sim_set_logreg's arrays): sklearn's predict() bit for bit.  NULL = off. */
 int rg_sim_set_logreg_fp16(rg_sim* sim, const uint16_t* d_coef16_t);
+
+/* RG_POLICY_LOGREG_POLY: the fitted binary model of the likelihood agent, float64 device arrays kept by pointer.  With w = coef_[0]:
+ * d_wf = w[:P] (the view counts' weights), d_wa = w[P:2P] (the action block, whose stored VALUE is the action's index), d_wk_t =
+ * w[2P:].reshape(P, P) TRANSPOSED, [viewed product][action] (lanes over actions read a row contiguously), intercept = intercept_[0].
+ * The decision of action a over the n distinct viewed products p_0 < ... < p_(n-1) with counts c_0 .. c_(n-1), float64, multiply
+ * then add, in exactly this order (sklearn's decision_function on the reference's features, bit for bit):
+ *     s = 0;  for j: s += c_j wf[p_j];   s += a wa[a];   for j: s += c_((a n + j) / P) wk[a][p_j];   z[a] = s + intercept
+ * (the cross term's count index is the reference's, reproduced: its transform lays out kron(counts, ones(P)) in slices of n).
+ * The action is the FIRST index of the maximum of expit(z).  d_expit_steps[k], k < n_steps, never increasing, is the smallest
+ * double whose scipy.special.expit is >= 1 - k 2^-53 (the host finds them by bisection with expit itself).  With z* = max z and
+ * a* = its first index: z* >= steps[n_steps - 1]: the action is the lowest index whose decision lies on z*'s step (an exact
+ * comparison of doubles; RG_CNT_POLY_TABLE); below: the action is a*, and the act is UNRESOLVED (RG_CNT_POLY_UNRESOLVED, listed)
+ * when some a < a* has 0 < z* - z[a] <= W, W = 2^-49 (1 + 2^m), m = ceil(z* 1.4426950408889634) + 1 — an upper bound of
+ * 8 2^-52 (1 + exp(z*)), inside which expit may round two decisions to one value; with z* < -700 (expit leaves the normal doubles) every act with a* > 0 is
+ * unresolved.  n_steps in [1, 1024]. */
+int rg_sim_set_logreg_poly(rg_sim* sim, const double* d_wf, const double* d_wa, const double* d_wk_t, double intercept,
+                           const double* d_expit_steps, uint32_t n_steps);
+
+/* The unresolved acts of the run so far (since rg_sim_reset_users): out[3 i .. 3 i + 2] = (user id, t, action taken) for the first
+ * min(listed, capacity) of them, in no particular order; t is the event index the act was computed at: its history is the user's
+ * organic rows with index <= t.  *n_out = entries written, *overflow = 1 when the run had more unresolved acts than the device list
+ * holds (4096) or than `capacity`.  `out` is host memory.  Synchronises `stream`. */
+int rg_sim_read_poly_unresolved(rg_sim* sim, uint32_t* out, uint32_t capacity, uint32_t* n_out, uint32_t* overflow, void* stream);
 
 /* Where rows go.  d_log == NULL (or capacity 0) disables logging: only counters are kept. */
 int rg_sim_set_log(rg_sim* sim, rg_event* d_log, uint64_t capacity);
@@ -408,6 +440,10 @@ int rg_sim_debug_click_decisions(rg_sim* sim, const int32_t* d_actions, const do
 int rg_sim_debug_set_history(rg_sim* sim, const uint32_t* d_nd, const uint32_t* d_products, const uint32_t* d_counts,
                              uint32_t stride, void* stream);
 int rg_sim_debug_ouc_acts(rg_sim* sim, const double* d_u1, int32_t* d_action, double* d_ps, uint8_t* d_flags, void* stream);
+/* rg_sim_debug_poly_acts: the RG_POLICY_LOGREG_POLY act of every user index on its current history (rg_sim_debug_set_history), by
+ * the device function the step loop uses: d_action[i], d_flags[i] = bit 0: decided on the step table, bit 1: unresolved, bit 2: a
+ * lower index than the first maximal decision won (a merge on a step).  Touches neither the counters nor the unresolved list. */
+int rg_sim_debug_poly_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, void* stream);
 
 /*
  * Off-policy evaluation (evaluate_IPS / evaluate_SNIPS, reference evaluate_agent.py:753-810): replay a sorted log under a

@@ -35,6 +35,13 @@ def evaluate_counts(env, agent, num_users, first_user_id=0):
             clicks, shown = cnt['clicks'], cnt['bandit'] + cnt['phantom']
             dev = sim.device
             sim.close()
+            if cnt.get('poly_unresolved'):
+                # the likelihood agent: acts the device could not resolve — the counters stand only if the host confirms every one
+                # of them, which needs the log: generate_logs runs the shard again with it, verifies, and falls back to the host
+                # route (with its warning) where an act is refuted
+                data = env.generate_logs(count, agent, first_user_id=first_user_id + first)
+                rewards = data[data['z'] == 'bandit']['c']
+                clicks, shown = int(rewards.sum()), int(rewards.shape[0])
         clicks, shown = parallel.all_reduce_counts([clicks, shown], dev)
         return clicks, shown - clicks
     # arbitrary Python agent: per-user path on rank 0's env (no sharding: agents are stateful)

@@ -1,4 +1,4 @@
-// rg_common.hpp — librecogym_hip.so: the reco-gym-v1 step loop as batched CDNA4 (gfx950) kernels (shared part of its thirteen units).
+// rg_common.hpp — librecogym_hip.so: the reco-gym-v1 step loop as batched CDNA4 (gfx950) kernels (shared part of its fifteen units).
 //
 // What runs here (reference file:line each kernel takes over; see DESIGN.md for the data layout
 // and the roofline of each kernel):
@@ -49,11 +49,11 @@
 #include "../../include/recogym_hip.h"
 #include "../../include/recogym_rng.h"
 
-// Translation units.  The library is built from thirteen units, one per kernel family — rg_host.hip (host code, the C ABI, small
+// Translation units.  The library is built from fifteen units, one per kernel family — rg_host.hip (host code, the C ABI, small
 // kernels), rg_exact.hip (float64 resolve), rg_draw_fp32.hip (fp32 / lean 16-bit sweeps), rg_draw_pipelined.hip (the pipelined sweep
 // + per-user cache kernels), rg_draw_wide.hip (wide-K sweep), rg_advance.hip (advance / tail / frozen LogReg), rg_walk.hip (the
 // user-major walk), rg_draw_exacthi.hip and rg_draw_lds.hip (the error-free and the tile-prefix sweeps), rg_ope.hip,
-// rg_ope_logreg.hip and rg_ope_eg.hip (off-policy replays), rg_count.hip (count agents' training) — compiled in parallel and
+// rg_ope_logreg.hip and rg_ope_eg.hip (off-policy replays), rg_count.hip (count agents' training), rg_evolve.hip (the exploration study), rg_logreg_poly.hip (the likelihood agent's act) — compiled in parallel and
 // linked by __graft_entry__.build(); recogym_hip.hip includes all of them (a one-unit build).  This header holds what they
 // share: types, the workspace layout, device helpers (namespace rgk, identical in every unit); a unit hands its kernels to the
 // host code through the *_kernel_for functions declared here.  rg_ope_common.hpp adds what the three replay units share.
@@ -72,6 +72,10 @@ constexpr uint32_t kMaxSteps = 1u << 16;       // P(a user survives that long) ~
 constexpr int kBlock = 256;                    // 4 waves of 64
 constexpr int kMaxGrid = 4096;
 constexpr uint32_t kDefaultHistoryCap = 256;
+constexpr uint32_t kPolyListCap = 4096;        // unresolved acts of a run the device lists (RG_POLICY_LOGREG_POLY)
+constexpr uint32_t kPolySteps = 1024;          // expit steps the table holds at most (8 KB of LDS)
+// the policies that act on the view history through the lr_* act list (k_logreg_select)
+inline bool lr_family(uint32_t policy) { return policy == RG_POLICY_LOGREG_FROZEN || policy == RG_POLICY_LOGREG_POLY; }
 // runs smaller than this keep slot == user index throughout (RECOGYM_REPACK_MIN overrides: tests)
 inline uint64_t repack_min_users() {
     const char* e = getenv("RECOGYM_REPACK_MIN");
@@ -309,6 +313,13 @@ struct DevSim {
     uint64_t eg_seed;
     double eg_eps, eg_ps_explore, eg_one_minus;
     const double* eg_cdf;     // [P - 1] (pure_new) or [P]: cumsum(full(n, 1 / n)) / last, caller-owned
+    // RG_POLICY_LOGREG_POLY (rg_sim_set_logreg_poly; rg_logreg_poly.hip): `policy` is RG_POLICY_LOGREG_FROZEN for such a handle too —
+    // the act list, the view history and the hand-over of lr_action to the advance kernels are that policy's — and lr_poly selects
+    // k_poly_acts as the act kernel.  Caller-owned float64 arrays; pl_list [kPolyListCap][3] = (user id, t, action) of unresolved acts.
+    uint32_t lr_poly, pl_nth;
+    const double* pl_wf; const double* pl_wa; const double* pl_wk_t; const double* pl_th;
+    double pl_b;
+    uint32_t* pl_list;
 };
 
 }  // namespace rgk
@@ -331,7 +342,7 @@ struct RunOpts {
 #define RG_LEDGER_FAMILIES(X) \
     X(draw_f64) X(draw_fp32) X(draw16_fused) X(draw16_sliced) X(search) X(draw_tp) X(pick) X(draw_cached) \
     X(sweep_xh) X(exact_m) X(exact_tile) X(exact_h) X(walk) X(walk2) X(walk_solo) \
-    X(advance) X(advance_run) X(tail) X(repack) X(env0) X(logreg_screen) X(logreg_acts) X(logreg_sample) \
+    X(advance) X(advance_run) X(tail) X(repack) X(env0) X(logreg_screen) X(logreg_acts) X(logreg_sample) X(logreg_poly) \
     X(sort_tiled) X(sort_plain)
 struct Ledger {
 #define RG_LEDGER_FIELD(f) uint64_t f = 0;
@@ -432,6 +443,8 @@ search_kernel_t logreg_acts_kernel();
 search_kernel_t logreg_screen_kernel();
 search_kernel_t logreg_decide_kernel();
 search_kernel_t logreg_sample_kernel();
+search_kernel_t poly_acts_kernel();                        // rg_logreg_poly.hip
+void (*poly_debug_kernel())(DevSim, int32_t*, uint8_t*);
 advance_kernel_t advance_kernel(bool eg);                  // eg: the instantiation that carries the EpsilonGreedy overlay
 advance_run_kernel_t advance_run_kernel(bool eg);
 round_rows_kernel_t round_rows_kernel();
@@ -587,7 +600,7 @@ inline uint32_t exact_kb_of(uint32_t K) {
 }
 
 inline uint32_t hist_cap_of(const rg_config& c) {
-    if (c.policy != RG_POLICY_ORGANIC_USER_COUNT && c.policy != RG_POLICY_LOGREG_FROZEN) return 0;
+    if (c.policy != RG_POLICY_ORGANIC_USER_COUNT && !lr_family(c.policy)) return 0;
     // entries per row: the header + the distinct products kept, rounded up to whole 128-byte lines of 16 entries (what
     // the register paths load at a time)
     return ((c.ouc_history_cap ? c.ouc_history_cap : kDefaultHistoryCap - 1u) + 1u + 15u) & ~15u;
@@ -651,7 +664,7 @@ inline size_t carve_all(const rg_config& c, uint64_t n, void* base, DevSim* d) {
     float* walk_scp = w.take<float>(cache ? (n + 1) * static_cast<size_t>(kMaxSC) : 1);
     uint8_t* f64_valid = w.take<uint8_t>(cache ? n : 1);
     uint32_t* exact_cnt_b = w.take<uint32_t>(kMaxSteps + 2);
-    const bool lr = c.policy == RG_POLICY_LOGREG_FROZEN;
+    const bool lr = lr_family(c.policy);
     uint32_t* lr_action = w.take<uint32_t>(lr ? n : 1);
     uint8_t* lr_dirty = w.take<uint8_t>(lr ? n : 1);
     uint32_t* lr_list = w.take<uint32_t>(lr ? n : 1);
@@ -662,8 +675,8 @@ inline size_t carve_all(const rg_config& c, uint64_t n, void* base, DevSim* d) {
     double* lr_ps2 = w.take<double>(lrs ? n : 1);
     // the screen's scratch: a row per act of a STEP, not per user — a step lists the users whose history changed and who act now
     // (a quarter of the organic users at the default transition matrix); what a step lists beyond the rows goes through k_logreg_acts
-    const size_t lr_part_cap = lr ? (n / 2 + 4096 < n ? n / 2 + 4096 : n) : 0;
-    uint32_t* lr_part = w.take<uint32_t>(lr ? lr_part_cap * static_cast<size_t>(8 * (4 + 2 * 8)) : 1);       // kLrSplit x kLrPartWords
+    const size_t lr_part_cap = lr && c.policy != RG_POLICY_LOGREG_POLY ? (n / 2 + 4096 < n ? n / 2 + 4096 : n) : 0;
+    uint32_t* lr_part = w.take<uint32_t>(lr_part_cap ? lr_part_cap * static_cast<size_t>(8 * (4 + 2 * 8)) : 1);       // kLrSplit x kLrPartWords
     // round 1's list (the users + kParkSlack for the blocks its waves leave part-used), then round 2's hand-overs (kParkSlack)
     uint32_t* park_list = w.take<uint32_t>(cache ? n + 128 + static_cast<size_t>(2) * kParkSlack : 1);
     unsigned long long* walk_ctl = w.take<unsigned long long>(kWalkCtlWords);
@@ -685,7 +698,9 @@ inline size_t carve_all(const rg_config& c, uint64_t n, void* base, DevSim* d) {
     const uint32_t tp_tiles = g.F16 == 2 ? kTpBins : g.n_chunks / 4;
     const uint32_t tp_sh = g.F16 == 2 ? kTpShards : tp_shards_of(tp_tiles);
     uint32_t* tp_order = w.take<uint32_t>(tp ? static_cast<size_t>(tp_tiles) * tp_sh * tp_shard_cap(n, tp_sh) : 1);
+    uint32_t* pl_list = w.take<uint32_t>(c.policy == RG_POLICY_LOGREG_POLY ? 3 * static_cast<size_t>(kPolyListCap) : 1);
     if (d) {
+        d->pl_list = pl_list;
         d->tp_rec = tp ? tp_rec : nullptr; d->tp_hist = tp_hist; d->tp_order = tp_order; d->tp_cap = tp_shard_cap(n, tp_sh); d->tp_shards = tp_sh; d->tp_cpt = 4;
         d->ev = ev; d->run_ctl = run_ctl; d->run_ahead = 0; d->pv0 = pv0;
         d->phantom_ps = phantom_ps; d->utime = utime; d->phantom_time = phantom_time;
@@ -729,12 +744,12 @@ inline int validate(const rg_config* c, uint64_t n) {
     if (sizeof(double) * (static_cast<size_t>(c->K) * 64 + 64 + 16 * c->K) > 64 * 1024)
         return fail(RG_EINVAL, "K %u exceeds the float64 draw kernel's LDS budget", c->K);
     if (n == 0 || n >= (1ull << 31)) return fail(RG_EINVAL, "n_users %llu out of range", (unsigned long long)n);
-    if (c->policy > RG_POLICY_LOGREG_FROZEN) return fail(RG_EINVAL, "unknown policy %u", c->policy);
+    if (c->policy > RG_POLICY_LOGREG_POLY) return fail(RG_EINVAL, "unknown policy %u", c->policy);
     if (c->time_mode > 1) return fail(RG_EINVAL, "unknown time_mode %u", c->time_mode);
     if (c->env_kind > 1) return fail(RG_EINVAL, "unknown env_kind %u", c->env_kind);
     if (c->lr_select_randomly && (c->policy != RG_POLICY_LOGREG_FROZEN || c->num_products > 1024))
         return fail(RG_EINVAL, "lr_select_randomly needs RG_POLICY_LOGREG_FROZEN and at most 1024 products (a class per product)");
-    if (c->env_kind == 1 && (c->time_mode || c->policy == RG_POLICY_LOGREG_FROZEN || c->policy == RG_POLICY_LAST_VIEW_TABLE))
+    if (c->env_kind == 1 && (c->time_mode || lr_family(c->policy) || c->policy == RG_POLICY_LAST_VIEW_TABLE))
         return fail(RG_EINVAL, "env_kind 1 (reco-gym-v0) runs the default clock and the uniform / random / organic-count / external policies");
     if (c->time_mode == 1 && !(c->time_sigma >= 0.0)) return fail(RG_EINVAL, "normal_time_sigma must be >= 0");
     for (int s = 0; s < 2; ++s)

@@ -751,7 +751,11 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
     if (d.policy == RG_POLICY_LOGREG_FROZEN) {
         // acts of the users whose view history changed since their last one (frozen LogReg at scale)
         hipLaunchKernelGGL(logreg_select_kernel(), dim3(grid_for(upper)), dim3(kBlock), 0, st, d, t);
-        if (d.lr_sample) {         // select_randomly: a softmax and a draw per act (a wave each)
+        if (d.lr_poly) {           // the likelihood agent: a wave per act, float64 throughout (rg_logreg_poly.hip)
+            const int g = grid_for(static_cast<uint64_t>(upper) / 4 + 64, kBlock / 64), cap = device_cus(sim) * 8;
+            hipLaunchKernelGGL(poly_acts_kernel(), dim3(g < cap ? g : cap), dim3(kBlock), 0, st, d, t);
+            sim->led.logreg_poly += 1;
+        } else if (d.lr_sample) {  // select_randomly: a softmax and a draw per act (a wave each)
             hipLaunchKernelGGL(logreg_sample_kernel(), dim3(grid_for(static_cast<uint64_t>(upper) + 64, kBlock / 64)), dim3(kBlock), 0, st, d, t);
             sim->led.logreg_sample += 1;
         } else if (d.lr_coef16_t) {       // screen (a wave per act and class range), then decide (a wave per act)
@@ -1161,7 +1165,9 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
     d.cdf_b0 = cfg->trans_cdf[1][0]; d.cdf_b1 = cfg->trans_cdf[1][1];
     d.sigma0 = cfg->sigma_omega_initial; d.sigma_omega = cfg->sigma_omega;
     d.change_omega_for_bandits = cfg->change_omega_for_bandits;
-    d.policy = cfg->policy;
+    // the likelihood agent runs wherever the frozen LogReg policy does, through the same act list: one policy for the kernels
+    d.policy = cfg->policy == RG_POLICY_LOGREG_POLY ? RG_POLICY_LOGREG_FROZEN : cfg->policy;
+    d.lr_poly = cfg->policy == RG_POLICY_LOGREG_POLY ? 1u : 0u;
     d.ouc_select_randomly = cfg->ouc_select_randomly;
     d.ouc_exploit_explore = cfg->ouc_exploit_explore;
     d.ouc_reverse_pop = cfg->ouc_reverse_pop;
@@ -1594,7 +1600,7 @@ int rg_eg_explore_actions(uint32_t num_products, uint32_t pure_new, const double
 int rg_sim_set_logreg(rg_sim* sim, const double* d_coef_t, const double* d_intercept,
                       const int32_t* d_classes, uint32_t n_classes) {
     if (!sim) return fail(RG_EINVAL, "sim is NULL");
-    if (sim->d.policy != RG_POLICY_LOGREG_FROZEN) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_FROZEN");
+    if (sim->cfg.policy != RG_POLICY_LOGREG_FROZEN) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_FROZEN");
     if (!d_coef_t || !d_intercept || !d_classes || n_classes == 0) return fail(RG_EINVAL, "NULL model array or no classes");
     if (sim->d.lr_sample && n_classes != sim->d.P)
         return fail(RG_EINVAL, "lr_select_randomly samples a PRODUCT from predict_proba: the model needs a class per product (%u classes, %u products)", n_classes, sim->d.P);
@@ -1608,7 +1614,7 @@ int rg_sim_set_logreg(rg_sim* sim, const double* d_coef_t, const double* d_inter
 
 int rg_sim_set_logreg_fp32(rg_sim* sim, const float* d_coef32_t, const float* d_intercept32, const float* d_wmax, float bmax) {
     if (!sim) return fail(RG_EINVAL, "sim is NULL");
-    if (sim->d.policy != RG_POLICY_LOGREG_FROZEN) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_FROZEN");
+    if (sim->cfg.policy != RG_POLICY_LOGREG_FROZEN) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_FROZEN");
     if (!sim->d.lr_coef_t) return fail(RG_ESTATE, "rg_sim_set_logreg must be called first");
     if ((d_coef32_t || d_intercept32 || d_wmax) && !(d_coef32_t && d_intercept32 && d_wmax)) return fail(RG_EINVAL, "all three arrays or none");
     if (!(bmax >= 0.0f)) return fail(RG_EINVAL, "bmax must be >= 0");
@@ -1619,10 +1625,41 @@ int rg_sim_set_logreg_fp32(rg_sim* sim, const float* d_coef32_t, const float* d_
 
 int rg_sim_set_logreg_fp16(rg_sim* sim, const uint16_t* d_coef16_t) {
     if (!sim) return fail(RG_EINVAL, "sim is NULL");
-    if (sim->d.policy != RG_POLICY_LOGREG_FROZEN) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_FROZEN");
+    if (sim->cfg.policy != RG_POLICY_LOGREG_FROZEN) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_FROZEN");
     if (d_coef16_t && !sim->d.lr_coef32_t) return fail(RG_ESTATE, "rg_sim_set_logreg_fp32 must be called first (intercept32, wmax, bmax)");
     if (d_coef16_t && sim->d.lr_n % 8u) return fail(RG_EINVAL, "the fp16 screening pass needs n_classes %% 8 == 0 (have %u)", sim->d.lr_n);
     sim->d.lr_coef16_t = d_coef16_t;
+    return RG_OK;
+}
+
+int rg_sim_set_logreg_poly(rg_sim* sim, const double* d_wf, const double* d_wa, const double* d_wk_t, double intercept,
+                           const double* d_expit_steps, uint32_t n_steps) {
+    if (!sim) return fail(RG_EINVAL, "sim is NULL");
+    if (sim->cfg.policy != RG_POLICY_LOGREG_POLY) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY");
+    if (!d_wf || !d_wa || !d_wk_t || !d_expit_steps) return fail(RG_EINVAL, "NULL model array");
+    if (n_steps == 0 || n_steps > kPolySteps) return fail(RG_EINVAL, "n_steps %u out of range [1, %u]", n_steps, kPolySteps);
+    if (!(intercept == intercept)) return fail(RG_EINVAL, "the intercept is NaN");
+    sim->d.pl_wf = d_wf; sim->d.pl_wa = d_wa; sim->d.pl_wk_t = d_wk_t; sim->d.pl_b = intercept;
+    sim->d.pl_th = d_expit_steps; sim->d.pl_nth = n_steps;
+    return RG_OK;
+}
+
+int rg_sim_read_poly_unresolved(rg_sim* sim, uint32_t* out, uint32_t capacity, uint32_t* n_out, uint32_t* overflow, void* stream) {
+    if (!sim || !n_out || !overflow || (capacity && !out)) return fail(RG_EINVAL, "NULL argument");
+    if (sim->cfg.policy != RG_POLICY_LOGREG_POLY) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY");
+    if (!sim->users_reset) return fail(RG_ESTATE, "no reset range");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned long long listed = 0;
+    HIP_TRY(hipMemcpyAsync(&listed, sim->d.counters + RG_CNT_POLY_UNRESOLVED, sizeof(listed), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    uint32_t n = listed < kPolyListCap ? static_cast<uint32_t>(listed) : kPolyListCap;
+    *overflow = (listed > kPolyListCap || n > capacity) ? 1u : 0u;
+    if (n > capacity) n = capacity;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(out, sim->d.pl_list, sizeof(uint32_t) * 3 * n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    *n_out = n;
     return RG_OK;
 }
 
@@ -1654,8 +1691,10 @@ int rg_sim_reset_users(rg_sim* sim, uint64_t first_user_id, uint64_t n, uint64_t
     if (!sim->tables_set) return fail(RG_ESTATE, "rg_sim_set_tables must be called first");
     if (sim->d.policy == RG_POLICY_LAST_VIEW_TABLE && !sim->d.pol_table)
         return fail(RG_ESTATE, "rg_sim_set_policy_table must be called first");
-    if (sim->d.policy == RG_POLICY_LOGREG_FROZEN && !sim->d.lr_coef_t)
+    if (sim->cfg.policy == RG_POLICY_LOGREG_FROZEN && !sim->d.lr_coef_t)
         return fail(RG_ESTATE, "rg_sim_set_logreg must be called first");
+    if (sim->cfg.policy == RG_POLICY_LOGREG_POLY && !sim->d.pl_wk_t)
+        return fail(RG_ESTATE, "rg_sim_set_logreg_poly must be called first");
     if (n == 0 || n > sim->d.n_cap) return fail(RG_EINVAL, "n %llu exceeds the %u users the workspace was sized for",
                                                  (unsigned long long)n, sim->d.n_cap);
     if (first_user_id + n > (1ull << 32)) return fail(RG_EINVAL, "user ids must fit 32 bits");
@@ -1943,6 +1982,17 @@ int rg_sim_debug_ouc_acts(rg_sim* sim, const double* d_u1, int32_t* d_action, do
     if (!sim->users_reset) return fail(RG_ESTATE, "no reset range");
     hipLaunchKernelGGL(k_debug_ouc_acts, dim3(grid_for(sim->d.n_users)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), sim->d,
                        d_u1, d_action, d_ps, d_flags);
+    HIP_TRY(hipGetLastError());
+    return RG_OK;
+}
+
+int rg_sim_debug_poly_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, void* stream) {
+    if (!sim || !d_action || !d_flags) return fail(RG_EINVAL, "NULL argument");
+    if (sim->cfg.policy != RG_POLICY_LOGREG_POLY) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY");
+    if (!sim->d.pl_wk_t) return fail(RG_ESTATE, "rg_sim_set_logreg_poly must be called first");
+    if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
+    hipLaunchKernelGGL(poly_debug_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+                       sim->d, d_action, d_flags);
     HIP_TRY(hipGetLastError());
     return RG_OK;
 }

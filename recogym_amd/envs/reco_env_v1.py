@@ -17,6 +17,7 @@ What is different, on purpose (DESIGN.md §"drop-in boundary"):
     overflows, SURVEY.md "facts");
   * there is no CPU fallback: without a GPU, constructing the simulator raises.
 """
+import warnings
 from copy import deepcopy
 
 import numpy as np
@@ -541,12 +542,18 @@ class RecoEnv1(_EnvBase):
         if pol is not None:
             cnt, sim = self.simulate(num_offline_users, use, num_organic_offline_users, first_user_id=first_user_id)
             cols = sim.log_columns()
+            # the likelihood agent: the few acts its device rule lists as unresolved are recomputed on the host; a refuted one
+            # (or more of them than the list holds) sends the whole call to the host route below
+            stands = pol.get('policy') != _abi.RG_POLICY_LOGREG_POLY or not cnt.get('poly_unresolved') or sim.poly_verify(cols)
             sim.close()
-            with_all = bool(getattr(self.config, 'with_ps_all', False)) and use is None
-            df = columns_to_dataframe(cols, self.config.num_products, with_all)
-            if pol.get('ps_all') is not None:              # the agent's whole distribution per bandit row
-                df['ps-a'] = pd.Series(pol['ps_all'](df), dtype=object, copy=False)
-            return df
+            if stands:
+                with_all = bool(getattr(self.config, 'with_ps_all', False)) and use is None
+                df = columns_to_dataframe(cols, self.config.num_products, with_all)
+                if pol.get('ps_all') is not None:              # the agent's whole distribution per bandit row
+                    df['ps-a'] = pd.Series(pol['ps_all'](df), dtype=object, copy=False)
+                return df
+            warnings.warn('LogregPolyAgent: the host refuted an act the device could not resolve (or the list of such acts '
+                          'overflowed); generate_logs repeats the call on the host route', RuntimeWarning)
         if self._time_mode or getattr(use, 'per_user_path', False) or getattr(self.config, 'per_user_path', False) or \
                 not batch_safe(use):
             return self._generate_logs_per_user(num_offline_users, use, num_organic_offline_users, first_user_id)

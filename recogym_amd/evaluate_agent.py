@@ -574,7 +574,10 @@ def _device_route(env, agent):
         return False
     if _trainable(agent) and not hasattr(agent, 'train_online_from_log'):
         return False
-    return device_policy_of(agent) is not None
+    pol = device_policy_of(agent)
+    # the likelihood agent's device acts need the host's confirmation of the unresolved ones, which generate_logs
+    # gives and this study's device loop does not: host route
+    return pol is not None and pol.get('policy') != _abi.RG_POLICY_LOGREG_POLY
 
 
 def _new_rewards(num_products):

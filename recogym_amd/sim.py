@@ -94,12 +94,15 @@ class Simulator:
     p_click      also keep the click probability of every bandit row (parity checks)
     epsilon_greedy  dict(epsilon, seed, pure_new): the EpsilonGreedy overlay over `policy` (agents/epsilon_greedy.py;
                  rg_sim_set_epsilon_greedy) — the explore table and both propensity factors are NumPy's, built here
+    logreg_poly  dict(wf (P,), wa (P,), wk (P, P) [action][product], intercept): the likelihood agent's fitted model
+                 (RG_POLICY_LOGREG_POLY; agents/logreg_poly.py) — the table of expit's top steps is built and uploaded here.
+                 After a run, `poly_verify(columns)` recomputes the acts the device could not resolve on the host.
     """
 
     def __init__(self, config, n_users, policy=_abi.RG_POLICY_UNIFORM_ENV, policy_seed=None,
                  ouc=None, epoch=0, log_capacity=None, device=None, tables=None, policy_table=None,
                  policy_ps=None, logreg=None, ps_float64=None, p_click=False, env0=None, policy_ps64=False,
-                 epsilon_greedy=None):
+                 epsilon_greedy=None, logreg_poly=None):
         if policy == _abi.RG_POLICY_LOGREG_FROZEN and ((logreg or {}).get('int8') or os.environ.get('RECOGYM_LOGREG') == 'int8'):
             # (refused, not ignored: a caller that labels the act's bytes from this switch would report 1 B per weight for an fp16 run)
             raise ValueError("the 8-bit LogReg screen is retired (measured slower than the fp16 screen): drop logreg['int8'] / RECOGYM_LOGREG=int8")
@@ -200,6 +203,21 @@ class Simulator:
                             and float(self.logreg[0].abs().max().item()) < 6.0e4):
                         self.logreg16 = self.logreg[0].to(torch.float16).contiguous()
                         _abi.check(self.lib.rg_sim_set_logreg_fp16(self._h, self.logreg16.data_ptr()), 'rg_sim_set_logreg_fp16')
+            if policy == _abi.RG_POLICY_LOGREG_POLY:
+                from .agents.logreg_poly import expit_steps
+                P = int(config.num_products)
+                wf, wa, wk = (np.ascontiguousarray(logreg_poly[k], dtype=np.float64) for k in ('wf', 'wa', 'wk'))
+                assert wf.shape == (P,) and wa.shape == (P,) and wk.shape == (P, P)
+                self.logreg_poly_host = (wf, wa, wk, float(logreg_poly['intercept']))
+                th = logreg_poly.get('expit_steps')
+                th = expit_steps() if th is None else np.ascontiguousarray(th, dtype=np.float64)
+                # wk transposed, [viewed product][action]: lanes over actions read a row contiguously
+                self.logreg_poly = tuple(torch.from_numpy(x).to(self.device) for x in (wf, wa, np.ascontiguousarray(wk.T), th))
+                _abi.check(self.lib.rg_sim_set_logreg_poly(self._h, *[t.data_ptr() for t in self.logreg_poly[:3]],
+                                                           C.c_double(self.logreg_poly_host[3]), self.logreg_poly[3].data_ptr(),
+                                                           int(th.size)), 'rg_sim_set_logreg_poly')
+            self.poly_unresolved = self.poly_refuted = None
+            self.poly_overflow = False
             if log_capacity is None:
                 log_capacity = default_log_capacity(config, self.n_users)
             self.log = None
@@ -317,7 +335,46 @@ class Simulator:
         res = {k: int(out[i]) for i, k in enumerate(names)}
         res['anchored'] = int(out[_abi.RG_CNT_ANCHORED])
         res['bad_actions'] = int(out[_abi.RG_CNT_BAD_ACTION])        # external actions outside [0, P) that reached the device
+        res['poly_table'] = int(out[_abi.RG_CNT_POLY_TABLE])         # likelihood agent: acts decided on the expit step table
+        res['poly_unresolved'] = int(out[_abi.RG_CNT_POLY_UNRESOLVED])   # ... acts listed for the host (poly_verify)
         return res
+
+    def poly_unresolved_acts(self):
+        """The acts of the run the likelihood agent's device rule could not resolve -> ((n, 3) uint32 array of (user id, t, action
+        taken), overflow): t is the event index the act was computed at, its history the user's organic rows with index <= t."""
+        out = np.zeros((4096, 3), dtype=np.uint32)
+        n, over = C.c_uint32(0), C.c_uint32(0)
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.rg_sim_read_poly_unresolved(self._h, out.ctypes.data, out.shape[0], C.byref(n), C.byref(over),
+                                                            self._stream()), 'rg_sim_read_poly_unresolved')
+        return out[:n.value].copy(), bool(over.value)
+
+    def poly_verify(self, columns=None):
+        """Recompute every unresolved act on the host — the views are the log's organic rows of that user up to the act's event,
+        the arithmetic is the host act's (scipy's expit) — and keep the outcome in `poly_unresolved` (the listed acts),
+        `poly_refuted` (those whose action the host does not confirm) and `poly_overflow`.  -> True when the device log stands:
+        nothing refuted, no overflow of the list.  `columns`: log_columns() of this run, where the caller has them already."""
+        from .agents.logreg_poly import poly_decisions
+        from scipy.special import expit
+        acts, self.poly_overflow = self.poly_unresolved_acts()
+        self.poly_unresolved = acts
+        self.poly_refuted = acts[:0]
+        if len(acts):
+            cols = self.log_columns() if columns is None else columns
+            u = np.asarray(cols['u']).view(np.uint32)
+            organic = ~np.asarray(cols['is_bandit'], dtype=bool)
+            v = np.asarray(cols['v'])
+            # the row's EVENT INDEX = its position among its user's rows (the `t` column is the clock of a NormalTimeGenerator)
+            first = np.flatnonzero(np.r_[True, u[1:] != u[:-1]])
+            t = np.arange(len(u)) - np.repeat(first, np.diff(np.r_[first, len(u)]))
+            bad = []
+            for user, t_act, a in acts:
+                rows = organic & (u == user) & (t <= t_act)
+                prods, cnts = np.unique(v[rows], return_counts=True)
+                if int(np.argmax(expit(poly_decisions(prods, cnts, *self.logreg_poly_host)))) != int(a):
+                    bad.append((user, t_act, a))
+            self.poly_refuted = np.asarray(bad, dtype=np.uint32).reshape(-1, 3)
+        return not self.poly_overflow and len(self.poly_refuted) == 0
 
     def set_profiling(self, on=True):
         _abi.check(self.lib.rg_sim_set_profiling(self._h, int(on)), 'rg_sim_set_profiling')
