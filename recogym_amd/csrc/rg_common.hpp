@@ -350,6 +350,10 @@ struct Ledger {
 #undef RG_LEDGER_FIELD
 };
 
+// what the stream does between two marks of the profiling timeline (rg_sim_get_profile reports a sum per class)
+enum ProfClass { kProfSweep, kProfSearch /* + finalize */, kProfResolve /* float64 */, kProfLogreg, kProfAdvance,
+                 kProfWalk1, kProfWalk2 /* every later round */, kProfTail, kProfNone /* closes an interval, opens none */ };
+
 struct rg_sim {
     rg_config cfg;
     Ledger led;
@@ -368,19 +372,17 @@ struct rg_sim {
     bool walk2;               // the walk is k_walk2 (prefix sums + memo; RECOGYM_WALK=1 keeps k_walk)
     bool walk_solo;           // its last round is k_walk_solo (RECOGYM_WALK_SOLO=0: k_walk2's)
     int n_cus;                // compute units of the device (grid of the persistent walk kernel)
-    double prof_walk_ms[2];   // round 1 / round 2 of k_walk
     // the walked run with its list lengths on the device (run_walk_pipe)
     int pipe_groups;          // 1 = run_walk_pipe: the serial chain without host read-backs; 0 = run_walk (host-side counts)
     int pipe_occ1, pipe_occ2; // blocks per CU of the round-1 / round-2 grids (<= what the kernel is compiled for)
     int pipe_xblocks;         // blocks of the float64 batch's grid
     bool fin_in_sweep;        // the sweep of run_walk_pipe leaves the finalize / prefix kernels' output itself (RECOGYM_FIN_IN_SWEEP=0: A/B)
     uint32_t pipe_min_users;  // users of such a run at least: an unsliced sweep's 1024 user tiles (RECOGYM_PIPE_MIN: tests)
-    double prof_pipe_ms;      // profiling: wall time of those runs
+    double prof_pipe_ms;      // profiling: wall time of those runs (first to last mark of each)
     // rg_sim_debug_walk_fate: where the last walked run left the list of its last round (null: there was none)
     uint32_t fate_base; const unsigned long long* fate_count;
     uint32_t repack_every;    // steps between repacks (RECOGYM_REPACK, 0 = never)
     uint32_t tail_below;      // rg_sim_run hands the run to k_tail once at most this many users live (RECOGYM_TAIL, 0 = never)
-    double prof_tail_ms;
     uint32_t* h_pinned;       // 4 x u32 staging for the live-count readback
     char* h_step;             // 128 pinned bytes of rg_sim_step_user: the action going down, the packed result coming back
     size_t mfma_smem, bf16_smem;
@@ -397,11 +399,14 @@ struct rg_sim {
     uint32_t sweep_lds;      // option: 1 = use it (default), 0 = k_draw_bf16p everywhere (A/B tests)
     bool handover_auto;      // walk_handover follows the reset range (16 below 2 M users, else 32) until it is set explicitly
     uint32_t draw_threads, draw_users;   // block size of that kernel and the users one block sweeps for (256 / 128; wide K: 512 / 256)
+    // profiling: ONE timeline of pooled HIP events for every run form (prof_mark).  Mark i opens an interval of class prof_cls[i]
+    // that mark i + 1 closes; prof_collect adds it to prof_ms[class] (kProfNone: to nothing)
     bool profiling;
-    std::vector<hipEvent_t> prof_events;   // 6 per profiled step: before draw, after mfma, after search, after exact, after the frozen LogReg acts, after advance
-    size_t prof_used;
-    double prof_ms[5];                     // sweep, search, float64 resolve, LogReg acts, advance
-    uint64_t prof_launches;
+    std::vector<hipEvent_t> prof_events;   // the pool: created on first use, reused by every later timeline, destroyed with the handle
+    std::vector<ProfClass> prof_cls;       // class of the interval each recorded event opens
+    size_t prof_used;                      // events of the pool recorded since the last prof_collect
+    double prof_ms[kProfNone];             // ms per class, in ProfClass order
+    uint64_t prof_launches;                // "steps": one per launch_step, one per walked run (none for k_tail)
 };
 
 namespace rgk {

@@ -585,22 +585,132 @@ __global__ void __launch_bounds__(kBlock) k_export_time(DevSim d, uint32_t t, do
         out[i] = d.time_mode ? d.utime[i] : static_cast<double>(d.n_events[i] ? d.n_events[i] : t);
 }
 
-inline int grid_for(uint64_t n, int per_block = kBlock) {
+constexpr int grid_for(uint64_t n, int per_block = kBlock) {
     uint64_t g = (n + per_block - 1) / per_block;
     if (g < 1) g = 1;
     if (g > kMaxGrid) g = kMaxGrid;
     return static_cast<int>(g);
 }
 
-int prof_mark(rg_sim* sim, hipStream_t st) {
+// ------------------------------------------------------------------------------------------
+// launch shapes of the run path: each rule once, for every launch that follows it
+// ------------------------------------------------------------------------------------------
+// grid of a walk round (k_walk / k_walk2): a block per 256 listed users, at most blocks_per_cu per CU and kMaxWalkWaves waves
+// (park_list's slack is sized for that many)
+constexpr int walk_blocks(uint32_t n_work, int blocks_per_cu, int n_cus) {
+    int blocks = static_cast<int>((static_cast<uint64_t>(n_work) + kBlock - 1) / kBlock);
+    if (blocks > n_cus * blocks_per_cu) blocks = n_cus * blocks_per_cu;
+    if (blocks > static_cast<int>(kMaxWalkWaves / 4)) blocks = kMaxWalkWaves / 4;
+    if (blocks < 1) blocks = 1;
+    return blocks;
+}
+// rows are reserved per wave in chunks: ~1/32 of what a wave will emit, within [256, 4096] (unused entries: < 64 per chunk and
+// the rest of every wave's last chunk — a few percent of the raw log)
+constexpr uint32_t walk_chunk_rows(uint64_t n_work, int blocks) {
+    uint64_t chunk = n_work * 100 / (static_cast<uint64_t>(blocks) * 4 * 32);
+    chunk = chunk / 64 * 64;
+    if (chunk < 256) chunk = 256;
+    if (chunk > 4096) chunk = 4096;
+    return static_cast<uint32_t>(chunk);
+}
+// k_walk_solo (a wave per user, a lane per consecutive event): >= 4 listed users per wave, at most 8 blocks per CU; rows reserved
+// per wave in chunks of ~1/8 of what it will emit, within [64, 1024] (a commit is <= 64 rows; what a wave leaves of its last
+// chunk are holes in the raw log: a few percent of this round's rows)
+struct SoloShape { uint32_t blocks, chunk_rows; };
+constexpr SoloShape solo_shape(uint32_t n_list, int n_cus) {
+    uint32_t blocks = (n_list + 15u) / 16u;
+    const uint32_t cap = static_cast<uint32_t>(n_cus) * 8u;
+    if (blocks > cap) blocks = cap;
+    uint64_t chunk = static_cast<uint64_t>(n_list) * 150 / (static_cast<uint64_t>(blocks) * 4 * 8);
+    chunk = chunk / 64 * 64;
+    if (chunk < 64) chunk = 64;
+    if (chunk > 1024) chunk = 1024;
+    return {blocks, static_cast<uint32_t>(chunk)};
+}
+// product slices S of the 16-bit sweep over `users`: few user tiles -> slice the products, so that the step's latency is a
+// slice, not a sweep (forced >= 0, the option `slices`: tests force either form); at most the n_sc super-chunks, at least 1
+struct SweepSlices { uint32_t tiles, S; };
+constexpr SweepSlices sweep_slices(uint32_t users, uint32_t draw_users, int forced, uint32_t n_sc) {
+    const uint32_t tiles_up = (users + draw_users - 1) / draw_users;
+    uint32_t S = tiles_up >= 131072u / draw_users ? 1u : (262144u / draw_users) / (tiles_up ? tiles_up : 1u);
+    if (forced >= 0) S = static_cast<uint32_t>(forced);
+    if (S > n_sc) S = n_sc;
+    if (S < 1) S = 1;
+    return {tiles_up, S};
+}
+// a grid of four-wave blocks for `waves` waves of work, capped at blocks_per_cu per CU (kernels that walk a list grid-stride)
+constexpr int capped_wave_grid(uint64_t waves, int blocks_per_cu, int n_cus) {
+    const int g = grid_for(waves, kBlock / 64);
+    return g < n_cus * blocks_per_cu ? g : n_cus * blocks_per_cu;
+}
+// the rules pinned at the sizes where they change form: one block, a part-filled block, below and at the CU cap, the wave cap
+// (the 10 M-user bench workloads at every occupancy, a 304-CU device), every chunk clamp, both sweep block sizes and a forced S
+constexpr bool operator==(SoloShape a, SoloShape b) { return a.blocks == b.blocks && a.chunk_rows == b.chunk_rows; }
+constexpr bool operator==(SweepSlices a, SweepSlices b) { return a.tiles == b.tiles && a.S == b.S; }
+static_assert(walk_blocks(1, 3, 256) == 1 && walk_chunk_rows(1, 1) == 256);
+static_assert(walk_blocks(300, 3, 256) == 2 && walk_chunk_rows(300, 2) == 256);
+static_assert(walk_blocks(100000, 3, 256) == 391 && walk_chunk_rows(100000, 391) == 256);
+static_assert(walk_blocks(131072, 3, 256) == 512 && walk_chunk_rows(131072, 512) == 256);
+static_assert(walk_blocks(10000000, 3, 256) == 768 && walk_chunk_rows(10000000, 768) == 4096);
+static_assert(walk_blocks(10000000, 2, 256) == 512 && walk_chunk_rows(10000000, 512) == 4096);
+static_assert(walk_blocks(10000000, 1, 256) == 256 && walk_chunk_rows(10000000, 256) == 4096);
+static_assert(walk_blocks(10000000, 3, 304) == 912);
+static_assert(walk_blocks(3337429, 3, 256) == 768 && walk_chunk_rows(3337429, 768) == 3392);
+static_assert(solo_shape(1, 256) == SoloShape{1, 64} && solo_shape(17, 256) == SoloShape{2, 64});
+static_assert(solo_shape(5000, 256) == SoloShape{313, 64} && solo_shape(40086, 256) == SoloShape{2048, 64});
+static_assert(solo_shape(1000000, 256) == SoloShape{2048, 1024});
+static_assert(sweep_slices(1, 128, -1, 32) == SweepSlices{1, 32});
+static_assert(sweep_slices(2000, 128, -1, 32) == SweepSlices{16, 32} && sweep_slices(2000, 128, -1, 4) == SweepSlices{16, 4});
+static_assert(sweep_slices(2000, 128, 0, 32) == SweepSlices{16, 1} && sweep_slices(2000, 128, 7, 32) == SweepSlices{16, 7});
+static_assert(sweep_slices(131071, 128, -1, 32) == SweepSlices{1024, 1} && sweep_slices(10000000, 128, -1, 32) == SweepSlices{78125, 1});
+static_assert(sweep_slices(2000, 256, -1, 32) == SweepSlices{8, 32} && sweep_slices(100000, 256, -1, 32) == SweepSlices{391, 2});
+
+// the pipelined fp16 sweep (k_draw_bf16p on the two-way fp16 split, K <= 64) serves the handle: what the forms behind it ask
+// (the fused-prefix sweep of a walked run, k_sweep_xh, k_draw_tp, run_walk_pipe)
+bool f16_pipelined(const rg_sim* sim) { return sim->bf16_kernel == bf16p_kernel_for(sim->d) && sim->d.f16 && !sim->d.wide; }
+
+// more than 64 KiB of dynamic LDS needs an explicit opt-in per kernel instantiation (set_max_lds: whatever the size)
+template <class Kernel> void set_max_lds(Kernel kernel, size_t bytes) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+}
+template <class Kernel> void opt_in_lds(Kernel kernel, size_t bytes) {
+    if (bytes > 64 * 1024) set_max_lds(kernel, bytes);
+}
+
+// ------------------------------------------------------------------------------------------
+// profiling: one timeline.  A mark records a pooled event; the stream's time from it to the next mark belongs to `cls`
+// (kProfNone: to nobody — it closes the timeline of a step or a run, and what is launched before the next mark is not timed)
+// ------------------------------------------------------------------------------------------
+int prof_mark(rg_sim* sim, hipStream_t st, ProfClass cls) {
     if (!sim->profiling) return RG_OK;
     if (sim->prof_used == sim->prof_events.size()) {
         hipEvent_t e;
         HIP_TRY(hipEventCreate(&e));
         sim->prof_events.push_back(e);
+        sim->prof_cls.push_back(kProfNone);
     }
+    sim->prof_cls[sim->prof_used] = cls;
     HIP_TRY(hipEventRecord(sim->prof_events[sim->prof_used++], st));
     return RG_OK;
+}
+
+// fold the recorded intervals into the totals per class (synchronises on the last event)
+int prof_collect(rg_sim* sim) {
+    if (!sim->prof_used) return RG_OK;
+    HIP_TRY(hipEventSynchronize(sim->prof_events[sim->prof_used - 1]));
+    for (size_t i = 0; i + 1 < sim->prof_used; ++i) {
+        if (sim->prof_cls[i] == kProfNone) continue;
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, sim->prof_events[i], sim->prof_events[i + 1]));
+        sim->prof_ms[sim->prof_cls[i]] += ms;
+    }
+    sim->prof_used = 0;
+    return RG_OK;
+}
+
+void prof_reset(rg_sim* sim) {
+    sim->prof_used = 0; sim->prof_launches = 0; sim->prof_pipe_ms = 0.0;
+    for (double& ms : sim->prof_ms) ms = 0.0;
 }
 
 // float64 draw of this step: from_list = 1 resolves the users the MFMA kernel could not certify
@@ -682,42 +792,36 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         sim->repacked = true;
         if (sim->opt.debug) fprintf(stderr, "[recogym] repack at t=%u (upper %u)\n", t, upper);
     }
-    if (int rc = prof_mark(sim, st)) return rc;
     // 1. organic product draws of this step (read omega before the transition drifts it)
     if (d.env_kind) {          // reco-gym-v0: a table look-up per organic user
+        if (int rc = prof_mark(sim, st, kProfSweep)) return rc;
         hipLaunchKernelGGL(k_draw_env0, dim3(grid_for(upper)), dim3(kBlock), 0, st, d, t);
         sim->led.env0 += 1;
-        if (int rc = prof_mark(sim, st)) return rc;
-        if (int rc = prof_mark(sim, st)) return rc;
     } else if (d.use_mfma == 2 && d.use_cache && t > 0) {
         // sigma_omega == 0, after step 0: every live user's exp-sums are in the per-user cache — search only
-        if (int rc = prof_mark(sim, st)) return rc;
+        if (int rc = prof_mark(sim, st, kProfSearch)) return rc;
         hipLaunchKernelGGL(cached_kernel_for(d), dim3(grid_for(upper, kBlock)), dim3(kBlock),
                            sizeof(float) * (kBlock / 64) * 64 * 2 * d.KH, st, d, t);
         sim->led.draw_cached += 1;
-        if (int rc = prof_mark(sim, st)) return rc;
+        if (int rc = prof_mark(sim, st, kProfResolve)) return rc;
         launch_exact(sim, t, 1, upper / 100 + 16, st);
     } else if (d.use_mfma == 2) {
-        // few user tiles: slice the products so that the step's latency is a slice, not a sweep
-        const uint32_t tiles_up = (upper + sim->draw_users - 1) / sim->draw_users;
-        uint32_t S = tiles_up >= 131072u / sim->draw_users ? 1u : (262144u / sim->draw_users) / (tiles_up ? tiles_up : 1u);
-        if (sim->opt.slices >= 0) S = static_cast<uint32_t>(sim->opt.slices);   // tests: force either form
-        if (S > d.n_sc) S = d.n_sc;
-        if (S < 1) S = 1;
+        const auto [tiles_up, S] = sweep_slices(upper, sim->draw_users, sim->opt.slices, d.n_sc);
         const int grid = sweep_grid(sim, static_cast<uint64_t>(tiles_up) * S);
         // (the search stays at the end of every user tile of the sweep: as its own kernel over the whole step — scratch slot
         // per user tile — the sweep got 15 % shorter and the step 6 % longer: profiles/r3/ab_call26_*, ab_call27_*)
         const bool tp = S == 1 && sim->tp_kernel && sim->sweep_lds && !d.use_cache;
+        if (int rc = prof_mark(sim, st, kProfSweep)) return rc;
         if (tp) { hipLaunchKernelGGL(sim->tp_kernel, dim3(grid), dim3(kBlock), sim->tp_smem, st, d, t, sim->tp_nts); sim->led.draw_tp += 1; }
         else {
         hipLaunchKernelGGL(sim->bf16_kernel, dim3(grid), dim3(sim->draw_threads), sim->bf16_smem, st, d, t, S);
         (S > 1 ? sim->led.draw16_sliced : sim->led.draw16_fused) += 1;
         }
-        if (int rc = prof_mark(sim, st)) return rc;
+        if (int rc = prof_mark(sim, st, kProfSearch)) return rc;
         if (tp) {
             // k_pick: a wave per 32 draws of one tile (the sweep listed the draws by tile), grid-stride over the groups
             const size_t psmem = (2 * kTpBins * kTpShards + 8) * sizeof(uint32_t) + 4 * 32 * 2 * static_cast<size_t>(d.KH) * sizeof(float);
-            if (psmem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sim->pick_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(psmem));
+            opt_in_lds(sim->pick_kernel, psmem);
             uint32_t pgrid = upper / 128u + kTpLists / 4u + 1u;      // groups / 4 waves (a part-filled group per (tile, shard))
             const uint32_t pcap = static_cast<uint32_t>(device_cus(sim)) * 4u;
             if (pgrid > pcap) pgrid = pcap;
@@ -731,29 +835,27 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         }
         if (d.use_cache)       // step 0 of a sigma_omega == 0 run: the rows every later draw starts from
             hipLaunchKernelGGL(finalize_kernel_for(d), dim3(grid_for(d.n_users)), dim3(kBlock), 0, st, d);
-        if (int rc = prof_mark(sim, st)) return rc;
+        if (int rc = prof_mark(sim, st, kProfResolve)) return rc;
         launch_exact(sim, t, 1, upper / 100 + 16, st);
     } else if (d.use_mfma) {
         const int grid = grid_for(upper, 128);
         const size_t smem = sim->mfma_smem;
+        if (int rc = prof_mark(sim, st, kProfSweep)) return rc;
         hipLaunchKernelGGL(mfma_kernel_for(d.KH), dim3(grid), dim3(kBlock), smem, st, d, t);
         sim->led.draw_fp32 += 1;
-        if (int rc = prof_mark(sim, st)) return rc;
-        if (int rc = prof_mark(sim, st)) return rc;
+        if (int rc = prof_mark(sim, st, kProfResolve)) return rc;
         // draws the fp32 path could not certify -> float64 (a few percent of the organic users)
         launch_exact(sim, t, 1, upper / 100 + 16, st);
     } else {
-        if (int rc = prof_mark(sim, st)) return rc;
-        if (int rc = prof_mark(sim, st)) return rc;
+        if (int rc = prof_mark(sim, st, kProfResolve)) return rc;
         launch_exact(sim, t, 0, upper, st);
     }
-    if (int rc = prof_mark(sim, st)) return rc;
     if (d.policy == RG_POLICY_LOGREG_FROZEN) {
+        if (int rc = prof_mark(sim, st, kProfLogreg)) return rc;
         // acts of the users whose view history changed since their last one (frozen LogReg at scale)
         hipLaunchKernelGGL(logreg_select_kernel(), dim3(grid_for(upper)), dim3(kBlock), 0, st, d, t);
         if (d.lr_poly) {           // the likelihood agent: a wave per act, float64 throughout (rg_logreg_poly.hip)
-            const int g = grid_for(static_cast<uint64_t>(upper) / 4 + 64, kBlock / 64), cap = device_cus(sim) * 8;
-            hipLaunchKernelGGL(poly_acts_kernel(), dim3(g < cap ? g : cap), dim3(kBlock), 0, st, d, t);
+            hipLaunchKernelGGL(poly_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), 0, st, d, t);
             sim->led.logreg_poly += 1;
         } else if (d.lr_sample) {  // select_randomly: a softmax and a draw per act (a wave each)
             hipLaunchKernelGGL(logreg_sample_kernel(), dim3(grid_for(static_cast<uint64_t>(upper) + 64, kBlock / 64)), dim3(kBlock), 0, st, d, t);
@@ -764,10 +866,7 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
             // mostly blocks that start and leave — and k_logreg_decide's three counter atomics per WAVE, one act each, were all of
             // its time: 41 of the 169 ms of C5's acts, profiles/r6/c5_fp16_kernel_stats_call31.csv)
             const int cus = device_cus(sim);
-            auto capped = [&](uint64_t waves, int blocks_per_cu) {
-                const int g = grid_for(waves, kBlock / 64);
-                return g < cus * blocks_per_cu ? g : cus * blocks_per_cu;
-            };
+            auto capped = [&](uint64_t waves, int blocks_per_cu) { return capped_wave_grid(waves, blocks_per_cu, cus); };
             hipLaunchKernelGGL(logreg_screen_kernel(), dim3(capped((static_cast<uint64_t>(upper) / 4 + 64) * kLrSplit, 16)),
                                dim3(kBlock), 0, st, d, t);
             sim->led.logreg_screen += 1;
@@ -777,13 +876,12 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
                 sim->led.logreg_acts += 1;
             }
         } else {
-            const int g = grid_for(static_cast<uint64_t>(upper) / 4 + 64, kBlock / 64), cap = device_cus(sim) * 8;
-            hipLaunchKernelGGL(logreg_acts_kernel(), dim3(g < cap ? g : cap), dim3(kBlock), 0, st, d, t);
+            hipLaunchKernelGGL(logreg_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), 0, st, d, t);
             sim->led.logreg_acts += 1;
         }
     }
-    if (int rc = prof_mark(sim, st)) return rc;
     // 2. click draws, transitions, drift, next lists, bandit + phantom rows
+    if (int rc = prof_mark(sim, st, kProfAdvance)) return rc;
     if (d.run_ahead) {     // a round: every listed user through its bandit run (k_advance_run), then the round's raw-log books
         hipLaunchKernelGGL(advance_run_kernel(d.eg_on != 0u), dim3(grid_for(upper, kAdvBlock)), dim3(kAdvBlock), 0, st, d, t, d.run_ahead);
         sim->led.advance_run += 1;
@@ -795,91 +893,86 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         hipLaunchKernelGGL(drift_kernel(), dim3(grid_for(static_cast<uint64_t>(upper) * ((d.K + 1) / 2))), dim3(kBlock), 0, st, d, t);
     if (d.run_ahead) hipLaunchKernelGGL(round_rows_kernel(), dim3(1), dim3(1), 0, st, d, t, 0u);
     HIP_TRY(hipGetLastError());
-    if (int rc = prof_mark(sim, st)) return rc;
+    if (int rc = prof_mark(sim, st, kProfNone)) return rc;
+    if (sim->profiling) sim->prof_launches += 1;
     sim->t = t + 1;
     return RG_OK;
 }
 
-// fold the recorded events into per-kernel totals (synchronises on the last event)
-int prof_collect(rg_sim* sim) {
-    if (!sim->prof_used) return RG_OK;
-    HIP_TRY(hipEventSynchronize(sim->prof_events[sim->prof_used - 1]));
-    for (size_t i = 0; i + 5 < sim->prof_used; i += 6) {
-        for (int k = 0; k < 5; ++k) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, sim->prof_events[i + k], sim->prof_events[i + k + 1]));
-            sim->prof_ms[k] += ms;
-        }
-        sim->prof_launches += 1;
+// A run that ended on the device (a walked run, k_tail): the step limit read back — the one host read-back of such a run,
+// it synchronises the stream — and the host's books closed at step t_end.  wall_from: the mark from which the run's wall time
+// (to the last mark; run_walk_pipe's) is taken, now that every mark has passed
+constexpr size_t kNoWall = ~static_cast<size_t>(0);
+int close_run(rg_sim* sim, hipStream_t st, uint32_t t_end, size_t wall_from = kNoWall) {
+    unsigned long long* h64 = reinterpret_cast<unsigned long long*>(sim->h_pinned);
+    HIP_TRY(hipMemcpyAsync(h64, sim->d.counters + kCntTailLimit, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (sim->profiling && wall_from != kNoWall) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, sim->prof_events[wall_from], sim->prof_events[sim->prof_used - 1]));
+        sim->prof_pipe_ms += ms;
     }
-    sim->prof_used = 0;
+    sim->t = t_end;
+    sim->live_upper = 0;
+    if (*h64) return fail(RG_ELIMIT, "more than %u steps", kMaxSteps);
     return RG_OK;
+}
+
+// prologue / epilogue of both walked runs
+int walk_begin(rg_sim* sim, hipStream_t st) {
+    (void)device_cus(sim);
+    if (sim->d.debug_row_base)      // test hook: the walk reserves its raw rows from this counter
+        HIP_TRY(hipMemcpyAsync(sim->d.counters + kCntTailRows, &sim->d.debug_row_base, sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    return RG_OK;
+}
+int walk_end(rg_sim* sim, hipStream_t st, size_t wall_from = kNoWall) {
+    if (int rc = prof_mark(sim, st, kProfNone)) return rc;       // the last round ends here ...
+    hipLaunchKernelGGL(k_walk_finish, dim3(1), dim3(1), 0, st, sim->d);
+    HIP_TRY(hipGetLastError());
+    if (int rc = prof_mark(sim, st, kProfNone)) return rc;       // ... and the run here
+    if (sim->profiling) sim->prof_launches += 1;
+    return close_run(sim, st, 1u, wall_from);
 }
 
 // rg_sim_run "to the end" of a sigma_omega == 0 run: sweep (fills the per-user cache) -> k_walk round 1 ->
 // float64 sums of the parked users in one batch -> k_walk round 2.  Five launches and one host read-back.
 int run_walk(rg_sim* sim, hipStream_t st) {
     const DevSim& d = sim->d;
-    (void)device_cus(sim);
-    if (d.debug_row_base)      // test hook: the walk reserves its raw rows from this counter
-        HIP_TRY(hipMemcpyAsync(d.counters + kCntTailRows, &sim->d.debug_row_base, sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    auto mark = [&](int i) -> int {
-        if (!sim->profiling) return RG_OK;
-        HIP_TRY(hipEventCreate(&ev[i]));
-        HIP_TRY(hipEventRecord(ev[i], st));
-        return RG_OK;
-    };
-    if (int rc = mark(0)) return rc;
+    if (int rc = walk_begin(sim, st)) return rc;
     sim->fate_count = nullptr;
     bool fused_prefix = false;
     // 1. every user's first product sweep: only the per-user sums are kept (no search, no rows)
+    if (int rc = prof_mark(sim, st, kProfSweep)) return rc;
     {
         DevSim ds = d;
-        const uint32_t tiles_up = (d.n_users + sim->draw_users - 1) / sim->draw_users;
-        uint32_t S = tiles_up >= 131072u / sim->draw_users ? 1u : (262144u / sim->draw_users) / (tiles_up ? tiles_up : 1u);
-        if (sim->opt.slices >= 0) S = static_cast<uint32_t>(sim->opt.slices);
-        if (S > d.n_sc) S = d.n_sc;
-        if (S < 1) S = 1;
+        const auto [tiles_up, S] = sweep_slices(d.n_users, sim->draw_users, sim->opt.slices, d.n_sc);
         // k_walk2 behind the fused (unsliced) form of the pipelined fp16 sweep of K <= 21: the sweep stores the sums in the
         // walk's prefix form itself (no conversion pass over the 1.3 KB of chunk sums per user)
-        fused_prefix = sim->walk2 && S == 1 && sim->bf16_kernel == bf16p_kernel_for(d) && d.f16 && !d.wide && !sim->opt.sweep_prefix_off;
+        fused_prefix = sim->walk2 && S == 1 && f16_pipelined(sim) && !sim->opt.sweep_prefix_off;
         ds.sweep_only = fused_prefix ? 2u : 1u;
         const int grid = sweep_grid(sim, static_cast<uint64_t>(tiles_up) * S);
         hipLaunchKernelGGL(sim->bf16_kernel, dim3(grid), dim3(sim->draw_threads), sim->bf16_smem, st, ds, 0u, S);
         (S > 1 ? sim->led.draw16_sliced : sim->led.draw16_fused) += 1;
     }
-    if (int rc = mark(1)) return rc;
+    if (int rc = prof_mark(sim, st, kProfSearch)) return rc;
     hipLaunchKernelGGL(finalize_kernel_for(d), dim3(grid_for(d.n_users)), dim3(kBlock), 0, st, d);
     if (sim->walk2)      // the sums in prefix form, the memo rows emptied
         hipLaunchKernelGGL(cache_prefix_kernel(), dim3(grid_for((static_cast<uint64_t>(d.n_users) + 7) / 8, kBlock / 64)), dim3(kBlock), 0, st, d,
                            fused_prefix ? 1 : 0);
-    if (int rc = mark(2)) return rc;
     // 2. round 1: every user from t = 0 to its end or to its first uncertified draw
+    if (int rc = prof_mark(sim, st, kProfWalk1)) return rc;
     const size_t smem = sim->walk2 ? (kBlock / 64) * walk2_wave_lds(d.policy == RG_POLICY_ORGANIC_USER_COUNT)
                                    : (kBlock / 64) * walk_wave_lds(d.KH);
     const walk_kernel_t wk = sim->walk2 ? walk2_kernel_for(d, sim->walk_occ) : walk_kernel_for(d, d.KH <= 16 ? sim->walk_occ : 1);
     auto launch_walk = [&](uint32_t n_work, int round, uint32_t in_base, uint32_t out_base) {
-        const int occ = d.KH <= 16 ? sim->walk_occ : 1;
-        const int blocks_cap = sim->n_cus * occ;
-        int blocks = static_cast<int>((static_cast<uint64_t>(n_work) + kBlock - 1) / kBlock);
-        if (blocks > blocks_cap) blocks = blocks_cap;
-        if (blocks > static_cast<int>(kMaxWalkWaves / 4)) blocks = kMaxWalkWaves / 4;     // (park_list's slack is sized for that many waves)
-        if (blocks < 1) blocks = 1;
-        // rows are reserved per wave in chunks: ~1/32 of what a wave will emit, within [256, 4096] (unused entries:
-        // < 64 per chunk and the rest of every wave's last chunk — a few percent of the raw log)
-        uint64_t chunk = static_cast<uint64_t>(n_work) * 100 / (static_cast<uint64_t>(blocks) * 4 * 32);
-        chunk = chunk / 64 * 64;
-        if (chunk < 256) chunk = 256;
-        if (chunk > 4096) chunk = 4096;
-        if (smem > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wk), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
-        hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, d, n_work, round, static_cast<uint32_t>(chunk), in_base, out_base);
+        const int blocks = walk_blocks(n_work, d.KH <= 16 ? sim->walk_occ : 1, sim->n_cus);
+        opt_in_lds(wk, smem);
+        hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, d, n_work, round, walk_chunk_rows(n_work, blocks), in_base, out_base);
         (sim->walk2 ? sim->led.walk2 : sim->led.walk) += 1;
     };
     launch_walk(d.n_users, 1, 0u, 0u);
-    if (int rc = mark(3)) return rc;
-    // 3. the users parked at an uncertified draw: float64 sums in one batch, then their round
+    // 3. the users parked at an uncertified draw: float64 sums in one batch (the host's read-back counts as its time), then their round
+    if (int rc = prof_mark(sim, st, kProfResolve)) return rc;
     unsigned long long* h64 = reinterpret_cast<unsigned long long*>(sim->h_pinned);
     HIP_TRY(hipMemcpyAsync(h64, d.counters + kCntParkCnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -889,79 +982,47 @@ int run_walk(rg_sim* sim, hipStream_t st) {
         HIP_TRY(hipMemcpy(ev2, d.counters + kCntTailOrganic, sizeof(ev2), hipMemcpyDeviceToHost));
         fprintf(stderr, "[recogym] walk round 1: %llu organic + %llu bandit events, %u users parked of %u\n", ev2[0], ev2[1], n_park, d.n_users);
     }
-    // round 2 over the parked (and handed-over) users; what IT hands over is appended behind them for round 3
-    auto later_rounds = [&](uint32_t n_list) -> int {
-        const uint32_t base3 = (n_list + 63u) & ~63u;
-        if (sim->walk2)      // the listed users' float64 sums as prefixes (anchored certificate, prefix pick)
-            hipLaunchKernelGGL(exact_prefix_kernel(), dim3(grid_for(n_list, kBlock / 64)), dim3(kBlock), 0, st, d, n_list);
-        HIP_TRY(hipMemsetAsync(d.counters + kCntWalkTicket, 0, sizeof(unsigned long long), st));
-        HIP_TRY(hipMemsetAsync(d.counters + kCntParkCnt, 0, sizeof(unsigned long long), st));
-        launch_walk(n_list, 2, 0u, base3);
-        if (!d.walk_handover) return RG_OK;
-        sim->fate_base = base3; sim->fate_count = d.counters + kCntParkCnt;
-        HIP_TRY(hipMemcpyAsync(h64, d.counters + kCntParkCnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const uint32_t n_left = static_cast<uint32_t>(*h64);
-        if (n_left) {
-            HIP_TRY(hipMemsetAsync(d.counters + kCntWalkTicket, 0, sizeof(unsigned long long), st));
-            const solo_kernel_t sk = (sim->walk2 && sim->walk_solo) ? solo_kernel_for(d) : nullptr;
-            if (sk) {      // a wave per user, a lane per consecutive event
-                // >= 4 listed users per wave; rows reserved per wave in chunks of ~1/8 of what it will emit (a commit is <= 64
-                // rows; what a wave leaves of its last chunk are holes in the raw log: a few percent of this round's rows)
-                uint32_t blocks = (n_left + 15u) / 16u;
-                const uint32_t cap = static_cast<uint32_t>(sim->n_cus) * 8u;
-                if (blocks > cap) blocks = cap;
-                uint64_t chunk = static_cast<uint64_t>(n_left) * 150 / (static_cast<uint64_t>(blocks) * 4 * 8);
-                chunk = chunk / 64 * 64;
-                if (chunk < 64) chunk = 64;
-                if (chunk > 1024) chunk = 1024;
-                hipLaunchKernelGGL(sk, dim3(blocks), dim3(kBlock), 0, st, d, n_left, static_cast<uint32_t>(chunk), base3);
-                sim->led.walk_solo += 1;
-            } else launch_walk(n_left, 3, base3, base3);
-        }
-        return RG_OK;
-    };
     if (n_park) {
         const uint32_t mfma_of_8 = static_cast<uint32_t>(sim->opt.exact_mix);     // groups of every 8 that take the matrix form (8 = all)
-        exact_h_kernel_t kh = mfma_of_8 < 8 ? exact_h_kernel_for(d.XKB) : nullptr;
+        const exact_h_kernel_t kh = mfma_of_8 < 8 ? exact_h_kernel_for(d.XKB) : nullptr;
+        const exact_m_kernel_t km = kh ? nullptr : exact_m_kernel_for(d.XKB);
         if (kh) {
             HIP_TRY(hipMemsetAsync(d.counters + kCntWalkTicket, 0, sizeof(unsigned long long), st));
             const uint32_t groups = (n_park + 255u) / 256u;
             const uint32_t grid = groups < 1024u ? groups : 1024u;
             hipLaunchKernelGGL(kh, dim3(grid), dim3(kBlock), exact_m_lds(d.XKB), st, d, n_park, mfma_of_8);
             sim->led.exact_h += 1;
-            if (int rc = mark(4)) return rc;
-            if (int rc = later_rounds(n_park)) return rc;
-            goto walked;
-        }
-        if (exact_m_kernel_t km = exact_m_kernel_for(d.XKB)) {
+        } else if (km) {
             launch_exact_m(km, d, n_park, 2, 1, n_park, st);
             sim->led.exact_m += 1;
-            if (int rc = mark(4)) return rc;
-            if (int rc = later_rounds(n_park)) return rc;
-            goto walked;
-        }
-        return fail(RG_ESTATE, "no float64 batch kernel for K = %u", d.K);
-    } else if (int rc = mark(4)) return rc;
-walked:
-    if (int rc = mark(5)) return rc;
-    hipLaunchKernelGGL(k_walk_finish, dim3(1), dim3(1), 0, st, d);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h64, d.counters + kCntTailLimit, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (sim->profiling) {
-        float ms[5];
-        for (int i = 0; i < 5; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
-        sim->prof_ms[0] += ms[0]; sim->prof_ms[1] += ms[1]; sim->prof_ms[2] += ms[3];
-        sim->prof_walk_ms[0] += ms[2]; sim->prof_walk_ms[1] += ms[4];
-        sim->prof_tail_ms += ms[2] + ms[4];
-        sim->prof_launches += 1;
-        for (int i = 0; i < 6; ++i) (void)hipEventDestroy(ev[i]);
+        } else return fail(RG_ESTATE, "no float64 batch kernel for K = %u", d.K);
     }
-    sim->t = 1;
-    sim->live_upper = 0;
-    if (*h64) return fail(RG_ELIMIT, "more than %u steps", kMaxSteps);
-    return RG_OK;
+    if (int rc = prof_mark(sim, st, kProfWalk2)) return rc;
+    if (n_park) {
+        // round 2 over the parked (and handed-over) users; what IT hands over is appended behind them for round 3
+        const uint32_t base3 = (n_park + 63u) & ~63u;
+        if (sim->walk2)      // the listed users' float64 sums as prefixes (anchored certificate, prefix pick)
+            hipLaunchKernelGGL(exact_prefix_kernel(), dim3(grid_for(n_park, kBlock / 64)), dim3(kBlock), 0, st, d, n_park);
+        HIP_TRY(hipMemsetAsync(d.counters + kCntWalkTicket, 0, sizeof(unsigned long long), st));
+        HIP_TRY(hipMemsetAsync(d.counters + kCntParkCnt, 0, sizeof(unsigned long long), st));
+        launch_walk(n_park, 2, 0u, base3);
+        uint32_t n_left = 0;
+        if (d.walk_handover) {
+            sim->fate_base = base3; sim->fate_count = d.counters + kCntParkCnt;
+            HIP_TRY(hipMemcpyAsync(h64, d.counters + kCntParkCnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            n_left = static_cast<uint32_t>(*h64);
+        }
+        if (n_left) {
+            HIP_TRY(hipMemsetAsync(d.counters + kCntWalkTicket, 0, sizeof(unsigned long long), st));
+            if (const solo_kernel_t sk = (sim->walk2 && sim->walk_solo) ? solo_kernel_for(d) : nullptr) {
+                const SoloShape sh = solo_shape(n_left, sim->n_cus);
+                hipLaunchKernelGGL(sk, dim3(sh.blocks), dim3(kBlock), 0, st, d, n_left, sh.chunk_rows, base3);
+                sim->led.walk_solo += 1;
+            } else launch_walk(n_left, 3, base3, base3);
+        }
+    }
+    return walk_end(sim, st);
 }
 
 // The same run as ONE CHAIN of launches whose list lengths stay on the device:
@@ -973,31 +1034,11 @@ walked:
 // lane at a time, and the sorted log does not depend on the raw order.
 int run_walk_pipe(rg_sim* sim, hipStream_t st) {
     const DevSim& d = sim->d;
-    const int n_cus = device_cus(sim);
-    if (d.debug_row_base)      // test hook: the walk reserves its raw rows from this counter
-        HIP_TRY(hipMemcpyAsync(d.counters + kCntTailRows, &sim->d.debug_row_base, sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    if (int rc = walk_begin(sim, st)) return rc;
+    const int n_cus = sim->n_cus;
     const uint32_t n = d.n_users;
-    // profiling: a pair of timing events around every launch group
-    struct Span { int cls; hipEvent_t a, b; };
-    std::vector<Span> spans;
-    auto span_begin = [&](int cls) -> int {
-        if (!sim->profiling) return RG_OK;
-        Span sp{cls, nullptr, nullptr};
-        HIP_TRY(hipEventCreate(&sp.a)); HIP_TRY(hipEventCreate(&sp.b));
-        HIP_TRY(hipEventRecord(sp.a, st));
-        spans.push_back(sp);
-        return RG_OK;
-    };
-    auto span_end = [&]() -> int {
-        if (!sim->profiling) return RG_OK;
-        HIP_TRY(hipEventRecord(spans.back().b, st));
-        return RG_OK;
-    };
-    hipEvent_t wall[2] = {nullptr, nullptr};
-    if (sim->profiling) {
-        HIP_TRY(hipEventCreate(&wall[0])); HIP_TRY(hipEventCreate(&wall[1]));
-        HIP_TRY(hipEventRecord(wall[0], st));
-    }
+    const size_t first_mark = sim->prof_used;       // profiling: the run's wall time is first mark to last
+    if (int rc = prof_mark(sim, st, kProfNone)) return rc;
     HIP_TRY(hipMemsetAsync(d.walk_ctl, 0, sizeof(unsigned long long) * kWalkCtlWords, st));
     const bool hist = d.policy == RG_POLICY_ORGANIC_USER_COUNT;
     const size_t smem = (kBlock / 64) * walk2_wave_lds(hist);
@@ -1006,13 +1047,6 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
     const exact_h_kernel_t kh = exact_h_kernel_for(d.XKB);
     if (!wk || !sk || !kh) return fail(RG_ESTATE, "run_walk_pipe: no kernel for this configuration");
     const uint32_t mfma_of_8 = static_cast<uint32_t>(sim->opt.exact_mix);
-    auto walk_chunk = [&](uint64_t n_work, int blocks) {
-        uint64_t chunk = n_work * 100 / (static_cast<uint64_t>(blocks) * 4 * 32);
-        chunk = chunk / 64 * 64;
-        if (chunk < 256) chunk = 256;
-        if (chunk > 4096) chunk = 4096;
-        return static_cast<uint32_t>(chunk);
-    };
     unsigned long long* ctl = d.walk_ctl;           // the rounds' queue counters; the last round's 8 words behind them
     unsigned long long* ctl_last = d.walk_ctl + 8;
     const uint32_t region = 0;                      // park_list: the users round 1 parked, then (behind its slack) the last round's list
@@ -1026,29 +1060,24 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         ds.sweep_only = 2u;
         ds.fin_in_sweep = dg.fin_in_sweep = sim->fin_in_sweep ? 1u : 0u;
         const uint32_t tiles_up = (n + sim->draw_users - 1) / sim->draw_users;
-        if (int rc = span_begin(0)) return rc;
+        if (int rc = prof_mark(sim, st, kProfSweep)) return rc;
         if (sim->xh_kernel) { hipLaunchKernelGGL(sim->xh_kernel, dim3(grid_for((n + 32u * sim->xh_waves - 1) / (32u * sim->xh_waves), 1)), dim3(64 * sim->xh_waves), sim->xh_smem, st, ds, 0u, 1u); sim->led.sweep_xh += 1; }
         else {
         hipLaunchKernelGGL(sim->bf16_kernel, dim3(sweep_grid(sim, tiles_up)), dim3(sim->draw_threads), sim->bf16_smem, st, ds, 0u, 1u);
         sim->led.draw16_fused += 1;
         }
-        if (int rc = span_end()) return rc;
-        if (int rc = span_begin(1)) return rc;
+        if (int rc = prof_mark(sim, st, kProfSearch)) return rc;
         hipLaunchKernelGGL(finalize_kernel_for(d), dim3(grid_for(n)), dim3(kBlock), 0, st, dg);
         hipLaunchKernelGGL(cache_prefix_kernel(), dim3(grid_for((static_cast<uint64_t>(n) + 7) / 8, kBlock / 64)), dim3(kBlock), 0, st, dg, 1);
-        if (int rc = span_end()) return rc;
     }
     // ---- round 1 ----
     {
         DevSim dw = dg;
         dw.q_ticket = ctl + 0; dw.q_park = ctl + 1; dw.q_count = nullptr;
-        int blocks = static_cast<int>((static_cast<uint64_t>(n) + kBlock - 1) / kBlock);
-        if (blocks > n_cus * sim->pipe_occ1) blocks = n_cus * sim->pipe_occ1;
-        if (blocks > static_cast<int>(kMaxWalkWaves / 4)) blocks = kMaxWalkWaves / 4;
-        if (int rc = span_begin(2)) return rc;
-        hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, dw, n, 1, walk_chunk(n, blocks), 0u, region);
+        const int blocks = walk_blocks(n, sim->pipe_occ1, n_cus);
+        if (int rc = prof_mark(sim, st, kProfWalk1)) return rc;
+        hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, dw, n, 1, walk_chunk_rows(n, blocks), 0u, region);
         sim->led.walk2 += 1;
-        if (int rc = span_end()) return rc;
     }
     // ---- the users it parked: float64 sums, prefixes, round 2 (what it hands over: the last round's list) ----
     {
@@ -1057,65 +1086,27 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         const uint32_t est = n / 3 + 4096u;                  // launch shapes only: the lengths are read on the device
         uint32_t xgrid = (n + 255u) / 256u;
         if (xgrid > static_cast<uint32_t>(sim->pipe_xblocks)) xgrid = static_cast<uint32_t>(sim->pipe_xblocks);
-        if (int rc = span_begin(3)) return rc;
+        if (int rc = prof_mark(sim, st, kProfResolve)) return rc;
         hipLaunchKernelGGL(kh, dim3(xgrid), dim3(kBlock), exact_m_lds(d.XKB), st, dx, n, mfma_of_8);
         sim->led.exact_h += 1;
         hipLaunchKernelGGL(exact_prefix_kernel(), dim3(grid_for(est, kBlock / 64)), dim3(kBlock), 0, st, dx, n);
-        if (int rc = span_end()) return rc;
         DevSim dr = dg;
         dr.q_ticket = ctl + 3; dr.q_park = ctl_last + 0; dr.q_count = ctl + 1;
-        int blocks = static_cast<int>((static_cast<uint64_t>(est) + kBlock - 1) / kBlock);
-        if (blocks > n_cus * sim->pipe_occ2) blocks = n_cus * sim->pipe_occ2;
-        if (blocks > static_cast<int>(kMaxWalkWaves / 4)) blocks = kMaxWalkWaves / 4;
-        if (int rc = span_begin(4)) return rc;
-        hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, dr, n, 2, walk_chunk(est, blocks), region, base_solo);
+        const int blocks = walk_blocks(est, sim->pipe_occ2, n_cus);
+        if (int rc = prof_mark(sim, st, kProfWalk2)) return rc;
+        hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, dr, n, 2, walk_chunk_rows(est, blocks), region, base_solo);
         sim->led.walk2 += 1;
-        if (int rc = span_end()) return rc;
     }
     // ---- last round: a wave per user (k_walk_solo) over what round 2 handed over ----
     sim->fate_base = base_solo; sim->fate_count = ctl_last + 0;
     if (d.walk_handover) {
         DevSim dl = d;
         dl.q_ticket = ctl_last + 1; dl.q_count = ctl_last + 0;
-        const uint32_t est = n / 256u + 1024u;
-        uint32_t blocks = (est + 15u) / 16u;
-        const uint32_t cap = static_cast<uint32_t>(n_cus) * 8u;
-        if (blocks > cap) blocks = cap;
-        uint64_t chunk = static_cast<uint64_t>(est) * 150 / (static_cast<uint64_t>(blocks) * 4 * 8);
-        chunk = chunk / 64 * 64;
-        if (chunk < 64) chunk = 64;
-        if (chunk > 1024) chunk = 1024;
-        if (int rc = span_begin(4)) return rc;
-        hipLaunchKernelGGL(sk, dim3(blocks), dim3(kBlock), 0, st, dl, n, static_cast<uint32_t>(chunk), base_solo);
+        const SoloShape sh = solo_shape(n / 256u + 1024u, n_cus);       // (an estimate too)
+        hipLaunchKernelGGL(sk, dim3(sh.blocks), dim3(kBlock), 0, st, dl, n, sh.chunk_rows, base_solo);
         sim->led.walk_solo += 1;
-        if (int rc = span_end()) return rc;
     }
-    hipLaunchKernelGGL(k_walk_finish, dim3(1), dim3(1), 0, st, d);
-    HIP_TRY(hipGetLastError());
-    if (sim->profiling) HIP_TRY(hipEventRecord(wall[1], st));
-    unsigned long long* h64 = reinterpret_cast<unsigned long long*>(sim->h_pinned);
-    HIP_TRY(hipMemcpyAsync(h64, d.counters + kCntTailLimit, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (sim->profiling) {
-        for (const Span& sp : spans) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, sp.a, sp.b));
-            if (sp.cls == 0) sim->prof_ms[0] += ms;
-            else if (sp.cls == 1) sim->prof_ms[1] += ms;
-            else if (sp.cls == 3) sim->prof_ms[2] += ms;
-            else { sim->prof_walk_ms[sp.cls == 2 ? 0 : 1] += ms; sim->prof_tail_ms += ms; }
-            (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b);
-        }
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, wall[0], wall[1]));
-        sim->prof_pipe_ms += ms;
-        (void)hipEventDestroy(wall[0]); (void)hipEventDestroy(wall[1]);
-        sim->prof_launches += 1;
-    }
-    sim->t = 1;
-    sim->live_upper = 0;
-    if (*h64) return fail(RG_ELIMIT, "more than %u steps", kMaxSteps);
-    return RG_OK;
+    return walk_end(sim, st, first_mark);
 }
 
 
@@ -1189,8 +1180,8 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
         const char* e_h = getenv("RECOGYM_WALK_HIST");
         d.walk_line64 = (e_h && e_h[0] == '1') ? 1u : 0u;
     }
-    s->profiling = false; s->prof_used = 0; s->prof_launches = 0;
-    s->prof_ms[0] = s->prof_ms[1] = s->prof_ms[2] = s->prof_ms[3] = s->prof_ms[4] = 0.0;
+    s->profiling = false;
+    prof_reset(s);
     s->mfma_smem = d.use_mfma ? mfma_smem_bytes(geom_of(*cfg)) : 0;
     // kernel choice: split-bf16 MFMA when a class exists for K, else fp32 MFMA; RECOGYM_DRAW=f64|fp32|bf16 overrides
     s->bf16_kernel = nullptr; s->bf16_smem = 0;
@@ -1221,12 +1212,10 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
     // the per-user sum cache is written by the pipelined 16-bit kernel only
     if (!(d.use_mfma == 2 && s->bf16_kernel &&
           (s->bf16_kernel == bf16p_kernel_for(d) || (d.wide && s->bf16_kernel == f16w_kernel_for(d))))) d.use_cache = 0;
-    if (s->bf16_kernel && s->bf16_smem > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(s->bf16_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(s->bf16_smem));
+    if (s->bf16_kernel) opt_in_lds(s->bf16_kernel, s->bf16_smem);
     // the walked run's sweep with an error-free leading accumulator (k_sweep_xh) where the pipelined fp16 sweep would run it
     s->xh_kernel = nullptr; s->xh_smem = 0;
-    if (d.XNH && d.use_cache && d.use_mfma == 2 && s->bf16_kernel && s->bf16_kernel == bf16p_kernel_for(d) && d.f16 && !d.wide &&
+    if (d.XNH && d.use_cache && d.use_mfma == 2 && s->bf16_kernel && f16_pipelined(s) &&
         static_cast<size_t>(d.P_pad) * d.XRS < (1ull << 31))
     {
         s->xh_waves = 4;
@@ -1236,14 +1225,13 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
     if (s->xh_kernel) {
         s->xh_smem = 2 * (128 * static_cast<size_t>(d.XRS) + 512) + 256 + static_cast<size_t>(s->xh_waves) * 32 * kMaxSC * sizeof(float);   // tiles, seeds, the super-chunk prefix stage
         if (const char* e = getenv("RECOGYM_XH_SMEM_PAD")) s->xh_smem += static_cast<size_t>(atoi(e));   // occupancy experiments: one block per CU
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(s->xh_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(s->xh_smem));
+        set_max_lds(s->xh_kernel, s->xh_smem);
     } else { d.XNH = d.XNL = d.XRS = 0; }
     // the sweep whose search stays in LDS (k_draw_tp): where every draw sweeps (no per-user cache) and the two-way fp16 split of
     // K <= 20 serves the table; a user's tile prefixes must fit beside the tiles (P <= ~12 000 at two blocks per CU)
     s->tp_kernel = nullptr; s->pick_kernel = nullptr; s->tp_smem = 0; s->tp_nts = 0; s->sweep_lds = 1;
     if (const char* e = getenv("RECOGYM_SWEEP_LDS")) s->sweep_lds = e[0] != '0';
-    if (d.use_mfma == 2 && !d.use_cache && s->bf16_kernel && s->bf16_kernel == bf16p_kernel_for(d) && d.f16 && !d.wide) {
+    if (d.use_mfma == 2 && !d.use_cache && s->bf16_kernel && f16_pipelined(s)) {
         draw_kernel_t kt = tp_kernel_for(d), kp = pick_kernel_for(d);
         if (kt && kp && d.tp_rec) {
             const uint32_t nts = ((d.n_chunks / 4) + 3u) & ~3u;
@@ -1253,7 +1241,7 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
             // list atomic on <= 3 x 128 counters would pace it: those tables keep k_draw_bf16p)
             if (smem <= 160 * 1024 && d.n_chunks / 4 <= 128u && d.n_chunks / 4 >= 4u) {
                 s->tp_kernel = kt; s->pick_kernel = kp; s->tp_smem = smem; s->tp_nts = nts;
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kt), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
+                set_max_lds(kt, smem);
             }
         }
     }
@@ -1275,7 +1263,7 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
             if (smem <= 160 * 1024) {
                 s->tp_kernel = kt; s->pick_kernel = kp; s->tp_smem = smem; s->tp_nts = nts;
                 d.tp_cpt = 2 * G;
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kt), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
+                set_max_lds(kt, smem);
             }
         }
     }
@@ -1298,7 +1286,6 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
         // score loops — the frozen LogReg policy stays in lock-step (wave-cooperative acts) to the end
         if (d.policy == RG_POLICY_LOGREG_FROZEN) s->tail_below = 0;
     }
-    s->prof_tail_ms = 0.0;
     // user-major walk: wherever the per-user cache exists and the policy acts lane by lane (the frozen LogReg
     // policy acts wave-cooperatively: lock-step); RECOGYM_WALK=0 keeps the lock-step loop (A/B tests)
     s->walk = d.use_cache && (d.policy == RG_POLICY_UNIFORM_ENV || d.policy == RG_POLICY_RANDOM_AGENT ||
@@ -1334,7 +1321,6 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
     if (s->walk2) s->walk_occ = d.KH <= 10 ? 3 : 2;     // (what k_walk2 is compiled for: K <= 20 three blocks per CU, K <= 32 two)
     s->walk_solo = true;
     if (const char* e = getenv("RECOGYM_WALK_SOLO")) s->walk_solo = e[0] != '0';
-    s->prof_walk_ms[0] = s->prof_walk_ms[1] = 0.0;
     // the walked run as one chain with its list lengths on the device (run_walk_pipe).  RECOGYM_PIPE=0: run_walk, host-side list
     // lengths; RECOGYM_PIPE_OCC1 / _OCC2 (blocks per CU of the rounds' grids), RECOGYM_PIPE_XBLOCKS: A/B tests.
     // The whole reset range is ONE group on the caller's stream.  More groups on two or three streams were measured on C3 and
@@ -1345,7 +1331,6 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
     s->pipe_occ1 = s->pipe_occ2 = s->walk_occ;
     s->pipe_xblocks = 1024;
     s->fate_base = 0; s->fate_count = nullptr;
-    s->prof_pipe_ms = 0.0;
     if (const char* e = getenv("RECOGYM_PIPE")) { const int o = atoi(e); if (o == 0 || o == 1) s->pipe_groups = o; }
     if (const char* e = getenv("RECOGYM_PIPE_OCC1")) { const int o = atoi(e); if (o >= 1 && o <= s->walk_occ) s->pipe_occ1 = o; }
     if (const char* e = getenv("RECOGYM_PIPE_OCC2")) { const int o = atoi(e); if (o >= 1 && o <= s->walk_occ) s->pipe_occ2 = o; }
@@ -1380,12 +1365,8 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(mfma_kernel_for(10)), kBlock, s->mfma_smem);
         fprintf(stderr, "[recogym] k_draw_mfma<10>: dynamic LDS %zu B, occupancy API %d blocks/CU\n", s->mfma_smem, nb);
     }
-    if (s->mfma_smem > 64 * 1024) {
-        // more than 64 KiB of dynamic LDS needs an explicit opt-in per kernel instantiation
-        const int bytes = static_cast<int>(s->mfma_smem);
-        for (uint32_t kh : {4u, 10u, 16u, 32u, 64u})
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mfma_kernel_for(kh)), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    }
+    if (s->mfma_smem > 64 * 1024)
+        for (uint32_t kh : {4u, 10u, 16u, 32u, 64u}) set_max_lds(mfma_kernel_for(kh), s->mfma_smem);
     *out = s;
     return RG_OK;
 }
@@ -1779,7 +1760,7 @@ int rg_sim_run(rg_sim* sim, uint32_t max_steps, void* stream) {
         // batch) and the reset range fills an unsliced sweep; else the serial chain with its list lengths read back by the host
         const int mix = sim->opt.exact_mix;
         const bool pipe = sim->pipe_groups >= 1 && sim->walk2 && sim->walk_solo && solo_kernel_for(sim->d) && sim->d.walk_handover &&
-                          sim->bf16_kernel == bf16p_kernel_for(sim->d) && sim->d.f16 && !sim->d.wide && sim->d.n_users >= sim->pipe_min_users &&
+                          f16_pipelined(sim) && sim->d.n_users >= sim->pipe_min_users &&
                           exact_h_kernel_for(sim->d.XKB) && mix < 8 && sim->opt.slices < 0 &&
                           !sim->opt.sweep_prefix_off;
         return pipe ? run_walk_pipe(sim, st) : run_walk(sim, st);
@@ -1808,29 +1789,14 @@ int rg_sim_run(rg_sim* sim, uint32_t max_steps, void* stream) {
         // few users left: finish them user by user (k_tail) instead of ~1 000 more latency-bound steps
         const size_t tail_smem = sizeof(double) * (((sim->d.K + 1) & ~1u) + ((sim->d.PT / 64 + 3) & ~3u));
         if (live <= sim->tail_below && max_steps >= kMaxSteps && tail_smem <= 48 * 1024 && sim->t + 2 < kMaxSteps) {
-            hipEvent_t ev[2] = {nullptr, nullptr};
-            if (sim->profiling) {
-                HIP_TRY(hipEventCreate(&ev[0])); HIP_TRY(hipEventCreate(&ev[1]));
-                HIP_TRY(hipEventRecord(ev[0], st));
-            }
+            if (int rc = prof_mark(sim, st, kProfTail)) return rc;
             const int grid = static_cast<int>(live < 2048 ? live : 2048);
             hipLaunchKernelGGL(tail_kernel(sim->d.eg_on != 0u), dim3(grid), dim3(kBlock), tail_smem, st, sim->d, sim->t);
             sim->led.tail += 1;
             hipLaunchKernelGGL(k_tail_finish, dim3(1), dim3(1), 0, st, sim->d, sim->t);
             HIP_TRY(hipGetLastError());
-            if (sim->profiling) HIP_TRY(hipEventRecord(ev[1], st));
-            unsigned long long* h64 = reinterpret_cast<unsigned long long*>(sim->h_pinned);
-            HIP_TRY(hipMemcpyAsync(h64, sim->d.counters + kCntTailLimit, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (sim->profiling) {
-                float ms = 0.f;
-                HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-                sim->prof_tail_ms += ms;
-                (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
-            }
-            sim->t += 1;
-            sim->live_upper = 0;
-            if (*h64) return fail(RG_ELIMIT, "more than %u steps", kMaxSteps);
+            if (int rc = prof_mark(sim, st, kProfNone)) return rc;
+            if (int rc = close_run(sim, st, sim->t + 1)) return rc;
             break;
         }
     }
@@ -1860,22 +1826,19 @@ int rg_sim_read_counters(rg_sim* sim, int64_t* out, void* stream) {
 int rg_sim_set_profiling(rg_sim* sim, int on) {
     if (!sim) return fail(RG_EINVAL, "sim is NULL");
     sim->profiling = on != 0;
-    sim->prof_used = 0; sim->prof_launches = 0;
-    sim->prof_ms[0] = sim->prof_ms[1] = sim->prof_ms[2] = sim->prof_ms[3] = sim->prof_ms[4] = 0.0;
-    sim->prof_tail_ms = 0.0;
-    sim->prof_walk_ms[0] = sim->prof_walk_ms[1] = 0.0;
-    sim->prof_pipe_ms = 0.0;
+    prof_reset(sim);
     return RG_OK;
 }
 
 int rg_sim_get_profile(rg_sim* sim, double* out) {
     if (!sim || !out) return fail(RG_EINVAL, "NULL argument");
     if (int rc = prof_collect(sim)) return rc;
-    out[0] = sim->prof_ms[0]; out[1] = sim->prof_ms[1]; out[2] = sim->prof_ms[2]; out[3] = sim->prof_ms[4];
+    const double* ms = sim->prof_ms;
+    out[0] = ms[kProfSweep]; out[1] = ms[kProfSearch]; out[2] = ms[kProfResolve]; out[3] = ms[kProfAdvance];
     out[4] = static_cast<double>(sim->prof_launches);
-    out[5] = sim->prof_tail_ms;
-    out[6] = sim->prof_walk_ms[0]; out[7] = sim->prof_walk_ms[1];
-    out[8] = sim->prof_ms[3]; out[9] = sim->prof_pipe_ms;
+    out[5] = ms[kProfWalk1] + ms[kProfWalk2] + ms[kProfTail];      // everything that ran user by user to the end
+    out[6] = ms[kProfWalk1]; out[7] = ms[kProfWalk2];
+    out[8] = ms[kProfLogreg]; out[9] = sim->prof_pipe_ms;
     return RG_OK;
 }
 
