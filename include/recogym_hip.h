@@ -44,7 +44,8 @@ extern "C" {
  * and rg_count_online_workspace_bytes / rg_count_train_online (the count agents' train calls under a row filter). */
 /* v13 (additive): RG_POLICY_LOGREG_POLY with rg_sim_set_logreg_poly, rg_sim_read_poly_unresolved and rg_sim_debug_poly_acts (the
  * likelihood agent LogregPolyAgent in the step loop), and the counters RG_CNT_POLY_TABLE / RG_CNT_POLY_UNRESOLVED. */
-#define RG_ABI_VERSION 13
+/* v14 (additive): rg_ope_poly_workspace_bytes / rg_ope_replay_poly (the off-policy replay of the likelihood agent). */
+#define RG_ABI_VERSION 14
 
 /* error codes */
 #define RG_OK 0
@@ -521,6 +522,41 @@ size_t rg_ope_logreg_workspace_bytes(const rg_ope_logreg* model, uint64_t n_user
 int rg_ope_replay_logreg(const rg_ope_logreg* model, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
                          uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
                          uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Off-policy evaluation of the likelihood agent (LogregPolyFrozenAgent, reference agents/logreg_poly.py:143-167 with
+ * with_ps_all = True): replay a sorted log under a fitted binary model of polynomial features.  Stateless (no rg_sim handle).  The
+ * model arrays are device arrays as rg_sim_set_logreg_poly takes them, th the table of expit's top steps (n_steps <= 1024, never
+ * increasing).  The policy sees the user's cumulative view counts (all organic rows so far, across sessions); the act is the step
+ * loop's (k_poly_acts: the same decisions, step table, margin and flags), pi = [action == a], r = pi / ps.
+ */
+typedef struct rg_ope_poly {
+    uint32_t num_products;          /* P <= RG_EV_INDEX_MASK */
+    uint32_t n_steps;               /* entries of th, 1 .. 1024 */
+    const double* wf;               /* [P] */
+    const double* wa;               /* [P] */
+    const double* wk_t;             /* [P][P], [viewed product][action] */
+    const double* th;               /* [n_steps] */
+    double intercept;
+} rg_ope_poly;
+
+/* rg_ope_poly_workspace_bytes: device workspace rg_ope_replay_poly needs for n_users users the longest of which has
+ * max_user_rows rows (0 = error, see rg_last_error).
+ * rg_ope_replay_poly: rows, offsets, the ps source and the outputs d_ratio / d_click / d_sums as rg_ope_replay.  The log is
+ * validated before any output is written, by rg_ope_replay_logreg's rules: RG_EINVAL for a user whose first row is a bandit row
+ * or that has more than max_user_rows rows, and for a product or an action >= P.  RG_EINVAL also for a null model or model
+ * array, n_steps == 0 or > 1024, and rows that are not 16-byte aligned; RG_ENOMEM for a workspace too small.  Afterwards the
+ * workspace's first int64 words hold [0] error bits (0), [1] acts computed (bandit rows whose user's history changed since its
+ * previous act; the rows between reuse it), [2] acts decided on the step table, [3] acts where a lower index than the first
+ * maximal decision won, [4] unresolved acts, [5] non-zero when more than 4096 acts were unresolved, [6] wk_t rows read.  The
+ * unresolved acts follow from byte 256: up to 4096 entries of three uint32 (user index, position of the bandit row the act was
+ * computed at within the user's rows, action taken), in no fixed order.  The ratios are written with the device's action; a
+ * caller that needs the reference's action on such acts recomputes them on the host (recogym_amd.sim.poly_replay_verify).
+ * d_sums holds the same bits on every run.  Synchronises `stream` once (it reads the validation's verdict). */
+size_t rg_ope_poly_workspace_bytes(const rg_ope_poly* model, uint64_t n_users, uint32_t max_user_rows);
+int rg_ope_replay_poly(const rg_ope_poly* model, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                       uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
+                       uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Off-policy evaluation of an EpsilonGreedy target (agents/epsilon_greedy.py:30-71 with with_ps_all = True on the wrapper and the

@@ -7,7 +7,7 @@ infrastructure and is never imported from this package.)
 import ctypes as C
 import os
 
-RG_ABI_VERSION = 13
+RG_ABI_VERSION = 14
 
 RG_STATE_ORGANIC, RG_STATE_BANDIT, RG_STATE_STOP = 0, 1, 2
 
@@ -91,6 +91,12 @@ class RgOpeLogreg(C.Structure):
                 ('bmax', C.c_float), ('reserved2', C.c_uint32)]
 
 
+class RgOpePoly(C.Structure):
+    """struct rg_ope_poly: the likelihood agent's model of rg_ope_replay_poly (device arrays)."""
+    _fields_ = [('num_products', C.c_uint32), ('n_steps', C.c_uint32), ('wf', C.c_void_p), ('wa', C.c_void_p), ('wk_t', C.c_void_p),
+                ('th', C.c_void_p), ('intercept', C.c_double)]
+
+
 class RgOpeEg(C.Structure):
     """struct rg_ope_eg: the EpsilonGreedy wrapper of rg_ope_replay_eg."""
     _fields_ = [('epsilon', C.c_double), ('seed', C.c_uint64), ('pure_new', C.c_uint32), ('reserved', C.c_uint32),
@@ -166,6 +172,10 @@ SYMBOLS = {
     'rg_ope_replay_logreg': (C.c_int, [C.POINTER(RgOpeLogreg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                        C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                        C.c_void_p]),
+    'rg_ope_poly_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpePoly), C.c_uint64, C.c_uint32]),
+    'rg_ope_replay_poly': (C.c_int, [C.POINTER(RgOpePoly), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                     C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
     'rg_ope_eg_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpePolicy), C.c_uint64, C.c_uint32]),
     'rg_ope_replay_eg': (C.c_int, [C.POINTER(RgOpePolicy), C.POINTER(RgOpeEg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
                                    C.c_uint32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

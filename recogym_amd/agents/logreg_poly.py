@@ -24,7 +24,8 @@ Inference (`LogregPolyFrozenAgent`): two facts of the reference are reproduced, 
    upwards and moves in steps of 2^-53 below that, so among confident decisions the LOWER INDEX wins, not the larger z.  The
    device decides that with the host's table of expit's top steps (`expit_steps`, built with scipy's expit itself) and, below
    the table, with the margin `poly_margin` inside which two decisions MAY round to one expit value; an act with a lower-index
-   decision inside that margin is reported as unresolved and recomputed here (`Simulator.poly_verify`).
+   decision inside that margin is reported as unresolved and recomputed here (`Simulator.poly_verify`; in an off-policy
+   replay, `sim.poly_replay_verify`).
 
 `act` on the host is (1), scipy.special.expit, first maximum — the reference's act bit for bit.
 """
@@ -190,8 +191,17 @@ class LogregPolyFrozenAgent(Agent):
                     logreg_poly=dict(wf=self.wf, wa=self.wa, wk=self.wk, intercept=self.b))
 
     def ope_policy(self):
-        """None: off-policy evaluation of this agent runs on the host loop (no device replay unit)."""
+        """None: `ope_policy` is the hook of replay forms that are exact without a host step; this agent's is `ope_policy_checked`."""
         return None
+
+    def ope_policy_checked(self):
+        """The replay form of rg_ope_replay_poly, or None where only the host loop is exact (no `ps-a` without with_ps_all; the
+        time-weighted features of a weight_history_function).  "Checked": the device lists the acts its rule cannot resolve and
+        the caller confirms them on the host (sim.poly_replay_verify) before it lets the result stand."""
+        if not getattr(self.config, 'with_ps_all', False) or self.history is not None:
+            return None
+        return dict(kind=_abi.RG_POLICY_LOGREG_POLY, num_products=int(self.config.num_products), policy_seed=0,
+                    logreg_poly=dict(wf=self.wf, wa=self.wa, wk=self.wk, intercept=self.b))
 
     def reset(self):
         self.views = np.zeros(self.config.num_products, dtype=np.int64)
@@ -230,6 +240,9 @@ class LogregPolyAgent(LogregMulticlassIpsAgent):
 
     def __init__(self, config=Configuration(logreg_poly_args)):
         super().__init__(config)
+
+    def ope_policy_checked(self):
+        return self._ready().ope_policy_checked()
 
     def _sample_weights(self, clicks, pss):
         """The fit's sample weights, or None without with_ips.  As in the reference, clipping takes click / ps as the weight to

@@ -1,4 +1,6 @@
-// rg_ope_common.hpp — the skeleton the off-policy replay units share (rg_ope.hip, rg_ope_logreg.hip, rg_ope_eg.hip).
+// rg_ope_common.hpp — the skeleton the off-policy replay units share (rg_ope.hip, rg_ope_logreg.hip, rg_ope_eg.hip, rg_ope_poly.hip;
+// DESIGN.md §4b), and what the two units that keep a sorted view history share besides: the list insert (ope_list_add) and the
+// validation of the log (ope_check_log).
 //
 // One wave per user, users assigned statically (wave w takes users w, w + W, ...).  A user's rows stream in coalesced 64-row
 // chunks (16-byte rg_event per lane + the row's float64 ps); a unit computes the target policy's pi of every bandit lane, the
@@ -67,6 +69,61 @@ __device__ __forceinline__ uint32_t ope_last_view(const OpeRow& r, uint32_t lane
     return mine;
 }
 
+// ---- what the units that keep a sorted (product, count) history per wave share (rg_ope_logreg.hip, rg_ope_poly.hip) ----
+constexpr uint32_t kOpeNone = 0xFFFFFFFFu;
+
+__device__ __forceinline__ unsigned long long ope_below(uint32_t lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }
+__device__ __forceinline__ uint32_t ope_lane_value(uint32_t x, uint32_t lane) {
+    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), static_cast<int>(lane)));
+}
+__device__ __forceinline__ uint32_t ope_uniform(uint32_t x) {
+    return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(x)));
+}
+
+// what one lane wrote to a list is read by the others: LDS within the workgroup's scope; the global list through the agent's
+// (the wave's own stores complete and its L1 lines are dropped before the next read)
+template <bool kLds>
+__device__ __forceinline__ void ope_list_sync() {
+    if (kLds) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// one view of product p into the sorted list (lp, lc)[0 .. n); false = the list is full (nothing written)
+template <bool kLds>
+__device__ __forceinline__ bool ope_list_add(uint32_t* lp, uint32_t* lc, uint32_t& n, uint32_t cap, uint32_t p, uint32_t lane) {
+    uint32_t pos = 0, found = kOpeNone;
+    for (uint32_t j0 = 0; j0 < n; j0 += 64) {
+        const uint32_t j = j0 + lane;
+        const uint32_t v = j < n ? lp[j] : kOpeNone;                   // (p < 2^29: never the filler)
+        const unsigned long long hit = __ballot(v == p);
+        if (hit) { found = j0 + static_cast<uint32_t>(__builtin_ctzll(hit)); break; }
+        const uint32_t less = static_cast<uint32_t>(__popcll(__ballot(v < p)));
+        pos += less;
+        if (less < 64) break;                                         // ascending: nothing smaller beyond
+    }
+    if (found != kOpeNone) {
+        if (lane == 0) lc[found] += 1;
+        ope_list_sync<kLds>();
+        return true;
+    }
+    if (n >= cap) return false;
+    // entries pos .. n-1 move up one place, 64 at a time from the top (a chunk is read whole before it is written)
+    for (uint32_t hi = n; hi > pos; hi = hi - pos > 64 ? hi - 64 : pos) {
+        const bool on = lane < hi - pos;
+        const uint32_t j = hi - 1 - lane;
+        uint32_t vp = 0, vc = 0;
+        if (on) { vp = lp[j]; vc = lc[j]; }
+        ope_list_sync<kLds>();
+        if (on) { lp[j + 1] = vp; lc[j + 1] = vc; }
+        ope_list_sync<kLds>();
+    }
+    if (lane == 0) { lp[pos] = p; lc[pos] = 1; }
+    ope_list_sync<kLds>();
+    n += 1;
+    return true;
+}
+
 // EpsilonGreedy's explore flip of the act at (user u, event t): words 0,1 of the policy block of (the wrapper's seed, u, t) against
 // the first entry of NumPy's normalised cdf of p = [eps, 1 - eps] (agents/epsilon_greedy.py: rng.choice([True, False], p)).
 // Shared by the off-policy replay (rg_ope_eg.hip) and the evolution statistics (rg_evolve.hip).
@@ -105,6 +162,12 @@ struct OpeAcc {
 
 // the per-wave slots -> d_sums = (n, sum c r, sum r): k_ope_reduce, one block, fixed order (rg_ope.hip)
 int ope_reduce(const double* slots, uint32_t n_waves, double* d_sums, hipStream_t stream);
+
+// a history-keeping unit's validation (rg_ope_logreg.hip): zeroes the 32 int64 head words of `ws` (word 0: error bits), then
+// refuses a user that opens with a bandit row or has more than max_user_rows rows and a product or an action >= P, before
+// anything is written.  Synchronises the stream once (the verdict).
+int ope_check_log(const char* who, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users, uint32_t P,
+                  uint32_t max_user_rows, unsigned long long* ws, hipStream_t stream);
 
 // the argument checks every replay entry point makes after those of its own policy; `need` = its workspace bytes
 inline int ope_args_ok(const char* who, uint32_t ps_mode, const double* d_ps, uint64_t n_users, const rg_event* d_rows,

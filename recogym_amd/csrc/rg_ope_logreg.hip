@@ -44,60 +44,9 @@ constexpr int kLrWsErr = 0, kLrWsActs = 1, kLrWsExact = 2, kLrWsRowsRead = 3, kL
 uint32_t lr_global_cap(uint32_t max_user_rows) { return max_user_rows > kLrLds ? max_user_rows : 0u; }
 size_t lr_head_bytes() { return kLrWsWords * sizeof(lr_u64); }
 
-__device__ __forceinline__ lr_u64 lr_below(uint32_t lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }
-__device__ __forceinline__ uint32_t lr_lane_value(uint32_t x, uint32_t lane) {
-    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), static_cast<int>(lane)));
-}
-__device__ __forceinline__ uint32_t lr_uniform(uint32_t x) {
-    return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(x)));
-}
 __device__ __forceinline__ double lr_wave_max(double x) {
     for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o));
     return x;
-}
-
-// what one lane wrote to a list is read by the others: LDS within the workgroup's scope; the global list through the agent's
-// (the wave's own stores complete and its L1 lines are dropped before the next read)
-template <bool kLds>
-__device__ __forceinline__ void lr_sync() {
-    if (kLds) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// one view of product p into the sorted list (lp, lc)[0 .. n); false = the list is full (nothing written)
-template <bool kLds>
-__device__ __forceinline__ bool lr_list_add(uint32_t* lp, uint32_t* lc, uint32_t& n, uint32_t cap, uint32_t p, uint32_t lane) {
-    uint32_t pos = 0, found = kLrNone;
-    for (uint32_t j0 = 0; j0 < n; j0 += 64) {
-        const uint32_t j = j0 + lane;
-        const uint32_t v = j < n ? lp[j] : kLrNone;                   // (p < 2^29: never the filler)
-        const lr_u64 hit = __ballot(v == p);
-        if (hit) { found = j0 + static_cast<uint32_t>(__builtin_ctzll(hit)); break; }
-        const uint32_t less = static_cast<uint32_t>(__popcll(__ballot(v < p)));
-        pos += less;
-        if (less < 64) break;                                         // ascending: nothing smaller beyond
-    }
-    if (found != kLrNone) {
-        if (lane == 0) lc[found] += 1;
-        lr_sync<kLds>();
-        return true;
-    }
-    if (n >= cap) return false;
-    // entries pos .. n-1 move up one place, 64 at a time from the top (a chunk is read whole before it is written)
-    for (uint32_t hi = n; hi > pos; hi = hi - pos > 64 ? hi - 64 : pos) {
-        const bool on = lane < hi - pos;
-        const uint32_t j = hi - 1 - lane;
-        uint32_t vp = 0, vc = 0;
-        if (on) { vp = lp[j]; vc = lc[j]; }
-        lr_sync<kLds>();
-        if (on) { lp[j + 1] = vp; lc[j + 1] = vc; }
-        lr_sync<kLds>();
-    }
-    if (lane == 0) { lp[pos] = p; lc[pos] = 1; }
-    lr_sync<kLds>();
-    n += 1;
-    return true;
 }
 
 // entry i of the history, wave-uniform (T = 0: registers, 1: LDS, 2: global)
@@ -107,8 +56,8 @@ struct LrHist {
     const uint32_t* lp;
     const uint32_t* lc;
     __device__ __forceinline__ void get(uint32_t i, uint32_t& p, uint32_t& c) const {
-        if (T == 0) { p = lr_lane_value(hp, i); c = lr_lane_value(hc, i); }
-        else { p = lr_uniform(lp[i]); c = lr_uniform(lc[i]); }
+        if (T == 0) { p = ope_lane_value(hp, i); c = ope_lane_value(hc, i); }
+        else { p = ope_uniform(lp[i]); c = ope_uniform(lc[i]); }
     }
 };
 
@@ -306,7 +255,7 @@ __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
             while (rem) {
                 const uint32_t k = static_cast<uint32_t>(__builtin_ctzll(rem));
                 if ((omask >> k) & 1) {
-                    const uint32_t p = lr_lane_value(idx, k);
+                    const uint32_t p = ope_lane_value(idx, k);
                     bool done = false;
                     if (tier == 0) {
                         const lr_u64 hit = __ballot(lane < n && hp == p);
@@ -323,21 +272,21 @@ __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
                             done = true;
                         } else {
                             lp[lane] = hp; lc[lane] = hc;             // the 65th product: on to the LDS list
-                            lr_sync<true>();
+                            ope_list_sync<true>();
                             tier = 1;
                         }
                     }
                     if (!done && tier == 1) {
                         if (n < kLrLds || !gp) {
                             done = true;
-                            if (!lr_list_add<true>(lp, lc, n, kLrLds, p, lane)) err |= kLrErrRows;
+                            if (!ope_list_add<true>(lp, lc, n, kLrLds, p, lane)) err |= kLrErrRows;
                         } else {
                             for (uint32_t j = lane; j < n; j += 64) { gp[j] = lp[j]; gc[j] = lc[j]; }   // on to the global list
-                            lr_sync<false>();
+                            ope_list_sync<false>();
                             tier = 2;
                         }
                     }
-                    if (!done && !lr_list_add<false>(gp, gc, n, g_cap, p, lane)) err |= kLrErrRows;
+                    if (!done && !ope_list_add<false>(gp, gc, n, g_cap, p, lane)) err |= kLrErrRows;
                     dirty = true;
                     rem &= rem - 1;
                     continue;
@@ -362,7 +311,7 @@ __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
                     dirty = false;
                 }
                 // the bandit rows up to the next organic row share this act
-                const lr_u64 next_o = omask & ~lr_below(k);
+                const lr_u64 next_o = omask & ~ope_below(k);
                 const uint32_t end = next_o ? static_cast<uint32_t>(__builtin_ctzll(next_o)) : 64u;
                 const bool mine = isb && lane >= k && lane < end;
                 if (kSoft) {
@@ -379,7 +328,7 @@ __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
                 } else if (mine) {
                     pi = act_class == idx ? 1.0 : 0.0;
                 }
-                rem &= end < 64 ? ~lr_below(end) : 0ull;
+                rem &= end < 64 ? ~ope_below(end) : 0ull;
             }
             if (isb) acc.emit(log, r, pi);
         }
@@ -410,6 +359,26 @@ int lr_model_ok(const rg_ope_logreg* m, const char* who) {
 
 }  // namespace
 
+// the head of a history-keeping unit's workspace zeroed (32 words) and the log validated, before anything is written (rg_ope_common.hpp)
+int rgk::ope_check_log(const char* who, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users, uint32_t P,
+                       uint32_t max_user_rows, unsigned long long* ws, hipStream_t s) {
+    hipLaunchKernelGGL(k_lr_init, dim3(1), dim3(64), 0, s, ws);
+    HIP_TRY(hipGetLastError());
+    if (!n_users) return RG_OK;
+    const uint32_t check_blocks = static_cast<uint32_t>(n_users / 256 + 1 > 2048 ? 2048 : n_users / 256 + 1);
+    hipLaunchKernelGGL(k_lr_check, dim3(check_blocks), dim3(256), 0, s, d_rows, d_offsets, n_users, P, max_user_rows, ws);
+    HIP_TRY(hipGetLastError());
+    lr_u64 verdict = 0;
+    HIP_TRY(hipMemcpyAsync(&verdict, ws + kLrWsErr, sizeof(verdict), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (verdict & kLrErrRows)
+        return fail(RG_EINVAL, "%s: a user has more than max_user_rows = %u rows (or its offsets descend); nothing was written", who, max_user_rows);
+    if (verdict & kLrErrFirstBandit) return fail(RG_EINVAL, "%s: a user opens with a bandit row; nothing was written", who);
+    if (verdict & kLrErrIndex)
+        return fail(RG_EINVAL, "%s: the log has a product or an action >= num_products %u; nothing was written", who, P);
+    return RG_OK;
+}
+
 extern "C" size_t rg_ope_logreg_workspace_bytes(const rg_ope_logreg* m, uint64_t n_users, uint32_t max_user_rows) {
     if (!m) { fail(RG_EINVAL, "rg_ope_logreg_workspace_bytes: null model"); return 0; }
     const uint32_t W = ope_waves(n_users, kLrMaxWaves);
@@ -439,22 +408,7 @@ extern "C" int rg_ope_replay_logreg(const rg_ope_logreg* m, const rg_event* d_ro
     lr_u64* ws = static_cast<lr_u64*>(d_workspace);
     double* slots = reinterpret_cast<double*>(static_cast<char*>(d_workspace) + lr_head_bytes());
     uint32_t* gscr = g_cap ? reinterpret_cast<uint32_t*>(static_cast<char*>(d_workspace) + lr_head_bytes() + ope_slot_bytes(W)) : nullptr;
-    hipLaunchKernelGGL(k_lr_init, dim3(1), dim3(64), 0, s, ws);
-    HIP_TRY(hipGetLastError());
-    if (n_users) {
-        const uint32_t check_blocks = static_cast<uint32_t>(n_users / 256 + 1 > 2048 ? 2048 : n_users / 256 + 1);
-        hipLaunchKernelGGL(k_lr_check, dim3(check_blocks), dim3(256), 0, s, d_rows, d_offsets, n_users, m->num_products, max_user_rows, ws);
-        HIP_TRY(hipGetLastError());
-        lr_u64 verdict = 0;
-        HIP_TRY(hipMemcpyAsync(&verdict, ws + kLrWsErr, sizeof(verdict), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (verdict & kLrErrRows)
-            return fail(RG_EINVAL, "rg_ope_replay_logreg: a user has more than max_user_rows = %u rows (or its offsets descend); nothing was written", max_user_rows);
-        if (verdict & kLrErrFirstBandit)
-            return fail(RG_EINVAL, "rg_ope_replay_logreg: a user opens with a bandit row; nothing was written");
-        if (verdict & kLrErrIndex)
-            return fail(RG_EINVAL, "rg_ope_replay_logreg: the log has a product or an action >= num_products %u; nothing was written", m->num_products);
-    }
+    if (int rc = ope_check_log("rg_ope_replay_logreg", d_rows, d_offsets, n_users, m->num_products, max_user_rows, ws, s)) return rc;
     if (m->select_randomly)
         hipLaunchKernelGGL(k_ope_logreg<true>, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, d_rows, d_offsets, n_users, ps_mode,
                            d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W);

@@ -11,7 +11,8 @@ verify_agents_IPS, verify_agents_SNIPS, evaluate_recall_at_k, verify_agents_reca
 Simulator.device_log().  Users 0 .. max(u) - 1 are evaluated (the reference's range(max(reco_log.u)):
 the user with the largest id is not), each user's rows in frame order.  Where a HIP device is present,
 the agent has a replay form (ope_policy_of) and the log qualifies, the rows are replayed on the device
-by rg_ope_replay (the frozen LogReg policy: by rg_ope_replay_logreg, an EpsilonGreedy target: by rg_ope_replay_eg); otherwise the
+by rg_ope_replay (the frozen LogReg policy: by rg_ope_replay_logreg, an EpsilonGreedy target: by rg_ope_replay_eg, the likelihood
+agent: by rg_ope_replay_poly and the host's confirmation of its unresolved acts, ope_checked_policy_of); otherwise the
 host loop below runs:
 the reference's loop made linear (one stable group-by instead of six frame filters per user), the same
 act() calls in the same order.
@@ -26,6 +27,7 @@ device.  Every other agent takes the host route: the reference's loop over env.r
 single-process; sharding the study over ranks is out of scope.  The module itself is callable —
 `recogym_amd.evaluate_agent(env, agent, ...)` is the function, as `recogym.evaluate_agent` is in the reference."""
 import ctypes as C
+import warnings
 from copy import deepcopy
 
 import numpy as np
@@ -145,6 +147,17 @@ def ope_policy_of(agent):
     return None
 
 
+def ope_checked_policy_of(agent):
+    """-> the policy dict of an agent whose replay form needs a host step before its result stands (`ope_policy_checked()`: the
+    likelihood agent, whose device rule lists the acts it cannot resolve — ope_replay confirms them with sim.poly_replay_verify),
+    else None.  Kept apart from ope_policy_of, whose forms are exact as the device leaves them.  The dict's `logreg_poly` entry
+    holds wf, wa, wk, intercept (host arrays) and may carry two optional keys: `expit_steps` (a step table other than
+    expit_steps()) and `device_model` (sim.poly_device_model's result for the log's device: a caller that replays several logs
+    under one model keeps it there instead of moving it per call; ope_replay asserts the device)."""
+    hook = getattr(agent, 'ope_policy_checked', None)
+    return hook() if hook is not None else None
+
+
 def _draws(pol):
     if pol.get('epsilon_greedy') is not None:
         return True                            # an EpsilonGreedy target always flips its coin, keyed by the event index
@@ -249,10 +262,14 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
     the log's first `n_users` users (default: all but the last, whose id is max(u)), in log order (device tensors);
     sums = float64 tensor (n, sum c r, sum r).  None where the agent has no replay form or the log does not qualify (a user
     that opens with a bandit row; a float clock under a policy that draws).  `stats` (a dict, frozen LogReg policies only)
-    receives rg_ope_replay_logreg's workspace words: error, acts, exact (acts decided by float64 scores), rows_read.  `eg_out` (a
+    receives rg_ope_replay_logreg's workspace words: error, acts, exact (acts decided by float64 scores), rows_read; under the
+    likelihood agent rg_ope_replay_poly's: error, acts, table, lower, unresolved, overflow, rows_read.  The likelihood agent's replay
+    is None, after one RuntimeWarning, also where the host refutes an unresolved act or the device's list of them overflowed.  `eg_out` (a
     dict, EpsilonGreedy targets only) receives `greedy` (uint8) and `h0` (int32) of the same bandit rows (device tensors)."""
     import torch
-    pol = ope_policy_of(agent) if pol is None else pol
+    if pol is None:
+        pol = ope_policy_of(agent)
+        pol = ope_checked_policy_of(agent) if pol is None else pol
     if pol is None or int(pol['num_products']) != int(dl.num_products):
         return None
     n_eval = max(int(dl.offsets.numel()) - 2, 0) if n_users is None else int(n_users)
@@ -270,7 +287,17 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
     eg = pol.get('epsilon_greedy')
     if eg is not None and pol.get('kind') not in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE):
         return None
-    if pol.get('logreg') is not None:
+    poly = pol.get('logreg_poly')
+    if poly is not None:
+        # the likelihood agent: the model and the step table move to the log's device as the step loop's do (sim.poly_device_model)
+        # (`device_model`, optional: that function's result for this device, where the caller keeps the model there between calls)
+        from .sim import poly_device_model, poly_replay_verify
+        poly_host, keep = poly.get('device_model') or poly_device_model(poly, int(pol['num_products']), device)
+        assert all(t.device == device and t.dtype == torch.float64 for t in keep), 'device_model lies on another device than the log'
+        cp = _abi.RgOpePoly(num_products=int(pol['num_products']), n_steps=int(keep[3].numel()), wf=keep[0].data_ptr(),
+                            wa=keep[1].data_ptr(), wk_t=keep[2].data_ptr(), th=keep[3].data_ptr(), intercept=poly_host[3])
+        size_fn, replay_fn, what = lib.rg_ope_poly_workspace_bytes, lib.rg_ope_replay_poly, 'rg_ope_replay_poly'
+    elif pol.get('logreg') is not None:
         # the frozen LogReg policy has an entry point of its own; the model moves to the log's device once per call
         cp, keep = _logreg_model(pol['logreg'], int(pol['num_products']), device)
         size_fn, replay_fn, what = lib.rg_ope_logreg_workspace_bytes, lib.rg_ope_replay_logreg, 'rg_ope_replay_logreg'
@@ -322,6 +349,24 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
         if stats is not None and pol.get('logreg') is not None:
             words = ws[:32].view(torch.int64).cpu().numpy()
             stats.update(error=int(words[0]), acts=int(words[1]), exact=int(words[2]), rows_read=int(words[3]))
+        if poly is not None or pol.get('logreg') is not None:
+            # error bits after the validation passed: a history list overflowed — the ratios are not to be trusted
+            err = int(ws[:8].view(torch.int64).item())
+            if err:
+                raise _abi.RecoGymHipError(f'{what}: the replay reported error bits {err:#x} (a view history outgrew its list)')
+        if poly is not None:
+            words = ws[:256].view(torch.int64).cpu().numpy()
+            unresolved, overflow = int(words[4]), bool(words[5])
+            if stats is not None:
+                stats.update(error=int(words[0]), acts=int(words[1]), table=int(words[2]), lower=int(words[3]), unresolved=unresolved,
+                             overflow=overflow, rows_read=int(words[6]))
+            if unresolved:
+                # the acts the device's rule could not resolve: confirmed on the host, or the whole replay is given up (no patching)
+                listed = ws[256:256 + 12 * min(unresolved, 4096)].view(torch.int32).cpu().numpy().view(np.uint32).reshape(-1, 3)
+                if not poly_replay_verify(dl, listed, overflow, poly_host):
+                    warnings.warn('the likelihood agent\'s replay has acts the host does not confirm (or more unresolved acts than the '
+                                  'device lists): the off-policy evaluation takes the host loop', RuntimeWarning, stacklevel=2)
+                    return None
         code = dl.rows[:total, 2]
         is_b = (code & _abi.RG_EV_BANDIT) != 0
         r = _masked(ratio[:total], is_b)
@@ -352,6 +397,7 @@ def _device_or_none(agent, reco_log):
     if dl is None and not _device_present():
         return None
     pol = ope_policy_of(agent)
+    pol = ope_checked_policy_of(agent) if pol is None else pol
     if pol is None:
         return None
     if dl is None:

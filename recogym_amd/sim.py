@@ -81,6 +81,52 @@ def logreg_fp32(coef_t, intercept):
     return w32.contiguous(), b32.contiguous(), wmax.contiguous(), bmax
 
 
+def poly_device_model(logreg_poly, num_products, device):
+    """A policy dict's `logreg_poly` entry (wf (P,), wa (P,), wk (P, P) [action][product], intercept, optionally expit_steps) ->
+    ((wf, wa, wk, b) host arrays, (wf, wa, wk_t, th) float64 tensors on `device`): wk transposed to [viewed product][action] (lanes
+    over actions read a row contiguously) and the table of expit's top steps — what rg_sim_set_logreg_poly and
+    rg_ope_replay_poly take.  evaluate_agent.ope_replay accepts the result as the entry's `device_model` key."""
+    from .agents.logreg_poly import expit_steps
+    P = int(num_products)
+    wf, wa, wk = (np.ascontiguousarray(logreg_poly[k], dtype=np.float64) for k in ('wf', 'wa', 'wk'))
+    assert wf.shape == (P,) and wa.shape == (P,) and wk.shape == (P, P)
+    th = logreg_poly.get('expit_steps')
+    th = expit_steps() if th is None else np.ascontiguousarray(th, dtype=np.float64)
+    dev = tuple(torch.from_numpy(x).to(device) for x in (wf, wa, np.ascontiguousarray(wk.T), th))
+    return (wf, wa, wk, float(logreg_poly['intercept'])), dev
+
+
+def poly_host_act(views, model):
+    """The host act of the likelihood agent on the organic views `views` (product ids, any order) under model = (wf, wa, wk, b):
+    the decisions in the contract's order, scipy's expit, first maximum — what the device's unresolved acts are judged by."""
+    from scipy.special import expit
+    from .agents.logreg_poly import poly_decisions
+    prods, cnts = np.unique(np.asarray(views, dtype=np.int64), return_counts=True)
+    return int(np.argmax(expit(poly_decisions(prods, cnts, *model))))
+
+
+def poly_replay_verify(dl, acts, overflow, model):
+    """The host's confirmation of the acts rg_ope_replay_poly could not resolve (Simulator.poly_verify's counterpart for a
+    replay).  `dl`: the replayed DeviceLog; `acts`: (n, 3) array of (user index, position of the bandit row the act was computed
+    at within the user's rows, action taken); `overflow`: the list did not hold them all; `model`: (wf, wa, wk, b) on the host.
+    The history of a listed act is the user's organic rows BEFORE that position; only the listed users' rows leave the device.
+    -> True when the replay stands: every listed act confirmed, no overflow."""
+    if overflow:
+        return False
+    acts = np.asarray(acts, dtype=np.int64).reshape(-1, 3)
+    if not len(acts):
+        return True
+    users = np.unique(acts[:, 0])
+    at = torch.as_tensor(users, device=dl.offsets.device)
+    begin, end = dl.offsets[at].cpu().numpy(), dl.offsets[at + 1].cpu().numpy()
+    code = {int(u): dl.rows[int(b):int(e), 2].contiguous().cpu().numpy().view(np.uint32) for u, b, e in zip(users, begin, end)}
+    for user, pos, a in acts:
+        c = code[int(user)][:int(pos)]
+        if poly_host_act(c[(c & _abi.RG_EV_BANDIT) == 0] & _abi.RG_EV_INDEX_MASK, model) != int(a):
+            return False
+    return True
+
+
 class Simulator:
     """N concurrent users of one reco-gym-v1 environment on one GPU.
 
@@ -204,18 +250,10 @@ class Simulator:
                         self.logreg16 = self.logreg[0].to(torch.float16).contiguous()
                         _abi.check(self.lib.rg_sim_set_logreg_fp16(self._h, self.logreg16.data_ptr()), 'rg_sim_set_logreg_fp16')
             if policy == _abi.RG_POLICY_LOGREG_POLY:
-                from .agents.logreg_poly import expit_steps
-                P = int(config.num_products)
-                wf, wa, wk = (np.ascontiguousarray(logreg_poly[k], dtype=np.float64) for k in ('wf', 'wa', 'wk'))
-                assert wf.shape == (P,) and wa.shape == (P,) and wk.shape == (P, P)
-                self.logreg_poly_host = (wf, wa, wk, float(logreg_poly['intercept']))
-                th = logreg_poly.get('expit_steps')
-                th = expit_steps() if th is None else np.ascontiguousarray(th, dtype=np.float64)
-                # wk transposed, [viewed product][action]: lanes over actions read a row contiguously
-                self.logreg_poly = tuple(torch.from_numpy(x).to(self.device) for x in (wf, wa, np.ascontiguousarray(wk.T), th))
+                self.logreg_poly_host, self.logreg_poly = poly_device_model(logreg_poly, int(config.num_products), self.device)
                 _abi.check(self.lib.rg_sim_set_logreg_poly(self._h, *[t.data_ptr() for t in self.logreg_poly[:3]],
                                                            C.c_double(self.logreg_poly_host[3]), self.logreg_poly[3].data_ptr(),
-                                                           int(th.size)), 'rg_sim_set_logreg_poly')
+                                                           int(self.logreg_poly[3].numel())), 'rg_sim_set_logreg_poly')
             self.poly_unresolved = self.poly_refuted = None
             self.poly_overflow = False
             if log_capacity is None:
@@ -354,8 +392,6 @@ class Simulator:
         the arithmetic is the host act's (scipy's expit) — and keep the outcome in `poly_unresolved` (the listed acts),
         `poly_refuted` (those whose action the host does not confirm) and `poly_overflow`.  -> True when the device log stands:
         nothing refuted, no overflow of the list.  `columns`: log_columns() of this run, where the caller has them already."""
-        from .agents.logreg_poly import poly_decisions
-        from scipy.special import expit
         acts, self.poly_overflow = self.poly_unresolved_acts()
         self.poly_unresolved = acts
         self.poly_refuted = acts[:0]
@@ -369,9 +405,7 @@ class Simulator:
             t = np.arange(len(u)) - np.repeat(first, np.diff(np.r_[first, len(u)]))
             bad = []
             for user, t_act, a in acts:
-                rows = organic & (u == user) & (t <= t_act)
-                prods, cnts = np.unique(v[rows], return_counts=True)
-                if int(np.argmax(expit(poly_decisions(prods, cnts, *self.logreg_poly_host)))) != int(a):
+                if poly_host_act(v[organic & (u == user) & (t <= t_act)], self.logreg_poly_host) != int(a):
                     bad.append((user, t_act, a))
             self.poly_refuted = np.asarray(bad, dtype=np.uint32).reshape(-1, 3)
         return not self.poly_overflow and len(self.poly_refuted) == 0
