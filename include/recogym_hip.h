@@ -45,6 +45,9 @@ extern "C" {
 /* v13 (additive): RG_POLICY_LOGREG_POLY with rg_sim_set_logreg_poly, rg_sim_read_poly_unresolved and rg_sim_debug_poly_acts (the
  * likelihood agent LogregPolyAgent in the step loop), and the counters RG_CNT_POLY_TABLE / RG_CNT_POLY_UNRESOLVED. */
 /* v14 (additive): rg_ope_poly_workspace_bytes / rg_ope_replay_poly (the off-policy replay of the likelihood agent). */
+/* v14, additive since: rg_sim_set_epsilon_greedy_model (the EpsilonGreedy overlay round the frozen LogReg argmax and the likelihood
+ * agent in the step loop) and rg_ope_replay_logreg_eg / rg_ope_replay_poly_eg (the off-policy replay of such a wrapper).  New
+ * symbols only: nothing an existing caller sees has changed, and the version stays 14. */
 #define RG_ABI_VERSION 14
 
 /* error codes */
@@ -254,6 +257,16 @@ int rg_sim_set_policy_table_f64(rg_sim* sim, const int32_t* d_action, const doub
  * k_tail), as with time_mode: the user-major walk has no overlay. */
 int rg_sim_set_epsilon_greedy(rg_sim* sim, double epsilon, uint64_t eg_seed, uint32_t pure_new, const double* d_cdf,
                               double ps_explore, double one_minus_eps);
+
+/* The same overlay round a MODEL: legal only for RG_POLICY_LOGREG_FROZEN without lr_select_randomly and for RG_POLICY_LOGREG_POLY
+ * (anything else: RG_EINVAL — a sampling LogReg's act is a sampled action whose propensity is not 1, and the policies above have
+ * rg_sim_set_epsilon_greedy).  The greedy action g of an act is the model's cached act of the user's view history — classes[argmax],
+ * or the likelihood agent's action — with inner propensity 1.0: an explored act takes the table's action and ps_explore, a greedy
+ * one g and one_minus_eps * 1.0.  Every event of a run-ahead round flips its own coin, keyed by its own event index.  The act
+ * kernels, the view history and the likelihood agent's unresolved list (which lists the GREEDY act) are what they are without the
+ * overlay.  Arguments, the other checks and the call window are rg_sim_set_epsilon_greedy's. */
+int rg_sim_set_epsilon_greedy_model(rg_sim* sim, double epsilon, uint64_t eg_seed, uint32_t pure_new, const double* d_cdf,
+                                    double ps_explore, double one_minus_eps);
 
 /* The overlay's explore action on caller-supplied uniforms (stateless; the part rg_sim_debug_ouc_acts plays for
  * OrganicUserEventCounter): d_out[i] = what rng.choice(P, p = product_probas) returns for the uniform d_u1[i] in [0, 1) when the
@@ -584,6 +597,24 @@ int rg_ope_replay_eg(const rg_ope_policy* inner, const rg_ope_eg* eg, const rg_e
                      uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const,
                      double* d_ratio, uint8_t* d_click, double* d_sums, uint8_t* d_greedy, int32_t* d_h0, void* d_workspace,
                      size_t workspace_bytes, void* stream);
+
+/* The EpsilonGreedy target round a model (with_ps_all on the wrapper and the inner agent): the plain unit's replay — history, act,
+ * workspace size and head words, the likelihood agent's unresolved list, the log validation — with the wrapper's pi per bandit
+ * row: g = the model's action (shared by the bandit rows up to the next organic row), the explore coin of the row's own
+ * (eg.seed, u, t), and
+ *   explored: epsilon * (pure_new && a == g ? 0.0 : prob_explore);   greedy: (1.0 - epsilon) * (a == g ? 1.0 : 0.0).
+ * d_greedy / d_h0: the optional outputs of rg_ope_replay_eg (h0 = g).  The workspace is rg_ope_logreg_workspace_bytes' /
+ * rg_ope_poly_workspace_bytes'.  RG_EINVAL besides the plain unit's: a null eg, epsilon outside [0, 1], pure_new with fewer than 2
+ * products, and (LogReg) select_randomly != 0.  With pure_new an unresolved act of the likelihood agent that the host refutes
+ * changes pi on explored rows too: the caller gives the whole replay up, as for the plain unit. */
+int rg_ope_replay_logreg_eg(const rg_ope_logreg* model, const rg_ope_eg* eg, const rg_event* d_rows, const int64_t* d_offsets,
+                            uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const,
+                            double* d_ratio, uint8_t* d_click, double* d_sums, uint8_t* d_greedy, int32_t* d_h0,
+                            void* d_workspace, size_t workspace_bytes, void* stream);
+int rg_ope_replay_poly_eg(const rg_ope_poly* model, const rg_ope_eg* eg, const rg_event* d_rows, const int64_t* d_offsets,
+                          uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const,
+                          double* d_ratio, uint8_t* d_click, double* d_sums, uint8_t* d_greedy, int32_t* d_h0,
+                          void* d_workspace, size_t workspace_bytes, void* stream);
 
 /*
  * The count agents' training (reference agents/organic_count.py:74-82, agents/bandit_count.py:49-62 under the offline protocol

@@ -131,6 +131,7 @@ SYMBOLS = {
     'rg_sim_set_policy_table': (C.c_int, [_SIM, C.c_void_p, C.c_void_p]),
     'rg_sim_set_policy_table_f64': (C.c_int, [_SIM, C.c_void_p, C.c_void_p]),
     'rg_sim_set_epsilon_greedy': (C.c_int, [_SIM, C.c_double, C.c_uint64, C.c_uint32, C.c_void_p, C.c_double, C.c_double]),
+    'rg_sim_set_epsilon_greedy_model': (C.c_int, [_SIM, C.c_double, C.c_uint64, C.c_uint32, C.c_void_p, C.c_double, C.c_double]),
     'rg_eg_explore_actions': (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     'rg_sim_set_logreg': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     'rg_sim_set_logreg_fp32': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
@@ -180,6 +181,12 @@ SYMBOLS = {
     'rg_ope_replay_eg': (C.c_int, [C.POINTER(RgOpePolicy), C.POINTER(RgOpeEg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
                                    C.c_uint32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rg_ope_replay_logreg_eg': (C.c_int, [C.POINTER(RgOpeLogreg), C.POINTER(RgOpeEg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                          C.c_uint32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rg_ope_replay_poly_eg': (C.c_int, [C.POINTER(RgOpePoly), C.POINTER(RgOpeEg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                        C.c_uint32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'rg_count_workspace_bytes': (C.c_size_t, []),
     'rg_count_train': (C.c_int, [C.POINTER(RgCountTables), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_void_p]),

@@ -10,6 +10,14 @@ explore action through NumPy's own cumsum / searchsorted.  Over an inner agent w
 OrganicUserEventCounterAgent, the last-view tables of OrganicCount / BanditCount / BanditMFSquare) the wrapper runs inside the
 device step loop (`device_policy()`: the inner dict plus `epsilon_greedy=`), and with `with_ps_all` over a RandomAgent or a
 last-view table it has a replay form for the off-policy estimators (`ope_policy()`).
+
+Over the two model agents — the frozen LogReg argmax (LogregFrozenAgent / LogregMulticlassIpsAgent without select_randomly) and
+the likelihood agent (LogregPolyFrozenAgent / LogregPolyAgent) — the same device forms exist and are opt-in: the wrapper's
+configuration key `device_models` (read with getattr, default False; not one of `epsilon_greedy_args`, whose keys are the
+reference's).  The rows and ratios are the same bits on either route; the key chooses where they are computed.  With it,
+`device_policy()` returns the model's dict plus `epsilon_greedy=`, `ope_policy()` the LogReg argmax replay dict and
+`ope_policy_checked()` the likelihood agent's checked dict (the host confirms the acts the device cannot resolve), each plus
+`epsilon_greedy=`.
 """
 import numpy as np
 
@@ -28,6 +36,8 @@ epsilon_greedy_args = {
 
 _DEVICE_INNER = (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_ORGANIC_USER_COUNT, _abi.RG_POLICY_LAST_VIEW_TABLE)
 _REPLAY_INNER = (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE)
+# with `device_models`: the agents whose act is a model's, computed once per change of the view history (its action is greedy, ps = 1)
+_MODEL_INNER = (_abi.RG_POLICY_LOGREG_FROZEN, _abi.RG_POLICY_LOGREG_POLY)
 # what the wrapper passes on to the inner agent only where that agent has it (test_agent asks with hasattr / getattr)
 _DELEGATED = ('train_from_log', 'train_online_from_log', 'accepts_device_log', 'needs_training')
 
@@ -76,13 +86,20 @@ class EpsilonGreedy(Agent):
 
     def device_policy(self):
         """The inner agent's device policy plus `epsilon_greedy=dict(epsilon, seed, pure_new)`; None where the inner agent has no
-        device form of the three kinds the overlay serves, with epsilon_select_worse and with with_ps_all."""
+        device form of the kinds the overlay serves (the two model kinds only with `device_models`, and never a sampling
+        LogReg), with epsilon_select_worse and with with_ps_all."""
         c = self.config
         if getattr(c, 'epsilon_select_worse', False) or getattr(c, 'with_ps_all', False):
             return None
         from ..envs.reco_env_v1 import device_policy_of
         pol = device_policy_of(self.agent)
-        if pol is None or pol.get('policy') not in _DEVICE_INNER or pol.get('epsilon_greedy') is not None:
+        if pol is None or pol.get('epsilon_greedy') is not None:
+            return None
+        if pol.get('policy') in _MODEL_INNER:
+            # opt-in; a sampling LogReg's act is a sampled action with a propensity of its own: host path
+            if not getattr(c, 'device_models', False) or (pol.get('logreg') or {}).get('select_randomly'):
+                return None
+        elif pol.get('policy') not in _DEVICE_INNER:
             return None
         if self._num_products() < 2 and c.epsilon_pure_new:
             return None
@@ -91,7 +108,8 @@ class EpsilonGreedy(Agent):
 
     def ope_policy(self):
         """The replay form of `ps-a` (evaluate_agent.evaluate_IPS on the device) under with_ps_all: the inner agent's replay
-        policy — RandomAgent or a last-view table; the others' `h0` is their SAMPLED action — plus `epsilon_greedy=`."""
+        policy — RandomAgent, a last-view table or, with `device_models`, the LogReg argmax; the others' `h0` is their SAMPLED
+        action — plus `epsilon_greedy=`."""
         c = self.config
         if getattr(c, 'epsilon_select_worse', False) or not getattr(c, 'with_ps_all', False):
             return None
@@ -99,12 +117,34 @@ class EpsilonGreedy(Agent):
         if type(self.agent).__module__.split('.')[0] != __name__.split('.')[0]:
             return None                     # a reference agent object inside: its greedy action comes from its own MT stream
         pol = ope_policy_of(self.agent)
-        if pol is None or pol.get('kind') not in _REPLAY_INNER or pol.get('epsilon_greedy') is not None:
+        if pol is None or pol.get('epsilon_greedy') is not None:
+            return None
+        if pol.get('kind') == _abi.RG_POLICY_LOGREG_FROZEN:
+            # opt-in (`device_models`): the argmax form only — exact as the device leaves it (rg_ope_replay_logreg_eg)
+            if not getattr(c, 'device_models', False) or (pol.get('logreg') or {}).get('select_randomly'):
+                return None
+        elif pol.get('kind') not in _REPLAY_INNER:
             return None
         if int(pol['num_products']) < 2 and c.epsilon_pure_new:
             return None
         if pol['kind'] == _abi.RG_POLICY_RANDOM_AGENT:
             pol = dict(pol, policy_seed=self.agent.config.random_seed)      # the greedy action is the inner agent's own draw
+        return dict(pol, epsilon_greedy=self._overlay())
+
+    def ope_policy_checked(self):
+        """With `device_models` and with_ps_all on the wrapper and the inner agent: the likelihood agent's checked replay dict
+        (rg_ope_replay_poly_eg; the host confirms the greedy acts the device lists as unresolved) plus `epsilon_greedy=`."""
+        c = self.config
+        if getattr(c, 'epsilon_select_worse', False) or not getattr(c, 'with_ps_all', False) or not getattr(c, 'device_models', False):
+            return None
+        if type(self.agent).__module__.split('.')[0] != __name__.split('.')[0]:
+            return None
+        from ..evaluate_agent import ope_checked_policy_of
+        pol = ope_checked_policy_of(self.agent)
+        if pol is None or pol.get('kind') != _abi.RG_POLICY_LOGREG_POLY or pol.get('epsilon_greedy') is not None:
+            return None
+        if int(pol['num_products']) < 2 and c.epsilon_pure_new:
+            return None
         return dict(pol, epsilon_greedy=self._overlay())
 
     def act(self, observation, reward, done):

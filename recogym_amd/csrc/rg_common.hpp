@@ -307,7 +307,7 @@ struct DevSim {
     double* utime;            // [n_cap] current time of every user (index = user index)
     double* phantom_time;     // [n_cap] time of the phantom row
     double* aux_time;         // optional side array of the log: time of every raw row
-    // EpsilonGreedy overlay (rg_sim_set_epsilon_greedy; agents/epsilon_greedy.py:30-71): the lock-step kernels' EG instantiations
+    // EpsilonGreedy overlay (rg_sim_set_epsilon_greedy, rg_sim_set_epsilon_greedy_model; agents/epsilon_greedy.py:30-71): the lock-step kernels' EG instantiations
     // read these, nothing else does.  The table and the two propensity factors are the host's NumPy values.
     uint32_t eg_on, eg_pure_new;
     uint64_t eg_seed;
@@ -1188,23 +1188,39 @@ __device__ __attribute__((noinline)) uint32_t eg_explore_action(uint32_t P, bool
     return (pure_new && m >= g) ? m + 1u : m;
 }
 
+// The overlay on a greedy action g whose propensity is *ps_out: the explore coin of (eg_seed, user, t) — an explored act takes the
+// table's action and the host's eps * (1 / n), a greedy one g and the inner propensity times the host's 1 - eps.  The inner act is
+// the caller's: policy_act (policy_act_eg), or the model's cached act lr_action[user] with propensity 1.0 at the sites that take it
+// (rg_sim_set_epsilon_greedy_model: the frozen LogReg argmax and the likelihood agent).
+__device__ __forceinline__ uint32_t eg_overlay(const DevSim& d, uint32_t user, uint32_t t, uint32_t g, double* ps_out) {
+    const rg_u32x4 w = rg_draw(d.eg_seed, user, t, 0, RG_DRAW_POLICY);
+    const double eps = d.eg_eps;
+    if (!(eps / (eps + (1.0 - eps)) <= rg_uniform(w.w[0], w.w[1]))) {
+        g = eg_explore_action(d.P, d.eg_pure_new != 0u, d.eg_cdf, rg_uniform(w.w[2], w.w[3]), g);
+        *ps_out = d.eg_ps_explore;
+    } else {
+        *ps_out = d.eg_one_minus * *ps_out;
+    }
+    return g;
+}
+
 // The act of the lock-step kernels.  EG = false is policy_act and nothing else (the kernels' plain instantiations are the code they
-// were before the overlay existed); EG = true flips the explore coin of (eg_seed, user, t) on top of it: an explored act takes the
-// table's action and the host's eps * (1 / n), a greedy one the inner propensity times the host's 1 - eps.
+// were before the overlay existed); EG = true puts the overlay on top of it.
 template <bool EG>
 __device__ __forceinline__ uint32_t policy_act_eg(const DevSim& d, uint32_t slot, uint32_t user, uint32_t t, double* ps_out) {
     uint32_t a = policy_act(d, slot, user, t, ps_out);
-    if constexpr (EG) {
-        const rg_u32x4 w = rg_draw(d.eg_seed, user, t, 0, RG_DRAW_POLICY);
-        const double eps = d.eg_eps;
-        if (!(eps / (eps + (1.0 - eps)) <= rg_uniform(w.w[0], w.w[1]))) {
-            a = eg_explore_action(d.P, d.eg_pure_new != 0u, d.eg_cdf, rg_uniform(w.w[2], w.w[3]), a);
-            *ps_out = d.eg_ps_explore;
-        } else {
-            *ps_out = d.eg_one_minus * *ps_out;
-        }
-    }
+    if constexpr (EG) a = eg_overlay(d, user, t, a, ps_out);
     return a;
+}
+
+// The EG act at the sites that hold the cached model action lr_a (RG_POLICY_LOGREG_FROZEN without select_randomly — the only
+// LogReg form rg_sim_set_epsilon_greedy_model admits — the likelihood agent included): the model's action, propensity 1.0, is the
+// GREEDY one.  One overlay per site: a handle of any other policy takes policy_act for g.
+__device__ __forceinline__ uint32_t model_act_overlay(const DevSim& d, uint32_t slot, uint32_t user, uint32_t t, uint32_t lr_a, double* ps_out) {
+    uint32_t g = lr_a;
+    *ps_out = 1.0;
+    if (d.policy != RG_POLICY_LOGREG_FROZEN) g = policy_act(d, slot, user, t, ps_out);
+    return eg_overlay(d, user, t, g, ps_out);
 }
 
 // ViewsFeaturesProvider.observe (agents/abstract.py:347-358): count one organic view, keeping the

@@ -133,6 +133,34 @@ __device__ __forceinline__ bool eg_explored(uint64_t seed, double thr, uint32_t 
     return !(thr <= rg_uniform(w.w[0], w.w[1]));
 }
 
+// The EpsilonGreedy form of a model unit's replay kernel (rg_ope_logreg.hip, rg_ope_poly.hip: templates on EG).  The EG
+// instantiation takes one more kernel argument, an OpeEg — the wrapper and the two optional outputs of rg_ope_replay_eg — and the
+// plain one takes none: its code and its kernel arguments are what they were.  ope_model_pi: pi of a bandit lane whose action is
+// `a` under a model whose act is g (one-hot inner pi); the flip is the row's own, the act is shared by the rows up to the next
+// organic row.
+struct OpeEg {
+    rg_ope_eg eg;
+    uint8_t* __restrict__ greedy;
+    int32_t* __restrict__ h0;
+};
+
+__device__ __forceinline__ double ope_model_pi(const OpeRow&, uint32_t g, uint32_t a) { return g == a ? 1.0 : 0.0; }
+__device__ __forceinline__ double ope_model_pi(const OpeRow& r, uint32_t g, uint32_t a, const OpeEg& x) {
+    const double eps = x.eg.epsilon;
+    const bool explore = eg_explored(x.eg.seed, eg_threshold(eps), r.x.x, r.x.y);
+    if (x.greedy) x.greedy[r.row] = explore ? 0 : 1;
+    if (x.h0) x.h0[r.row] = static_cast<int32_t>(g);
+    return explore ? eps * ((x.eg.pure_new && a == g) ? 0.0 : x.eg.prob_explore) : (1.0 - eps) * (a == g ? 1.0 : 0.0);
+}
+
+// the wrapper's own argument checks (rg_ope_replay_eg's)
+inline int ope_eg_ok(const char* who, const rg_ope_eg* eg, uint32_t num_products) {
+    if (!eg) return fail(RG_EINVAL, "%s: null eg", who);
+    if (!(eg->epsilon >= 0.0 && eg->epsilon <= 1.0)) return fail(RG_EINVAL, "%s: epsilon %g outside [0, 1]", who, eg->epsilon);
+    if (eg->pure_new && num_products < 2u) return fail(RG_EINVAL, "%s: epsilon_pure_new needs at least 2 products", who);
+    return RG_OK;
+}
+
 // a lane's (n, sum c r, sum r) over its bandit rows, in row order
 struct OpeAcc {
     double n = 0.0, cr = 0.0, r = 0.0;

@@ -6,7 +6,8 @@
 //   pi  = act()['ps-a'][a] on that branch: explored eps * (pure_new && a == g ? 0.0 : prob_explore), greedy
 //         (1.0 - eps) * pi_inner[a] (1 / P, or the table's one-hot) — one float64 multiply of the host's constants, as the reference
 //   r   = pi / ps
-// OrganicUserEventCounter and frozen-LogReg inner policies have no form here: their `h0` is the inner policy's SAMPLED action.
+// OrganicUserEventCounter and a sampling frozen LogReg have no replay form: their `h0` is the inner policy's SAMPLED action.  The
+// LogReg argmax and the likelihood agent inside are their own units' EG instantiations (rg_ope_replay_logreg_eg, rg_ope_replay_poly_eg).
 #include "rg_ope_common.hpp"
 
 namespace {

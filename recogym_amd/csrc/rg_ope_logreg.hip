@@ -2,7 +2,8 @@
 // reference agents/logreg_ips.py:60-87) over a sorted device log: pi(a | the user's views so far) / ps for every bandit row.
 //
 // The skeleton is rg_ope_common.hpp's (one wave per user, 64-row chunks, per-wave sums and the fixed-order reduction).  What is
-// this unit's own is the state a user carries and the act:
+// this unit's own is the state a user carries and the act.  EpsilonGreedy round the argmax form (rg_ope_replay_logreg_eg) is
+// k_ope_logreg<false, true>: the same replay, classes[argmax] as the wrapper's GREEDY action, pi from ope_model_pi's EG form.
 //
 // History.  The user's views are a (product, count) list in ASCENDING PRODUCT ORDER (the float64 walk adds the terms of a class
 // in that order, as scipy's CSR x dense product does).  An organic row inserts or increments:
@@ -217,11 +218,14 @@ __global__ __launch_bounds__(256) void k_lr_check(const rg_event* __restrict__ r
     if (err) (void)__hip_atomic_fetch_or(&ws[kLrWsErr], err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <bool kSoft>
+template <bool kSoft, bool EG, typename... Eg>     // EG (argmax form only): pi is the EpsilonGreedy wrapper's round this act (rg_ope_replay_logreg_eg)
 __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
     rg_ope_logreg m, const rg_event* __restrict__ rows, const int64_t* __restrict__ offsets, uint64_t n_users, uint32_t ps_mode,
     const double* __restrict__ ps64, double ps_const, double* __restrict__ ratio, uint8_t* __restrict__ click,
-    double* __restrict__ slots, uint32_t* __restrict__ gscr, uint32_t g_cap, lr_u64* __restrict__ ws, uint32_t n_waves) {
+    double* __restrict__ slots, uint32_t* __restrict__ gscr, uint32_t g_cap, lr_u64* __restrict__ ws, uint32_t n_waves,
+    Eg... ega) {
+    static_assert(sizeof...(Eg) == (EG ? 1 : 0), "the EG instantiation takes an OpeEg, the plain one nothing");
+    static_assert(!(kSoft && EG), "the wrapper's greedy action is the argmax form's");
     __shared__ uint32_t s_p[kOpeWaves][kLrLds];
     __shared__ uint32_t s_c[kOpeWaves][kLrLds];
     const uint32_t lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
@@ -326,7 +330,7 @@ __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
                     }
                     if (mine) pi = v / esum;
                 } else if (mine) {
-                    pi = act_class == idx ? 1.0 : 0.0;
+                    pi = ope_model_pi(r, act_class, idx, ega...);
                 }
                 rem &= end < 64 ? ~ope_below(end) : 0ull;
             }
@@ -385,11 +389,13 @@ extern "C" size_t rg_ope_logreg_workspace_bytes(const rg_ope_logreg* m, uint64_t
     return lr_head_bytes() + ope_slot_bytes(W) + static_cast<size_t>(W) * 2 * lr_global_cap(max_user_rows) * sizeof(uint32_t);
 }
 
-extern "C" int rg_ope_replay_logreg(const rg_ope_logreg* m, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
-                                    uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
-                                    uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = lr_model_ok(m, "rg_ope_replay_logreg")) return rc;
-    if (int rc = ope_args_ok("rg_ope_replay_logreg", ps_mode, d_ps, n_users, d_rows, d_offsets, d_ratio, d_sums, d_workspace,
+namespace {
+
+template <bool EG>       // ega: null iff !EG
+int lr_replay(const char* who, const rg_ope_logreg* m, const OpeEg* ega, const rg_event* d_rows, const int64_t* d_offsets,
+              uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
+              uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = ope_args_ok(who, ps_mode, d_ps, n_users, d_rows, d_offsets, d_ratio, d_sums, d_workspace,
                              workspace_bytes, rg_ope_logreg_workspace_bytes(m, n_users, max_user_rows)))
         return rc;
     if (rg_device_count() <= 0) return fail(RG_ENODEV, "no HIP device");
@@ -401,20 +407,48 @@ extern "C" int rg_ope_replay_logreg(const rg_ope_logreg* m, const rg_event* d_ro
         HIP_TRY(hipStreamSynchronize(s));
         for (uint32_t c = 0; c < m->n_classes; ++c)
             if (cls[c] != static_cast<int32_t>(c))
-                return fail(RG_EINVAL, "rg_ope_replay_logreg: select_randomly needs classes[c] == c (classes[%u] = %d)", c, cls[c]);
+                return fail(RG_EINVAL, "%s: select_randomly needs classes[c] == c (classes[%u] = %d)", who, c, cls[c]);
     }
     const uint32_t W = ope_waves(n_users, kLrMaxWaves);
     const uint32_t g_cap = lr_global_cap(max_user_rows);
     lr_u64* ws = static_cast<lr_u64*>(d_workspace);
     double* slots = reinterpret_cast<double*>(static_cast<char*>(d_workspace) + lr_head_bytes());
     uint32_t* gscr = g_cap ? reinterpret_cast<uint32_t*>(static_cast<char*>(d_workspace) + lr_head_bytes() + ope_slot_bytes(W)) : nullptr;
-    if (int rc = ope_check_log("rg_ope_replay_logreg", d_rows, d_offsets, n_users, m->num_products, max_user_rows, ws, s)) return rc;
-    if (m->select_randomly)
-        hipLaunchKernelGGL(k_ope_logreg<true>, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, d_rows, d_offsets, n_users, ps_mode,
-                           d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W);
-    else
-        hipLaunchKernelGGL(k_ope_logreg<false>, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, d_rows, d_offsets, n_users, ps_mode,
-                           d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W);
+    if (int rc = ope_check_log(who, d_rows, d_offsets, n_users, m->num_products, max_user_rows, ws, s)) return rc;
+    if constexpr (!EG) {
+        if (m->select_randomly)
+            hipLaunchKernelGGL((k_ope_logreg<true, false>), dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, d_rows, d_offsets, n_users,
+                               ps_mode, d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W);
+        else
+            hipLaunchKernelGGL((k_ope_logreg<false, false>), dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, d_rows, d_offsets, n_users,
+                               ps_mode, d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W);
+    } else {
+        hipLaunchKernelGGL((k_ope_logreg<false, true, OpeEg>), dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, d_rows, d_offsets, n_users,
+                           ps_mode, d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W, *ega);
+    }
     HIP_TRY(hipGetLastError());
     return ope_reduce(slots, W, d_sums, s);
+}
+
+}  // namespace
+
+extern "C" int rg_ope_replay_logreg(const rg_ope_logreg* m, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                                    uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
+                                    uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = lr_model_ok(m, "rg_ope_replay_logreg")) return rc;
+    return lr_replay<false>("rg_ope_replay_logreg", m, nullptr, d_rows, d_offsets, n_users, max_user_rows, ps_mode, d_ps, ps_const,
+                            d_ratio, d_click, d_sums, d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int rg_ope_replay_logreg_eg(const rg_ope_logreg* m, const rg_ope_eg* eg, const rg_event* d_rows, const int64_t* d_offsets,
+                                       uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const,
+                                       double* d_ratio, uint8_t* d_click, double* d_sums, uint8_t* d_greedy, int32_t* d_h0,
+                                       void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = lr_model_ok(m, "rg_ope_replay_logreg_eg")) return rc;
+    if (m->select_randomly)
+        return fail(RG_EINVAL, "rg_ope_replay_logreg_eg: a select_randomly model samples its act: no replay form under EpsilonGreedy");
+    if (int rc = ope_eg_ok("rg_ope_replay_logreg_eg", eg, m->num_products)) return rc;
+    const OpeEg ega{*eg, d_greedy, d_h0};
+    return lr_replay<true>("rg_ope_replay_logreg_eg", m, &ega, d_rows, d_offsets, n_users, max_user_rows,
+                           ps_mode, d_ps, ps_const, d_ratio, d_click, d_sums, d_workspace, workspace_bytes, stream);
 }

@@ -21,6 +21,9 @@
 // (sim.poly_replay_verify); the ratios are written with the device's action whatever the host decides.  The order of the list
 // is not fixed (one atomic counter); ratios and sums do not depend on it.
 //
+// EpsilonGreedy round the agent (rg_ope_replay_poly_eg): k_ope_poly<true> — the same replay, the act above as the wrapper's GREEDY
+// action g, and pi from ope_model_pi's EG form (rg_ope_common.hpp).  The unresolved list holds g; workspace and head words are the same.
+//
 // W, the wave cap: 4 096 = 256 CUs x 4 blocks of 4 waves (a block holds 36 KB of LDS: 8 KB step table, 3 KB of act rows and 4 KB
 // of list per wave).  W is part of the bits of d_sums (rg_ope_common.hpp).
 #include "rg_ope_common.hpp"
@@ -40,11 +43,13 @@ uint32_t pl_global_cap(uint32_t max_user_rows) { return max_user_rows > kPlLds ?
 size_t pl_head_bytes() { return kPlWsWords * sizeof(pl_u64); }
 size_t pl_list_bytes() { return (static_cast<size_t>(kPolyListCap) * 3 * sizeof(uint32_t) + 255) & ~size_t(255); }
 
+template <bool EG, typename... Eg>       // EG: pi is the EpsilonGreedy wrapper's round this act (rg_ope_replay_poly_eg)
 __global__ __launch_bounds__(64 * kOpeWaves, 4) void k_ope_poly(
     PolyModel m, const rg_event* __restrict__ rows, const int64_t* __restrict__ offsets, uint64_t n_users, uint32_t ps_mode,
     const double* __restrict__ ps64, double ps_const, double* __restrict__ ratio, uint8_t* __restrict__ click,
     double* __restrict__ slots, uint32_t* __restrict__ gscr, uint32_t g_cap, pl_u64* __restrict__ ws, uint32_t* __restrict__ ulist,
-    uint32_t n_waves) {
+    uint32_t n_waves, Eg... ega) {
+    static_assert(sizeof...(Eg) == (EG ? 1 : 0), "the EG instantiation takes an OpeEg, the plain one nothing");
     __shared__ double s_th[kPolySteps];
     __shared__ double s_cnt[kOpeWaves][kPolyHist];
     __shared__ uint32_t s_prod[kOpeWaves][kPolyHist];
@@ -120,7 +125,7 @@ __global__ __launch_bounds__(64 * kOpeWaves, 4) void k_ope_poly(
                 // the bandit rows up to the next organic row share this act
                 const pl_u64 next_o = omask & ~ope_below(k);
                 const uint32_t end = next_o ? static_cast<uint32_t>(__builtin_ctzll(next_o)) : 64u;
-                if (isb && lane >= k && lane < end) pi = action == idx ? 1.0 : 0.0;
+                if (isb && lane >= k && lane < end) pi = ope_model_pi(r, action, idx, ega...);
                 rem &= end < 64 ? ~ope_below(end) : 0ull;
             }
             if (isb) acc.emit(log, r, pi);
@@ -154,11 +159,13 @@ extern "C" size_t rg_ope_poly_workspace_bytes(const rg_ope_poly* m, uint64_t n_u
     return pl_head_bytes() + pl_list_bytes() + ope_slot_bytes(W) + static_cast<size_t>(W) * 2 * pl_global_cap(max_user_rows) * sizeof(uint32_t);
 }
 
-extern "C" int rg_ope_replay_poly(const rg_ope_poly* m, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
-                                  uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
-                                  uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = pl_model_ok(m, "rg_ope_replay_poly")) return rc;
-    if (int rc = ope_args_ok("rg_ope_replay_poly", ps_mode, d_ps, n_users, d_rows, d_offsets, d_ratio, d_sums, d_workspace,
+namespace {
+
+template <bool EG>       // ega: null iff !EG
+int pl_replay(const char* who, const rg_ope_poly* m, const OpeEg* ega, const rg_event* d_rows, const int64_t* d_offsets,
+              uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
+              uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = ope_args_ok(who, ps_mode, d_ps, n_users, d_rows, d_offsets, d_ratio, d_sums, d_workspace,
                              workspace_bytes, rg_ope_poly_workspace_bytes(m, n_users, max_user_rows)))
         return rc;
     if (rg_device_count() <= 0) return fail(RG_ENODEV, "no HIP device");
@@ -170,10 +177,35 @@ extern "C" int rg_ope_replay_poly(const rg_ope_poly* m, const rg_event* d_rows, 
     uint32_t* ulist = reinterpret_cast<uint32_t*>(base + pl_head_bytes());
     double* slots = reinterpret_cast<double*>(base + pl_head_bytes() + pl_list_bytes());
     uint32_t* gscr = g_cap ? reinterpret_cast<uint32_t*>(base + pl_head_bytes() + pl_list_bytes() + ope_slot_bytes(W)) : nullptr;
-    if (int rc = ope_check_log("rg_ope_replay_poly", d_rows, d_offsets, n_users, m->num_products, max_user_rows, ws, s)) return rc;
+    if (int rc = ope_check_log(who, d_rows, d_offsets, n_users, m->num_products, max_user_rows, ws, s)) return rc;
     const PolyModel pm{m->num_products, m->n_steps, m->wf, m->wa, m->wk_t, m->th, m->intercept};
-    hipLaunchKernelGGL(k_ope_poly, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, pm, d_rows, d_offsets, n_users, ps_mode, d_ps,
-                       ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, ulist, W);
+    if constexpr (EG)
+        hipLaunchKernelGGL((k_ope_poly<true, OpeEg>), dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, pm, d_rows, d_offsets, n_users, ps_mode,
+                           d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, ulist, W, *ega);
+    else
+        hipLaunchKernelGGL(k_ope_poly<false>, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, pm, d_rows, d_offsets, n_users, ps_mode, d_ps,
+                           ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, ulist, W);
     HIP_TRY(hipGetLastError());
     return ope_reduce(slots, W, d_sums, s);
+}
+
+}  // namespace
+
+extern "C" int rg_ope_replay_poly(const rg_ope_poly* m, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                                  uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
+                                  uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = pl_model_ok(m, "rg_ope_replay_poly")) return rc;
+    return pl_replay<false>("rg_ope_replay_poly", m, nullptr, d_rows, d_offsets, n_users, max_user_rows, ps_mode, d_ps, ps_const,
+                            d_ratio, d_click, d_sums, d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int rg_ope_replay_poly_eg(const rg_ope_poly* m, const rg_ope_eg* eg, const rg_event* d_rows, const int64_t* d_offsets,
+                                     uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const,
+                                     double* d_ratio, uint8_t* d_click, double* d_sums, uint8_t* d_greedy, int32_t* d_h0,
+                                     void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = pl_model_ok(m, "rg_ope_replay_poly_eg")) return rc;
+    if (int rc = ope_eg_ok("rg_ope_replay_poly_eg", eg, m->num_products)) return rc;
+    const OpeEg ega{*eg, d_greedy, d_h0};
+    return pl_replay<true>("rg_ope_replay_poly_eg", m, &ega, d_rows, d_offsets, n_users, max_user_rows,
+                           ps_mode, d_ps, ps_const, d_ratio, d_click, d_sums, d_workspace, workspace_bytes, stream);
 }

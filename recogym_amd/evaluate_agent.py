@@ -12,7 +12,8 @@ Simulator.device_log().  Users 0 .. max(u) - 1 are evaluated (the reference's ra
 the user with the largest id is not), each user's rows in frame order.  Where a HIP device is present,
 the agent has a replay form (ope_policy_of) and the log qualifies, the rows are replayed on the device
 by rg_ope_replay (the frozen LogReg policy: by rg_ope_replay_logreg, an EpsilonGreedy target: by rg_ope_replay_eg, the likelihood
-agent: by rg_ope_replay_poly and the host's confirmation of its unresolved acts, ope_checked_policy_of); otherwise the
+agent: by rg_ope_replay_poly and the host's confirmation of its unresolved acts, ope_checked_policy_of; an EpsilonGreedy target
+with `device_models` round either model: by rg_ope_replay_logreg_eg / rg_ope_replay_poly_eg); otherwise the
 host loop below runs:
 the reference's loop made linear (one stable group-by instead of six frame filters per user), the same
 act() calls in the same order.
@@ -264,7 +265,8 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
     that opens with a bandit row; a float clock under a policy that draws).  `stats` (a dict, frozen LogReg policies only)
     receives rg_ope_replay_logreg's workspace words: error, acts, exact (acts decided by float64 scores), rows_read; under the
     likelihood agent rg_ope_replay_poly's: error, acts, table, lower, unresolved, overflow, rows_read.  The likelihood agent's replay
-    is None, after one RuntimeWarning, also where the host refutes an unresolved act or the device's list of them overflowed.  `eg_out` (a
+    is None, after one RuntimeWarning, also where the host refutes an unresolved act or the device's list of them overflowed (under an
+    EpsilonGreedy wrapper the listed acts are the GREEDY ones; with pure_new a wrong one changes pi on explored rows too).  `eg_out` (a
     dict, EpsilonGreedy targets only) receives `greedy` (uint8) and `h0` (int32) of the same bandit rows (device tensors)."""
     import torch
     if pol is None:
@@ -285,8 +287,14 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
     max_rows = int(lens.max().item()) if n_eval else 0
     lib = _abi.load()
     eg = pol.get('epsilon_greedy')
-    if eg is not None and pol.get('kind') not in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE):
+    if eg is not None and (pol.get('kind') not in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE, _abi.RG_POLICY_LOGREG_FROZEN,
+                                                    _abi.RG_POLICY_LOGREG_POLY) or (pol.get('logreg') or {}).get('select_randomly')):
         return None
+    if eg is not None:
+        from .agents.epsilon_greedy import explore_table
+        pure_new = bool(eg.get('pure_new', True))
+        ce = _abi.RgOpeEg(epsilon=float(eg['epsilon']), seed=int(eg['seed']) & 0xFFFFFFFFFFFFFFFF, pure_new=int(pure_new),
+                          reserved=0, prob_explore=explore_table(int(pol['num_products']), pure_new)[1])
     poly = pol.get('logreg_poly')
     if poly is not None:
         # the likelihood agent: the model and the step table move to the log's device as the step loop's do (sim.poly_device_model)
@@ -297,10 +305,14 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
         cp = _abi.RgOpePoly(num_products=int(pol['num_products']), n_steps=int(keep[3].numel()), wf=keep[0].data_ptr(),
                             wa=keep[1].data_ptr(), wk_t=keep[2].data_ptr(), th=keep[3].data_ptr(), intercept=poly_host[3])
         size_fn, replay_fn, what = lib.rg_ope_poly_workspace_bytes, lib.rg_ope_replay_poly, 'rg_ope_replay_poly'
+        if eg is not None:                     # the wrapper round the model: the plain unit's workspace, list and head words
+            replay_fn, what = lib.rg_ope_replay_poly_eg, 'rg_ope_replay_poly_eg'
     elif pol.get('logreg') is not None:
         # the frozen LogReg policy has an entry point of its own; the model moves to the log's device once per call
         cp, keep = _logreg_model(pol['logreg'], int(pol['num_products']), device)
         size_fn, replay_fn, what = lib.rg_ope_logreg_workspace_bytes, lib.rg_ope_replay_logreg, 'rg_ope_replay_logreg'
+        if eg is not None:
+            replay_fn, what = lib.rg_ope_replay_logreg_eg, 'rg_ope_replay_logreg_eg'
     else:
         o = pol.get('ouc') or {}
         table = pol.get('table')
@@ -314,11 +326,7 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
                               table=None if keep is None else keep.data_ptr())
         size_fn, replay_fn, what = lib.rg_ope_workspace_bytes, lib.rg_ope_replay, 'rg_ope_replay'
         if eg is not None:
-            from .agents.epsilon_greedy import explore_table
-            pure_new = bool(eg.get('pure_new', True))
-            ce = _abi.RgOpeEg(epsilon=float(eg['epsilon']), seed=int(eg['seed']) & 0xFFFFFFFFFFFFFFFF, pure_new=int(pure_new),
-                              reserved=0, prob_explore=explore_table(int(pol['num_products']), pure_new)[1])
-            size_fn, what = lib.rg_ope_eg_workspace_bytes, 'rg_ope_replay_eg'
+            size_fn, replay_fn, what = lib.rg_ope_eg_workspace_bytes, lib.rg_ope_replay_eg, 'rg_ope_replay_eg'
     with torch.cuda.device(device):
         need = size_fn(C.byref(cp), n_eval, max_rows)
         if need == 0:
@@ -339,10 +347,10 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
             want = eg_out is not None
             greedy = torch.zeros(max(total, 1), dtype=torch.uint8, device=device) if want else None
             h0 = torch.zeros(max(total, 1), dtype=torch.int32, device=device) if want else None
-            _abi.check(lib.rg_ope_replay_eg(C.byref(cp), C.byref(ce), dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows,
-                                            mode, ps_ptr, ps_const, ratio.data_ptr(), None, sums.data_ptr(),
-                                            greedy.data_ptr() if want else None, h0.data_ptr() if want else None,
-                                            ws.data_ptr(), need, stream), what)
+            _abi.check(replay_fn(C.byref(cp), C.byref(ce), dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows,
+                                 mode, ps_ptr, ps_const, ratio.data_ptr(), None, sums.data_ptr(),
+                                 greedy.data_ptr() if want else None, h0.data_ptr() if want else None,
+                                 ws.data_ptr(), need, stream), what)
         else:
             _abi.check(replay_fn(C.byref(cp), dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows, mode, ps_ptr,
                                  ps_const, ratio.data_ptr(), None, sums.data_ptr(), ws.data_ptr(), need, stream), what)
@@ -383,6 +391,7 @@ def epsilon_greedy_branches(agent, reco_log):
     addressed draws.  All users of the log are covered.  None where the agent has no replay form or the log does not qualify."""
     dl = _as_device_log(reco_log)
     pol = ope_policy_of(agent)
+    pol = ope_checked_policy_of(agent) if pol is None else pol      # (second, in ope_replay's order)
     if dl is None or pol is None or pol.get('epsilon_greedy') is None:
         return None
     out = {}

@@ -139,7 +139,8 @@ class Simulator:
                  the reference's `ps` column); default: on for the policies whose ps is not a constant
     p_click      also keep the click probability of every bandit row (parity checks)
     epsilon_greedy  dict(epsilon, seed, pure_new): the EpsilonGreedy overlay over `policy` (agents/epsilon_greedy.py;
-                 rg_sim_set_epsilon_greedy) — the explore table and both propensity factors are NumPy's, built here
+                 rg_sim_set_epsilon_greedy, or rg_sim_set_epsilon_greedy_model where the policy is the frozen LogReg argmax or
+                 the likelihood agent) — the explore table and both propensity factors are NumPy's, built here
     logreg_poly  dict(wf (P,), wa (P,), wk (P, P) [action][product], intercept): the likelihood agent's fitted model
                  (RG_POLICY_LOGREG_POLY; agents/logreg_poly.py) — the table of expit's top steps is built and uploaded here.
                  After a run, `poly_verify(columns)` recomputes the acts the device could not resolve on the host.
@@ -192,9 +193,11 @@ class Simulator:
                     raise _abi.RecoGymHipError('rg_sim_set_epsilon_greedy: RG_EINVAL: epsilon_pure_new needs at least 2 products')
                 cdf, prob = explore_table(config.num_products, pure_new)
                 self.eg_cdf = torch.from_numpy(cdf).to(self.device)
-                _abi.check(self.lib.rg_sim_set_epsilon_greedy(self._h, eps, int(epsilon_greedy['seed']) & 0xFFFFFFFFFFFFFFFF,
-                                                              int(pure_new), self.eg_cdf.data_ptr(), eps * prob, 1.0 - eps),
-                           'rg_sim_set_epsilon_greedy')
+                # (a model inside — its cached act is the greedy action — has an entry point of its own)
+                model = policy in (_abi.RG_POLICY_LOGREG_FROZEN, _abi.RG_POLICY_LOGREG_POLY)
+                what = 'rg_sim_set_epsilon_greedy_model' if model else 'rg_sim_set_epsilon_greedy'
+                _abi.check(getattr(self.lib, what)(self._h, eps, int(epsilon_greedy['seed']) & 0xFFFFFFFFFFFFFFFF,
+                                                   int(pure_new), self.eg_cdf.data_ptr(), eps * prob, 1.0 - eps), what)
             if env0 is not None:
                 p = np.ascontiguousarray(env0['click_probs'], dtype=np.float64)
                 qn, px1 = np.empty_like(p), np.empty_like(p)
