@@ -103,6 +103,16 @@ class RgOpeEg(C.Structure):
                 ('prob_explore', C.c_double)]
 
 
+# What a history-keeping replay unit leaves in its workspace (include/recogym_hip.h, the prose of rg_ope_replay_logreg and of
+# rg_ope_replay_poly, near lines 530-533 and 560-566): a head of OPE_HEAD_BYTES whose first int64 words are named here, in word order, per
+# unit; after the likelihood agent's head its unresolved acts, up to OPE_POLY_LIST_CAP entries of three uint32 (user index, position of
+# the bandit row within the user's rows, action taken).
+OPE_HEAD_BYTES = 256
+OPE_HEADS = {'logreg': ('error', 'acts', 'exact', 'rows_read'),
+             'poly': ('error', 'acts', 'table', 'lower', 'unresolved', 'overflow', 'rows_read')}
+OPE_POLY_LIST_CAP = 4096
+OPE_POLY_LIST_ENTRY_BYTES = 12
+
 RG_COUNT_ORGANIC, RG_COUNT_BANDIT = 0, 1
 
 

@@ -1,4 +1,4 @@
-// rg_common.hpp — librecogym_hip.so: the reco-gym-v1 step loop as batched CDNA4 (gfx950) kernels (shared part of its fifteen units).
+// rg_common.hpp — librecogym_hip.so: the reco-gym-v1 step loop as batched CDNA4 (gfx950) kernels (shared part of its sixteen units).
 //
 // What runs here (reference file:line each kernel takes over; see DESIGN.md for the data layout
 // and the roofline of each kernel):
@@ -49,14 +49,14 @@
 #include "../../include/recogym_hip.h"
 #include "../../include/recogym_rng.h"
 
-// Translation units.  The library is built from fifteen units, one per kernel family — rg_host.hip (host code, the C ABI, small
+// Translation units.  The library is built from sixteen units, one per kernel family — rg_host.hip (host code, the C ABI, small
 // kernels), rg_exact.hip (float64 resolve), rg_draw_fp32.hip (fp32 / lean 16-bit sweeps), rg_draw_pipelined.hip (the pipelined sweep
 // + per-user cache kernels), rg_draw_wide.hip (wide-K sweep), rg_advance.hip (advance / tail / frozen LogReg), rg_walk.hip (the
 // user-major walk), rg_draw_exacthi.hip and rg_draw_lds.hip (the error-free and the tile-prefix sweeps), rg_ope.hip,
-// rg_ope_logreg.hip and rg_ope_eg.hip (off-policy replays), rg_count.hip (count agents' training), rg_evolve.hip (the exploration study), rg_logreg_poly.hip (the likelihood agent's act) — compiled in parallel and
+// rg_ope_logreg.hip, rg_ope_eg.hip and rg_ope_poly.hip (off-policy replays), rg_count.hip (count agents' training), rg_evolve.hip (the exploration study), rg_logreg_poly.hip (the likelihood agent's act) — compiled in parallel and
 // linked by __graft_entry__.build(); recogym_hip.hip includes all of them (a one-unit build).  This header holds what they
 // share: types, the workspace layout, device helpers (namespace rgk, identical in every unit); a unit hands its kernels to the
-// host code through the *_kernel_for functions declared here.  rg_ope_common.hpp adds what the three replay units share.
+// host code through the *_kernel_for functions declared here.  rg_ope_common.hpp adds what the four replay units share.
 #pragma once
 
 // RG_WALK_PRECISE_CHUNK = 1 (default): the walk behind k_sweep_xh recomputes a draw's chunk as a float64 dot (one budget delta for
@@ -773,6 +773,17 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ uint32_t prefix_in_mask(unsigned long long mask) {
     return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32),
                                      __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
+}
+
+// wave-wide row walks (the replay units, the count agents' reductions): the mask of the lanes below `lane`, the highest set bit of a
+// non-zero mask, x of lane `lane` (wave-uniform) and x of the first active lane — a value that is the same in every lane, as a scalar
+__device__ __forceinline__ unsigned long long lanes_below(uint32_t lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }
+__device__ __forceinline__ uint32_t top_bit(unsigned long long m) { return 63u - static_cast<uint32_t>(__clzll(static_cast<long long>(m))); }
+__device__ __forceinline__ uint32_t lane_value(uint32_t x, uint32_t lane) {
+    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), static_cast<int>(lane)));
+}
+__device__ __forceinline__ uint32_t wave_uniform(uint32_t x) {
+    return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(x)));
 }
 
 // a 64-bit value of the wave's first active lane, as a scalar (the builtin returns a SIGNED int: OR-ing its low word into a 64-bit

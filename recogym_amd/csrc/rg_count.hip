@@ -37,7 +37,7 @@ __device__ uint32_t cnt_lookback(const rg_event* __restrict__ rows, int64_t pos,
         if (!found) {
             if (!bm) continue;
             found = true;
-            om &= below(top_bit(bm));
+            om &= lanes_below(top_bit(bm));
         }
         if (om) return lane_value(code, top_bit(om)) & RG_EV_INDEX_MASK;
     }
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(64 * kCntWaves) void k_count_train(rg_count_tables 
                     const u64 next = (m == 0 && !longs) ? (rem & omask) : rem;
                     if (!next) break;
                     const uint32_t k = static_cast<uint32_t>(__builtin_ctzll(next));
-                    rem &= ~below(k) & ~(1ull << k);
+                    rem &= ~lanes_below(k) & ~(1ull << k);
                     if ((omask >> k) & 1) {
                         if (m == 0 && !longs) sess_start = base + k;
                         if (!longs) {
@@ -157,9 +157,9 @@ __global__ __launch_bounds__(64 * kCntWaves) void k_count_train(rg_count_tables 
                     have_in = true;
                 }
                 // ix = last_product_viewed after the previous bandit row: the last organic view in front of that row
-                const u64 pb = bmask & below(lane);
+                const u64 pb = bmask & lanes_below(lane);
                 const uint32_t r1 = pb ? top_bit(pb) : 0u;
-                const u64 po = pb ? (omask & below(r1)) : 0ull;
+                const u64 po = pb ? (omask & lanes_below(r1)) : 0ull;
                 const uint32_t from = static_cast<uint32_t>(__shfl(static_cast<int>(idx), static_cast<int>(po ? top_bit(po) : 0u)));
                 const uint32_t ix = pb ? (po ? from : lastv) : aprev;
                 if (isb) {
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(64 * kCntWaves) void k_count_train(rg_count_tables 
                 }
                 n_upd += static_cast<u64>(__popcll(bmask)) + static_cast<u64>(__popcll(__ballot(isb && (x.z & RG_EV_CLICK))));
                 const uint32_t rl = top_bit(bmask);
-                const u64 pl = omask & below(rl);
+                const u64 pl = omask & lanes_below(rl);
                 aprev = pl ? lane_value(idx, top_bit(pl)) : lastv;
             }
             if (omask) lastv = lane_value(idx, top_bit(omask));

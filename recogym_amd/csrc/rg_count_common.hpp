@@ -1,6 +1,6 @@
 // rg_count_common.hpp — what the count agents' reductions share (rg_count.hip: the offline protocol over a whole log;
 // rg_evolve.hip: the filtered, online protocol of the evolution study): the per-block LDS table of 64-bit sums in front of the
-// global tables, the wave helpers of the session list, and the argument check of an rg_count_tables.
+// global tables and the argument check of an rg_count_tables (the wave helpers of the session list: rg_common.hpp).
 #pragma once
 
 #include "rg_common.hpp"
@@ -50,12 +50,6 @@ __device__ __forceinline__ void cnt_add(CntCtx& c, uint32_t tab, u64* base, u64 
         s = (s + 1) & (kCntHashSlots - 1);
     }
     cnt_global(c, base, cell, val);
-}
-
-__device__ __forceinline__ u64 below(uint32_t lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }
-__device__ __forceinline__ uint32_t top_bit(u64 m) { return 63u - static_cast<uint32_t>(__clzll(static_cast<long long>(m))); }
-__device__ __forceinline__ uint32_t lane_value(uint32_t x, uint32_t lane) {
-    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), static_cast<int>(lane)));
 }
 
 inline int count_tables_ok(const rg_count_tables* t, const char* who) {

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(64) void k_online_tile_scan(int32_t* __restrict__ t
         const uint32_t i = base + lane;
         const int32_t v = i < n_tiles ? tile[i] : -1;
         const u64 m = __ballot(v >= 0);
-        const u64 prior = m & below(lane);
+        const u64 prior = m & lanes_below(lane);
         const int32_t from = __shfl(v, static_cast<int>(prior ? top_bit(prior) : 0u));
         if (i < n_tiles) tile[i] = prior ? from : run;
         if (m) run = static_cast<int32_t>(lane_value(static_cast<uint32_t>(v), top_bit(m)));
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(64 * kCntWaves) void k_online_train(rg_count_tables
                     const u64 next = (m == 0 && !longs) ? (rem & omask) : rem;
                     if (!next) break;
                     const uint32_t k = static_cast<uint32_t>(__builtin_ctzll(next));
-                    rem &= ~below(k) & ~(1ull << k);
+                    rem &= ~lanes_below(k) & ~(1ull << k);
                     if ((omask >> k) & 1) {
                         if (m == 0 && !longs) sess_start = base + k;
                         if (!longs) {
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(64 * kCntWaves) void k_online_train(rg_count_tables
                 const uint32_t pcode = lane ? up : prev_code;
                 // counted rows with a non-empty session: last_product_viewed moves to the view directly in front of them
                 const u64 svm = __ballot(counted && !(pcode & RG_EV_BANDIT));
-                const u64 prior = svm & below(lane);
+                const u64 prior = svm & lanes_below(lane);
                 const uint32_t from = static_cast<uint32_t>(__shfl(static_cast<int>(pcode), static_cast<int>(prior ? top_bit(prior) : 0u)));
                 const uint32_t ix = prior ? (from & RG_EV_INDEX_MASK) : cur;
                 if (counted) {

@@ -238,16 +238,15 @@ extern "C" int rg_ope_replay(const rg_ope_policy* pol, const rg_event* d_rows, c
         return fail(RG_EINVAL, "rg_ope_replay: policy kind %u has no replay form", pol->kind);
     if (pol->num_products == 0 || pol->num_products > RG_EV_INDEX_MASK) return fail(RG_EINVAL, "rg_ope_replay: bad num_products");
     if (pol->kind == RG_POLICY_LAST_VIEW_TABLE && !pol->table) return fail(RG_EINVAL, "rg_ope_replay: null table");
-    if (int rc = ope_args_ok("rg_ope_replay", ps_mode, d_ps, n_users, d_rows, d_offsets, d_ratio, d_sums, d_workspace, workspace_bytes,
-                             rg_ope_workspace_bytes(pol, n_users, max_user_rows)))
-        return rc;
+    const OpeCall c{d_rows, d_offsets, n_users, max_user_rows, ps_mode, d_ps, ps_const, d_ratio, d_click, d_sums, d_workspace, workspace_bytes,
+                    static_cast<hipStream_t>(stream)};
+    if (int rc = ope_args_ok("rg_ope_replay", c, rg_ope_workspace_bytes(pol, n_users, max_user_rows))) return rc;
     const uint32_t W = ope_waves(n_users, kOpeMaxWaves);
     const uint32_t l = ope_global_log2(pol, max_user_rows);
-    double* slots = static_cast<double*>(d_workspace);
-    uint32_t* gtab = l ? reinterpret_cast<uint32_t*>(static_cast<char*>(d_workspace) + ope_slot_bytes(W)) : nullptr;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(k_ope_replay, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *pol, d_rows, d_offsets, n_users, ps_mode,
-                       d_ps, ps_const, d_ratio, d_click, slots, gtab, l, W);
+    double* slots = c.at<double>(0);
+    uint32_t* gtab = l ? c.at<uint32_t>(ope_slot_bytes(W)) : nullptr;
+    hipLaunchKernelGGL(k_ope_replay, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, c.stream, *pol, c.d_rows, c.d_offsets, c.n_users, c.ps_mode,
+                       c.d_ps, c.ps_const, c.d_ratio, c.d_click, slots, gtab, l, W);
     HIP_TRY(hipGetLastError());
-    return ope_reduce(slots, W, d_sums, s);
+    return ope_reduce(slots, W, c.d_sums, c.stream);
 }

@@ -72,14 +72,6 @@ __device__ __forceinline__ uint32_t ope_last_view(const OpeRow& r, uint32_t lane
 // ---- what the units that keep a sorted (product, count) history per wave share (rg_ope_logreg.hip, rg_ope_poly.hip) ----
 constexpr uint32_t kOpeNone = 0xFFFFFFFFu;
 
-__device__ __forceinline__ unsigned long long ope_below(uint32_t lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }
-__device__ __forceinline__ uint32_t ope_lane_value(uint32_t x, uint32_t lane) {
-    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(x), static_cast<int>(lane)));
-}
-__device__ __forceinline__ uint32_t ope_uniform(uint32_t x) {
-    return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(x)));
-}
-
 // what one lane wrote to a list is read by the others: LDS within the workgroup's scope; the global list through the agent's
 // (the wave's own stores complete and its L1 lines are dropped before the next read)
 template <bool kLds>
@@ -153,7 +145,7 @@ __device__ __forceinline__ double ope_model_pi(const OpeRow& r, uint32_t g, uint
     return explore ? eps * ((x.eg.pure_new && a == g) ? 0.0 : x.eg.prob_explore) : (1.0 - eps) * (a == g ? 1.0 : 0.0);
 }
 
-// the wrapper's own argument checks (rg_ope_replay_eg's)
+// the wrapper's own argument checks (the three EpsilonGreedy entry points')
 inline int ope_eg_ok(const char* who, const rg_ope_eg* eg, uint32_t num_products) {
     if (!eg) return fail(RG_EINVAL, "%s: null eg", who);
     if (!(eg->epsilon >= 0.0 && eg->epsilon <= 1.0)) return fail(RG_EINVAL, "%s: epsilon %g outside [0, 1]", who, eg->epsilon);
@@ -191,22 +183,42 @@ struct OpeAcc {
 // the per-wave slots -> d_sums = (n, sum c r, sum r): k_ope_reduce, one block, fixed order (rg_ope.hip)
 int ope_reduce(const double* slots, uint32_t n_waves, double* d_sums, hipStream_t stream);
 
+// What every replay entry point receives besides its policy or model — the log, the ps source, the outputs and the workspace — packed
+// once by the extern "C" function and handed on whole.  Host side only: a kernel takes the pointers as loose __restrict__ arguments
+// (a member of a by-value struct would lose the qualifier).
+struct OpeCall {
+    const rg_event* d_rows;
+    const int64_t* d_offsets;
+    uint64_t n_users;
+    uint32_t max_user_rows;
+    uint32_t ps_mode;
+    const double* d_ps;
+    double ps_const;
+    double* d_ratio;
+    uint8_t* d_click;
+    double* d_sums;
+    void* d_workspace;
+    size_t workspace_bytes;
+    hipStream_t stream;
+
+    // the workspace from byte `first` on
+    template <typename T>
+    T* at(size_t first) const { return reinterpret_cast<T*>(static_cast<char*>(d_workspace) + first); }
+};
+
+// the argument checks every replay entry point makes after those of its own policy; `need` = its workspace bytes
+inline int ope_args_ok(const char* who, const OpeCall& c, size_t need) {
+    if (c.ps_mode > RG_OPE_PS_ROW || (c.ps_mode == RG_OPE_PS_ARRAY && !c.d_ps && c.n_users)) return fail(RG_EINVAL, "%s: bad ps source", who);
+    if (c.n_users && (!c.d_rows || !c.d_offsets || !c.d_ratio)) return fail(RG_EINVAL, "%s: null rows / offsets / ratio", who);
+    if (!c.d_sums || !c.d_workspace) return fail(RG_EINVAL, "%s: null sums / workspace", who);
+    if (c.workspace_bytes < need) return fail(RG_ENOMEM, "%s: workspace %zu < %zu bytes", who, c.workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(c.d_rows) % 16) return fail(RG_EINVAL, "%s: rows not 16-byte aligned", who);
+    return RG_OK;
+}
+
 // a history-keeping unit's validation (rg_ope_logreg.hip): zeroes the 32 int64 head words of `ws` (word 0: error bits), then
 // refuses a user that opens with a bandit row or has more than max_user_rows rows and a product or an action >= P, before
 // anything is written.  Synchronises the stream once (the verdict).
-int ope_check_log(const char* who, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users, uint32_t P,
-                  uint32_t max_user_rows, unsigned long long* ws, hipStream_t stream);
-
-// the argument checks every replay entry point makes after those of its own policy; `need` = its workspace bytes
-inline int ope_args_ok(const char* who, uint32_t ps_mode, const double* d_ps, uint64_t n_users, const rg_event* d_rows,
-                       const int64_t* d_offsets, const double* d_ratio, const double* d_sums, const void* d_workspace,
-                       size_t workspace_bytes, size_t need) {
-    if (ps_mode > RG_OPE_PS_ROW || (ps_mode == RG_OPE_PS_ARRAY && !d_ps && n_users)) return fail(RG_EINVAL, "%s: bad ps source", who);
-    if (n_users && (!d_rows || !d_offsets || !d_ratio)) return fail(RG_EINVAL, "%s: null rows / offsets / ratio", who);
-    if (!d_sums || !d_workspace) return fail(RG_EINVAL, "%s: null sums / workspace", who);
-    if (workspace_bytes < need) return fail(RG_ENOMEM, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(d_rows) % 16) return fail(RG_EINVAL, "%s: rows not 16-byte aligned", who);
-    return RG_OK;
-}
+int ope_check_log(const char* who, const OpeCall& c, uint32_t P, unsigned long long* ws);
 
 }  // namespace rgk

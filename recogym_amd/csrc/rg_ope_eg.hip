@@ -69,21 +69,19 @@ extern "C" int rg_ope_replay_eg(const rg_ope_policy* inner, const rg_ope_eg* eg,
                                 uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const,
                                 double* d_ratio, uint8_t* d_click, double* d_sums, uint8_t* d_greedy, int32_t* d_h0,
                                 void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!inner || !eg) return fail(RG_EINVAL, "rg_ope_replay_eg: null policy");
+    if (!inner) return fail(RG_EINVAL, "rg_ope_replay_eg: null policy");
     if (inner->kind != RG_POLICY_RANDOM_AGENT && inner->kind != RG_POLICY_LAST_VIEW_TABLE)
         return fail(RG_EINVAL, "rg_ope_replay_eg: inner policy kind %u has no replay form under EpsilonGreedy", inner->kind);
     if (inner->num_products == 0 || inner->num_products > RG_EV_INDEX_MASK) return fail(RG_EINVAL, "rg_ope_replay_eg: bad num_products");
     if (inner->kind == RG_POLICY_LAST_VIEW_TABLE && !inner->table) return fail(RG_EINVAL, "rg_ope_replay_eg: null table");
-    if (!(eg->epsilon >= 0.0 && eg->epsilon <= 1.0)) return fail(RG_EINVAL, "rg_ope_replay_eg: epsilon %g outside [0, 1]", eg->epsilon);
-    if (eg->pure_new && inner->num_products < 2u) return fail(RG_EINVAL, "rg_ope_replay_eg: epsilon_pure_new needs at least 2 products");
-    if (int rc = ope_args_ok("rg_ope_replay_eg", ps_mode, d_ps, n_users, d_rows, d_offsets, d_ratio, d_sums, d_workspace, workspace_bytes,
-                             rg_ope_eg_workspace_bytes(inner, n_users, max_user_rows)))
-        return rc;
+    if (int rc = ope_eg_ok("rg_ope_replay_eg", eg, inner->num_products)) return rc;
+    const OpeCall c{d_rows, d_offsets, n_users, max_user_rows, ps_mode, d_ps, ps_const, d_ratio, d_click, d_sums, d_workspace, workspace_bytes,
+                    static_cast<hipStream_t>(stream)};
+    if (int rc = ope_args_ok("rg_ope_replay_eg", c, rg_ope_eg_workspace_bytes(inner, n_users, max_user_rows))) return rc;
     const uint32_t W = ope_waves(n_users, kEgMaxWaves);
-    double* slots = static_cast<double*>(d_workspace);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(k_ope_eg_replay, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *inner, *eg, d_rows, d_offsets, n_users, ps_mode,
-                       d_ps, ps_const, d_ratio, d_click, d_greedy, d_h0, slots, W);
+    double* slots = c.at<double>(0);
+    hipLaunchKernelGGL(k_ope_eg_replay, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, c.stream, *inner, *eg, c.d_rows, c.d_offsets, c.n_users,
+                       c.ps_mode, c.d_ps, c.ps_const, c.d_ratio, c.d_click, d_greedy, d_h0, slots, W);
     HIP_TRY(hipGetLastError());
-    return ope_reduce(slots, W, d_sums, s);
+    return ope_reduce(slots, W, c.d_sums, c.stream);
 }

@@ -57,8 +57,8 @@ struct LrHist {
     const uint32_t* lp;
     const uint32_t* lc;
     __device__ __forceinline__ void get(uint32_t i, uint32_t& p, uint32_t& c) const {
-        if (T == 0) { p = ope_lane_value(hp, i); c = ope_lane_value(hc, i); }
-        else { p = ope_uniform(lp[i]); c = ope_uniform(lc[i]); }
+        if (T == 0) { p = lane_value(hp, i); c = lane_value(hc, i); }
+        else { p = wave_uniform(lp[i]); c = wave_uniform(lc[i]); }
     }
 };
 
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
             while (rem) {
                 const uint32_t k = static_cast<uint32_t>(__builtin_ctzll(rem));
                 if ((omask >> k) & 1) {
-                    const uint32_t p = ope_lane_value(idx, k);
+                    const uint32_t p = lane_value(idx, k);
                     bool done = false;
                     if (tier == 0) {
                         const lr_u64 hit = __ballot(lane < n && hp == p);
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
                     dirty = false;
                 }
                 // the bandit rows up to the next organic row share this act
-                const lr_u64 next_o = omask & ~ope_below(k);
+                const lr_u64 next_o = omask & ~lanes_below(k);
                 const uint32_t end = next_o ? static_cast<uint32_t>(__builtin_ctzll(next_o)) : 64u;
                 const bool mine = isb && lane >= k && lane < end;
                 if (kSoft) {
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
                 } else if (mine) {
                     pi = ope_model_pi(r, act_class, idx, ega...);
                 }
-                rem &= end < 64 ? ~ope_below(end) : 0ull;
+                rem &= end < 64 ? ~lanes_below(end) : 0ull;
             }
             if (isb) acc.emit(log, r, pi);
         }
@@ -364,19 +364,19 @@ int lr_model_ok(const rg_ope_logreg* m, const char* who) {
 }  // namespace
 
 // the head of a history-keeping unit's workspace zeroed (32 words) and the log validated, before anything is written (rg_ope_common.hpp)
-int rgk::ope_check_log(const char* who, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users, uint32_t P,
-                       uint32_t max_user_rows, unsigned long long* ws, hipStream_t s) {
+int rgk::ope_check_log(const char* who, const OpeCall& c, uint32_t P, unsigned long long* ws) {
+    const hipStream_t s = c.stream;
     hipLaunchKernelGGL(k_lr_init, dim3(1), dim3(64), 0, s, ws);
     HIP_TRY(hipGetLastError());
-    if (!n_users) return RG_OK;
-    const uint32_t check_blocks = static_cast<uint32_t>(n_users / 256 + 1 > 2048 ? 2048 : n_users / 256 + 1);
-    hipLaunchKernelGGL(k_lr_check, dim3(check_blocks), dim3(256), 0, s, d_rows, d_offsets, n_users, P, max_user_rows, ws);
+    if (!c.n_users) return RG_OK;
+    const uint32_t check_blocks = static_cast<uint32_t>(c.n_users / 256 + 1 > 2048 ? 2048 : c.n_users / 256 + 1);
+    hipLaunchKernelGGL(k_lr_check, dim3(check_blocks), dim3(256), 0, s, c.d_rows, c.d_offsets, c.n_users, P, c.max_user_rows, ws);
     HIP_TRY(hipGetLastError());
     lr_u64 verdict = 0;
     HIP_TRY(hipMemcpyAsync(&verdict, ws + kLrWsErr, sizeof(verdict), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (verdict & kLrErrRows)
-        return fail(RG_EINVAL, "%s: a user has more than max_user_rows = %u rows (or its offsets descend); nothing was written", who, max_user_rows);
+        return fail(RG_EINVAL, "%s: a user has more than max_user_rows = %u rows (or its offsets descend); nothing was written", who, c.max_user_rows);
     if (verdict & kLrErrFirstBandit) return fail(RG_EINVAL, "%s: a user opens with a bandit row; nothing was written", who);
     if (verdict & kLrErrIndex)
         return fail(RG_EINVAL, "%s: the log has a product or an action >= num_products %u; nothing was written", who, P);
@@ -392,42 +392,35 @@ extern "C" size_t rg_ope_logreg_workspace_bytes(const rg_ope_logreg* m, uint64_t
 namespace {
 
 template <bool EG>       // ega: null iff !EG
-int lr_replay(const char* who, const rg_ope_logreg* m, const OpeEg* ega, const rg_event* d_rows, const int64_t* d_offsets,
-              uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
-              uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = ope_args_ok(who, ps_mode, d_ps, n_users, d_rows, d_offsets, d_ratio, d_sums, d_workspace,
-                             workspace_bytes, rg_ope_logreg_workspace_bytes(m, n_users, max_user_rows)))
-        return rc;
+int lr_replay(const char* who, const rg_ope_logreg* m, const OpeEg* ega, const OpeCall& c) {
+    if (int rc = ope_args_ok(who, c, rg_ope_logreg_workspace_bytes(m, c.n_users, c.max_user_rows))) return rc;
     if (rg_device_count() <= 0) return fail(RG_ENODEV, "no HIP device");
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    const hipStream_t s = c.stream;
     if (m->select_randomly) {
         static_assert(kLrSoftMax <= 1024, "the class check reads them into a stack array");
         int32_t cls[kLrSoftMax];
         HIP_TRY(hipMemcpyAsync(cls, m->classes, m->n_classes * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        for (uint32_t c = 0; c < m->n_classes; ++c)
-            if (cls[c] != static_cast<int32_t>(c))
-                return fail(RG_EINVAL, "%s: select_randomly needs classes[c] == c (classes[%u] = %d)", who, c, cls[c]);
+        for (uint32_t k = 0; k < m->n_classes; ++k)
+            if (cls[k] != static_cast<int32_t>(k))
+                return fail(RG_EINVAL, "%s: select_randomly needs classes[c] == c (classes[%u] = %d)", who, k, cls[k]);
     }
-    const uint32_t W = ope_waves(n_users, kLrMaxWaves);
-    const uint32_t g_cap = lr_global_cap(max_user_rows);
-    lr_u64* ws = static_cast<lr_u64*>(d_workspace);
-    double* slots = reinterpret_cast<double*>(static_cast<char*>(d_workspace) + lr_head_bytes());
-    uint32_t* gscr = g_cap ? reinterpret_cast<uint32_t*>(static_cast<char*>(d_workspace) + lr_head_bytes() + ope_slot_bytes(W)) : nullptr;
-    if (int rc = ope_check_log(who, d_rows, d_offsets, n_users, m->num_products, max_user_rows, ws, s)) return rc;
-    if constexpr (!EG) {
-        if (m->select_randomly)
-            hipLaunchKernelGGL((k_ope_logreg<true, false>), dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, d_rows, d_offsets, n_users,
-                               ps_mode, d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W);
-        else
-            hipLaunchKernelGGL((k_ope_logreg<false, false>), dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, d_rows, d_offsets, n_users,
-                               ps_mode, d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W);
-    } else {
-        hipLaunchKernelGGL((k_ope_logreg<false, true, OpeEg>), dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, d_rows, d_offsets, n_users,
-                           ps_mode, d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, W, *ega);
-    }
+    const uint32_t W = ope_waves(c.n_users, kLrMaxWaves);
+    const uint32_t g_cap = lr_global_cap(c.max_user_rows);
+    lr_u64* ws = c.at<lr_u64>(0);
+    double* slots = c.at<double>(lr_head_bytes());
+    uint32_t* gscr = g_cap ? c.at<uint32_t>(lr_head_bytes() + ope_slot_bytes(W)) : nullptr;
+    if (int rc = ope_check_log(who, c, m->num_products, ws)) return rc;
+    // one spelling of the launch: the kernel, and the EG form's one more argument
+    auto launch = [&](auto kernel, auto... eg) {
+        hipLaunchKernelGGL(kernel, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, c.d_rows, c.d_offsets, c.n_users, c.ps_mode, c.d_ps,
+                           c.ps_const, c.d_ratio, c.d_click, slots, gscr, g_cap, ws, W, eg...);
+    };
+    if constexpr (EG) launch(k_ope_logreg<false, true, OpeEg>, *ega);
+    else if (m->select_randomly) launch(k_ope_logreg<true, false>);
+    else launch(k_ope_logreg<false, false>);
     HIP_TRY(hipGetLastError());
-    return ope_reduce(slots, W, d_sums, s);
+    return ope_reduce(slots, W, c.d_sums, s);
 }
 
 }  // namespace
@@ -436,8 +429,9 @@ extern "C" int rg_ope_replay_logreg(const rg_ope_logreg* m, const rg_event* d_ro
                                     uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
                                     uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream) {
     if (int rc = lr_model_ok(m, "rg_ope_replay_logreg")) return rc;
-    return lr_replay<false>("rg_ope_replay_logreg", m, nullptr, d_rows, d_offsets, n_users, max_user_rows, ps_mode, d_ps, ps_const,
-                            d_ratio, d_click, d_sums, d_workspace, workspace_bytes, stream);
+    const OpeCall c{d_rows, d_offsets, n_users, max_user_rows, ps_mode, d_ps, ps_const, d_ratio, d_click, d_sums, d_workspace, workspace_bytes,
+                    static_cast<hipStream_t>(stream)};
+    return lr_replay<false>("rg_ope_replay_logreg", m, nullptr, c);
 }
 
 extern "C" int rg_ope_replay_logreg_eg(const rg_ope_logreg* m, const rg_ope_eg* eg, const rg_event* d_rows, const int64_t* d_offsets,
@@ -449,6 +443,7 @@ extern "C" int rg_ope_replay_logreg_eg(const rg_ope_logreg* m, const rg_ope_eg* 
         return fail(RG_EINVAL, "rg_ope_replay_logreg_eg: a select_randomly model samples its act: no replay form under EpsilonGreedy");
     if (int rc = ope_eg_ok("rg_ope_replay_logreg_eg", eg, m->num_products)) return rc;
     const OpeEg ega{*eg, d_greedy, d_h0};
-    return lr_replay<true>("rg_ope_replay_logreg_eg", m, &ega, d_rows, d_offsets, n_users, max_user_rows,
-                           ps_mode, d_ps, ps_const, d_ratio, d_click, d_sums, d_workspace, workspace_bytes, stream);
+    const OpeCall c{d_rows, d_offsets, n_users, max_user_rows, ps_mode, d_ps, ps_const, d_ratio, d_click, d_sums, d_workspace, workspace_bytes,
+                    static_cast<hipStream_t>(stream)};
+    return lr_replay<true>("rg_ope_replay_logreg_eg", m, &ega, c);
 }

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(64 * kOpeWaves, 4) void k_ope_poly(
             while (rem) {
                 const uint32_t k = static_cast<uint32_t>(__builtin_ctzll(rem));
                 if ((omask >> k) & 1) {
-                    const uint32_t p = ope_lane_value(idx, k);
+                    const uint32_t p = lane_value(idx, k);
                     bool done = false;
                     if (!global) {
                         if (n < kPlLds || !gp) {
@@ -105,8 +105,8 @@ __global__ __launch_bounds__(64 * kOpeWaves, 4) void k_ope_poly(
                 if (dirty && n) {                     // (n == 0: a user that opens with a bandit row, refused by the validation)
                     uint32_t fl = 0;
                     const PolyListHist hist{global ? gp : lp, global ? gc : lc, n};
-                    action = ope_uniform(poly_act(m, hist, static_cast<int>(lane), s_th, s_cnt[wib], s_prod[wib], &fl));
-                    fl = ope_uniform(fl);             // (both are the same in every lane: kept in scalar registers)
+                    action = wave_uniform(poly_act(m, hist, static_cast<int>(lane), s_th, s_cnt[wib], s_prod[wib], &fl));
+                    fl = wave_uniform(fl);             // (both are the same in every lane: kept in scalar registers)
                     c_acts += 1;
                     c_rows += n;
                     c_table += fl & 1u;
@@ -123,10 +123,10 @@ __global__ __launch_bounds__(64 * kOpeWaves, 4) void k_ope_poly(
                     dirty = false;
                 }
                 // the bandit rows up to the next organic row share this act
-                const pl_u64 next_o = omask & ~ope_below(k);
+                const pl_u64 next_o = omask & ~lanes_below(k);
                 const uint32_t end = next_o ? static_cast<uint32_t>(__builtin_ctzll(next_o)) : 64u;
                 if (isb && lane >= k && lane < end) pi = ope_model_pi(r, action, idx, ega...);
-                rem &= end < 64 ? ~ope_below(end) : 0ull;
+                rem &= end < 64 ? ~lanes_below(end) : 0ull;
             }
             if (isb) acc.emit(log, r, pi);
         }
@@ -162,31 +162,26 @@ extern "C" size_t rg_ope_poly_workspace_bytes(const rg_ope_poly* m, uint64_t n_u
 namespace {
 
 template <bool EG>       // ega: null iff !EG
-int pl_replay(const char* who, const rg_ope_poly* m, const OpeEg* ega, const rg_event* d_rows, const int64_t* d_offsets,
-              uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
-              uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = ope_args_ok(who, ps_mode, d_ps, n_users, d_rows, d_offsets, d_ratio, d_sums, d_workspace,
-                             workspace_bytes, rg_ope_poly_workspace_bytes(m, n_users, max_user_rows)))
-        return rc;
+int pl_replay(const char* who, const rg_ope_poly* m, const OpeEg* ega, const OpeCall& c) {
+    if (int rc = ope_args_ok(who, c, rg_ope_poly_workspace_bytes(m, c.n_users, c.max_user_rows))) return rc;
     if (rg_device_count() <= 0) return fail(RG_ENODEV, "no HIP device");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t W = ope_waves(n_users, kPlMaxWaves);
-    const uint32_t g_cap = pl_global_cap(max_user_rows);
-    char* const base = static_cast<char*>(d_workspace);
-    pl_u64* ws = reinterpret_cast<pl_u64*>(base);
-    uint32_t* ulist = reinterpret_cast<uint32_t*>(base + pl_head_bytes());
-    double* slots = reinterpret_cast<double*>(base + pl_head_bytes() + pl_list_bytes());
-    uint32_t* gscr = g_cap ? reinterpret_cast<uint32_t*>(base + pl_head_bytes() + pl_list_bytes() + ope_slot_bytes(W)) : nullptr;
-    if (int rc = ope_check_log(who, d_rows, d_offsets, n_users, m->num_products, max_user_rows, ws, s)) return rc;
+    const uint32_t W = ope_waves(c.n_users, kPlMaxWaves);
+    const uint32_t g_cap = pl_global_cap(c.max_user_rows);
+    pl_u64* ws = c.at<pl_u64>(0);
+    uint32_t* ulist = c.at<uint32_t>(pl_head_bytes());
+    double* slots = c.at<double>(pl_head_bytes() + pl_list_bytes());
+    uint32_t* gscr = g_cap ? c.at<uint32_t>(pl_head_bytes() + pl_list_bytes() + ope_slot_bytes(W)) : nullptr;
+    if (int rc = ope_check_log(who, c, m->num_products, ws)) return rc;
     const PolyModel pm{m->num_products, m->n_steps, m->wf, m->wa, m->wk_t, m->th, m->intercept};
-    if constexpr (EG)
-        hipLaunchKernelGGL((k_ope_poly<true, OpeEg>), dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, pm, d_rows, d_offsets, n_users, ps_mode,
-                           d_ps, ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, ulist, W, *ega);
-    else
-        hipLaunchKernelGGL(k_ope_poly<false>, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, pm, d_rows, d_offsets, n_users, ps_mode, d_ps,
-                           ps_const, d_ratio, d_click, slots, gscr, g_cap, ws, ulist, W);
+    // one spelling of the launch: the kernel, and the EG form's one more argument
+    auto launch = [&](auto kernel, auto... eg) {
+        hipLaunchKernelGGL(kernel, dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, c.stream, pm, c.d_rows, c.d_offsets, c.n_users, c.ps_mode,
+                           c.d_ps, c.ps_const, c.d_ratio, c.d_click, slots, gscr, g_cap, ws, ulist, W, eg...);
+    };
+    if constexpr (EG) launch(k_ope_poly<true, OpeEg>, *ega);
+    else launch(k_ope_poly<false>);
     HIP_TRY(hipGetLastError());
-    return ope_reduce(slots, W, d_sums, s);
+    return ope_reduce(slots, W, c.d_sums, c.stream);
 }
 
 }  // namespace
@@ -195,8 +190,9 @@ extern "C" int rg_ope_replay_poly(const rg_ope_poly* m, const rg_event* d_rows, 
                                   uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
                                   uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream) {
     if (int rc = pl_model_ok(m, "rg_ope_replay_poly")) return rc;
-    return pl_replay<false>("rg_ope_replay_poly", m, nullptr, d_rows, d_offsets, n_users, max_user_rows, ps_mode, d_ps, ps_const,
-                            d_ratio, d_click, d_sums, d_workspace, workspace_bytes, stream);
+    const OpeCall c{d_rows, d_offsets, n_users, max_user_rows, ps_mode, d_ps, ps_const, d_ratio, d_click, d_sums, d_workspace, workspace_bytes,
+                    static_cast<hipStream_t>(stream)};
+    return pl_replay<false>("rg_ope_replay_poly", m, nullptr, c);
 }
 
 extern "C" int rg_ope_replay_poly_eg(const rg_ope_poly* m, const rg_ope_eg* eg, const rg_event* d_rows, const int64_t* d_offsets,
@@ -206,6 +202,7 @@ extern "C" int rg_ope_replay_poly_eg(const rg_ope_poly* m, const rg_ope_eg* eg, 
     if (int rc = pl_model_ok(m, "rg_ope_replay_poly_eg")) return rc;
     if (int rc = ope_eg_ok("rg_ope_replay_poly_eg", eg, m->num_products)) return rc;
     const OpeEg ega{*eg, d_greedy, d_h0};
-    return pl_replay<true>("rg_ope_replay_poly_eg", m, &ega, d_rows, d_offsets, n_users, max_user_rows,
-                           ps_mode, d_ps, ps_const, d_ratio, d_click, d_sums, d_workspace, workspace_bytes, stream);
+    const OpeCall c{d_rows, d_offsets, n_users, max_user_rows, ps_mode, d_ps, ps_const, d_ratio, d_click, d_sums, d_workspace, workspace_bytes,
+                    static_cast<hipStream_t>(stream)};
+    return pl_replay<true>("rg_ope_replay_poly_eg", m, &ega, c);
 }

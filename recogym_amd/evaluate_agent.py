@@ -10,11 +10,11 @@ verify_agents_IPS, verify_agents_SNIPS, evaluate_recall_at_k, verify_agents_reca
 `reco_log` is a DataFrame with the reference's columns (t, u, z, v, a, c, ps), a Simulator or a
 Simulator.device_log().  Users 0 .. max(u) - 1 are evaluated (the reference's range(max(reco_log.u)):
 the user with the largest id is not), each user's rows in frame order.  Where a HIP device is present,
-the agent has a replay form (ope_policy_of) and the log qualifies, the rows are replayed on the device
-by rg_ope_replay (the frozen LogReg policy: by rg_ope_replay_logreg, an EpsilonGreedy target: by rg_ope_replay_eg, the likelihood
-agent: by rg_ope_replay_poly and the host's confirmation of its unresolved acts, ope_checked_policy_of; an EpsilonGreedy target
-with `device_models` round either model: by rg_ope_replay_logreg_eg / rg_ope_replay_poly_eg); otherwise the
-host loop below runs:
+the agent has a replay form (ope_policy_of; the likelihood agent's, which the host confirms: ope_checked_policy_of) and the log
+qualifies, the rows are replayed on the device by one of the six entry points of the table _REPLAY_ENTRY — a plain policy, the
+frozen LogReg policy or the likelihood agent, each bare or under an EpsilonGreedy wrapper (`device_models` for a model inside).
+ope_replay is four steps: the log qualifies (_replay_users), the policy dict finds its entry point (_replay_target), one call,
+and the workspace's head decoded once from the layouts _abi names (_replay_head).  Otherwise the host loop below runs:
 the reference's loop made linear (one stable group-by instead of six frame filters per user), the same
 act() calls in the same order.
 
@@ -29,6 +29,7 @@ single-process; sharding the study over ranks is out of scope.  The module itsel
 `recogym_amd.evaluate_agent(env, agent, ...)` is the function, as `recogym.evaluate_agent` is in the reference."""
 import ctypes as C
 import warnings
+from collections import namedtuple
 from copy import deepcopy
 
 import numpy as np
@@ -234,28 +235,102 @@ def _masked(x, mask, step=1 << 24):
 
 
 def _logreg_model(lr, num_products, device):
-    """A policy dict's `logreg` entry -> (RgOpeLogreg, the device tensors it points into): the model moved to the log's device,
-    with the fp32 copy and the certificate's bounds the step loop uses (sim.logreg_fp32) for the argmax form."""
-    import torch
-    from .sim import logreg_fp32
-    def put(x, np_type, t_type):            # (arrays that already are tensors, e.g. on the device, are taken as they are)
-        if torch.is_tensor(x):
-            return x.to(device=device, dtype=t_type).contiguous()
-        return torch.as_tensor(np.ascontiguousarray(x, dtype=np_type)).to(device)
-    coef_t = put(lr['coef_t'], np.float64, torch.float64)
-    intercept = put(lr['intercept'], np.float64, torch.float64)
-    classes = put(lr['classes'], np.int32, torch.int32)
-    assert coef_t.shape == (num_products, classes.numel()) and intercept.shape == (classes.numel(),)
-    keep = [coef_t, intercept, classes]
-    sr = bool(lr.get('select_randomly'))
-    m = _abi.RgOpeLogreg(num_products=int(num_products), n_classes=int(classes.numel()), select_randomly=int(sr), reserved=0,
-                         coef_t=coef_t.data_ptr(), intercept=intercept.data_ptr(), classes=classes.data_ptr(),
+    """A policy dict's `logreg` entry -> (RgOpeLogreg, the device tensors it points into): the model moved to the log's device as
+    the step loop's is (sim.logreg_device_model), with the fp32 copy and the certificate's bounds for the argmax form."""
+    from .sim import logreg_device_model
+    (coef_t, intercept, classes), fp32 = logreg_device_model(lr, num_products, device)
+    m = _abi.RgOpeLogreg(num_products=int(num_products), n_classes=int(classes.numel()), select_randomly=int(bool(lr.get('select_randomly'))),
+                         reserved=0, coef_t=coef_t.data_ptr(), intercept=intercept.data_ptr(), classes=classes.data_ptr(),
                          coef32_t=None, intercept32=None, wmax=None, bmax=0.0, reserved2=0)
-    if not sr and lr.get('fp32', True):
-        w32, b32, wmax, bmax = logreg_fp32(coef_t, intercept)
+    keep = [coef_t, intercept, classes]
+    if fp32 is not None:
+        w32, b32, wmax, bmax = fp32
         keep += [w32, b32, wmax]
         m.coef32_t, m.intercept32, m.wmax, m.bmax = w32.data_ptr(), b32.data_ptr(), wmax.data_ptr(), bmax
     return m, keep
+
+
+def _replay_policy_of(agent):
+    """-> the agent's policy dict, exact (ope_policy_of) or to be confirmed on the host (ope_checked_policy_of), else None."""
+    pol = ope_policy_of(agent)
+    return ope_checked_policy_of(agent) if pol is None else pol
+
+
+# The one place that knows which entry point serves which policy dict: (the unit, under an EpsilonGreedy wrapper) -> (workspace-size
+# function, replay function).  The unit also names the head its workspace carries (_abi.OPE_HEADS; 'plain': none).
+_REPLAY_ENTRY = {
+    ('plain', False): ('rg_ope_workspace_bytes', 'rg_ope_replay'),
+    ('plain', True): ('rg_ope_eg_workspace_bytes', 'rg_ope_replay_eg'),
+    ('logreg', False): ('rg_ope_logreg_workspace_bytes', 'rg_ope_replay_logreg'),
+    ('logreg', True): ('rg_ope_logreg_workspace_bytes', 'rg_ope_replay_logreg_eg'),       # (the wrapper round a model: the plain
+    ('poly', False): ('rg_ope_poly_workspace_bytes', 'rg_ope_replay_poly'),               # unit's workspace, list and head words)
+    ('poly', True): ('rg_ope_poly_workspace_bytes', 'rg_ope_replay_poly_eg'),
+}
+# structs: what leads the argument list (the policy or model, then the wrapper); keep: the tensors they point into; size_fn / replay_fn /
+# what: the entry point and its name; head: the word names of the workspace's head or None; poly_host: the likelihood agent's host model
+_ReplayTarget = namedtuple('_ReplayTarget', 'structs keep size_fn replay_fn what head poly_host')
+
+
+def _replay_target(pol, device):
+    """A policy dict -> the _ReplayTarget that replays it on `device`, or None where an EpsilonGreedy wrapper has no replay form round
+    what it wraps (an inner policy that samples its act)."""
+    import torch
+    P = int(pol['num_products'])
+    eg, poly_host = pol.get('epsilon_greedy'), None
+    if eg is not None and (pol.get('kind') not in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE, _abi.RG_POLICY_LOGREG_FROZEN,
+                                                    _abi.RG_POLICY_LOGREG_POLY) or (pol.get('logreg') or {}).get('select_randomly')):
+        return None
+    if pol.get('logreg_poly') is not None:
+        # the likelihood agent: the model and the step table move to the log's device as the step loop's do (sim.poly_device_model)
+        # (`device_model`, optional: that function's result for this device, where the caller keeps the model there between calls)
+        from .sim import poly_device_model
+        unit, poly = 'poly', pol['logreg_poly']
+        poly_host, keep = poly.get('device_model') or poly_device_model(poly, P, device)
+        assert all(t.device == device and t.dtype == torch.float64 for t in keep), 'device_model lies on another device than the log'
+        cp = _abi.RgOpePoly(num_products=P, n_steps=int(keep[3].numel()), wf=keep[0].data_ptr(), wa=keep[1].data_ptr(),
+                            wk_t=keep[2].data_ptr(), th=keep[3].data_ptr(), intercept=poly_host[3])
+    elif pol.get('logreg') is not None:
+        # the frozen LogReg policy: the model moves to the log's device once per call
+        unit = 'logreg'
+        cp, keep = _logreg_model(pol['logreg'], P, device)
+    else:
+        unit, o, table = 'plain', pol.get('ouc') or {}, pol.get('table')
+        keep = None if table is None else torch.as_tensor(np.ascontiguousarray(table, dtype=np.int32)).to(device)
+        cp = _abi.RgOpePolicy(kind=int(pol['kind']), num_products=P, policy_seed=int(pol.get('policy_seed') or 0) & 0xFFFFFFFFFFFFFFFF,
+                              ouc_select_randomly=int(bool(o.get('select_randomly', True))),
+                              ouc_exploit_explore=int(bool(o.get('exploit_explore', True))),
+                              ouc_reverse_pop=int(bool(o.get('reverse_pop', False))), reserved=0,
+                              ouc_epsilon=float(o.get('epsilon', 0.0)), table=None if keep is None else keep.data_ptr())
+    structs = [cp]
+    if eg is not None:
+        from .agents.epsilon_greedy import explore_table
+        pure_new = bool(eg.get('pure_new', True))
+        structs.append(_abi.RgOpeEg(epsilon=float(eg['epsilon']), seed=int(eg['seed']) & 0xFFFFFFFFFFFFFFFF, pure_new=int(pure_new),
+                                    reserved=0, prob_explore=explore_table(P, pure_new)[1]))
+    lib = _abi.load()
+    size_name, what = _REPLAY_ENTRY[unit, eg is not None]
+    return _ReplayTarget(structs, keep, getattr(lib, size_name), getattr(lib, what), what, _abi.OPE_HEADS.get(unit), poly_host)
+
+
+def _replay_users(dl, pol, n_users):
+    """-> (n_eval, the offsets of the log's first n_eval users, the rows of the longest of them), or None where the log does not
+    qualify: a user that opens with a bandit row; a float clock under a policy that draws."""
+    n_eval = max(int(dl.offsets.numel()) - 2, 0) if n_users is None else int(n_users)
+    offsets = dl.offsets[:n_eval + 1].contiguous()
+    if not n_eval:
+        return 0, offsets, 0
+    lens = offsets[1:] - offsets[:-1]
+    firsts = dl.rows[offsets[:-1][lens > 0], 2]
+    if bool(((firsts & _abi.RG_EV_BANDIT) != 0).any()) or (_draws(pol) and dl.time is not None):
+        return None
+    return n_eval, offsets, int(lens.max().item())
+
+
+def _replay_head(ws, names):
+    """The head of a history-keeping unit's workspace after the call, read once -> dict(word name: int; `overflow`: bool)."""
+    import torch
+    words = ws[:_abi.OPE_HEAD_BYTES].view(torch.int64).cpu().numpy()
+    return {name: bool(words[i]) if name == 'overflow' else int(words[i]) for i, name in enumerate(names)}
 
 
 def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
@@ -263,74 +338,28 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
     the log's first `n_users` users (default: all but the last, whose id is max(u)), in log order (device tensors);
     sums = float64 tensor (n, sum c r, sum r).  None where the agent has no replay form or the log does not qualify (a user
     that opens with a bandit row; a float clock under a policy that draws).  `stats` (a dict, frozen LogReg policies only)
-    receives rg_ope_replay_logreg's workspace words: error, acts, exact (acts decided by float64 scores), rows_read; under the
-    likelihood agent rg_ope_replay_poly's: error, acts, table, lower, unresolved, overflow, rows_read.  The likelihood agent's replay
+    receives the head words of the LogReg unit's workspace: error, acts, exact (acts decided by float64 scores), rows_read; under the
+    likelihood agent those of its unit: error, acts, table, lower, unresolved, overflow, rows_read (_abi.OPE_HEADS).  The likelihood agent's replay
     is None, after one RuntimeWarning, also where the host refutes an unresolved act or the device's list of them overflowed (under an
     EpsilonGreedy wrapper the listed acts are the GREEDY ones; with pure_new a wrong one changes pi on explored rows too).  `eg_out` (a
     dict, EpsilonGreedy targets only) receives `greedy` (uint8) and `h0` (int32) of the same bandit rows (device tensors)."""
     import torch
-    if pol is None:
-        pol = ope_policy_of(agent)
-        pol = ope_checked_policy_of(agent) if pol is None else pol
+    pol = _replay_policy_of(agent) if pol is None else pol
     if pol is None or int(pol['num_products']) != int(dl.num_products):
         return None
-    n_eval = max(int(dl.offsets.numel()) - 2, 0) if n_users is None else int(n_users)
-    device = dl.rows.device
-    offsets = dl.offsets[:n_eval + 1].contiguous()
-    lens = offsets[1:] - offsets[:-1]
-    if n_eval:
-        firsts = dl.rows[offsets[:-1][lens > 0], 2]
-        if bool(((firsts & _abi.RG_EV_BANDIT) != 0).any()):
-            return None
-        if _draws(pol) and dl.time is not None:
-            return None
-    max_rows = int(lens.max().item()) if n_eval else 0
-    lib = _abi.load()
-    eg = pol.get('epsilon_greedy')
-    if eg is not None and (pol.get('kind') not in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE, _abi.RG_POLICY_LOGREG_FROZEN,
-                                                    _abi.RG_POLICY_LOGREG_POLY) or (pol.get('logreg') or {}).get('select_randomly')):
+    users = _replay_users(dl, pol, n_users)
+    if users is None:
         return None
-    if eg is not None:
-        from .agents.epsilon_greedy import explore_table
-        pure_new = bool(eg.get('pure_new', True))
-        ce = _abi.RgOpeEg(epsilon=float(eg['epsilon']), seed=int(eg['seed']) & 0xFFFFFFFFFFFFFFFF, pure_new=int(pure_new),
-                          reserved=0, prob_explore=explore_table(int(pol['num_products']), pure_new)[1])
-    poly = pol.get('logreg_poly')
-    if poly is not None:
-        # the likelihood agent: the model and the step table move to the log's device as the step loop's do (sim.poly_device_model)
-        # (`device_model`, optional: that function's result for this device, where the caller keeps the model there between calls)
-        from .sim import poly_device_model, poly_replay_verify
-        poly_host, keep = poly.get('device_model') or poly_device_model(poly, int(pol['num_products']), device)
-        assert all(t.device == device and t.dtype == torch.float64 for t in keep), 'device_model lies on another device than the log'
-        cp = _abi.RgOpePoly(num_products=int(pol['num_products']), n_steps=int(keep[3].numel()), wf=keep[0].data_ptr(),
-                            wa=keep[1].data_ptr(), wk_t=keep[2].data_ptr(), th=keep[3].data_ptr(), intercept=poly_host[3])
-        size_fn, replay_fn, what = lib.rg_ope_poly_workspace_bytes, lib.rg_ope_replay_poly, 'rg_ope_replay_poly'
-        if eg is not None:                     # the wrapper round the model: the plain unit's workspace, list and head words
-            replay_fn, what = lib.rg_ope_replay_poly_eg, 'rg_ope_replay_poly_eg'
-    elif pol.get('logreg') is not None:
-        # the frozen LogReg policy has an entry point of its own; the model moves to the log's device once per call
-        cp, keep = _logreg_model(pol['logreg'], int(pol['num_products']), device)
-        size_fn, replay_fn, what = lib.rg_ope_logreg_workspace_bytes, lib.rg_ope_replay_logreg, 'rg_ope_replay_logreg'
-        if eg is not None:
-            replay_fn, what = lib.rg_ope_replay_logreg_eg, 'rg_ope_replay_logreg_eg'
-    else:
-        o = pol.get('ouc') or {}
-        table = pol.get('table')
-        keep = None if table is None else torch.as_tensor(np.ascontiguousarray(table, dtype=np.int32)).to(device)
-        cp = _abi.RgOpePolicy(kind=int(pol['kind']), num_products=int(pol['num_products']),
-                              policy_seed=int(pol.get('policy_seed') or 0) & 0xFFFFFFFFFFFFFFFF,
-                              ouc_select_randomly=int(bool(o.get('select_randomly', True))),
-                              ouc_exploit_explore=int(bool(o.get('exploit_explore', True))),
-                              ouc_reverse_pop=int(bool(o.get('reverse_pop', False))), reserved=0,
-                              ouc_epsilon=float(o.get('epsilon', 0.0)),
-                              table=None if keep is None else keep.data_ptr())
-        size_fn, replay_fn, what = lib.rg_ope_workspace_bytes, lib.rg_ope_replay, 'rg_ope_replay'
-        if eg is not None:
-            size_fn, replay_fn, what = lib.rg_ope_eg_workspace_bytes, lib.rg_ope_replay_eg, 'rg_ope_replay_eg'
+    n_eval, offsets, max_rows = users
+    device = dl.rows.device
+    target = _replay_target(pol, device)
+    if target is None:
+        return None
+    wrapped = pol.get('epsilon_greedy') is not None
     with torch.cuda.device(device):
-        need = size_fn(C.byref(cp), n_eval, max_rows)
+        need = target.size_fn(C.byref(target.structs[0]), n_eval, max_rows)
         if need == 0:
-            raise _abi.RecoGymHipError(what + ' workspace: ' + lib.rg_last_error().decode())
+            raise _abi.RecoGymHipError(target.what + ' workspace: ' + _abi.load().rg_last_error().decode())
         ws = torch.empty(need, dtype=torch.uint8, device=device)
         total = int(offsets[-1].item()) if n_eval else 0
         ratio = torch.empty(max(total, 1), dtype=torch.float64, device=device)
@@ -342,36 +371,28 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
             mode, ps_ptr, ps_const = _abi.RG_OPE_PS_CONST, None, float(ps)
         else:
             mode, ps_ptr, ps_const = _abi.RG_OPE_PS_ARRAY, ps.data_ptr(), 0.0
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        if eg is not None:
-            want = eg_out is not None
-            greedy = torch.zeros(max(total, 1), dtype=torch.uint8, device=device) if want else None
-            h0 = torch.zeros(max(total, 1), dtype=torch.int32, device=device) if want else None
-            _abi.check(replay_fn(C.byref(cp), C.byref(ce), dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows,
-                                 mode, ps_ptr, ps_const, ratio.data_ptr(), None, sums.data_ptr(),
-                                 greedy.data_ptr() if want else None, h0.data_ptr() if want else None,
-                                 ws.data_ptr(), need, stream), what)
-        else:
-            _abi.check(replay_fn(C.byref(cp), dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows, mode, ps_ptr,
-                                 ps_const, ratio.data_ptr(), None, sums.data_ptr(), ws.data_ptr(), need, stream), what)
-        if stats is not None and pol.get('logreg') is not None:
-            words = ws[:32].view(torch.int64).cpu().numpy()
-            stats.update(error=int(words[0]), acts=int(words[1]), exact=int(words[2]), rows_read=int(words[3]))
-        if poly is not None or pol.get('logreg') is not None:
-            # error bits after the validation passed: a history list overflowed — the ratios are not to be trusted
-            err = int(ws[:8].view(torch.int64).item())
-            if err:
-                raise _abi.RecoGymHipError(f'{what}: the replay reported error bits {err:#x} (a view history outgrew its list)')
-        if poly is not None:
-            words = ws[:256].view(torch.int64).cpu().numpy()
-            unresolved, overflow = int(words[4]), bool(words[5])
+        # the wrapper's two optional outputs go between the sums and the workspace
+        want = wrapped and eg_out is not None
+        greedy = torch.zeros(max(total, 1), dtype=torch.uint8, device=device) if want else None
+        h0 = torch.zeros(max(total, 1), dtype=torch.int32, device=device) if want else None
+        eg_ptrs = [greedy.data_ptr() if want else None, h0.data_ptr() if want else None] if wrapped else []
+        _abi.check(target.replay_fn(*[C.byref(x) for x in target.structs], dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows, mode,
+                                    ps_ptr, ps_const, ratio.data_ptr(), None, sums.data_ptr(), *eg_ptrs, ws.data_ptr(), need,
+                                    C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), target.what)
+        if target.head is not None:
+            head = _replay_head(ws, target.head)
             if stats is not None:
-                stats.update(error=int(words[0]), acts=int(words[1]), table=int(words[2]), lower=int(words[3]), unresolved=unresolved,
-                             overflow=overflow, rows_read=int(words[6]))
-            if unresolved:
+                stats.update(head)
+            if head['error']:
+                # error bits after the validation passed: a history list overflowed — the ratios are not to be trusted
+                raise _abi.RecoGymHipError(f'{target.what}: the replay reported error bits {head["error"]:#x} (a view history outgrew its list)')
+            if head.get('unresolved'):
                 # the acts the device's rule could not resolve: confirmed on the host, or the whole replay is given up (no patching)
-                listed = ws[256:256 + 12 * min(unresolved, 4096)].view(torch.int32).cpu().numpy().view(np.uint32).reshape(-1, 3)
-                if not poly_replay_verify(dl, listed, overflow, poly_host):
+                from .sim import poly_replay_verify
+                n_listed = min(head['unresolved'], _abi.OPE_POLY_LIST_CAP)
+                listed = ws[_abi.OPE_HEAD_BYTES:_abi.OPE_HEAD_BYTES + _abi.OPE_POLY_LIST_ENTRY_BYTES * n_listed]
+                listed = listed.view(torch.int32).cpu().numpy().view(np.uint32).reshape(-1, 3)
+                if not poly_replay_verify(dl, listed, head['overflow'], target.poly_host):
                     warnings.warn('the likelihood agent\'s replay has acts the host does not confirm (or more unresolved acts than the '
                                   'device lists): the off-policy evaluation takes the host loop', RuntimeWarning, stacklevel=2)
                     return None
@@ -379,7 +400,7 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
         is_b = (code & _abi.RG_EV_BANDIT) != 0
         r = _masked(ratio[:total], is_b)
         c = _masked(((code & _abi.RG_EV_CLICK) != 0).to(torch.float64), is_b)
-        if eg is not None and eg_out is not None:
+        if want:
             eg_out.update(greedy=_masked(greedy[:total], is_b), h0=_masked(h0[:total], is_b))
     return r, c, sums
 
@@ -390,8 +411,7 @@ def epsilon_greedy_branches(agent, reco_log):
     the reference's act reports on explored acts) — rg_event has no bit for either, the replay recomputes them from the
     addressed draws.  All users of the log are covered.  None where the agent has no replay form or the log does not qualify."""
     dl = _as_device_log(reco_log)
-    pol = ope_policy_of(agent)
-    pol = ope_checked_policy_of(agent) if pol is None else pol      # (second, in ope_replay's order)
+    pol = _replay_policy_of(agent)
     if dl is None or pol is None or pol.get('epsilon_greedy') is None:
         return None
     out = {}
@@ -405,8 +425,7 @@ def _device_or_none(agent, reco_log):
     dl = _as_device_log(reco_log)
     if dl is None and not _device_present():
         return None
-    pol = ope_policy_of(agent)
-    pol = ope_checked_policy_of(agent) if pol is None else pol
+    pol = _replay_policy_of(agent)
     if pol is None:
         return None
     if dl is None:

@@ -81,6 +81,23 @@ def logreg_fp32(coef_t, intercept):
     return w32.contiguous(), b32.contiguous(), wmax.contiguous(), bmax
 
 
+def logreg_device_model(logreg, num_products, device):
+    """A policy dict's `logreg` entry (coef_t (P, C) = sklearn's coef_.T, intercept (C,), classes (C,): host arrays, or tensors, which are
+    taken as they are) -> ((coef_t, intercept float64, classes int32) on `device`, logreg_fp32's (coef32_t, intercept32, wmax, bmax) for
+    the argmax form — None with select_randomly or fp32 = False): what rg_sim_set_logreg / rg_sim_set_logreg_fp32 and
+    rg_ope_replay_logreg take."""
+    def put(x, np_type, t_type):
+        if torch.is_tensor(x):
+            return x.to(device=device, dtype=t_type).contiguous()
+        return torch.as_tensor(np.ascontiguousarray(x, dtype=np_type)).to(device)
+    coef_t = put(logreg['coef_t'], np.float64, torch.float64)
+    intercept = put(logreg['intercept'], np.float64, torch.float64)
+    classes = put(logreg['classes'], np.int32, torch.int32)
+    assert coef_t.shape == (int(num_products), classes.numel()) and intercept.shape == (classes.numel(),)
+    fp32 = logreg.get('fp32', True) and not logreg.get('select_randomly')
+    return (coef_t, intercept, classes), (logreg_fp32(coef_t, intercept) if fp32 else None)
+
+
 def poly_device_model(logreg_poly, num_products, device):
     """A policy dict's `logreg_poly` entry (wf (P,), wa (P,), wk (P, P) [action][product], intercept, optionally expit_steps) ->
     ((wf, wa, wk, b) host arrays, (wf, wa, wk_t, th) float64 tensors on `device`): wk transposed to [viewed product][action] (lanes
@@ -231,17 +248,13 @@ class Simulator:
                                   coef_t=np.concatenate([logreg['coef_t'], np.repeat(np.asarray(logreg['coef_t'])[:, -1:], pad, axis=1)], axis=1),
                                   intercept=np.concatenate([logreg['intercept'], np.repeat(np.asarray(logreg['intercept'])[-1:], pad)]),
                                   classes=np.concatenate([logreg['classes'], np.repeat(np.asarray(logreg['classes'])[-1:], pad)]))
-                self.logreg = (
-                    torch.as_tensor(np.ascontiguousarray(logreg['coef_t'], dtype=np.float64)).to(self.device),
-                    torch.as_tensor(np.ascontiguousarray(logreg['intercept'], dtype=np.float64)).to(self.device),
-                    torch.as_tensor(np.ascontiguousarray(logreg['classes'], dtype=np.int32)).to(self.device))
-                assert self.logreg[0].shape == (config.num_products, self.logreg[2].numel())
+                self.logreg, fp32 = logreg_device_model(logreg, config.num_products, self.device)
                 _abi.check(self.lib.rg_sim_set_logreg(self._h, self.logreg[0].data_ptr(), self.logreg[1].data_ptr(),
                                                       self.logreg[2].data_ptr(), self.logreg[2].numel()),
                            'rg_sim_set_logreg')
-                if logreg.get('fp32', True) and not logreg.get('select_randomly'):
+                if fp32 is not None:
                     # fp32 copies for the certified fast scores (the float64 arrays stay the arbiter); bounds rounded up
-                    *self.logreg32, bmax = logreg_fp32(self.logreg[0], self.logreg[1])
+                    *self.logreg32, bmax = fp32
                     self.logreg32 = tuple(self.logreg32)
                     _abi.check(self.lib.rg_sim_set_logreg_fp32(self._h, self.logreg32[0].data_ptr(), self.logreg32[1].data_ptr(),
                                                                self.logreg32[2].data_ptr(), C.c_float(bmax)), 'rg_sim_set_logreg_fp32')

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from device_util import HostOnly
 import golden_util as gu
 import recogym_amd as recogym
 from make_golden_counts import LOGS
@@ -190,24 +191,6 @@ def test_overflow_paths():
     assert np.array_equal(oc_d.co_counts, oc_h.co_counts)
     assert oc_d.co_counts.sum() == 5 ** 2 + 1500 ** 2 + 3 ** 2 + 64 ** 2 + 130 ** 2 + 130 ** 2
     assert np.array_equal(bc_d.pulls_a, bc_h.pulls_a) and np.array_equal(bc_d.clicks_a, bc_h.clicks_a)
-
-
-class HostOnly:
-    """The agent as an arbitrary Python agent: act / train / reset only, so that test_agent takes the per-user host path."""
-    per_user_path = True
-
-    def __init__(self, agent):
-        self.agent = agent
-        self.config = agent.config
-
-    def act(self, observation, reward, done):
-        return self.agent.act(observation, reward, done)
-
-    def train(self, observation, action, reward, done=False):
-        return self.agent.train(observation, action, reward, done)
-
-    def reset(self):
-        return self.agent.reset()
 
 
 @pytest.mark.parametrize('which', [0, 1])

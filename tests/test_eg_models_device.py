@@ -11,10 +11,10 @@ import pytest
 import torch
 from scipy.special import expit
 
+from device_util import HostOnly, assert_frames_equal, constant_agent, handle, make_env
 import eg_models_util as mu
 import eg_util as eu
 import golden_util as gu
-import recogym_amd as recogym
 from make_golden_ope import log_frame
 from recogym_amd import _abi
 from recogym_amd import evaluate_agent as ev
@@ -187,40 +187,6 @@ def test_a_float_clock_goes_to_the_host_loop():
 
 
 # ---- (d) small shapes against this package's host route --------------------------------------------------------------------
-class HostOnly:
-    """The agent as an arbitrary Python agent: act / train / reset only, so that generate_logs takes the per-user host path."""
-    per_user_path = True
-
-    def __init__(self, agent):
-        self.agent = agent
-        self.config = agent.config
-
-    def act(self, observation, reward, done):
-        return self.agent.act(observation, reward, done)
-
-    def train(self, observation, action, reward, done=False):
-        return self.agent.train(observation, action, reward, done)
-
-    def reset(self):
-        return self.agent.reset()
-
-
-def make_env(over):
-    env = recogym.make('reco-gym-v1')
-    env.init_gym({**env_1_args, **over})
-    return env
-
-
-def frame_key(df):
-    return [df[k].to_numpy(dtype=np.float64, na_value=np.nan) for k in ('t', 'u', 'v', 'a', 'c', 'ps')] + [(df['z'] == 'bandit').to_numpy()]
-
-
-def assert_frames_equal(got, want):
-    assert len(got) == len(want)
-    for g, w in zip(frame_key(got), frame_key(want)):
-        assert np.array_equal(g, w, equal_nan=True)
-
-
 def logs(env, n, agent):
     """generate_logs on the device route (no warning: nothing was refuted) and on the per-user host route"""
     assert agent.device_policy() is not None
@@ -286,15 +252,6 @@ def test_two_products_with_pure_new_explore_the_other_one(which):
 
 
 # ---- (e) the unresolved-act protocol under the wrapper ---------------------------------------------------------------------
-def constant_agent(z1, z2, P=10, with_ps_all=False):
-    """test_logreg_poly_device.constant_agent: wf = wk = 0, every history decides on z[1] = z1, z[2] = z2, the rest 0."""
-    wa = np.zeros(P)
-    wa[1], wa[2] = z1, z2 / 2.0
-    assert 2.0 * wa[2] == z2
-    return LogregPolyFrozenAgent(Configuration({'num_products': P, 'with_ps_all': with_ps_all}),
-                                 np.r_[np.zeros(P), wa, np.zeros(P * P)][None, :], [0.0])
-
-
 OVER = dict(random_seed=321, num_products=10, K=4)
 CONFIRMED = (25.0, 25.0 + 2.0 ** -12)              # inside W(z2) = 4.9e-4, far beyond one step of expit: the host confirms action 2
 
@@ -376,19 +333,6 @@ def test_two_runs_give_the_same_log_and_the_same_sums(name):
 
 
 # ---- (g) error paths -------------------------------------------------------------------------------------------------------
-def handle(policy, P=10, **cfg_over):
-    from recogym_amd.envs.static_params import make_rg_config
-    lib = _abi.load()
-    sel = cfg_over.pop('lr_select_randomly', False)
-    cfg = make_rg_config(Configuration({**env_1_args, 'random_seed': 1, 'num_products': P, 'K': 5, **cfg_over}), 1, policy, 3,
-                         lr_select_randomly=sel)
-    need = lib.rg_sim_workspace_bytes(C.byref(cfg), 64)
-    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
-    h = C.c_void_p()
-    assert lib.rg_sim_create(C.byref(h), C.byref(cfg), 64, ws.data_ptr(), need) == 0
-    return lib, h, ws
-
-
 def test_step_loop_error_paths():
     table = torch.from_numpy(explore_table(10, True)[0]).to(DEV)
     args = (0.1, 7, 1, table.data_ptr(), 0.1 / 9, 0.9)

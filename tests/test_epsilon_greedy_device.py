@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from device_util import HostOnly, handle
 import eg_util as eu
 import golden_util as gu
 import recogym_amd as recogym
@@ -197,24 +198,6 @@ def test_shards_concatenate_and_runs_repeat():
     assert np.concatenate([a[1], b[1]]).tobytes() == whole[1].tobytes()
 
 
-class HostOnly:
-    """The agent as an arbitrary Python agent: act / train / reset only, so that test_agent takes the per-user host path."""
-    per_user_path = True
-
-    def __init__(self, agent):
-        self.agent = agent
-        self.config = agent.config
-
-    def act(self, observation, reward, done):
-        return self.agent.act(observation, reward, done)
-
-    def train(self, observation, action, reward, done=False):
-        return self.agent.train(observation, action, reward, done)
-
-    def reset(self):
-        return self.agent.reset()
-
-
 def test_test_agent_on_the_device_equals_the_per_user_host_path():
     env = recogym.make('reco-gym-v1')
     env.init_gym({**recogym.env_1_args, 'random_seed': 42, 'num_products': 10})
@@ -237,30 +220,19 @@ def test_test_agent_on_the_device_equals_the_per_user_host_path():
     assert (cnt['clicks'], cnt['bandit'] + cnt['phantom']) == (int(b['c'].sum()), len(b))
 
 
-def _handle(policy, P=10, **cfg_over):
-    from recogym_amd.envs.static_params import make_rg_config
-    lib = _abi.load()
-    cfg = make_rg_config(Configuration({**env_1_args, 'random_seed': 1, 'num_products': P, 'K': 5, **cfg_over}), 1, policy, 3)
-    need = lib.rg_sim_workspace_bytes(C.byref(cfg), 64)
-    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
-    h = C.c_void_p()
-    assert lib.rg_sim_create(C.byref(h), C.byref(cfg), 64, ws.data_ptr(), need) == 0
-    return lib, h, ws
-
-
 def test_error_paths():
     table = torch.from_numpy(explore_table(10, True)[0]).to(DEV)
     for policy in (_abi.RG_POLICY_UNIFORM_ENV, _abi.RG_POLICY_EXTERNAL, _abi.RG_POLICY_LOGREG_FROZEN):
-        lib, h, ws = _handle(policy)
+        lib, h, ws = handle(policy)
         assert lib.rg_sim_set_epsilon_greedy(h, 0.1, 7, 1, table.data_ptr(), 0.1 / 9, 0.9) == -1 and b'EpsilonGreedy wraps' in lib.rg_last_error()
         lib.rg_sim_destroy(h)
-    lib, h, ws = _handle(_abi.RG_POLICY_RANDOM_AGENT)
+    lib, h, ws = handle(_abi.RG_POLICY_RANDOM_AGENT)
     for eps in (-0.01, 1.01, float('nan')):
         assert lib.rg_sim_set_epsilon_greedy(h, eps, 7, 1, table.data_ptr(), 0.0, 0.0) == -1 and b'epsilon' in lib.rg_last_error()
     assert lib.rg_sim_set_epsilon_greedy(h, 0.1, 7, 1, None, 0.1 / 9, 0.9) == -1 and b'NULL' in lib.rg_last_error()
     assert lib.rg_sim_set_epsilon_greedy(h, 0.1, 7, 1, table.data_ptr(), 0.1 / 9, 0.9) == 0
     lib.rg_sim_destroy(h)
-    lib, h, ws = _handle(_abi.RG_POLICY_RANDOM_AGENT, P=1)
+    lib, h, ws = handle(_abi.RG_POLICY_RANDOM_AGENT, P=1)
     assert lib.rg_sim_set_epsilon_greedy(h, 0.1, 7, 1, table.data_ptr(), 0.1, 0.9) == -1 and b'at least 2' in lib.rg_last_error()
     assert lib.rg_sim_set_epsilon_greedy(h, 0.1, 7, 0, table.data_ptr(), 0.1, 0.9) == 0          # without pure_new one product is enough
     lib.rg_sim_destroy(h)

@@ -10,6 +10,7 @@ import pytest
 import torch
 from scipy.special import expit
 
+from device_util import assert_frames_equal, constant_agent, make_env
 import golden_util as gu
 import recogym_amd as recogym
 from recogym_amd import _abi
@@ -66,22 +67,6 @@ def test_some_fixture_proves_the_table_and_a_merge():
 def test_two_runs_give_the_same_log():
     a, b = run_fixture('poly_p40'), run_fixture('poly_p40')
     assert np.array_equal(a[4], b[4]) and a[3] == b[3]
-
-
-def make_env(over):
-    env = recogym.make('reco-gym-v1')
-    env.init_gym({**env_1_args, **over})
-    return env
-
-
-def frame_key(df):
-    return [df[k].to_numpy(dtype=np.float64, na_value=np.nan) for k in ('t', 'u', 'v', 'a', 'c', 'ps')] + [(df['z'] == 'bandit').to_numpy()]
-
-
-def assert_frames_equal(got, want):
-    assert len(got) == len(want)
-    for g, w in zip(frame_key(got), frame_key(want)):
-        assert np.array_equal(g, w, equal_nan=True)
 
 
 def test_generate_logs_with_the_trained_agent_equals_the_host_route():
@@ -231,14 +216,6 @@ def test_random_models_and_histories(P, sizes, th):
 # ------------------------------------------------------------------------------------------------
 # unresolved acts: confirmed by the host -> the device log stands; refuted -> the host route
 # ------------------------------------------------------------------------------------------------
-def constant_agent(z1, z2, P=10):
-    """wf = wk = 0: every history decides on z[a] = a wa[a] + 0 — z[1] = z1, z[2] = z2 (2 wa[2]: exact), the rest 0."""
-    wa = np.zeros(P)
-    wa[1], wa[2] = z1, z2 / 2.0
-    assert 2.0 * wa[2] == z2
-    return LogregPolyFrozenAgent(Configuration({'num_products': P}), np.r_[np.zeros(P), wa, np.zeros(P * P)][None, :], [0.0])
-
-
 OVER = dict(random_seed=321, num_products=10, K=4)
 
 

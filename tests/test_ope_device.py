@@ -7,6 +7,7 @@ import pandas as pd
 import pytest
 import torch
 
+from device_util import close
 import golden_util as gu
 from make_golden_ope import LOGS, OUC_VARIANTS, log_frame
 from recogym_amd import _abi
@@ -27,17 +28,6 @@ def ouc(P, seed=11, **v):
 def dense(v):
     # the forms that sum over all P products in float64 (host: numpy's pairwise sum): relative 1e-12
     return v.get('select_randomly') and not v.get('exploit_explore') and (v.get('epsilon') or v.get('reverse_pop'))
-
-
-def close(got, want, rel):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape
-    if rel == 0:
-        assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), np.nonzero(got != want)[0][:8]
-    else:
-        assert np.array_equal(np.isnan(got), np.isnan(want))
-        ok = ~np.isnan(want)
-        assert np.all(np.abs(got[ok] - want[ok]) <= rel * np.abs(want[ok])), np.max(np.abs(got[ok] - want[ok]) / np.abs(want[ok]))
 
 
 def our_agent(key, P, cols):

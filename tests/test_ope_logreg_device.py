@@ -10,6 +10,7 @@ import pandas as pd
 import pytest
 import torch
 
+from device_util import close
 import golden_util as gu
 from make_golden_ope import log_frame
 from recogym_amd import _abi
@@ -20,17 +21,6 @@ from recogym_amd.envs.reco_env_v1 import env_1_args, rows_to_dataframe
 from recogym_amd.sim import Simulator
 
 pytestmark = pytest.mark.gpu
-
-
-def close(got, want, rel):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape
-    if rel == 0:
-        assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), np.nonzero(got != want)[0][:8]
-    else:
-        assert np.array_equal(np.isnan(got), np.isnan(want))
-        ok = ~np.isnan(want)
-        assert np.all(np.abs(got[ok] - want[ok]) <= rel * np.abs(want[ok])), np.max(np.abs(got[ok] - want[ok]) / np.abs(want[ok]))
 
 
 def agent(P, coef, intercept, classes, select_randomly=False):
