@@ -503,6 +503,8 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) k_sweep_xh(DevSim d,
 #pragma unroll
             for (int k = ((2 * KH) / 4) * 4; k < 2 * KH; ++k) reinterpret_cast<float*>(row4)[44 + k] = ou[k];
             float* hot = d.walk_hot + urow * 32;
+            // (INVARIANT the walk relies on: every writer of the hot row leaves the memo EMPTY — n_hot = 0 —, so k_walk2 sends a
+            // user's first draw of round 1 straight to the search without looking at the memo)
             *reinterpret_cast<float4*>(hot) = make_float4(static_cast<float>(run_pref), dlt * 1.000001f, q, __builtin_bit_cast(float, 0u));
             // float 31: the in-chunk budget of the walk's fp32 recompute (hot_budgets: rho_rel = 2^-23 with it), or rho_rel = 2^-20
             // for a user whose delta is the loose one anyway

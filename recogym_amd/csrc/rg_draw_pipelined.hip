@@ -359,6 +359,8 @@ __global__ void __launch_bounds__(kBlock, RG_SWEEP_OCC) k_draw_bf16p(DevSim d, u
 #pragma unroll
             for (int k = ((2 * KH) / 4) * 4; k < 2 * KH; ++k) reinterpret_cast<float*>(row4)[44 + k] = ou[k];
             for (uint32_t sc = d.n_sc; sc < kMaxSC; ++sc) scp_row[sc] = INFINITY;
+            // (INVARIANT the walk relies on: every writer of the hot row leaves the memo EMPTY — n_hot = 0 —, so k_walk2 sends a
+            // user's first draw of round 1 straight to the search without looking at the memo)
             *reinterpret_cast<float4*>(d.walk_hot + urow * 32) =
                 make_float4(static_cast<float>(run_pref), dlt * 1.000001f + 4.8e-7f, q, __builtin_bit_cast(float, 0u));
             d.walk_hot[urow * 32 + 31] = kRhoLoose;

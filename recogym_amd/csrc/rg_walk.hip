@@ -598,6 +598,8 @@ __global__ void __launch_bounds__(kBlock) k_cache_prefix(DevSim d, int fused) {
             if (gl == 0) {
                 // S~ as the search sees it (the last prefix), the certificate's delta + 2^-21 for the roundings of the stored
                 // prefixes (<= 5 of 2^-24 each, relative to the prefix: the same kind of error the budget is made of), Q, an empty memo
+                // (INVARIANT the walk relies on: every writer of the hot row leaves the memo EMPTY — n_hot = 0 —, so k_walk2 sends a
+                // user's first draw of round 1 straight to the search without looking at the memo)
                 float4* hot = reinterpret_cast<float4*>(d.walk_hot + row * 32);
                 hot[0] = make_float4(static_cast<float>(run), hdr.y * 1.000001f + 4.8e-7f, hdr.x, __builtin_bit_cast(float, 0u));
                 // (these prefixes went through several fp32 / rescaling roundings: rho = 2^-20.  Behind k_sweep_xh the records of a
@@ -681,12 +683,14 @@ __device__ __forceinline__ uint32_t exact_pick_call(const DevSim& d, const doubl
 
 // k_walk2's COMPACT history line (HIST == 2: products < 65 535, hist_cap <= 32 768): the same 128 bytes of LDS per lane hold
 // 32 words instead of 16 64-bit entries — word 0 the header (views << 15 | distinct), words 1 .. 31 the 31 smallest products as
-// (PREFIX << 16 | product): the running view count up to and including the product in the high half (a user has < 65 536
-// events), so the words ascend with the index, an unused word is 0xFFFFFFFF, and the policy's act — first product whose
-// cumulative count exceeds u x views — is a COUNT of words below a key: two LDS round trips (the last word of every 8-word
-// segment, then the segment) and ~40 vector instructions instead of a 10-instruction step per entry, and all but ~1 % of C3's
-// events find their whole history in the line (15 products in 64-bit entries: 11.6 % beyond).  Word w of the line is half
-// (w & 1) of the 64-bit LDS entry hl[(w >> 1) * 64]; the user's ROW keeps the (product, count) form every other kernel reads.
+// (product << 16 | PREFIX): the running view count up to and including the product in the low half (a user has < 65 536
+// events, so it never carries into the product), so the words ascend with the index — the products do —, an unused word is
+// 0xFFFFFFFF, the position of a viewed product v is a search with whole-word compares against v << 16, a view raises a prefix
+// by adding 1 to the word, and the policy's act — first product whose cumulative count exceeds u x views — is a COUNT of
+// low halves below a key: two LDS round trips (the last word of every 8-word segment, then the segment) and ~50 vector
+// instructions instead of a 10-instruction step per entry, and all but ~1 % of C3's events find their whole history in the
+// line (15 products in 64-bit entries: 11.6 % beyond).  Word w of the line is half (w & 1) of the 64-bit LDS entry
+// hl[(w >> 1) * 64]; the line is private to k_walk2: the user's ROW keeps the (product, count) form every other kernel reads.
 constexpr uint32_t kHcLine = 32;     // words of the compact line (header + 31 products)
 
 // Three blocks per CU (168 VGPRs, no spills).  Four (128 VGPRs) were measured in two forms — omega32 re-read from the cache
@@ -757,8 +761,8 @@ __global__ void __launch_bounds__(kBlock, (KH <= 10 ? 3 : 2)) k_walk2(DevSim d_a
                     const uint32_t w0 = static_cast<uint32_t>(x), w1 = static_cast<uint32_t>(x >> 32);
                     hent_t e0, e1;
                     if (i == 0) e0 = (static_cast<hent_t>(h0 >> 15) << 32) | nd;
-                    else { e0 = (static_cast<hent_t>(w0 & 0xFFFFu) << 32) | ((w0 >> 16) - prev); prev = w0 >> 16; }
-                    e1 = (static_cast<hent_t>(w1 & 0xFFFFu) << 32) | ((w1 >> 16) - prev); prev = w1 >> 16;
+                    else { e0 = (static_cast<hent_t>(w0 >> 16) << 32) | ((w0 & 0xFFFFu) - prev); prev = w0 & 0xFFFFu; }
+                    e1 = (static_cast<hent_t>(w1 >> 16) << 32) | ((w1 & 0xFFFFu) - prev); prev = w1 & 0xFFFFu;
                     if (static_cast<uint32_t>(2 * i) <= nd) hw[i] = make_ulonglong2(e0, e1);
                 }
             } else
@@ -771,6 +775,15 @@ __global__ void __launch_bounds__(kBlock, (KH <= 10 ? 3 : 2)) k_walk2(DevSim d_a
         // the compact line from the user's row (its first 32 entries): running prefixes of the counts, unused words all ones
         auto load_compact = [&](uint32_t s_row) {
             const ulonglong2* hr2 = reinterpret_cast<const ulonglong2*>(hist_row(d, s_row));
+            // the header first: where none of the lanes that load has a history — round 1, unless histories were preset after the
+            // reset — the line is empty and the other fifteen 16-byte loads of the row are not issued
+            const hent_t hd = hist_row(d, s_row)[0];
+            if (__ballot(h_cnt(hd) != 0u) == 0ull) {
+                hl[0] = static_cast<hent_t>((h_prod(hd) << 15) | h_cnt(hd)) | (0xFFFFFFFFull << 32);
+#pragma unroll
+                for (int i = 1; i < 16; ++i) hl[i * 64] = ~0ull;
+                return;
+            }
             uint32_t run = 0u, nd = 0u;
 #pragma unroll
             for (int b = 0; b < 16; b += 8) {           // (two batches of eight 16-byte loads: 32 registers in flight, not 64)
@@ -782,10 +795,10 @@ __global__ void __launch_bounds__(kBlock, (KH <= 10 ? 3 : 2)) k_walk2(DevSim d_a
                     uint32_t w0, w1;
                     const bool in0 = static_cast<uint32_t>(2 * (b + i)) <= nd || b + i == 0;
                     if (b + i == 0) { nd = h_cnt(x[0].x); w0 = (h_prod(x[0].x) << 15) | nd; }
-                    else { run += in0 ? h_cnt(x[i].x) : 0u; w0 = in0 ? ((run << 16) | h_prod(x[i].x)) : 0xFFFFFFFFu; }
+                    else { run += in0 ? h_cnt(x[i].x) : 0u; w0 = in0 ? ((h_prod(x[i].x) << 16) | (run & 0xFFFFu)) : 0xFFFFFFFFu; }
                     const bool in1 = static_cast<uint32_t>(2 * (b + i) + 1) <= nd;
                     run += in1 ? h_cnt(x[i].y) : 0u;
-                    w1 = in1 ? ((run << 16) | h_prod(x[i].y)) : 0xFFFFFFFFu;
+                    w1 = in1 ? ((h_prod(x[i].y) << 16) | (run & 0xFFFFu)) : 0xFFFFFFFFu;
                     hl[(b + i) * 64] = static_cast<hent_t>(w0) | (static_cast<hent_t>(w1) << 32);
                 }
                 asm volatile("" ::: "memory");
@@ -816,7 +829,10 @@ __global__ void __launch_bounds__(kBlock, (KH <= 10 ? 3 : 2)) k_walk2(DevSim d_a
                         uint32_t s2 = d.grp_lo + idx;
                         if (round >= 2) s2 = d.park_list[in_base + idx];
                         if (s2 != 0xFFFFFFFFu) {
-                            slot = s2; st = RG_STATE_ORGANIC; t = 0u; pend = false; hdirty = false;
+                            // (round 1: a new user, t = 0, and every writer of the hot row — the sweeps' finalize, k_cache_prefix — has
+                            // just left its memo empty: the first draw cannot be answered by it and goes straight to the search,
+                            // which loads the hot row itself.  A guaranteed miss never counted as a memo hit)
+                            slot = s2; st = kWSlow; t = 0u; pend = false; hdirty = false;
                             if (round >= 2) {
                                 const uint32_t pt = d.park_t[s2];
                                 t = pt & 0xFFFFFFu; st = static_cast<int>((pt >> 24) & 7u); pend = (pt >> 27) & 1u;
@@ -1252,7 +1268,8 @@ __global__ void __launch_bounds__(kBlock, (KH <= 10 ? 3 : 2)) k_walk2(DevSim d_a
             if (is_ban || is_ph) {
                 if (HIST == 2) {
                     // the same act on the COMPACT line (prefix form): the first product whose cumulative count exceeds u x views
-                    // = the number of words below the key (Thi + 1) << 16 — the last word of each 8-word segment, then the segment
+                    // = the number of words whose prefix (low half) is below the key Thi + 1 — the last word of each 8-word segment,
+                    // then the segment (11 masks more than whole-word compares took: the price of the view's cheaper insertion)
                     const rg_u32x4 pw = rg_draw(d.policy_seed, user, e_t, 0, RG_DRAW_POLICY);
                     const double u1 = rg_uniform(pw.w[2], pw.w[3]);
                     const hent_t* hr = hist_row(d, e_slot);
@@ -1265,8 +1282,8 @@ __global__ void __launch_bounds__(kBlock, (KH <= 10 ? 3 : 2)) k_walk2(DevSim d_a
                     const uint32_t Thi = static_cast<uint32_t>(fmin(floor(T * (1.0 + 0x1p-36)), 4294967295.0));
                     const uint32_t Tlo = static_cast<uint32_t>(fmin(ceil(T * (1.0 - 0x1p-36)), 4294967295.0));
                     const bool over = Thi >= 65535u;                                     // (u x views at the top of the range: no entry exceeds it)
-                    const uint32_t khi = over ? 0u : (Thi + 1u) << 16;                   // prefix <= Thi  <=>  word < khi
-                    const uint32_t seg = (p7 < khi ? 1u : 0u) + (p15 < khi ? 1u : 0u) + (p23 < khi ? 1u : 0u);
+                    const uint32_t khi = over ? 0u : Thi + 1u;                           // prefix <= Thi  <=>  low half < khi (unused: 0xFFFF)
+                    const uint32_t seg = ((p7 & 0xFFFFu) < khi ? 1u : 0u) + ((p15 & 0xFFFFu) < khi ? 1u : 0u) + ((p23 & 0xFFFFu) < khi ? 1u : 0u);
                     uint32_t x[8];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
@@ -1276,7 +1293,7 @@ __global__ void __launch_bounds__(kBlock, (KH <= 10 ? 3 : 2)) k_walk2(DevSim d_a
                     if (seg == 0u) x[0] = 0u;                                             // (the header: counted, prefix 0)
                     uint32_t in_seg = 0u;
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) in_seg += x[j] < khi ? 1u : 0u;
+                    for (int j = 0; j < 8; ++j) in_seg += (x[j] & 0xFFFFu) < khi ? 1u : 0u;
                     const uint32_t idx = seg * 8u + in_seg;                              // first entry with prefix > Thi (32: none in the line)
                     // its word and the one before it (the entry before a segment's first: the segment end read above)
                     uint32_t w_at = 0xFFFFFFFFu, w_prev = seg == 0u ? 0u : (seg == 1u ? p7 : (seg == 2u ? p15 : p23));
@@ -1287,10 +1304,10 @@ __global__ void __launch_bounds__(kBlock, (KH <= 10 ? 3 : 2)) k_walk2(DevSim d_a
                     }
                     bool found = !over && idx <= nd && idx < kHcLine;
                     // an entry inside the 2^-36 band of u x views: only the last one at or below Thi can be (prefixes ascend)
-                    bool amb = idx >= 2u && (w_prev >> 16) >= Tlo;
-                    uint32_t c_f = (w_at >> 16) - (idx >= 2u ? (w_prev >> 16) : 0u);
-                    a = w_at & 0xFFFFu;
-                    uint32_t C = p31 >> 16;                                              // (nd >= 31: the line's last prefix)
+                    bool amb = idx >= 2u && (w_prev & 0xFFFFu) >= Tlo;
+                    uint32_t c_f = (w_at & 0xFFFFu) - (idx >= 2u ? (w_prev & 0xFFFFu) : 0u);
+                    a = w_at >> 16;
+                    uint32_t C = p31 & 0xFFFFu;                                            // (nd >= 31: the line's last prefix)
                     // (a helper leaves a history beyond the line to its owner: with 64 lanes evaluating, half the iterations had
                     // some lane in this loop)
                     for (uint32_t base = kHcLine; base <= nd && !found && !helper; base += kHistRegs) {      // longer histories: from the row
@@ -1311,9 +1328,9 @@ __global__ void __launch_bounds__(kBlock, (KH <= 10 ? 3 : 2)) k_walk2(DevSim d_a
                         auto ent = [&](uint32_t i, uint32_t* prev) -> hent_t {       // (product, count) of entry i, walked in order
                             if (i >= kHcLine) return hr[i];
                             const uint32_t w = hw32[(i >> 1) * 128 + (i & 1u)];
-                            const uint32_t cnt = (w >> 16) - *prev;
-                            *prev = w >> 16;
-                            return (static_cast<hent_t>(w & 0xFFFFu) << 32) | cnt;
+                            const uint32_t cnt = (w & 0xFFFFu) - *prev;
+                            *prev = w & 0xFFFFu;
+                            return (static_cast<hent_t>(w >> 16) << 32) | cnt;
                         };
                         double last = 0.0;
                         uint32_t pv = 0u;
@@ -1533,42 +1550,55 @@ __global__ void __launch_bounds__(kBlock, (KH <= 10 ? 3 : 2)) k_walk2(DevSim d_a
                     }
                     const uint32_t h0 = e[0];
                     const uint32_t nd = h0 & 0x7FFFu;
-                    // first entry with product >= v (min(nd, 31) + 1 if none: an unused word holds 0xFFFF, above every product);
-                    // the products ascend, so v is in the line iff it is the product of that entry (one more look at the line)
-                    uint32_t pos = 1;
+                    // first entry with product >= v (min(nd, 31) + 1 if none: an unused word is above every key): the words ascend, so
+                    // a binary search over the 31 words in registers — at step L the word to test is picked by the L decisions before
+                    // it (26 selects and 5 whole-word compares against v << 16 in all, not a compare and an add per word)
+                    const uint32_t key = v << 16;
+                    bool below[5];
 #pragma unroll
-                    for (int i = 1; i < static_cast<int>(kHcLine); ++i) pos += static_cast<uint16_t>(e[i]) < static_cast<uint16_t>(v) ? 1u : 0u;
+                    for (int L = 0; L < 5; ++L) {
+                        const int s = 16 >> L;
+                        uint32_t c[16];
+#pragma unroll
+                        for (int j = 0; j < (1 << L); ++j) c[j] = e[s * (2 * j + 1)];
+#pragma unroll
+                        for (int k = L - 1; k >= 0; --k) {
+#pragma unroll
+                            for (int j = 0; j < (1 << k); ++j) c[j] = below[k] ? c[2 * j + 1] : c[2 * j];
+                        }
+                        below[L] = c[0] < key;
+                    }
+                    const uint32_t pos = 1u + (below[0] ? 16u : 0u) + (below[1] ? 8u : 0u) + (below[2] ? 4u : 0u) + (below[3] ? 2u : 0u) + (below[4] ? 1u : 0u);
+                    // the products ascend, so v is in the line iff it is the product of that entry; the entry before it gives a new
+                    // product its prefix (one more look at the line for both: the words below pos do not change)
                     uint32_t* hw32 = reinterpret_cast<uint32_t*>(hl);           // word w of this lane's line: hw32[(w >> 1) * 128 + (w & 1)]
                     const uint32_t wp = pos < kHcLine ? hw32[(pos >> 1) * 128u + (pos & 1u)] : 0xFFFFFFFFu;
-                    const bool hit = (wp & 0xFFFFu) == v;
+                    const uint32_t wq = hw32[((pos - 1u) >> 1) * 128u + ((pos - 1u) & 1u)];
+                    const bool hit = (wp >> 16) == v;
                     const bool room = nd < kHcLine - 1u;
                     if (hit || room) {
                         const bool full = !hit && nd + 1 >= d.hist_cap;
                         if (full) atomicAdd(&d.counters[RG_CNT_HIST_OVERFLOW], 1ull);
-                        // new word i: below pos unchanged; from pos on raised by the view (a repeat view), or — a new product —
-                        // the old word below it raised (entries pos + 1 .. nd + 1; its own word is written last).  Which words
-                        // are raised / shifted: two bit masks per lane, two instructions per word each
-                        const uint32_t last = min(hit ? nd : nd + 1u, kHcLine - 1u);          // last entry of the line in use after the view
-                        const uint32_t upto = 0xFFFFFFFFu >> (31u - last), from = 0xFFFFFFFFu << pos;      // (pos <= 31 here)
-                        const uint32_t shifted = (full || hit) ? 0u : (upto & (from << 1));
-                        const uint32_t raised = full ? 0u : (hit ? (upto & from) : shifted);
+                        // new word i: below pos unchanged; from pos on raised by the view (a repeat view), or — a new product — the
+                        // old word below it raised (entries pos + 1 .. nd + 1; its own word is written last).  So from `from` on, word
+                        // i is the word that moves there — one select per word on `fresh`, the same mask for all —, raised: a compare
+                        // of `from` against an immediate picks it.  The add saturates: an unused word stays all ones
+                        const bool fresh = !hit && !full;
+                        const uint32_t from = full ? 2u * kHcLine : pos + (fresh ? 1u : 0u);          // (full: the line is left alone)
                         auto word = [&](int i) -> uint32_t {
                             if (i == 0) return full ? h0 : h0 + (1u << 15) + (hit ? 0u : 1u);
-                            const uint32_t x = ((shifted >> i) & 1u) ? e[i - 1] : e[i];
-                            return x + (((raised >> i) & 1u) << 16);
+                            const uint32_t x = (i >= 2 && fresh) ? e[i - 1] : e[i];
+                            return from <= static_cast<uint32_t>(i) ? __builtin_elementwise_add_sat(x, 1u) : e[i];
                         };
 #pragma unroll
                         for (int i = 15; i >= 0; --i) {       // (from the top: word i reads e[i - 1], nothing above it)
                             const uint32_t f0 = word(2 * i), f1 = word(2 * i + 1);
                             hl[i * 64] = static_cast<hent_t>(f0) | (static_cast<hent_t>(f1) << 32);
                         }
-                        if (!hit && !full) {
-                            // the new product's own word: the prefix of the entry before it (unchanged above; 0 before the first) + 1
-                            const uint32_t wq = pos > 1u ? hw32[((pos - 1u) >> 1) * 128u + ((pos - 1u) & 1u)] : 0u;
-                            hw32[(pos >> 1) * 128u + (pos & 1u)] = ((wq & 0xFFFF0000u) + 0x10000u) | v;
-                        }
+                        // the new product's own word: the prefix of the entry before it (0 before the first) + 1
+                        if (fresh) hw32[(pos >> 1) * 128u + (pos & 1u)] = key | ((pos > 1u ? (wq & 0xFFFFu) : 0u) + 1u);
                         hdirty = true;
-                    } else if (v > (e[kHcLine - 1] & 0xFFFFu)) {
+                    } else if (v > (e[kHcLine - 1] >> 16)) {
                         // a longer history, v behind the line's 31 products: entries >= 32 of the row (always current), the
                         // header in LDS — one round trip, nothing to read back
                         if (nd + 1 >= d.hist_cap) {

@@ -1,0 +1,168 @@
+"""k_walk2's compact view-history line (words product << 16 | running prefix) and the cold start of a round-1 user, against the
+oracle in Philox mode: sigma_omega = 0, K = 20, the OrganicUserEventCounter policy, every row and counter exact (float64 ps too).
+
+Shapes: few products (seven views of eight are repeats: prefixes raised across the line), many products (a quarter of the
+views insert a new product — at the front, in the middle, behind the last entry — and the longest histories pass the line's 31
+products: the line-full boundary, history_tail_add, the general insertion on the row), histories preset before the run (a
+refill that has to load rows; lines that start full or behind a longer history; a first act on a preset history), and a
+population below the pipeline's threshold (the same kernel behind the other host path).  The popularity of this environment
+is concentrated: at 40 products no user of 4 096 gets beyond 13 distinct ones, so the full line is the other shapes' part."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import adversarial_util as au
+import golden_util as gu
+from recogym_amd import _abi
+from recogym_amd.envs.configuration import Configuration
+from recogym_amd.envs.reco_env_v1 import env_1_args
+from test_hip_parity import assert_walk_pipe, run_sim
+
+pytestmark = pytest.mark.gpu
+
+K = 20
+POL = dict(policy=_abi.RG_POLICY_ORGANIC_USER_COUNT, policy_seed=31, ouc=dict(gu.OUC_DEFAULTS))
+COLS = ('u', 't', 'z', 'v', 'a', 'c', 'ps')
+
+
+def config(P, seed):
+    return Configuration({**env_1_args, 'random_seed': seed, 'num_products': P, 'K': K, 'sigma_omega': 0.0})
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_log(P, n, seed):
+    """(rows, counters) of the oracle's own run of n users; computed once per shape, read-only."""
+    from oracle import oracle as orc
+    env = orc.OracleEnv(config(P, seed), rng_mode=orc.RNG_PHILOX, **POL)
+    rows = env.generate_logs(n)
+    rows.setflags(write=False)
+    return rows, env.counters()
+
+
+def assert_exact(rows, cnt, want, oc, what):
+    gu.assert_rows_equal(rows, {k: want[k] for k in COLS}, ps_rtol=0.0, what=what)
+    assert (rows['phantom'] == want['phantom']).all()
+    assert (cnt['organic'], cnt['bandit'], cnt['clicks'], cnt['phantom']) == (oc['organic'], oc['bandit'], oc['clicks'], oc['phantom'])
+    assert cnt['live'] == 0 and cnt['log_dropped'] == 0 and cnt['hist_overflow'] == 0
+
+
+def distinct_per_user(want):
+    """number of distinct products each user of the oracle's log has viewed"""
+    org = want[want['z'] == 0]
+    pairs = np.unique(np.stack([org['u'].astype(np.int64), org['v'].astype(np.int64)], axis=1), axis=0)
+    return np.bincount(pairs[:, 0])
+
+
+@pytest.mark.parametrize('P,seed', [(40, 7101), (2000, 7102)], ids=['P40_repeats', 'P2000_new_products'])
+def test_pipelined_walk_on_the_compact_line_matches_the_oracle(P, seed, monkeypatch):
+    """4 096 users through run_walk_pipe.  P = 40: nearly every view raises prefixes; P = 2 000: new products all over the
+    range, and histories that grow through the line's last word into the row behind it."""
+    monkeypatch.setenv('RECOGYM_PIPE_MIN', '256')
+    n = 4096
+    want, oc = oracle_log(P, n, seed)
+    nd = distinct_per_user(want)
+    if P == 40:
+        assert nd.sum() < 0.2 * oc['organic']                                  # repeats
+    else:
+        assert nd.sum() > 0.2 * oc['organic'] and (nd > 32).sum() >= 3        # new products; through the full line and beyond
+    rows, cnt, led = run_sim(config(P, seed), n, 0, p_click=False, with_ledger=True, **POL)
+    assert_walk_pipe(led)
+    assert_exact(rows, cnt, want, oc, f'compact line P={P}')
+
+
+def test_serial_walk_on_the_compact_line_matches_the_oracle(monkeypatch):
+    """300 users, the pipeline's threshold as it comes (131 072 users): run_walk launches the same k_walk2."""
+    monkeypatch.delenv('RECOGYM_PIPE_MIN', raising=False)
+    P, n, seed = 300, 300, 7103
+    want, oc = oracle_log(P, n, seed)
+    rows, cnt, led = run_sim(config(P, seed), n, 0, p_click=False, with_ledger=True, **POL)
+    assert led['walk2'] >= 1 and led['sweep_xh'] == led['walk'] == led['advance'] == led['advance_run'] == 0, led
+    assert_exact(rows, cnt, want, oc, 'compact line, run_walk')
+
+
+def preset_histories(P, n, seed):
+    """0, 1, 31 and 40 distinct products (ascending) with 1 .. 5 views each, spread over the users"""
+    rng = np.random.RandomState(seed)
+    nd = np.array([0, 1, 31, 40], dtype=np.uint32)[rng.randint(0, 4, n)]
+    stride = 48
+    prod = np.zeros((n, stride), dtype=np.uint32)
+    cnt = np.zeros((n, stride), dtype=np.uint32)
+    for i in range(n):
+        k = int(nd[i])
+        prod[i, :k] = np.sort(rng.choice(P, k, replace=False))
+        cnt[i, :k] = rng.randint(1, 6, k)
+    return nd, prod, cnt, stride
+
+
+def oracle_log_with_presets(cfg, n, nd, prod, cnt):
+    """The oracle's environment (reset / step) driven user by user with OrganicUserEventCounterModel.act
+    (organic_user_count.py:45-96: epsilon = 0, exploit_explore, select_randomly — p = counts / sum, cumsum, / last,
+    searchsorted 'right', ps = p[a]) on view counts that start at the preset ones; the act's uniform is the policy draw of
+    (user, t), words 2 and 3.  A user without a preset: the oracle's own generate_logs."""
+    from oracle import oracle as orc
+    env = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **POL)
+    seed = int(env.rg_config.policy_seed)
+    key = (seed & 0xFFFFFFFF, seed >> 32)
+    uniform = orc.lib().rgo_uniform
+    P = cfg.num_products
+    out = []
+
+    def act(views, user, t):
+        w = orc.philox((user, t, 0, 1), key)                        # RG_DRAW_POLICY = 1
+        u1 = uniform(int(w[2]), int(w[3]))
+        p = views / np.sum(views)
+        cdf = p.cumsum()
+        cdf /= cdf[-1]
+        a = int(cdf.searchsorted(u1, side='right'))
+        return a, p[a]
+
+    for user in range(n):
+        if nd[user] == 0:
+            for r in env.generate_logs(1, 0, first_user_id=user):
+                out.append((r['u'], r['t'], r['z'], r['v'], r['a'], r['c'], r['ps'], r['phantom']))
+            continue
+        views = np.zeros(P)
+        views[prod[user, :nd[user]]] = cnt[user, :nd[user]]
+        env.reset(user)
+        org, _, done = env.step(None)
+        while True:
+            for r in org:
+                out.append((user, r['t'], 0, r['v'], -1, -1, np.nan, 0))
+                views[r['v']] += 1.0
+            t = env.time
+            a, ps = act(views, user, t)
+            if done:
+                out.append((user, t, 1, -1, a, 0, ps, 1))            # the act of the last step_offline: the phantom row
+                break
+            org, reward, done = env.step(a)
+            out.append((user, t, 1, -1, a, reward, ps, 0))
+    dt = np.dtype([('u', np.int64), ('t', np.int64), ('z', np.int64), ('v', np.int64), ('a', np.int64), ('c', np.int64),
+                   ('ps', np.float64), ('phantom', np.int64)])
+    return np.array(out, dtype=dt)
+
+
+def test_preset_histories_on_the_compact_line_match_the_oracle(monkeypatch):
+    """2 048 users whose histories are written through rg_sim_debug_set_history after the reset: the refill loads rows (some
+    lanes have a history), lines that start full, histories that start beyond the line, and a first act on a preset history.
+    The oracle keeps no preset, so its environment is stepped with the reference's act on the preset counts (see above)."""
+    from recogym_amd.sim import Simulator
+    monkeypatch.setenv('RECOGYM_PIPE_MIN', '256')
+    P, n, seed = 300, 2048, 7104
+    cfg = config(P, seed)
+    nd, prod, cnt_h, stride = preset_histories(P, n, seed)
+    assert all((nd == k).sum() > n // 8 for k in (0, 1, 31, 40))
+    want = oracle_log_with_presets(cfg, n, nd, prod, cnt_h)
+    sim = Simulator(cfg, n, device='cuda:0', p_click=False, **POL)
+    sim.reset_users(0, n)
+    d_nd, d_p, d_c = (torch.from_numpy(x.view(np.int32)).to('cuda:0') for x in (nd, prod, cnt_h))
+    _abi.check(sim.lib.rg_sim_debug_set_history(sim._h, d_nd.data_ptr(), d_p.data_ptr(), d_c.data_ptr(), stride, sim._stream()),
+               'debug_set_history')
+    sim.run()
+    rows, cnt, led = sim.rows(), sim.counters(), au.ledger(sim)
+    sim.close()
+    assert_walk_pipe(led)
+    ban = (want['z'] == 1) & (want['phantom'] == 0)
+    oc = dict(organic=int((want['z'] == 0).sum()), bandit=int(ban.sum()), clicks=int(want['c'][ban].sum()), phantom=n)
+    assert_exact(rows, cnt, want, oc, 'preset histories')
