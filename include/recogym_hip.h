@@ -189,7 +189,8 @@ int rg_sim_destroy(rg_sim* sim);
 
 /* Run-path tuning knobs by name (none changes a result or the workspace layout; the defaults are the measured optima, DESIGN.md
  * §4 / §9).  rg_sim_create takes their initial values from the RECOGYM_* environment variables of the same meaning (the A/B
- * tests' way in); after that the library never reads the environment on the run path.  Names: walk_bias, walk_refill,
+ * tests' way in; rg_sim_workspace_bytes and rg_sim_create each read the environment once, as one record, so set the variables before
+ * the pair of calls); after that the library never reads the environment.  Names: walk_bias, walk_refill,
  * walk_handover, walk_click_batch, walk_search_batch, walk_helpers (0 .. 7), walk_click_join, walk_line64, pipe_groups (1: the walked
  * run keeps its list lengths on the device; 0: the host reads them back), pipe_occ1, pipe_occ2, pipe_xblocks,
  * pipe_min_users, exact_mix, exact_tile, slices (-1 = by population), sweep_prefix_off, tail_below,
@@ -207,7 +208,14 @@ int rg_sim_destroy(rg_sim* sim);
  * (the ordered log's scatter).  What rg_sim_create chose for the fast draw: draw_kh, draw_n1 (the class: KH, k-steps N1),
  * draw_split (0 none, 1 three-way bf16, 2 two-way fp16, 3 two-way fp16 wide), draw_kernel (0 float64 only, 1 fp32 MFMA, 2 a 16-bit
  * sweep), draw_pipelined (1: that sweep is k_draw_bf16p), xh_class (100 KH + 10 NH + NL of k_sweep_xh where it serves the walked
- * run, else 0) and xh_waves (its waves per block, else 0).  Setting any of them fails like an unknown name.
+ * run, else 0) and xh_waves (its waves per block, else 0).  What else rg_sim_create decided (tests/test_create_plan.py pins all of
+ * it): walk_form (0 lock-step, 1 k_walk, 2 k_walk2), walk_occ (blocks per CU the walk kernel is compiled for), walk_solo (the last
+ * round is k_walk_solo's), use_cache (the per-user sum cache is in use), fin_in_sweep (the sweep leaves the finalize output itself),
+ * handover_auto (walk_handover follows the reset range), draw_smem / mfma_smem / xh_smem / tp_smem (dynamic LDS bytes of the 16-bit
+ * sweep, k_draw_mfma, k_sweep_xh, k_draw_tp / k_draw_tpw), tp_nts (LDS row stride of a user's tile prefixes), tp_cpt (chunks per tile
+ * of the wide sweep), draw_threads (block size of the draw kernel), exact_rows (rows of the float64 chunk-sum scratch), hist_cap
+ * (history entries per user row), repack_min (users below which slot == user index), ablate (timing-experiment bits).
+ * Setting any of them fails like an unknown name.
  * RG_EINVAL for an unknown name or a value out of range. */
 int rg_sim_set_option(rg_sim* sim, const char* name, int64_t value);
 int rg_sim_get_option(rg_sim* sim, const char* name, int64_t* value);

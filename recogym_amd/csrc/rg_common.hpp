@@ -76,11 +76,7 @@ constexpr uint32_t kPolyListCap = 4096;        // unresolved acts of a run the d
 constexpr uint32_t kPolySteps = 1024;          // expit steps the table holds at most (8 KB of LDS)
 // the policies that act on the view history through the lr_* act list (k_logreg_select)
 inline bool lr_family(uint32_t policy) { return policy == RG_POLICY_LOGREG_FROZEN || policy == RG_POLICY_LOGREG_POLY; }
-// runs smaller than this keep slot == user index throughout (RECOGYM_REPACK_MIN overrides: tests)
-inline uint64_t repack_min_users() {
-    const char* e = getenv("RECOGYM_REPACK_MIN");
-    return e ? static_cast<uint64_t>(strtoull(e, nullptr, 10)) : (1ull << 18);
-}
+constexpr uint64_t kRepackMinUsers = 1ull << 18;   // runs smaller than this keep slot == user index throughout (RECOGYM_REPACK_MIN overrides: tests)
 
 inline thread_local char g_err[512] = "";
 
@@ -325,8 +321,52 @@ struct DevSim {
 }  // namespace rgk
 using namespace rgk;
 
-// Run-path options: every switch the launch code consults, read ONCE (rg_sim_create, from the RECOGYM_* environment: the A/B
-// tests' way in) and settable through rg_sim_set_option — no getenv on the run path.
+// The RECOGYM_* environment (the A/B tests' way in; what each variable means and what it measured: DESIGN.md §9, HISTORY.md §9) as
+// one record: rg_sim_workspace_bytes and rg_sim_create each read it ONCE (read_switches, the library's only getenv) and size,
+// carve and plan from that one record.  A Switch: whether the variable was set, its first character and atoi of it.
+struct Switch {
+    bool set = false; char c0 = '\0'; int num = 0;
+    bool is(char c) const { return set && c0 == c; }  uint32_t u32() const { return static_cast<uint32_t>(num); }
+};
+#define RG_SWITCHES(X) \
+    X(exact_tile, "EXACT_TILE") X(exact_mix, "EXACT_MIX") X(slices, "SLICES") X(sweep_prefix_off, "SWEEP_PREFIX_OFF") /* RunOpts */ \
+    X(debug, "DEBUG") X(walk_hist, "WALK_HIST")                          /* =1: the 64-bit view-history line in k_walk2 */ \
+    X(force_exact, "FORCE_EXACT")                                        /* =1: the float64 kernels draw */ \
+    X(f16w, "F16W") X(xh, "XH") X(cache, "CACHE")                        /* =0: no k_draw_f16w class / k_sweep_xh class / per-user sum cache (sizing) */ \
+    X(xh_waves, "XH_WAVES") X(xh_smem_pad, "XH_SMEM_PAD") X(lds_pad, "LDS_PAD")   /* k_sweep_xh's block (4 | 8 waves); extra LDS bytes: occupancy experiments */ \
+    X(sweep_lds, "SWEEP_LDS")                                            /* =0: k_draw_bf16p / k_draw_f16w where k_draw_tp / k_draw_tpw would serve */ \
+    X(walk, "WALK")                                                      /* =0: lock-step, =1: k_walk where k_walk2 would serve */ \
+    X(walk_handover, "WALK_HANDOVER") X(walk_click_batch, "WALK_CLICK_BATCH") X(walk_click_join, "WALK_CLICK_JOIN") \
+    X(walk_helpers, "WALK_HELPERS") X(walk_search_batch, "WALK_SEARCH_BATCH") X(walk_refill, "WALK_REFILL") X(walk_bias, "WALK_BIAS") \
+    X(walk_solo, "WALK_SOLO")                                            /* =0: the last round is k_walk2's */ \
+    X(pipe, "PIPE")                                                      /* =0: run_walk (list lengths read back by the host) */ \
+    X(pipe_occ1, "PIPE_OCC1") X(pipe_occ2, "PIPE_OCC2") X(pipe_xblocks, "PIPE_XBLOCKS") X(pipe_min, "PIPE_MIN") \
+    X(fin_in_sweep, "FIN_IN_SWEEP") X(tail, "TAIL") X(repack, "REPACK") X(run_ahead, "RUN_AHEAD") X(lr_part_cap, "LR_PART_CAP") \
+    X(ablate, "ABLATE")                                                  /* timing-experiment bits (results wrong by design) */ \
+    X(sort_plain, "SORT_PLAIN")                                          /* set: the ordered log's scatter without the LDS tiles */
+struct Switches {
+#define RG_SWITCH_FIELD(f, name) Switch f;
+    RG_SWITCHES(RG_SWITCH_FIELD)
+#undef RG_SWITCH_FIELD
+    enum Draw { kDrawAuto, kDrawF64, kDrawFp32, kDrawBf16, kDrawF16 };
+    Draw draw = kDrawAuto;                          // RECOGYM_DRAW=f64|fp32|bf16|f16 (anything else: as if unset)
+    bool bf16_lean = false;                         // RECOGYM_BF16=lean: the one-accumulator three-way bf16 kernel
+    uint64_t repack_min = rgk::kRepackMinUsers;     // RECOGYM_REPACK_MIN
+};
+inline Switches read_switches() {
+    Switches w;
+    const auto rd = [](const char* name) { Switch s; if (const char* e = getenv(name)) { s.set = true; s.c0 = e[0]; s.num = atoi(e); } return s; };
+#define RG_SWITCH_READ(f, name) w.f = rd("RECOGYM_" name);
+    RG_SWITCHES(RG_SWITCH_READ)
+#undef RG_SWITCH_READ
+    const char* const draws[] = {"", "f64", "fp32", "bf16", "f16"};      // (in the order of Switches::Draw)
+    if (const char* e = getenv("RECOGYM_DRAW")) for (int i = 1; i < 5; ++i) if (!strcmp(e, draws[i])) w.draw = static_cast<Switches::Draw>(i);
+    if (const char* e = getenv("RECOGYM_BF16")) w.bf16_lean = !strcmp(e, "lean");
+    if (const char* e = getenv("RECOGYM_REPACK_MIN")) w.repack_min = static_cast<uint64_t>(strtoull(e, nullptr, 10));
+    return w;
+}
+
+// Run-path options: every switch the launch code consults, taken from the record at rg_sim_create, settable through rg_sim_set_option
 struct RunOpts {
     int exact_tile;          // RECOGYM_EXACT_TILE: the K > 64 tile kernel for every float64 resolve
     int exact_mix;           // RECOGYM_EXACT_MIX: groups of every 8 of the walk's float64 batch in the matrix form (8 = all)
@@ -382,6 +422,7 @@ struct rg_sim {
     // rg_sim_debug_walk_fate: where the last walked run left the list of its last round (null: there was none)
     uint32_t fate_base; const unsigned long long* fate_count;
     uint32_t repack_every;    // steps between repacks (RECOGYM_REPACK, 0 = never)
+    bool sort_plain;          // rg_sim_sort_log scatters without the LDS tiles (RECOGYM_SORT_PLAIN: A/B)
     uint32_t tail_below;      // rg_sim_run hands the run to k_tail once at most this many users live (RECOGYM_TAIL, 0 = never)
     uint32_t* h_pinned;       // 4 x u32 staging for the live-count readback
     char* h_step;             // 128 pinned bytes of rg_sim_step_user: the action going down, the packed result coming back
@@ -497,14 +538,21 @@ constexpr uint32_t kMaxWalkWaves = 4096;
 constexpr uint32_t kParkSlack = 2u * 64u * kMaxWalkWaves;
 constexpr uint32_t kWalkCtlWords = 16;
 
-struct Geom { uint32_t KH, KS, TP, P_pad, n_chunks, sc_chunks, n_sc, N1, N2, N3, RS, TPB, F16, XNH, XNL, XRS; };
+// the draw kernels' classes and tile shapes for a configuration, and the sizing decisions that follow from them and the switches: cache (the
+// per-user sum cache exists), all_f64 (every draw a float64 sweep), repack (a second copy of the per-user state), tp (k_draw_tp's records)
+struct Geom { uint32_t KH, KS, TP, P_pad, n_chunks, sc_chunks, n_sc, N1, N2, N3, RS, TPB, F16, XNH, XNL, XRS; bool cache, all_f64, repack, tp; };
 
-inline Geom geom_of(const rg_config& c) {
+// k_draw_tp's / k_draw_tpw's classes (tp_kernel_for), every draw a sweep; k_draw_tp: a user's <= 128 tile prefixes in LDS
+inline bool tp_class_exists(const Geom& g) { return (g.F16 == 1 && g.KH <= 10 && g.n_chunks / 4 <= kTpBins) || g.F16 == 2; }
+
+inline Geom geom_of(const rg_config& c, uint64_t n, const Switches& sw) {
     Geom g{};
+    g.all_f64 = sw.draw == Switches::kDrawF64 || sw.force_exact.is('1');
+    g.repack = n >= sw.repack_min;                  // small runs never repack: no second copy
     const uint32_t need = (c.K + 1) / 2;
     const uint32_t opts[] = {4, 10, 16, 32, 64};
     for (uint32_t o : opts) if (!g.KH && need <= o) g.KH = o;
-    if (!g.KH) return g;                            // K > 128: float64 kernel only
+    if (!g.KH) { g.all_f64 = true; return g; }      // K > 128: float64 kernel only
     g.KS = 2 * g.KH;
     while (g.KS % 4 != 2) ++g.KS;
     g.TP = 256;
@@ -522,17 +570,14 @@ inline Geom geom_of(const rg_config& c) {
             }
         // two-way fp16 split (one MFMA group: A = [G1|G2|G1|..|1], B = [w1|w1|w2|..|-q]) where 3K + 1 columns fit
         // 64 and a kernel exists for (KH, N1); RECOGYM_DRAW=bf16 / RECOGYM_BF16=lean keep the three-way bf16 split
-        const char* e_draw = getenv("RECOGYM_DRAW");
-        const char* e_lean = getenv("RECOGYM_BF16");
-        const bool want_f16 = !(e_draw && !strcmp(e_draw, "bf16")) && !(e_lean && !strcmp(e_lean, "lean"));
+        const bool want_f16 = sw.draw != Switches::kDrawBf16 && !sw.bf16_lean;
         if (want_f16 && 3 * c.K + 1 <= 64 && g.KH <= 16) {
             g.F16 = 1;
             g.N1 = (3 * c.K + 1 + 15) / 16; g.N2 = 0; g.N3 = 0;
         }
         // wide embeddings (21 < K <= 64): the same two-way fp16 split, k_draw_f16w (N1 classes 7 / 10 / 13 k-steps,
         // tiles of one pair of chunks); RECOGYM_F16W=0 keeps the older choice (bf16 classes / fp32 MFMA)
-        const char* e_w = getenv("RECOGYM_F16W");
-        if (want_f16 && !g.F16 && c.K > 21 && c.K <= 64 && (g.KH == 16 || g.KH == 32) && !(e_w && e_w[0] == '0')) {
+        if (want_f16 && !g.F16 && c.K > 21 && c.K <= 64 && (g.KH == 16 || g.KH == 32) && !sw.f16w.is('0')) {
             g.F16 = 2;
             g.N1 = 3 * c.K + 1 <= 112 ? 7 : (3 * c.K + 1 <= 160 ? 10 : 13); g.N2 = 0; g.N3 = 0;
         }
@@ -542,38 +587,29 @@ inline Geom geom_of(const rg_config& c) {
         }
     }
     // k_sweep_xh classes (exact group: K + 3 slots of 16 NH; residual group: 4 K slots of 16 NL); RECOGYM_XH=0: A/B tests
-    if (g.F16 == 1 && (g.KH == 4 || g.KH == 10)) {
-        const char* e_x = getenv("RECOGYM_XH");
-        if (!(e_x && e_x[0] == '0')) {
-            g.XNH = g.KH == 4 ? 1 : 2; g.XNL = g.KH == 4 ? 2 : 5;
-            if (c.K + 3 > 16 * g.XNH || 4 * c.K > 16 * g.XNL) g.XNH = g.XNL = 0;
-            g.XRS = g.XNH ? 32 * (g.XNH + g.XNL) + 16 : 0;
-        }
+    if (g.F16 == 1 && (g.KH == 4 || g.KH == 10) && !sw.xh.is('0')) {
+        g.XNH = g.KH == 4 ? 1 : 2; g.XNL = g.KH == 4 ? 2 : 5;
+        if (c.K + 3 > 16 * g.XNH || 4 * c.K > 16 * g.XNL) g.XNH = g.XNL = 0;
+        g.XRS = g.XNH ? 32 * (g.XNH + g.XNL) + 16 : 0;
     }
     g.sc_chunks = (g.n_chunks + kMaxSC - 1) / kMaxSC;
     g.sc_chunks = (g.sc_chunks + 3) & ~3u;
     g.n_sc = (g.n_chunks + g.sc_chunks - 1) / g.sc_chunks;
+    // the per-user sum cache exists where omega cannot change (sigma_omega == 0) and a 16-bit MFMA kernel class serves K
+    // (RECOGYM_CACHE=0: A/B tests)
+    g.cache = c.sigma_omega == 0.0 && g.N1 != 0 && !sw.cache.is('0');
+    g.tp = tp_class_exists(g) && !g.cache;
     return g;
-}
-
-// the per-user sum cache exists where omega cannot change (sigma_omega == 0) and a 16-bit MFMA kernel class serves K
-// (RECOGYM_CACHE=0: A/B tests)
-inline bool cache_wanted(const rg_config& c, const Geom& g) {
-    const char* e = getenv("RECOGYM_CACHE");
-    return c.sigma_omega == 0.0 && g.N1 != 0 && !(e && e[0] == '0');
 }
 
 // The chunk-major fp32 copy of Gamma (gamma32t): the recompute of a draw's chunk reads it as one 128-byte run per k and user
 // (eight lanes per user); the row-major gather it replaces was address-rate-bound.  The walk's and the cached draw's searches
 // need it, and the lock-step search of K <= 32 uses it too.
-inline bool gamma32t_wanted(const rg_config& c, const Geom& g) { return g.KH != 0 && (cache_wanted(c, g) || g.KH <= 16); }
+inline bool gamma32t_wanted(const Geom& g) { return g.KH != 0 && (g.cache || g.KH <= 16); }
 
 // rows of the float64 chunk-sum scratch (see DevSim::exact_rows)
-inline size_t exact_rows_of(const rg_config& c, const Geom& g, uint64_t n) {
-    const char* e = getenv("RECOGYM_DRAW");
-    const char* f = getenv("RECOGYM_FORCE_EXACT");
-    const bool all_f64 = !g.KH || (e && !strcmp(e, "f64")) || (f && f[0] == '1');
-    if (cache_wanted(c, g) || all_f64) return n;
+inline size_t exact_rows_of(const Geom& g, uint64_t n) {
+    if (g.cache || g.all_f64) return n;
     const uint64_t r = n / 8;
     return r < 4096 ? (n < 4096 ? n : 4096) : r;
 }
@@ -611,26 +647,24 @@ inline uint32_t hist_cap_of(const rg_config& c) {
     return ((c.ouc_history_cap ? c.ouc_history_cap : kDefaultHistoryCap - 1u) + 1u + 15u) & ~15u;
 }
 
-inline size_t carve_all(const rg_config& c, uint64_t n, void* base, DevSim* d) {
+inline size_t carve_all(const rg_config& c, uint64_t n, const Geom& g, void* base, DevSim* d) {
     Carve w(base);
     const size_t n_pad = align_up(n, 64);
     const size_t P = c.num_products, K = c.K;
-    const Geom g = geom_of(c);
-    (void)P; (void)K;
     float* gamma32 = w.take<float>(static_cast<size_t>(g.P_pad) * (g.KS ? g.KS : 1));
     float* mu32 = w.take<float>(g.P_pad ? g.P_pad : 1);
-    float* gamma32t = w.take<float>(gamma32t_wanted(c, g) ? static_cast<size_t>(g.n_chunks) * 2 * g.KH * 32 : 1);
+    float* gamma32t = w.take<float>(gamma32t_wanted(g) ? static_cast<size_t>(g.n_chunks) * 2 * g.KH * 32 : 1);
     float* stats = w.take<float>(2 * g.KH + 2 + kAhatGrid);
     const size_t PT = align_up(P, 64);
     double* gammaT = w.take<double>(K * PT);
     const uint32_t xkb = exact_kb_of(c.K);
     double* gamma_rm = w.take<double>(xkb ? PT * (4 * static_cast<size_t>(xkb) + 4) : 1);
     float* exact_ref = w.take<float>(n);
-    const size_t exact_rows = exact_rows_of(c, g, n);
+    const size_t exact_rows = exact_rows_of(g, n);
     double* exact_sums = w.take<double>(exact_rows * (PT / 64));
     unsigned short* gsplit = w.take<unsigned short>(g.N1 ? static_cast<size_t>(g.P_pad) * (g.RS / 2) : 1);
     float* mu32s = w.take<float>(g.N1 ? g.P_pad : 1);
-    const bool xh = g.XNH != 0 && cache_wanted(c, g);
+    const bool xh = g.XNH != 0 && g.cache;
     unsigned short* xsplit = w.take<unsigned short>(xh ? static_cast<size_t>(g.P_pad) * (g.XRS / 2) : 1);
     float* xmulo = w.take<float>(xh ? g.P_pad : 1);
     float* xstats = w.take<float>(2 * g.KH + 2);
@@ -657,17 +691,16 @@ inline size_t carve_all(const rg_config& c, uint64_t n, void* base, DevSim* d) {
     double* phantom_ps = w.take<double>(n);
     double* utime = w.take<double>(c.time_mode ? n : 1);
     double* phantom_time = w.take<double>(c.time_mode ? n : 1);
-    const bool cache = cache_wanted(c, g);
-    float2* cache_rec = w.take<float2>(cache ? (n + 1) * kMaxSC : 1);
-    float* cache_chunk = w.take<float>(cache ? (n + 1) * static_cast<size_t>(g.n_chunks) : 1);
-    uint8_t* cache_resc = w.take<uint8_t>(cache ? n + 1 : 1);
+    float2* cache_rec = w.take<float2>(g.cache ? (n + 1) * kMaxSC : 1);
+    float* cache_chunk = w.take<float>(g.cache ? (n + 1) * static_cast<size_t>(g.n_chunks) : 1);
+    uint8_t* cache_resc = w.take<uint8_t>(g.cache ? n + 1 : 1);
     const size_t KB4 = (K + 3) & ~static_cast<size_t>(3);
-    float* beta32 = w.take<float>(cache ? P * KB4 : 4);
+    float* beta32 = w.take<float>(g.cache ? P * KB4 : 4);
     const uint32_t cache_row_f = (44u + 2u * g.KH + 31u) & ~31u;
-    float* cache_row = w.take<float>(cache ? (n + 1) * static_cast<size_t>(cache_row_f) : 1);
-    float* walk_hot = w.take<float>(cache ? (n + 1) * 32 : 1);
-    float* walk_scp = w.take<float>(cache ? (n + 1) * static_cast<size_t>(kMaxSC) : 1);
-    uint8_t* f64_valid = w.take<uint8_t>(cache ? n : 1);
+    float* cache_row = w.take<float>(g.cache ? (n + 1) * static_cast<size_t>(cache_row_f) : 1);
+    float* walk_hot = w.take<float>(g.cache ? (n + 1) * 32 : 1);
+    float* walk_scp = w.take<float>(g.cache ? (n + 1) * static_cast<size_t>(kMaxSC) : 1);
+    uint8_t* f64_valid = w.take<uint8_t>(g.cache ? n : 1);
     uint32_t* exact_cnt_b = w.take<uint32_t>(kMaxSteps + 2);
     const bool lr = lr_family(c.policy);
     uint32_t* lr_action = w.take<uint32_t>(lr ? n : 1);
@@ -683,44 +716,41 @@ inline size_t carve_all(const rg_config& c, uint64_t n, void* base, DevSim* d) {
     const size_t lr_part_cap = lr && c.policy != RG_POLICY_LOGREG_POLY ? (n / 2 + 4096 < n ? n / 2 + 4096 : n) : 0;
     uint32_t* lr_part = w.take<uint32_t>(lr_part_cap ? lr_part_cap * static_cast<size_t>(8 * (4 + 2 * 8)) : 1);       // kLrSplit x kLrPartWords
     // round 1's list (the users + kParkSlack for the blocks its waves leave part-used), then round 2's hand-overs (kParkSlack)
-    uint32_t* park_list = w.take<uint32_t>(cache ? n + 128 + static_cast<size_t>(2) * kParkSlack : 1);
+    uint32_t* park_list = w.take<uint32_t>(g.cache ? n + 128 + static_cast<size_t>(2) * kParkSlack : 1);
     unsigned long long* walk_ctl = w.take<unsigned long long>(kWalkCtlWords);
     unsigned long long* step1_buf = w.take<unsigned long long>(16);      // rg_sim_step_user: {action | result}
-    uint32_t* park_t = w.take<uint32_t>(cache ? n : 1);
-    const bool rp = n >= repack_min_users();      // small runs never repack: no second copy
-    double* omega_alt = w.take<double>(rp ? ((K + 1) & ~static_cast<size_t>(1)) * n_pad : 1);
-    unsigned long long* hist_alt = w.take<unsigned long long>(rp ? hc * n_pad : 1);
-    uint32_t* lpv_alt = w.take<uint32_t>(rp && c.policy == RG_POLICY_LAST_VIEW_TABLE ? n : 1);
-    uint32_t* uid_alt = w.take<uint32_t>(rp ? n : 1);
+    uint32_t* park_t = w.take<uint32_t>(g.cache ? n : 1);
+    double* omega_alt = w.take<double>(g.repack ? ((K + 1) & ~static_cast<size_t>(1)) * n_pad : 1);
+    unsigned long long* hist_alt = w.take<unsigned long long>(g.repack ? hc * n_pad : 1);
+    uint32_t* lpv_alt = w.take<uint32_t>(g.repack && c.policy == RG_POLICY_LAST_VIEW_TABLE ? n : 1);
+    uint32_t* uid_alt = w.take<uint32_t>(g.repack ? n : 1);
     uint32_t* ev = w.take<uint32_t>(n);
     uint32_t* pv0 = w.take<uint32_t>(c.env_kind ? n : 1);
     unsigned long long* run_ctl = w.take<unsigned long long>(4);
-    // k_draw_tp's / k_draw_tpw's classes (tp_kernel_for), every draw a sweep; k_draw_tp: a user's <= 128 tile prefixes in LDS
-    const bool tp = ((g.F16 == 1 && g.KH <= 10 && g.n_chunks / 4 <= kTpBins) || g.F16 == 2) && !cache;
-    char* tp_rec = w.take<char>(tp ? static_cast<size_t>(n) * tp_rec_stride(g.KH) : 1);
+    char* tp_rec = w.take<char>(g.tp ? static_cast<size_t>(n) * tp_rec_stride(g.KH) : 1);
     uint32_t* tp_hist = w.take<uint32_t>(kTpBins * kTpShards + 4);
     // (lists: tiles x shards; the wide sweep's super-tiles are fixed at create: sized for the 16-shard case, which is the largest product)
     const uint32_t tp_tiles = g.F16 == 2 ? kTpBins : g.n_chunks / 4;
     const uint32_t tp_sh = g.F16 == 2 ? kTpShards : tp_shards_of(tp_tiles);
-    uint32_t* tp_order = w.take<uint32_t>(tp ? static_cast<size_t>(tp_tiles) * tp_sh * tp_shard_cap(n, tp_sh) : 1);
+    uint32_t* tp_order = w.take<uint32_t>(g.tp ? static_cast<size_t>(tp_tiles) * tp_sh * tp_shard_cap(n, tp_sh) : 1);
     uint32_t* pl_list = w.take<uint32_t>(c.policy == RG_POLICY_LOGREG_POLY ? 3 * static_cast<size_t>(kPolyListCap) : 1);
     if (d) {
         d->pl_list = pl_list;
-        d->tp_rec = tp ? tp_rec : nullptr; d->tp_hist = tp_hist; d->tp_order = tp_order; d->tp_cap = tp_shard_cap(n, tp_sh); d->tp_shards = tp_sh; d->tp_cpt = 4;
+        d->tp_rec = g.tp ? tp_rec : nullptr; d->tp_hist = tp_hist; d->tp_order = tp_order; d->tp_cap = tp_shard_cap(n, tp_sh); d->tp_shards = tp_sh; d->tp_cpt = 4;
         d->ev = ev; d->run_ctl = run_ctl; d->run_ahead = 0; d->pv0 = pv0;
         d->phantom_ps = phantom_ps; d->utime = utime; d->phantom_time = phantom_time;
         d->drift_list = drift_list; d->drift_sig = drift_sig; d->drift_cnt = drift_cnt;
-        d->use_cache = cache ? 1u : 0u; d->cache_rec = cache_rec; d->cache_chunk = cache_chunk; d->cache_resc = cache_resc;
-        d->beta32 = cache ? beta32 : nullptr; d->KB4 = static_cast<uint32_t>(KB4);
+        d->use_cache = g.cache ? 1u : 0u; d->cache_rec = cache_rec; d->cache_chunk = cache_chunk; d->cache_resc = cache_resc;
+        d->beta32 = g.cache ? beta32 : nullptr; d->KB4 = static_cast<uint32_t>(KB4);
         d->f64_valid = f64_valid; d->exact_cnt_b = exact_cnt_b; d->cache_row = cache_row; d->cache_row_f = cache_row_f;
         d->park_list = park_list; d->park_t = park_t; d->sweep_only = 0;
         d->walk_ctl = walk_ctl; d->step1_buf = step1_buf;
-        d->walk_hot = cache ? walk_hot : nullptr; d->walk_scp = walk_scp;
+        d->walk_hot = g.cache ? walk_hot : nullptr; d->walk_scp = walk_scp;
         d->lr_ps = lr_ps; d->lr_action2 = lr_action2; d->lr_ps2 = lr_ps2; d->lr_sample = lrs ? 1u : 0u;
         d->lr_action = lr_action; d->lr_dirty = lr ? lr_dirty : nullptr; d->lr_list = lr_list; d->lr_cnt = lr_cnt; d->lr_part = lr_part; d->lr_part_cap = static_cast<uint32_t>(lr_part_cap);
         d->uid = uid; d->omega_alt = omega_alt; d->hist_alt = hist_alt;
         d->lpv_alt = lpv_alt; d->uid_alt = uid_alt;
-        d->gamma32 = gamma32; d->mu32 = mu32; d->gamma32t = gamma32t; d->has_g32t = gamma32t_wanted(c, g) ? 1u : 0u; d->stats = stats; d->omega = omega; d->list = list;
+        d->gamma32 = gamma32; d->mu32 = mu32; d->gamma32t = gamma32t; d->has_g32t = gamma32t_wanted(g) ? 1u : 0u; d->stats = stats; d->omega = omega; d->list = list;
         d->gamma_rm = gamma_rm; d->XKB = xkb;
         d->exact_rows = static_cast<uint32_t>(exact_rows); d->exact_base = 0;
         d->gammaT = gammaT; d->PT = static_cast<uint32_t>(PT); d->exact_ref = exact_ref; d->exact_sums = exact_sums; d->sc_scratch = sc_scratch; d->chunk_scratch = chunk_scratch;

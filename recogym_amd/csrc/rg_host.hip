@@ -1112,6 +1112,209 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
 
 }  // namespace rgk
 
+// rg_sim_create's plan: what a handle runs with, decided once from the configuration, the workspace geometry and the switch record.
+// One step per family, in the order they depend on each other; in each the default first, the switch's override under it.
+namespace {
+void plan_config(rg_sim* s, const rg_config* cfg, uint64_t n_users, const Switches& w) {
+    DevSim& d = s->d;
+    d.P = cfg->num_products; d.K = cfg->K;
+    d.seed = cfg->seed; d.policy_seed = cfg->policy_seed;
+    d.cdf_o0 = cfg->trans_cdf[0][0]; d.cdf_o1 = cfg->trans_cdf[0][1];
+    d.cdf_b0 = cfg->trans_cdf[1][0]; d.cdf_b1 = cfg->trans_cdf[1][1];
+    d.sigma0 = cfg->sigma_omega_initial; d.sigma_omega = cfg->sigma_omega; d.change_omega_for_bandits = cfg->change_omega_for_bandits;
+    // the likelihood agent runs wherever the frozen LogReg policy does, through the same act list: one policy for the kernels
+    d.policy = cfg->policy == RG_POLICY_LOGREG_POLY ? RG_POLICY_LOGREG_FROZEN : cfg->policy;
+    d.lr_poly = cfg->policy == RG_POLICY_LOGREG_POLY ? 1u : 0u;
+    d.ouc_select_randomly = cfg->ouc_select_randomly; d.ouc_exploit_explore = cfg->ouc_exploit_explore;
+    d.ouc_reverse_pop = cfg->ouc_reverse_pop; d.ouc_epsilon = cfg->ouc_epsilon;
+    d.time_mode = cfg->time_mode; d.time_mu = cfg->time_mu; d.time_sigma = cfg->time_sigma; d.env_kind = cfg->env_kind;
+    d.n_users = d.n_cap = static_cast<uint32_t>(n_users);
+    d.grp_lo = 0; d.grp_n = d.n_users; d.list_in = 0;
+    d.q_ticket = d.counters + kCntWalkTicket; d.q_park = d.counters + kCntParkCnt; d.q_count = nullptr;
+    RunOpts& o = s->opt;
+    o.exact_tile = w.exact_tile.set ? 1 : 0; o.sweep_prefix_off = w.sweep_prefix_off.set ? 1 : 0; o.debug = w.debug.set ? 1 : 0;
+    o.exact_mix = w.exact_mix.set ? w.exact_mix.num : 5;
+    o.slices = w.slices.set ? w.slices.num : -1;
+    o.repack_min = w.repack_min;
+    d.walk_line64 = w.walk_hist.is('1') ? 1u : 0u; s->sort_plain = w.sort_plain.set;
+}
+// kernel choice: split-bf16 MFMA when a class exists for K, else fp32 MFMA; RECOGYM_DRAW=f64|fp32|bf16 overrides
+void plan_draw(rg_sim* s, const Switches& w, const Geom& g) {
+    DevSim& d = s->d;
+    s->mfma_smem = d.use_mfma ? mfma_smem_bytes(g) : 0;
+    s->bf16_kernel = nullptr; s->bf16_smem = 0; s->draw_threads = kBlock; s->draw_users = 128;
+    if (d.use_mfma && d.N1) {
+        s->bf16_kernel = d.f16 ? nullptr : bf16_kernel_for(d);
+        // the pipelined form (two chunks in flight, exp-sum and operand loads inside the MFMA stream)
+        // where its ~200 VGPRs fit; RECOGYM_BF16=lean keeps the one-accumulator kernel (A/B tests)
+        if (!w.bf16_lean)
+            if (static_cast<size_t>(d.P_pad) * d.RS < (1ull << 31))     // its DMA uses 31-bit buffer offsets
+                if (draw_kernel_t kp = bf16p_kernel_for(d)) s->bf16_kernel = kp;
+        s->bf16_smem = bf16_smem_bytes(g, 2 * d.KH, s->bf16_kernel == bf16p_kernel_for(d) ? static_cast<uint32_t>(RG_SWEEP_NB) : 2u);
+        if (d.wide) {
+            s->bf16_kernel = static_cast<size_t>(d.P_pad) * d.RS < (1ull << 31) ? f16w_kernel_for(d) : nullptr;
+            s->bf16_smem = 3 * (64 * static_cast<size_t>(d.RS) + 256) + 8 * 32 * 2 * static_cast<size_t>(d.KH) * 4;
+            s->draw_threads = 512; s->draw_users = 256;
+        }
+        // the larger classes still spill registers; the fp32 kernel is faster there for now
+        if (s->bf16_kernel && (d.f16 || (d.N1 <= 4 && d.KH <= 10))) d.use_mfma = 2;
+    }
+    if (w.draw == Switches::kDrawF64) d.use_mfma = 0;
+    else if (w.draw == Switches::kDrawFp32 && d.KH) d.use_mfma = 1;
+    else if ((w.draw == Switches::kDrawBf16 || w.draw == Switches::kDrawF16) && s->bf16_kernel) d.use_mfma = 2;
+    if (w.force_exact.is('1')) d.use_mfma = 0;   // A/B switch for tests
+    // the per-user sum cache is written by the pipelined 16-bit kernel only
+    if (!(d.use_mfma == 2 && s->bf16_kernel &&
+          (s->bf16_kernel == bf16p_kernel_for(d) || (d.wide && s->bf16_kernel == f16w_kernel_for(d))))) d.use_cache = 0;
+    if (s->bf16_kernel) opt_in_lds(s->bf16_kernel, s->bf16_smem);
+}
+// the walked run's sweep with an error-free leading accumulator (k_sweep_xh) where the pipelined fp16 sweep would run it
+void plan_sweep_xh(rg_sim* s, const Switches& w) {
+    DevSim& d = s->d;
+    s->xh_kernel = nullptr; s->xh_smem = 0;
+    if (d.XNH && d.use_cache && d.use_mfma == 2 && s->bf16_kernel && f16_pipelined(s) && static_cast<size_t>(d.P_pad) * d.XRS < (1ull << 31)) {
+        s->xh_waves = w.xh_waves.set && w.xh_waves.num == 8 ? 8 : 4;
+        s->xh_kernel = xh_kernel_for(d, s->xh_waves);
+    }
+    if (s->xh_kernel) {
+        s->xh_smem = 2 * (128 * static_cast<size_t>(d.XRS) + 512) + 256 + static_cast<size_t>(s->xh_waves) * 32 * kMaxSC * sizeof(float);   // tiles, seeds, the super-chunk prefix stage
+        if (w.xh_smem_pad.set) s->xh_smem += static_cast<size_t>(w.xh_smem_pad.num);   // occupancy experiments: one block per CU
+        set_max_lds(s->xh_kernel, s->xh_smem);
+    } else { d.XNH = d.XNL = d.XRS = 0; }
+}
+// the sweep whose search stays in LDS, where every draw sweeps (g.tp: a class exists, no per-user cache, the records are carved) and
+// the 16-bit sweep serves the table.  k_draw_tp: the two-way fp16 split of K <= 20; a user's tile prefixes must fit beside the tiles
+// (P <= ~12 000 at two blocks per CU).  k_draw_tpw: wide K, a prefix per SUPER-TILE of G 64-product tiles — what fits beside its three tile buffers
+void plan_sweep_lds(rg_sim* s, const Switches& w, const Geom& g) {
+    DevSim& d = s->d;
+    s->tp_kernel = nullptr; s->pick_kernel = nullptr; s->tp_smem = 0; s->tp_nts = 0;
+    s->sweep_lds = w.sweep_lds.is('0') ? 0 : 1;
+    const draw_kernel_t kp = pick_kernel_for(d);
+    if (!g.tp || d.use_mfma != 2 || !s->bf16_kernel || !kp) return;
+    draw_kernel_t kt = nullptr;
+    size_t smem = 0;
+    uint32_t nts = 0;
+    if (f16_pipelined(s)) {
+        kt = tp_kernel_for(d);
+        nts = ((d.n_chunks / 4) + 3u) & ~3u;
+        // (-DRG_TP_SMEM_PAD=bytes: a timing build that pushes the kernel to ONE block per CU — what the second block is worth)
+        smem = 2 * (128 * static_cast<size_t>(d.RS) + 512) + 256 + 4 * 32 * static_cast<size_t>(nts) * sizeof(float) + RG_TP_SMEM_PAD;
+        // (<= 128 tile lists; and >= 4 tiles: below that — P <= 384 — the sweep is a few hundred MFMAs per draw and the per-draw
+        // list atomic on <= 3 x 128 counters would pace it: those tables keep k_draw_bf16p)
+        if (d.n_chunks / 4 > 128u || d.n_chunks / 4 < 4u) kt = nullptr;
+    } else if (d.wide && s->bf16_kernel == f16w_kernel_for(d)) {
+        const size_t tile_b = 64 * static_cast<size_t>(d.RS);
+        const size_t avail = 160 * 1024 - 3 * tile_b - 1024;
+        uint32_t nts_max = static_cast<uint32_t>(avail / (256 * sizeof(float))) & ~3u;
+        if (nts_max > kTpBins) nts_max = kTpBins;
+        if (nts_max < 8) return;
+        kt = tpw_kernel_for(d);
+        const uint32_t n_t = d.n_chunks / 2;
+        const uint32_t G = (n_t + nts_max - 1) / nts_max;
+        const uint32_t n_s = (n_t + G - 1) / G;
+        nts = (n_s + 3u) & ~3u;
+        // (the omega32 stage of the block's 256 users lies over tile buffers 1, 2 and the prefix rows)
+        while (2 * tile_b + 256 * static_cast<size_t>(nts) * sizeof(float) < 256 * 2 * static_cast<size_t>(d.KH) * sizeof(float)) nts += 4;
+        smem = 3 * tile_b + 1024 + 256 * static_cast<size_t>(nts) * sizeof(float);
+        if (kt && smem <= 160 * 1024) d.tp_cpt = 2 * G;
+    }
+    if (!kt || smem > 160 * 1024) return;
+    s->tp_kernel = kt; s->pick_kernel = kp; s->tp_smem = smem; s->tp_nts = nts;
+    set_max_lds(kt, smem);
+}
+void plan_repack_tail(rg_sim* s, const Switches& w) {
+    DevSim& d = s->d;
+    d.ablate = w.ablate.set ? w.ablate.u32() : 0;
+    s->repack_every = w.repack.set ? w.repack.u32() : 16;
+    s->repacked = false;
+    // a per-user draw streams the whole Gamma table through one CU: the population at which the tail
+    // kernel beats the latency floor of the lock-step steps shrinks with P * K (4096 users at 10^4 x 20)
+    const double scale = 2.0e5 / (static_cast<double>(d.P) * static_cast<double>(d.K));
+    // (only where the lock-step draw kernel slices products for small populations; the fp32 and float64
+    // kernels sweep all P per step, so for them the tail kernel wins much earlier)
+    const double tb = 4096.0 * ((scale < 1.0 && d.use_mfma == 2) ? scale : 1.0);
+    s->tail_below = tb < 64.0 ? 64u : static_cast<uint32_t>(tb);
+    // ... and not at all beyond P x K = 10^6 there: a block streams the whole float64 table per draw (51 MB at 10^5 x 64: 0.4 ms,
+    // as long as a sliced round of ALL the users left).  A C4 shard with the tail from 128 users 1 615 ms, from 32 1 582, from 2
+    // 1 538, never 1 503 (profiles/r6/ab_call45_c4_tail.jsonl, ab_call46_c4_tail.jsonl); at 10^4 x 20 it makes no difference
+    // (c3drift 801 / 795 / 801 ms from 4 096 / 1 024 / never: ab_call47_tail.jsonl)
+    if (d.use_mfma == 2 && static_cast<double>(d.P) * static_cast<double>(d.K) > 1.0e6) s->tail_below = 0;
+    if (d.time_mode) s->tail_below = 0;           // per-user clocks: the lock-step kernels only
+    // the tail kernel runs a policy on one thread: fine for a history walk, not for n_classes x views score loops — the frozen
+    // LogReg policy stays in lock-step (wave-cooperative acts) to the end, whatever RECOGYM_TAIL says (k_tail: 46 s per C5 step)
+    if (d.policy == RG_POLICY_LOGREG_FROZEN) s->tail_below = 0;
+    else if (w.tail.set) s->tail_below = w.tail.u32();
+}
+// user-major walk: wherever the per-user cache exists and the policy acts lane by lane (the frozen LogReg policy acts
+// wave-cooperatively: lock-step) and the clock is the default one; RECOGYM_WALK=0 keeps the lock-step loop (A/B tests)
+void plan_walk(rg_sim* s, const Switches& w) {
+    DevSim& d = s->d;
+    s->walk = d.use_cache && !d.time_mode && !w.walk.is('0') && (d.policy == RG_POLICY_UNIFORM_ENV || d.policy == RG_POLICY_RANDOM_AGENT ||
+                                                                 d.policy == RG_POLICY_ORGANIC_USER_COUNT || d.policy == RG_POLICY_LAST_VIEW_TABLE);
+    // k_walk2 where it is instantiated for the configuration (RECOGYM_WALK=1: k_walk)
+    s->walk2 = s->walk && walk2_kernel_for(d, 4) != nullptr && !w.walk.is('1');
+    s->walk_occ = s->walk2 && d.KH > 10 ? 2 : 3;  // (what the kernel is compiled for: k_walk and k_walk2 at K <= 20 three blocks per CU, k_walk2 at K <= 32 two)
+    s->walk_solo = !w.walk_solo.is('0');
+    s->n_cus = 0;
+    d.walk_refill = w.walk_refill.set ? w.walk_refill.u32() : 8;
+    d.walk_handover = w.walk_handover.set ? w.walk_handover.u32() : 32;
+    s->handover_auto = !w.walk_handover.set;
+    d.walk_click_batch = w.walk_click_batch.set ? w.walk_click_batch.u32() : 8;
+    d.walk_click_join = w.walk_click_join.is('0') ? 0 : 1;
+    d.walk_helpers = w.walk_helpers.set && w.walk_helpers.u32() < kWalkHelpersMax ? w.walk_helpers.u32() : kWalkHelpersMax;
+    // (k_walk2: 4 since the act is a count on the compact history line — the bandit iteration got shorter, so the organic kind
+    // waits for more lanes: profiles/r4/ab_call6_walk_bias.jsonl; k_walk keeps round 2's 8)
+    // (round 5, with helpers: a bandit iteration is full whatever the number of bandit lanes, so the organic kinds wait for
+    // more of theirs — bias 2, search batch 24: profiles/r5/ab_call18_walk_tuning.jsonl)
+    d.walk_bias = !s->walk2 ? 8 : (d.walk_helpers ? 2 : 4);
+    if (w.walk_bias.set) d.walk_bias = w.walk_bias.u32();
+    d.walk_search_batch = s->walk2 && d.walk_helpers ? 24 : 16;
+    if (w.walk_search_batch.set) d.walk_search_batch = w.walk_search_batch.u32() ? w.walk_search_batch.u32() : 1u;
+}
+// the walked run as one chain with its list lengths on the device (run_walk_pipe).  RECOGYM_PIPE=0: run_walk, host-side list
+// lengths; RECOGYM_PIPE_OCC1 / _OCC2 (blocks per CU of the rounds' grids), RECOGYM_PIPE_XBLOCKS: A/B tests.
+// The whole reset range is ONE group on the caller's stream.  More groups on two or three streams were measured on C3 and
+// did not pay (profiles/r4/ab_call1_pipe_forms.jsonl): the walk's three waves per SIMD fill the register file,
+// so nothing co-resides with it, and every group adds a drain tail to both walk rounds and a partial last wave of blocks to
+// the float64 batch.  A value out of range leaves the default.
+void plan_pipe(rg_sim* s, const Switches& w) {
+    const auto in = [](const Switch& x, int lo, int hi) { return x.set && x.num >= lo && x.num <= hi; };
+    s->pipe_groups = in(w.pipe, 0, 1) ? w.pipe.num : 1;
+    s->pipe_occ1 = in(w.pipe_occ1, 1, s->walk_occ) ? w.pipe_occ1.num : s->walk_occ;
+    s->pipe_occ2 = in(w.pipe_occ2, 1, s->walk_occ) ? w.pipe_occ2.num : s->walk_occ;
+    s->pipe_xblocks = in(w.pipe_xblocks, 1, INT_MAX) ? w.pipe_xblocks.num : 1024;
+    s->pipe_min_users = in(w.pipe_min, 256, INT_MAX) ? static_cast<uint32_t>(w.pipe_min.num) : 1u << 17;
+    s->fin_in_sweep = !w.fin_in_sweep.is('0');
+    s->d.fin_in_sweep = 0;
+    s->fate_base = 0; s->fate_count = nullptr;
+}
+void plan_logreg_run_ahead(rg_sim* s, const Switches& w) {
+    s->run_ahead = w.run_ahead.set ? w.run_ahead.u32() : 32;   // events a round of a run to the end may take a user through (0: lock-step, an event per launch)
+    if (s->d.lr_sample) s->run_ahead = 0;  // a sampled act per event: lock-step (k_advance_run reuses one act for a whole bandit run)
+    s->lr_part_rows = s->d.lr_part_cap;    // (the switch, as the option, can only lower it)
+    if (w.lr_part_cap.set && w.lr_part_cap.u32() < s->lr_part_rows) s->d.lr_part_cap = w.lr_part_cap.u32();
+}
+// reco-gym-v0: no omega, no product sweep — the lock-step loop with its own draw kernel (k_draw_env0), nothing else
+void plan_env0(rg_sim* s) {
+    DevSim& d = s->d;
+    if (!d.env_kind) return;
+    d.use_mfma = 0; d.use_cache = 0; d.XNH = d.XNL = d.XRS = 0;
+    s->bf16_kernel = nullptr; s->xh_kernel = nullptr;
+    s->walk = s->walk2 = false; s->tail_below = 0; s->run_ahead = 0;
+}
+void plan_mfma_lds(rg_sim* s, const Switches& w) {
+    if (w.lds_pad.set) s->mfma_smem += static_cast<size_t>(w.lds_pad.num);
+    if (s->opt.debug && s->d.use_mfma && rg_device_count() > 0) {
+        int nb = -1;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(mfma_kernel_for(10)), kBlock, s->mfma_smem);
+        fprintf(stderr, "[recogym] k_draw_mfma<10>: dynamic LDS %zu B, occupancy API %d blocks/CU\n", s->mfma_smem, nb);
+    }
+    if (s->mfma_smem > 64 * 1024)
+        for (uint32_t kh : {4u, 10u, 16u, 32u, 64u}) set_max_lds(mfma_kernel_for(kh), s->mfma_smem);
+}
+
+}  // namespace
+
 // ==========================================================================================
 // C ABI
 // ==========================================================================================
@@ -1128,7 +1331,7 @@ int rg_device_count(void) {
 
 size_t rg_sim_workspace_bytes(const rg_config* cfg, uint64_t n_users) {
     if (validate(cfg, n_users) != RG_OK) return 0;
-    return carve_all(*cfg, n_users, nullptr, nullptr);
+    return carve_all(*cfg, n_users, geom_of(*cfg, n_users, read_switches()), nullptr, nullptr);
 }
 
 int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_workspace,
@@ -1137,236 +1340,30 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
     *out = nullptr;
     if (int rc = validate(cfg, n_users)) return rc;
     if (!d_workspace) return fail(RG_EINVAL, "workspace is NULL");
-    const size_t need = carve_all(*cfg, n_users, nullptr, nullptr);
+    const Switches w = read_switches();             // the size check, the carve and the plan: one reading of the environment
+    const Geom g = geom_of(*cfg, n_users, w);
+    const size_t need = carve_all(*cfg, n_users, g, nullptr, nullptr);
     if (workspace_bytes < need)
         return fail(RG_ENOMEM, "workspace has %zu bytes, %zu needed", workspace_bytes, need);
     if ((reinterpret_cast<uintptr_t>(d_workspace) & 255u) != 0)
         return fail(RG_EINVAL, "workspace must be 256-byte aligned");
     rg_sim* s = new (std::nothrow) rg_sim();
     if (!s) return fail(RG_ENOMEM, "host allocation failed");
-    s->cfg = *cfg;
-    s->workspace = d_workspace;
-    s->workspace_bytes = workspace_bytes;
-    DevSim& d = s->d;
-    memset(&d, 0, sizeof(d));
-    carve_all(*cfg, n_users, d_workspace, &d);
-    d.P = cfg->num_products; d.K = cfg->K;
-    d.seed = cfg->seed; d.policy_seed = cfg->policy_seed;
-    d.cdf_o0 = cfg->trans_cdf[0][0]; d.cdf_o1 = cfg->trans_cdf[0][1];
-    d.cdf_b0 = cfg->trans_cdf[1][0]; d.cdf_b1 = cfg->trans_cdf[1][1];
-    d.sigma0 = cfg->sigma_omega_initial; d.sigma_omega = cfg->sigma_omega;
-    d.change_omega_for_bandits = cfg->change_omega_for_bandits;
-    // the likelihood agent runs wherever the frozen LogReg policy does, through the same act list: one policy for the kernels
-    d.policy = cfg->policy == RG_POLICY_LOGREG_POLY ? RG_POLICY_LOGREG_FROZEN : cfg->policy;
-    d.lr_poly = cfg->policy == RG_POLICY_LOGREG_POLY ? 1u : 0u;
-    d.ouc_select_randomly = cfg->ouc_select_randomly;
-    d.ouc_exploit_explore = cfg->ouc_exploit_explore;
-    d.ouc_reverse_pop = cfg->ouc_reverse_pop;
-    d.ouc_epsilon = cfg->ouc_epsilon;
-    d.time_mode = cfg->time_mode; d.time_mu = cfg->time_mu; d.time_sigma = cfg->time_sigma;
-    d.env_kind = cfg->env_kind;
-    d.n_users = d.n_cap = static_cast<uint32_t>(n_users);
-    s->h_pinned = nullptr; s->h_step = nullptr;
-    {   // run-path options from the environment, once
-        RunOpts& o = s->opt;
-        o.exact_tile = getenv("RECOGYM_EXACT_TILE") ? 1 : 0;
-        o.exact_mix = 5;
-        if (const char* e = getenv("RECOGYM_EXACT_MIX")) o.exact_mix = atoi(e);
-        o.slices = -1;
-        if (const char* e = getenv("RECOGYM_SLICES")) o.slices = atoi(e);
-        o.sweep_prefix_off = getenv("RECOGYM_SWEEP_PREFIX_OFF") ? 1 : 0;
-        o.debug = getenv("RECOGYM_DEBUG") ? 1 : 0;
-        o.repack_min = repack_min_users();
-        const char* e_h = getenv("RECOGYM_WALK_HIST");
-        d.walk_line64 = (e_h && e_h[0] == '1') ? 1u : 0u;
-    }
-    s->profiling = false;
+    s->cfg = *cfg; s->workspace = d_workspace; s->workspace_bytes = workspace_bytes;
+    s->h_pinned = nullptr; s->h_step = nullptr; s->profiling = false;
     prof_reset(s);
-    s->mfma_smem = d.use_mfma ? mfma_smem_bytes(geom_of(*cfg)) : 0;
-    // kernel choice: split-bf16 MFMA when a class exists for K, else fp32 MFMA; RECOGYM_DRAW=f64|fp32|bf16 overrides
-    s->bf16_kernel = nullptr; s->bf16_smem = 0;
-    s->draw_threads = kBlock; s->draw_users = 128;
-    if (d.use_mfma && d.N1) {
-        s->bf16_kernel = d.f16 ? nullptr : bf16_kernel_for(d);
-        // the pipelined form (two chunks in flight, exp-sum and operand loads inside the MFMA stream)
-        // where its ~200 VGPRs fit; RECOGYM_BF16=lean keeps the one-accumulator kernel (A/B tests)
-        const char* lean = getenv("RECOGYM_BF16");
-        if (!(lean && !strcmp(lean, "lean")))
-            if (static_cast<size_t>(d.P_pad) * d.RS < (1ull << 31))     // its DMA uses 31-bit buffer offsets
-                if (draw_kernel_t kp = bf16p_kernel_for(d)) s->bf16_kernel = kp;
-        s->bf16_smem = bf16_smem_bytes(geom_of(*cfg), 2 * d.KH, s->bf16_kernel == bf16p_kernel_for(d) ? static_cast<uint32_t>(RG_SWEEP_NB) : 2u);
-        if (d.wide) {
-            s->bf16_kernel = static_cast<size_t>(d.P_pad) * d.RS < (1ull << 31) ? f16w_kernel_for(d) : nullptr;
-            s->bf16_smem = 3 * (64 * static_cast<size_t>(d.RS) + 256) + 8 * 32 * 2 * static_cast<size_t>(d.KH) * 4;
-            s->draw_threads = 512; s->draw_users = 256;
-        }
-        // the larger classes still spill registers; the fp32 kernel is faster there for now
-        if (s->bf16_kernel && (d.f16 || (d.N1 <= 4 && d.KH <= 10))) d.use_mfma = 2;
-    }
-    if (const char* e = getenv("RECOGYM_DRAW")) {
-        if (!strcmp(e, "f64")) d.use_mfma = 0;
-        else if (!strcmp(e, "fp32") && d.KH) d.use_mfma = 1;
-        else if ((!strcmp(e, "bf16") || !strcmp(e, "f16")) && s->bf16_kernel) d.use_mfma = 2;
-    }
-    if (const char* e = getenv("RECOGYM_FORCE_EXACT")) if (e[0] == '1') d.use_mfma = 0;   // A/B switch for tests
-    // the per-user sum cache is written by the pipelined 16-bit kernel only
-    if (!(d.use_mfma == 2 && s->bf16_kernel &&
-          (s->bf16_kernel == bf16p_kernel_for(d) || (d.wide && s->bf16_kernel == f16w_kernel_for(d))))) d.use_cache = 0;
-    if (s->bf16_kernel) opt_in_lds(s->bf16_kernel, s->bf16_smem);
-    // the walked run's sweep with an error-free leading accumulator (k_sweep_xh) where the pipelined fp16 sweep would run it
-    s->xh_kernel = nullptr; s->xh_smem = 0;
-    if (d.XNH && d.use_cache && d.use_mfma == 2 && s->bf16_kernel && f16_pipelined(s) &&
-        static_cast<size_t>(d.P_pad) * d.XRS < (1ull << 31))
-    {
-        s->xh_waves = 4;
-        if (const char* e = getenv("RECOGYM_XH_WAVES")) s->xh_waves = atoi(e) == 8 ? 8 : 4;
-        s->xh_kernel = xh_kernel_for(d, s->xh_waves);
-    }
-    if (s->xh_kernel) {
-        s->xh_smem = 2 * (128 * static_cast<size_t>(d.XRS) + 512) + 256 + static_cast<size_t>(s->xh_waves) * 32 * kMaxSC * sizeof(float);   // tiles, seeds, the super-chunk prefix stage
-        if (const char* e = getenv("RECOGYM_XH_SMEM_PAD")) s->xh_smem += static_cast<size_t>(atoi(e));   // occupancy experiments: one block per CU
-        set_max_lds(s->xh_kernel, s->xh_smem);
-    } else { d.XNH = d.XNL = d.XRS = 0; }
-    // the sweep whose search stays in LDS (k_draw_tp): where every draw sweeps (no per-user cache) and the two-way fp16 split of
-    // K <= 20 serves the table; a user's tile prefixes must fit beside the tiles (P <= ~12 000 at two blocks per CU)
-    s->tp_kernel = nullptr; s->pick_kernel = nullptr; s->tp_smem = 0; s->tp_nts = 0; s->sweep_lds = 1;
-    if (const char* e = getenv("RECOGYM_SWEEP_LDS")) s->sweep_lds = e[0] != '0';
-    if (d.use_mfma == 2 && !d.use_cache && s->bf16_kernel && f16_pipelined(s)) {
-        draw_kernel_t kt = tp_kernel_for(d), kp = pick_kernel_for(d);
-        if (kt && kp && d.tp_rec) {
-            const uint32_t nts = ((d.n_chunks / 4) + 3u) & ~3u;
-            // (-DRG_TP_SMEM_PAD=bytes: a timing build that pushes the kernel to ONE block per CU — what the second block is worth)
-            const size_t smem = 2 * (128 * static_cast<size_t>(d.RS) + 512) + 256 + 4 * 32 * static_cast<size_t>(nts) * sizeof(float) + RG_TP_SMEM_PAD;
-            // (<= 128 tile lists; and >= 4 tiles: below that — P <= 384 — the sweep is a few hundred MFMAs per draw and the per-draw
-            // list atomic on <= 3 x 128 counters would pace it: those tables keep k_draw_bf16p)
-            if (smem <= 160 * 1024 && d.n_chunks / 4 <= 128u && d.n_chunks / 4 >= 4u) {
-                s->tp_kernel = kt; s->pick_kernel = kp; s->tp_smem = smem; s->tp_nts = nts;
-                set_max_lds(kt, smem);
-            }
-        }
-    }
-    if (d.use_mfma == 2 && !d.use_cache && d.wide && s->bf16_kernel && s->bf16_kernel == f16w_kernel_for(d) && d.tp_rec) {
-        // wide K: k_draw_tpw keeps a prefix per SUPER-TILE of G 64-product tiles — what fits beside its three tile buffers
-        draw_kernel_t kt = tpw_kernel_for(d), kp = pick_kernel_for(d);
-        const size_t tile_b = 64 * static_cast<size_t>(d.RS);
-        const size_t avail = 160 * 1024 - 3 * tile_b - 1024;
-        uint32_t nts_max = static_cast<uint32_t>(avail / (256 * sizeof(float))) & ~3u;
-        if (nts_max > kTpBins) nts_max = kTpBins;
-        if (kt && kp && nts_max >= 8) {
-            const uint32_t n_t = d.n_chunks / 2;
-            const uint32_t G = (n_t + nts_max - 1) / nts_max;
-            const uint32_t n_s = (n_t + G - 1) / G;
-            uint32_t nts = (n_s + 3u) & ~3u;
-            // (the omega32 stage of the block's 256 users lies over tile buffers 1, 2 and the prefix rows)
-            while (2 * tile_b + 256 * static_cast<size_t>(nts) * sizeof(float) < 256 * 2 * static_cast<size_t>(d.KH) * sizeof(float)) nts += 4;
-            const size_t smem = 3 * tile_b + 1024 + 256 * static_cast<size_t>(nts) * sizeof(float);
-            if (smem <= 160 * 1024) {
-                s->tp_kernel = kt; s->pick_kernel = kp; s->tp_smem = smem; s->tp_nts = nts;
-                d.tp_cpt = 2 * G;
-                set_max_lds(kt, smem);
-            }
-        }
-    }
-    d.ablate = 0;
-    s->repack_every = 16;
-    s->repacked = false;
-    {   // a per-user draw streams the whole Gamma table through one CU: the population at which the tail
-        // kernel beats the latency floor of the lock-step steps shrinks with P * K (4096 users at 10^4 x 20)
-        const double scale = 2.0e5 / (static_cast<double>(d.P) * static_cast<double>(d.K));
-        // (only where the lock-step draw kernel slices products for small populations; the fp32 and float64
-        // kernels sweep all P per step, so for them the tail kernel wins much earlier)
-        const double tb = 4096.0 * ((scale < 1.0 && d.use_mfma == 2) ? scale : 1.0);
-        s->tail_below = tb < 64.0 ? 64u : static_cast<uint32_t>(tb);
-        // ... and not at all beyond P x K = 10^6 there: a block streams the whole float64 table per draw (51 MB at 10^5 x 64: 0.4 ms,
-        // as long as a sliced round of ALL the users left).  A C4 shard with the tail from 128 users 1 615 ms, from 32 1 582, from 2
-        // 1 538, never 1 503 (profiles/r6/ab_call45_c4_tail.jsonl, ab_call46_c4_tail.jsonl); at 10^4 x 20 it makes no difference
-        // (c3drift 801 / 795 / 801 ms from 4 096 / 1 024 / never: ab_call47_tail.jsonl)
-        if (d.use_mfma == 2 && static_cast<double>(d.P) * static_cast<double>(d.K) > 1.0e6) s->tail_below = 0;
-        // the tail kernel runs a policy on one thread: fine for a history walk, not for n_classes x views
-        // score loops — the frozen LogReg policy stays in lock-step (wave-cooperative acts) to the end
-        if (d.policy == RG_POLICY_LOGREG_FROZEN) s->tail_below = 0;
-    }
-    // user-major walk: wherever the per-user cache exists and the policy acts lane by lane (the frozen LogReg
-    // policy acts wave-cooperatively: lock-step); RECOGYM_WALK=0 keeps the lock-step loop (A/B tests)
-    s->walk = d.use_cache && (d.policy == RG_POLICY_UNIFORM_ENV || d.policy == RG_POLICY_RANDOM_AGENT ||
-                              d.policy == RG_POLICY_ORGANIC_USER_COUNT || d.policy == RG_POLICY_LAST_VIEW_TABLE);
-    if (const char* e = getenv("RECOGYM_WALK")) if (e[0] == '0') s->walk = false;
-    if (d.time_mode) { s->walk = false; s->tail_below = 0; }      // per-user clocks: the lock-step kernels only
-    s->n_cus = 0;
-    s->walk_occ = 3;
-    d.walk_bias = 8;
-    d.walk_refill = 8;
-    d.walk_handover = 32;
-    s->handover_auto = true;
-    if (const char* e = getenv("RECOGYM_WALK_HANDOVER")) { d.walk_handover = static_cast<uint32_t>(atoi(e)); s->handover_auto = false; }
-    d.walk_click_batch = 8;
-    if (const char* e = getenv("RECOGYM_WALK_CLICK_BATCH")) d.walk_click_batch = static_cast<uint32_t>(atoi(e));
-    d.walk_search_batch = 16;
-    d.walk_helpers = kWalkHelpersMax;
-    d.walk_click_join = 1;
-    if (const char* e = getenv("RECOGYM_WALK_CLICK_JOIN")) d.walk_click_join = e[0] != '0';
-    if (const char* e = getenv("RECOGYM_WALK_HELPERS")) d.walk_helpers = static_cast<uint32_t>(atoi(e)) > kWalkHelpersMax ? kWalkHelpersMax : static_cast<uint32_t>(atoi(e));
-    if (const char* e = getenv("RECOGYM_WALK_SEARCH_BATCH")) d.walk_search_batch = static_cast<uint32_t>(atoi(e)) ? static_cast<uint32_t>(atoi(e)) : 1u;
-    if (const char* e = getenv("RECOGYM_WALK_REFILL")) d.walk_refill = static_cast<uint32_t>(atoi(e));
-    if (const char* e = getenv("RECOGYM_WALK_BIAS")) d.walk_bias = static_cast<uint32_t>(atoi(e));
-    // k_walk2 where it is instantiated for the configuration (RECOGYM_WALK=1: k_walk), four blocks per CU at K <= 20
-    s->walk2 = s->walk && walk2_kernel_for(d, 4) != nullptr;
-    if (const char* e = getenv("RECOGYM_WALK")) if (e[0] == '1') s->walk2 = false;
-    // (k_walk2: 4 since the act is a count on the compact history line — the bandit iteration got shorter, so the organic kind
-    // waits for more lanes: profiles/r4/ab_call6_walk_bias.jsonl; k_walk keeps round 2's 8)
-    // (round 5, with helpers: a bandit iteration is full whatever the number of bandit lanes, so the organic kinds wait for
-    // more of theirs — bias 2, search batch 24: profiles/r5/ab_call18_walk_tuning.jsonl)
-    if (s->walk2 && !getenv("RECOGYM_WALK_BIAS")) d.walk_bias = d.walk_helpers ? 2 : 4;
-    if (s->walk2 && !getenv("RECOGYM_WALK_SEARCH_BATCH") && d.walk_helpers) d.walk_search_batch = 24;
-    if (s->walk2) s->walk_occ = d.KH <= 10 ? 3 : 2;     // (what k_walk2 is compiled for: K <= 20 three blocks per CU, K <= 32 two)
-    s->walk_solo = true;
-    if (const char* e = getenv("RECOGYM_WALK_SOLO")) s->walk_solo = e[0] != '0';
-    // the walked run as one chain with its list lengths on the device (run_walk_pipe).  RECOGYM_PIPE=0: run_walk, host-side list
-    // lengths; RECOGYM_PIPE_OCC1 / _OCC2 (blocks per CU of the rounds' grids), RECOGYM_PIPE_XBLOCKS: A/B tests.
-    // The whole reset range is ONE group on the caller's stream.  More groups on two or three streams were measured on C3 and
-    // did not pay (profiles/r4/ab_call1_pipe_forms.jsonl): the walk's three waves per SIMD fill the register file,
-    // so nothing co-resides with it, and every group adds a drain tail to both walk rounds and a partial last wave of blocks to
-    // the float64 batch.
-    s->pipe_groups = 1;
-    s->pipe_occ1 = s->pipe_occ2 = s->walk_occ;
-    s->pipe_xblocks = 1024;
-    s->fate_base = 0; s->fate_count = nullptr;
-    if (const char* e = getenv("RECOGYM_PIPE")) { const int o = atoi(e); if (o == 0 || o == 1) s->pipe_groups = o; }
-    if (const char* e = getenv("RECOGYM_PIPE_OCC1")) { const int o = atoi(e); if (o >= 1 && o <= s->walk_occ) s->pipe_occ1 = o; }
-    if (const char* e = getenv("RECOGYM_PIPE_OCC2")) { const int o = atoi(e); if (o >= 1 && o <= s->walk_occ) s->pipe_occ2 = o; }
-    if (const char* e = getenv("RECOGYM_PIPE_XBLOCKS")) { const int o = atoi(e); if (o >= 1) s->pipe_xblocks = o; }
-    s->fin_in_sweep = true;
-    if (const char* e = getenv("RECOGYM_FIN_IN_SWEEP")) s->fin_in_sweep = e[0] != '0';
-    d.fin_in_sweep = 0;
-    s->pipe_min_users = 1u << 17;
-    if (const char* e = getenv("RECOGYM_PIPE_MIN")) { const int o = atoi(e); if (o >= 256) s->pipe_min_users = static_cast<uint32_t>(o); }
-    d.grp_lo = 0; d.grp_n = d.n_users; d.list_in = 0;
-    d.q_ticket = d.counters + kCntWalkTicket; d.q_park = d.counters + kCntParkCnt; d.q_count = nullptr;
-    if (const char* e = getenv("RECOGYM_TAIL"))        // (never for the frozen LogReg policy: k_tail acts on one thread — 46 s per C5 step)
-        if (d.policy != RG_POLICY_LOGREG_FROZEN) s->tail_below = static_cast<uint32_t>(atoi(e));
-    if (const char* e = getenv("RECOGYM_REPACK")) s->repack_every = static_cast<uint32_t>(atoi(e));
-    s->run_ahead = 32;         // events a round of a run to the end may take a user through (0: lock-step, an event per launch)
-    if (const char* e = getenv("RECOGYM_RUN_AHEAD")) s->run_ahead = static_cast<uint32_t>(atoi(e));
-    s->lr_part_rows = d.lr_part_cap;
-    if (const char* e = getenv("RECOGYM_LR_PART_CAP")) { const uint32_t v = static_cast<uint32_t>(atoi(e)); if (v < d.lr_part_cap) d.lr_part_cap = v; }
-    if (const char* e = getenv("RECOGYM_ABLATE")) d.ablate = static_cast<uint32_t>(atoi(e));
-    if (d.lr_sample) s->run_ahead = 0;     // a sampled act per event: lock-step (k_advance_run reuses one act for a whole bandit run)
-    if (d.env_kind) {
-        // reco-gym-v0: no omega, no product sweep — the lock-step loop with its own draw kernel (k_draw_env0), nothing else
-        d.use_mfma = 0; d.use_cache = 0; d.XNH = d.XNL = d.XRS = 0;
-        s->bf16_kernel = nullptr; s->xh_kernel = nullptr;
-        s->walk = s->walk2 = false;
-        s->tail_below = 0;
-        s->run_ahead = 0;
-    }
-    if (const char* e = getenv("RECOGYM_LDS_PAD")) s->mfma_smem += static_cast<size_t>(atoi(e));
-    if (s->opt.debug && d.use_mfma && rg_device_count() > 0) {
-        int nb = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(mfma_kernel_for(10)), kBlock, s->mfma_smem);
-        fprintf(stderr, "[recogym] k_draw_mfma<10>: dynamic LDS %zu B, occupancy API %d blocks/CU\n", s->mfma_smem, nb);
-    }
-    if (s->mfma_smem > 64 * 1024)
-        for (uint32_t kh : {4u, 10u, 16u, 32u, 64u}) set_max_lds(mfma_kernel_for(kh), s->mfma_smem);
+    memset(&s->d, 0, sizeof(s->d));
+    carve_all(*cfg, n_users, g, d_workspace, &s->d);
+    plan_config(s, cfg, n_users, w);
+    plan_draw(s, w, g);
+    plan_sweep_xh(s, w);
+    plan_sweep_lds(s, w, g);
+    plan_repack_tail(s, w);
+    plan_walk(s, w);
+    plan_pipe(s, w);
+    plan_logreg_run_ahead(s, w);
+    plan_env0(s);
+    plan_mfma_lds(s, w);
     *out = s;
     return RG_OK;
 }
@@ -1380,89 +1377,81 @@ int rg_sim_destroy(rg_sim* sim) {
     return RG_OK;
 }
 
-// name -> the field it sets; every entry is a run-path tuning knob (none changes the workspace layout or a result)
+// Every option rg_sim_set_option / rg_sim_get_option know by name (include/recogym_hip.h): how it is read and, for a run-path knob
+// (none changes the workspace layout or a result), how it is written: into an int or a uint32_t, a value in [lo, hi], else
+// `refusal` ("%s": the name).  `range_first`: that text also for a value too wide for the field.  set = nullptr: read-only.
 namespace {
-int* opt_int(rg_sim* s, const char* n) {
-    if (!strcmp(n, "pipe_groups")) return &s->pipe_groups;
-    if (!strcmp(n, "pipe_occ1")) return &s->pipe_occ1;
-    if (!strcmp(n, "pipe_occ2")) return &s->pipe_occ2;
-    if (!strcmp(n, "pipe_xblocks")) return &s->pipe_xblocks;
-    if (!strcmp(n, "exact_mix")) return &s->opt.exact_mix;
-    if (!strcmp(n, "exact_tile")) return &s->opt.exact_tile;
-    if (!strcmp(n, "slices")) return &s->opt.slices;
-    if (!strcmp(n, "sweep_prefix_off")) return &s->opt.sweep_prefix_off;
-    if (!strcmp(n, "debug")) return &s->opt.debug;
-    return nullptr;
-}
-uint32_t* opt_u32(rg_sim* s, const char* n) {
-    if (!strcmp(n, "walk_bias")) return &s->d.walk_bias;
-    if (!strcmp(n, "walk_refill")) return &s->d.walk_refill;
-    if (!strcmp(n, "walk_handover")) return &s->d.walk_handover;
-    if (!strcmp(n, "walk_click_batch")) return &s->d.walk_click_batch;
-    if (!strcmp(n, "walk_search_batch")) return &s->d.walk_search_batch;
-    if (!strcmp(n, "walk_line64")) return &s->d.walk_line64;
-    if (!strcmp(n, "walk_helpers")) return &s->d.walk_helpers;
-    if (!strcmp(n, "walk_click_join")) return &s->d.walk_click_join;
-    if (!strcmp(n, "pipe_min_users")) return &s->pipe_min_users;
-    if (!strcmp(n, "tail_below")) return &s->tail_below;
-    if (!strcmp(n, "repack_every")) return &s->repack_every;
-    if (!strcmp(n, "run_ahead")) return &s->run_ahead;
-    if (!strcmp(n, "sweep_lds")) return &s->sweep_lds;
-    if (!strcmp(n, "lr_part_cap")) return &s->d.lr_part_cap;
+struct Option {
+    const char* name; int64_t (*get)(rg_sim*); void (*set)(rg_sim*, int64_t);
+    bool is_u32; int64_t lo, hi; bool range_first; const char* refusal;
+};
+#define RG_OPT(name, field, T, lo, hi, first, refusal) \
+    {name, [](rg_sim* s) -> int64_t { return s->field; }, [](rg_sim* s, int64_t v) { s->field = static_cast<T>(v); }, std::is_unsigned<T>::value, lo, hi, first, refusal}
+#define RG_OPT_I(name, field) RG_OPT(name, field, int, INT64_MIN, INT64_MAX, false, nullptr)
+#define RG_OPT_U(name, field) RG_OPT(name, field, uint32_t, INT64_MIN, INT64_MAX, false, nullptr)
+#define RG_OPT_R(name, expr) {name, [](rg_sim* s) -> int64_t { return static_cast<int64_t>(expr); }, nullptr, false, 0, 0, false, nullptr},
+#define RG_OPT_LEDGER(f) RG_OPT_R("launched_" #f, s->led.f)
+constexpr const char* kFlagText = "%s is a flag (0 or 1)";
+static_assert(kWalkHelpersMax == 7, "the refusal text of walk_helpers names the bound");
+const Option kOptions[] = {
+    RG_OPT_I("pipe_occ1", pipe_occ1), RG_OPT_I("pipe_occ2", pipe_occ2),      // (bounded by walk_occ: rg_sim_set_option)
+    RG_OPT("pipe_groups", pipe_groups, int, 0, 1, false, "pipe_groups must be 1 (list lengths on the device) or 0 (run_walk: read back by the host)"),
+    RG_OPT("pipe_xblocks", pipe_xblocks, int, 1, INT64_MAX, true, "pipe_xblocks must be >= 1"),
+    RG_OPT("exact_mix", opt.exact_mix, int, 0, 8, true, "exact_mix must be in [0, 8]"),
+    RG_OPT("slices", opt.slices, int, -1, INT64_MAX, false, "slices must be >= -1 (-1 = by population)"),
+    RG_OPT("exact_tile", opt.exact_tile, int, 0, 1, false, kFlagText), RG_OPT("sweep_prefix_off", opt.sweep_prefix_off, int, 0, 1, false, kFlagText),
+    RG_OPT("debug", opt.debug, int, 0, 1, false, kFlagText), RG_OPT("walk_click_join", d.walk_click_join, uint32_t, 0, 1, false, kFlagText),
+    RG_OPT_U("walk_bias", d.walk_bias), RG_OPT_U("walk_refill", d.walk_refill), RG_OPT_U("walk_handover", d.walk_handover),
+    RG_OPT_U("walk_click_batch", d.walk_click_batch), RG_OPT_U("walk_search_batch", d.walk_search_batch), RG_OPT_U("walk_line64", d.walk_line64),
+    RG_OPT("walk_helpers", d.walk_helpers, uint32_t, 0, kWalkHelpersMax, false, "walk_helpers must be in [0, 7]"),
+    RG_OPT("pipe_min_users", pipe_min_users, uint32_t, 256, INT64_MAX, false, "pipe_min_users must be >= 256"),
+    RG_OPT_U("tail_below", tail_below), RG_OPT_U("repack_every", repack_every), RG_OPT_U("sweep_lds", sweep_lds),
+    RG_OPT("run_ahead", run_ahead, uint32_t, 0, 64, false, "run_ahead must be <= 64 events"),
+    RG_OPT_U("lr_part_cap", d.lr_part_cap),
+    // read-only: the launch ledger (launched_<family>) and what rg_sim_create chose
+    RG_LEDGER_FAMILIES(RG_OPT_LEDGER)
+    RG_OPT_R("sweep_lds_kernel", s->tp_kernel ? 1 : 0)      // k_draw_tp / k_draw_tpw serves the configuration
+    RG_OPT_R("draw_kh", s->d.KH) RG_OPT_R("draw_n1", s->d.N1) RG_OPT_R("draw_kernel", s->d.use_mfma)
+    RG_OPT_R("draw_split", !s->d.N1 ? 0 : (!s->d.f16 ? 1 : (s->d.wide ? 3 : 2)))
+    RG_OPT_R("draw_pipelined", (s->bf16_kernel && s->bf16_kernel == bf16p_kernel_for(s->d)) ? 1 : 0)
+    RG_OPT_R("xh_waves", s->xh_kernel ? s->xh_waves : 0)
+    RG_OPT_R("xh_class", s->xh_kernel ? s->d.KH * 100 + s->d.XNH * 10 + s->d.XNL : 0)
+    RG_OPT_R("walk_form", !s->walk ? 0 : (s->walk2 ? 2 : 1)) RG_OPT_R("walk_occ", s->walk_occ) RG_OPT_R("walk_solo", s->walk_solo)
+    RG_OPT_R("use_cache", s->d.use_cache) RG_OPT_R("fin_in_sweep", s->fin_in_sweep) RG_OPT_R("handover_auto", s->handover_auto)
+    RG_OPT_R("draw_smem", s->bf16_smem) RG_OPT_R("mfma_smem", s->mfma_smem) RG_OPT_R("xh_smem", s->xh_smem) RG_OPT_R("tp_smem", s->tp_smem)
+    RG_OPT_R("tp_nts", s->tp_nts) RG_OPT_R("tp_cpt", s->d.tp_cpt) RG_OPT_R("draw_threads", s->draw_threads)
+    RG_OPT_R("exact_rows", s->d.exact_rows) RG_OPT_R("hist_cap", s->d.hist_cap) RG_OPT_R("repack_min", s->opt.repack_min) RG_OPT_R("ablate", s->d.ablate)
+};
+const Option* find_option(const char* name) {
+    for (const Option& o : kOptions) if (!strcmp(o.name, name)) return &o;
     return nullptr;
 }
 }  // namespace
 
 int rg_sim_set_option(rg_sim* sim, const char* name, int64_t value) {
     if (!sim || !name) return fail(RG_EINVAL, "NULL argument");
-    if (int* p = opt_int(sim, name)) {
-        if ((!strcmp(name, "pipe_occ1") || !strcmp(name, "pipe_occ2")) && (value < 1 || value > sim->walk_occ))
-            return fail(RG_EINVAL, "%s must be in [1, %d]", name, sim->walk_occ);
-        if (!strcmp(name, "pipe_xblocks") && value < 1) return fail(RG_EINVAL, "pipe_xblocks must be >= 1");
-        if (!strcmp(name, "exact_mix") && (value < 0 || value > 8)) return fail(RG_EINVAL, "exact_mix must be in [0, 8]");
-        if (value < -2147483647 || value > 2147483647) return fail(RG_EINVAL, "%s out of the range of an int", name);
-        if (!strcmp(name, "pipe_groups") && (value < 0 || value > 1))
-            return fail(RG_EINVAL, "pipe_groups must be 1 (list lengths on the device) or 0 (run_walk: read back by the host)");
-        if (!strcmp(name, "slices") && value < -1) return fail(RG_EINVAL, "slices must be >= -1 (-1 = by population)");
-        if ((!strcmp(name, "exact_tile") || !strcmp(name, "sweep_prefix_off") || !strcmp(name, "debug")) &&
-            (value < 0 || value > 1)) return fail(RG_EINVAL, "%s is a flag (0 or 1)", name);
-        *p = static_cast<int>(value);
-        return RG_OK;
-    }
-    if (uint32_t* p = opt_u32(sim, name)) {
-        if (value < 0 || value > 0xFFFFFFFFll) return fail(RG_EINVAL, "%s must be in [0, 2^32)", name);
-        if (!strcmp(name, "run_ahead") && value > 64) return fail(RG_EINVAL, "run_ahead must be <= 64 events");
-        if (!strcmp(name, "run_ahead") && value && sim->d.env_kind) return fail(RG_EINVAL, "env_kind 1 (reco-gym-v0) runs lock-step (run_ahead = 0)");
-        if (!strcmp(name, "walk_search_batch") && value < 1) value = 1;
-        if (!strcmp(name, "walk_handover")) sim->handover_auto = false;
-        if (!strcmp(name, "walk_click_join") && value > 1) return fail(RG_EINVAL, "walk_click_join is a flag (0 or 1)");
-        if (!strcmp(name, "walk_helpers") && value > kWalkHelpersMax) return fail(RG_EINVAL, "walk_helpers must be in [0, %u]", kWalkHelpersMax);
-        if (!strcmp(name, "pipe_min_users") && value < 256) return fail(RG_EINVAL, "pipe_min_users must be >= 256");
-        if (!strcmp(name, "lr_part_cap") && static_cast<uint64_t>(value) > sim->lr_part_rows)
-            return fail(RG_EINVAL, "lr_part_cap can only be lowered (the workspace holds %u rows)", sim->lr_part_rows);
-        *p = static_cast<uint32_t>(value);
-        return RG_OK;
-    }
-    return fail(RG_EINVAL, "unknown option '%s'", name);
+    const Option* o = find_option(name);
+    if (!o || !o->set) return fail(RG_EINVAL, "unknown option '%s'", name);
+    if (!strncmp(name, "pipe_occ", 8) && (value < 1 || value > sim->walk_occ)) return fail(RG_EINVAL, "%s must be in [1, %d]", name, sim->walk_occ);
+    const bool fits = o->is_u32 ? (value >= 0 && value <= 0xFFFFFFFFll) : (value >= -2147483647 && value <= 2147483647);
+    if ((value < o->lo || value > o->hi) && (fits || o->range_first)) return fail(RG_EINVAL, o->refusal, name);
+    if (!fits) return fail(RG_EINVAL, o->is_u32 ? "%s must be in [0, 2^32)" : "%s out of the range of an int", name);
+    // the rules that are no plain range
+    if (!strcmp(name, "run_ahead") && value && sim->d.env_kind) return fail(RG_EINVAL, "env_kind 1 (reco-gym-v0) runs lock-step (run_ahead = 0)");
+    if (!strcmp(name, "lr_part_cap") && static_cast<uint64_t>(value) > sim->lr_part_rows)
+        return fail(RG_EINVAL, "lr_part_cap can only be lowered (the workspace holds %u rows)", sim->lr_part_rows);
+    if (!strcmp(name, "walk_search_batch") && value < 1) value = 1;
+    if (!strcmp(name, "walk_handover")) sim->handover_auto = false;
+    o->set(sim, value);
+    return RG_OK;
 }
 
 int rg_sim_get_option(rg_sim* sim, const char* name, int64_t* value) {
     if (!sim || !name || !value) return fail(RG_EINVAL, "NULL argument");
-    if (!strcmp(name, "sweep_lds_kernel")) { *value = sim->tp_kernel ? 1 : 0; return RG_OK; }     // read-only: k_draw_tp serves the configuration
-    // read-only: the launch ledger (launched_<family>) and what rg_sim_create chose for the fast draw
-#define RG_LEDGER_GET(f) if (!strcmp(name, "launched_" #f)) { *value = static_cast<int64_t>(sim->led.f); return RG_OK; }
-    RG_LEDGER_FAMILIES(RG_LEDGER_GET)
-#undef RG_LEDGER_GET
-    if (!strcmp(name, "draw_kh")) { *value = sim->d.KH; return RG_OK; }
-    if (!strcmp(name, "draw_n1")) { *value = sim->d.N1; return RG_OK; }
-    if (!strcmp(name, "draw_split")) { *value = !sim->d.N1 ? 0 : (!sim->d.f16 ? 1 : (sim->d.wide ? 3 : 2)); return RG_OK; }
-    if (!strcmp(name, "draw_kernel")) { *value = sim->d.use_mfma; return RG_OK; }
-    if (!strcmp(name, "draw_pipelined")) { *value = (sim->bf16_kernel && sim->bf16_kernel == bf16p_kernel_for(sim->d)) ? 1 : 0; return RG_OK; }
-    if (!strcmp(name, "xh_waves")) { *value = sim->xh_kernel ? sim->xh_waves : 0; return RG_OK; }
-    if (!strcmp(name, "xh_class")) { *value = sim->xh_kernel ? static_cast<int64_t>(sim->d.KH * 100 + sim->d.XNH * 10 + sim->d.XNL) : 0; return RG_OK; }
-    if (int* p = opt_int(sim, name)) { *value = *p; return RG_OK; }
-    if (uint32_t* p = opt_u32(sim, name)) { *value = *p; return RG_OK; }
-    return fail(RG_EINVAL, "unknown option '%s'", name);
+    const Option* o = find_option(name);
+    if (!o) return fail(RG_EINVAL, "unknown option '%s'", name);
+    *value = o->get(sim);
+    return RG_OK;
 }
 
 int rg_sim_set_tables(rg_sim* sim, const double* d_gamma, const double* d_mu_organic,
@@ -2020,11 +2009,10 @@ int rg_sim_sort_log(rg_sim* sim, int64_t* d_row_offsets, int64_t* d_scratch, rg_
     HIP_TRY(hipStreamSynchronize(st));
     if (n_rows > d.log_cap) return fail(RG_ELIMIT, "log overflow: %llu rows emitted, capacity %llu",
                                         (unsigned long long)n_rows, (unsigned long long)d.log_cap);
-    {
-        static const bool plain = getenv("RECOGYM_SORT_PLAIN") != nullptr;      // (A/B: the scatter without the LDS tiles)
+    {   // (sort_plain, A/B: the scatter without the LDS tiles)
         const uint64_t tiles = (n_rows + kSortTile - 1) / kSortTile;
         const uint64_t cap = static_cast<uint64_t>(device_cus(sim)) * 12u;
-        if (plain) { hipLaunchKernelGGL(k_scatter_rows, dim3(grid_for(n_rows)), dim3(kBlock), 0, st, d, n_rows, d_row_offsets, d_sorted, sorted_capacity); sim->led.sort_plain += 1; }
+        if (sim->sort_plain) { hipLaunchKernelGGL(k_scatter_rows, dim3(grid_for(n_rows)), dim3(kBlock), 0, st, d, n_rows, d_row_offsets, d_sorted, sorted_capacity); sim->led.sort_plain += 1; }
         else {
             hipLaunchKernelGGL(k_scatter_rows_tiled, dim3(static_cast<unsigned>(tiles < cap ? (tiles ? tiles : 1) : cap)), dim3(kBlock), 0, st, d, n_rows,
                                d_row_offsets, d_sorted, sorted_capacity);
