@@ -148,7 +148,16 @@ typedef struct rg_event {
 #define RG_CNT_LOG_ROWS 6       /* rows written to the log buffer */
 #define RG_CNT_LOG_DROPPED 7    /* rows that did not fit (capacity exceeded) */
 #define RG_CNT_EXACT_DRAWS 8    /* organic draws resolved by the float64 path */
-#define RG_CNT_HIST_OVERFLOW 9  /* OrganicUserEventCounter views that did not fit ouc_history_cap */
+#define RG_CNT_HIST_OVERFLOW 9  /* views DROPPED from a full view-history row (OrganicUserEventCounter, the frozen LogReg, the likelihood
+                                   agent).  A row has hist_cap = ((ouc_history_cap or 255) + 1 + 15) & ~15 entries (the read-only option
+                                   "hist_cap": 15 -> 16, 16 -> 32, 31 -> 32, 47 -> 48, 0 -> 256) and keeps keep = hist_cap - 1 distinct
+                                   products.  A view of a kept product raises its count and the row's view total; a view of a new
+                                   product with fewer than `keep` kept is inserted in ascending product order, total + 1; a view of a
+                                   new product at `keep` kept leaves the row and the total as they are and adds ONE to this counter —
+                                   per dropped view, not per user — and the policy acts on the kept counts from then on.  The organic
+                                   row is logged either way.  Zero means every act of the run saw its user's whole history; a caller
+                                   that needs that runs again with a larger ouc_history_cap when it is not (RecoEnv1.simulate does).
+                                   Held on every run form by tests/test_history_capacity.py */
 #define RG_CNT_EXACT_SWEEPS 10  /* float64 product sweeps those draws needed (== EXACT_DRAWS unless sigma_omega = 0,
                                    where a user's float64 sums are taken once and reused) */
 #define RG_CNT_EXACT_OVERFLOW 11 /* uncertified draws beyond what the float64 resolve scratch covers in a step (25 % of the

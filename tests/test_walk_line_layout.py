@@ -18,6 +18,7 @@ import golden_util as gu
 from recogym_amd import _abi
 from recogym_amd.envs.configuration import Configuration
 from recogym_amd.envs.reco_env_v1 import env_1_args
+from history_model import oracle_log_with_presets
 from test_hip_parity import assert_walk_pipe, run_sim
 
 pytestmark = pytest.mark.gpu
@@ -96,57 +97,10 @@ def preset_histories(P, n, seed):
     return nd, prod, cnt, stride
 
 
-def oracle_log_with_presets(cfg, n, nd, prod, cnt):
-    """The oracle's environment (reset / step) driven user by user with OrganicUserEventCounterModel.act
-    (organic_user_count.py:45-96: epsilon = 0, exploit_explore, select_randomly — p = counts / sum, cumsum, / last,
-    searchsorted 'right', ps = p[a]) on view counts that start at the preset ones; the act's uniform is the policy draw of
-    (user, t), words 2 and 3.  A user without a preset: the oracle's own generate_logs."""
-    from oracle import oracle as orc
-    env = orc.OracleEnv(cfg, rng_mode=orc.RNG_PHILOX, **POL)
-    seed = int(env.rg_config.policy_seed)
-    key = (seed & 0xFFFFFFFF, seed >> 32)
-    uniform = orc.lib().rgo_uniform
-    P = cfg.num_products
-    out = []
-
-    def act(views, user, t):
-        w = orc.philox((user, t, 0, 1), key)                        # RG_DRAW_POLICY = 1
-        u1 = uniform(int(w[2]), int(w[3]))
-        p = views / np.sum(views)
-        cdf = p.cumsum()
-        cdf /= cdf[-1]
-        a = int(cdf.searchsorted(u1, side='right'))
-        return a, p[a]
-
-    for user in range(n):
-        if nd[user] == 0:
-            for r in env.generate_logs(1, 0, first_user_id=user):
-                out.append((r['u'], r['t'], r['z'], r['v'], r['a'], r['c'], r['ps'], r['phantom']))
-            continue
-        views = np.zeros(P)
-        views[prod[user, :nd[user]]] = cnt[user, :nd[user]]
-        env.reset(user)
-        org, _, done = env.step(None)
-        while True:
-            for r in org:
-                out.append((user, r['t'], 0, r['v'], -1, -1, np.nan, 0))
-                views[r['v']] += 1.0
-            t = env.time
-            a, ps = act(views, user, t)
-            if done:
-                out.append((user, t, 1, -1, a, 0, ps, 1))            # the act of the last step_offline: the phantom row
-                break
-            org, reward, done = env.step(a)
-            out.append((user, t, 1, -1, a, reward, ps, 0))
-    dt = np.dtype([('u', np.int64), ('t', np.int64), ('z', np.int64), ('v', np.int64), ('a', np.int64), ('c', np.int64),
-                   ('ps', np.float64), ('phantom', np.int64)])
-    return np.array(out, dtype=dt)
-
-
 def test_preset_histories_on_the_compact_line_match_the_oracle(monkeypatch):
     """2 048 users whose histories are written through rg_sim_debug_set_history after the reset: the refill loads rows (some
     lanes have a history), lines that start full, histories that start beyond the line, and a first act on a preset history.
-    The oracle keeps no preset, so its environment is stepped with the reference's act on the preset counts (see above)."""
+    The oracle keeps no preset, so its environment is stepped with the reference's act on the preset counts (history_model.py)."""
     from recogym_amd.sim import Simulator
     monkeypatch.setenv('RECOGYM_PIPE_MIN', '256')
     P, n, seed = 300, 2048, 7104
