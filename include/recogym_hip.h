@@ -634,6 +634,44 @@ int rg_ope_replay_poly_eg(const rg_ope_poly* model, const rg_ope_eg* eg, const r
                           void* d_workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * recall@k (evaluate_recall_at_k, reference evaluate_agent.py:832-870) over a sorted log.  A bandit row i of user u is COUNTED
+ * when it has no click, row i + 1 lies inside user u's range and row i + 1 is organic; it is a HIT when that row's product is
+ * among the k largest entries of the target's `ps-a` at row i.  No row at or beyond d_offsets[n_users] is read.
+ * d_hit[row] (uint8, written for EVERY row of the evaluated users): RG_RECALL_MISS, RG_RECALL_HIT, RG_RECALL_NOT_COUNTED
+ * (organic rows too) or, from the ranking form only, RG_RECALL_UNRESOLVED.  d_sums (2 int64) = (counted rows, hits): integer
+ * sums, the same on every run.
+ */
+#define RG_RECALL_MISS 0
+#define RG_RECALL_HIT 1
+#define RG_RECALL_NOT_COUNTED 2
+#define RG_RECALL_UNRESOLVED 3
+#define RG_OPE_RECALL_LIST_CAP 4096     /* default entries of the ranking form's list of unresolved rows */
+
+/* The table form, for targets whose top-k SET is a function of a small key (a one-hot `ps-a`: the model's act; under EpsilonGreedy
+ * the act and the explore flip; one constant vector): d_key[row] (int32, read on counted rows only) selects one of n_keys sets,
+ * d_sets[key][0 .. k-1] (int32, ASCENDING within a key) holds the set the caller built — with NumPy's own np.argpartition on
+ * the host, so that its order among ties is reproduced by construction — and the device only tests membership.  A counted row
+ * whose key is outside [0, n_keys) is marked RG_RECALL_NOT_COUNTED and not counted (the caller builds the keys).  Stateless, no
+ * workspace, enqueued on `stream`, no synchronisation.  RG_EINVAL: null arrays, k == 0, n_keys == 0, rows not 16-byte aligned. */
+int rg_ope_recall_hits(const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users, const int32_t* d_key, uint32_t n_keys,
+                       const int32_t* d_sets, uint32_t k, uint8_t* d_hit, int64_t* d_sums, void* stream);
+
+/* The ranking form, for the sampling LogReg (rg_ope_logreg with select_randomly != 0: the preconditions and the validation of
+ * the log are rg_ope_replay_logreg's), whose `ps-a` is a softmax: the replay's own float64 scores and e[j] = exp(s[j] - max),
+ * then the rank rule on the e's of the row's act with v = the next organic view.  Two e's are ordered only where they differ by
+ * more than 2^-48 relative and do not both lie under 2^-1000 (inside that margin the host's quotients may compare either way):
+ *   HIT where at most k classes are not certainly below v;  MISS where at least k classes are certainly above v;
+ *   RG_RECALL_UNRESOLVED otherwise: the row is counted in d_sums[0], not in d_sums[1], and appended to the list.
+ * Workspace: the first int64 words hold [0] error bits (0), [1] acts computed, [2] the same, [3] coef_t rows read, [4] unresolved
+ * rows, [5] non-zero when they outgrew the list; from byte 256 the list: up to list_cap (0 = RG_OPE_RECALL_LIST_CAP; at most
+ * 2^20) entries of three uint32 (user index, position of the row within the user's rows, v), in no fixed order.  RG_EINVAL
+ * besides rg_ope_replay_logreg's: select_randomly == 0, k outside 1 .. P.  Synchronises `stream` twice. */
+size_t rg_ope_recall_logreg_workspace_bytes(const rg_ope_logreg* model, uint64_t n_users, uint32_t max_user_rows, uint32_t list_cap);
+int rg_ope_recall_logreg(const rg_ope_logreg* model, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                         uint32_t max_user_rows, uint32_t k, uint32_t list_cap, uint8_t* d_hit, int64_t* d_sums,
+                         void* d_workspace, size_t workspace_bytes, void* stream);
+
+/*
  * The count agents' training (reference agents/organic_count.py:74-82, agents/bandit_count.py:49-62 under the offline protocol
  * of bench_agents.py:90-190): a sorted log reduced to P x P tables of 64-bit integer counters.  Stateless (no rg_sim handle).
  * The tables are caller-owned row-major int64 device arrays; either group (co_counts | pulls + clicks) may be NULL.

@@ -112,6 +112,13 @@ OPE_HEADS = {'logreg': ('error', 'acts', 'exact', 'rows_read'),
              'poly': ('error', 'acts', 'table', 'lower', 'unresolved', 'overflow', 'rows_read')}
 OPE_POLY_LIST_CAP = 4096
 OPE_POLY_LIST_ENTRY_BYTES = 12
+# recall@k (rg_ope_recall_hits, rg_ope_recall_logreg): the values of d_hit; the ranking form's head words and, from byte
+# OPE_HEAD_BYTES of its workspace, its list of unresolved rows: three uint32 (user index, position of the row within the user's
+# rows, next view), OPE_RECALL_LIST_CAP entries unless the call names another capacity
+RG_RECALL_MISS, RG_RECALL_HIT, RG_RECALL_NOT_COUNTED, RG_RECALL_UNRESOLVED = 0, 1, 2, 3
+OPE_RECALL_HEAD = ('error', 'acts', 'exact', 'rows_read', 'unresolved', 'overflow')
+OPE_RECALL_LIST_CAP = 4096
+OPE_RECALL_LIST_ENTRY_BYTES = 12
 
 RG_COUNT_ORGANIC, RG_COUNT_BANDIT = 0, 1
 
@@ -197,6 +204,11 @@ SYMBOLS = {
     'rg_ope_replay_poly_eg': (C.c_int, [C.POINTER(RgOpePoly), C.POINTER(RgOpeEg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
                                         C.c_uint32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rg_ope_recall_hits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    'rg_ope_recall_logreg_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpeLogreg), C.c_uint64, C.c_uint32, C.c_uint32]),
+    'rg_ope_recall_logreg': (C.c_int, [C.POINTER(RgOpeLogreg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'rg_count_workspace_bytes': (C.c_size_t, []),
     'rg_count_train': (C.c_int, [C.POINTER(RgCountTables), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_void_p]),

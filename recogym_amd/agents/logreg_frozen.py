@@ -15,6 +15,21 @@ from .. import _abi, rng
 from .abstract import Agent
 
 
+def softmax(score):
+    """sklearn's multinomial predict_proba: softmax(decision_function) (sklearn.utils.extmath.softmax)."""
+    e = np.exp(score - score.max())
+    return e / e.sum()
+
+
+def view_proba(coef_t, intercept, views):
+    """`ps-a` of the sampling model over the view counts `views` (P int64), act()'s own arithmetic: the viewed products ascending,
+    multiply then add, intercept last, softmax (evaluate_agent.recall_replay recomputes single acts with it)."""
+    score = np.zeros(len(intercept))
+    for p in np.flatnonzero(views):
+        score = score + np.float64(views[p]) * coef_t[p]
+    return softmax(score + intercept)
+
+
 class LogregFrozenAgent(Agent):
     def __init__(self, config, coef, intercept, classes):
         """coef (n_classes, P) / intercept (n_classes,) / classes (n_classes,) as sklearn stores them;
@@ -96,9 +111,7 @@ class LogregFrozenAgent(Agent):
                 score = score + np.float64(self.views[p]) * self.coef_t[p]
         score = score + self.intercept
         if self.select_randomly:
-            # sklearn's multinomial predict_proba: softmax(decision_function) (sklearn.utils.extmath.softmax)
-            e = np.exp(score - score.max())
-            proba = e / e.sum()
+            proba = softmax(score)
             assert len(proba) == self.config.num_products, 'select_randomly needs every product as a class'
             ctx = observation.context()
             key = ctx.draw_key() if hasattr(ctx, 'draw_key') else (ctx.user(), ctx.time())

@@ -145,6 +145,40 @@ __device__ __forceinline__ double ope_model_pi(const OpeRow& r, uint32_t g, uint
     return explore ? eps * ((x.eg.pure_new && a == g) ? 0.0 : x.eg.prob_explore) : (1.0 - eps) * (a == g ? 1.0 : 0.0);
 }
 
+// ---- recall@k (evaluate_recall_at_k: rg_ope_recall.hip the table form, rg_ope_logreg.hip the ranking form) ----
+// d_hit values.  A bandit row is COUNTED when it has no click and its successor INSIDE THE USER'S RANGE is an organic row.
+constexpr uint8_t kRecallMiss = RG_RECALL_MISS, kRecallHit = RG_RECALL_HIT, kRecallNotCounted = RG_RECALL_NOT_COUNTED,
+                  kRecallUnresolved = RG_RECALL_UNRESOLVED;
+
+// The `code` word of every lane's successor row, or 0 with has_next = false where the lane's row is its user's last (or beyond
+// `e`).  Lane i < 63 takes lane i + 1's; lane 63 reads the first row of the next chunk, and only where base + 64 < e: no row at
+// or beyond the user's end e <= d_offsets[n_users] is ever addressed.
+__device__ __forceinline__ uint32_t ope_next_code(const rg_event* __restrict__ rows, int64_t row, int64_t e, uint32_t code, uint32_t lane,
+                                                  bool& has_next) {
+    has_next = row + 1 < e;
+    uint32_t next = static_cast<uint32_t>(__shfl_down(static_cast<int>(code), 1));
+    if (lane == 63 && has_next) next = rows[row + 1].code;
+    return has_next ? next : 0u;
+}
+
+__device__ __forceinline__ bool ope_recall_counted(uint32_t code, uint32_t next, bool has_next) {
+    return (code & RG_EV_BANDIT) && !(code & RG_EV_CLICK) && has_next && !(next & RG_EV_BANDIT);
+}
+
+// The ranking form of a model unit's replay kernel (rg_ope_logreg.hip: one more kernel argument, as OpeEg is for the EG form).
+// sums = (counted, hits); list = (user, position of the row within the user's rows, next view) of the rows inside the margin.
+struct OpeRecall {
+    uint8_t* __restrict__ hit;
+    unsigned long long* __restrict__ sums;
+    uint32_t* __restrict__ list;
+    uint32_t list_cap;
+    uint32_t k;
+};
+
+// the first (only) argument of a kernel's trailing pack
+template <typename T>
+__device__ __forceinline__ const T& ope_pack_arg(const T& x) { return x; }
+
 // the wrapper's own argument checks (the three EpsilonGreedy entry points')
 inline int ope_eg_ok(const char* who, const rg_ope_eg* eg, uint32_t num_products) {
     if (!eg) return fail(RG_EINVAL, "%s: null eg", who);

@@ -24,6 +24,9 @@
 //                 the xor butterfly, e / sum — k_logreg_sample's arithmetic and decomposition, so a log the step loop wrote
 //                 under the same model replays to ratios of exactly 1.  Classes 0 .. P-1, P <= 1024: the scores of a lane's
 //                 (at most 16) classes stay in registers.
+//   ranking form  recall@k of the sampling model (rg_ope_recall_logreg: k_ope_logreg<true, false, OpeRecall>): the softmax form's
+//                 scores and numerators, then per counted row the rank rule on the numerators with a relative margin — HIT, MISS
+//                 or, inside the margin at the k-th place, listed for the host.  No ratio, no float sums.
 #include "rg_ope_common.hpp"
 
 namespace {
@@ -40,6 +43,14 @@ constexpr uint32_t kLrFp32MaxTerms = 1u << 16;   // longer histories go to the f
 
 constexpr lr_u64 kLrErrFirstBandit = 1, kLrErrIndex = 2, kLrErrRows = 4;
 constexpr int kLrWsErr = 0, kLrWsActs = 1, kLrWsExact = 2, kLrWsRowsRead = 3, kLrWsWords = 32;
+constexpr int kLrWsUnresolved = 4, kLrWsOverflow = 5;      // the ranking form's (rg_ope_recall_logreg)
+
+// recall@k, the ranking form: two softmax numerators e = exp(s - max) are ORDERED only where they differ by more than kRcRho
+// relative — the host's p = e' / S' of the two classes then compare the same way (1 ulp per exp on either side,
+// half an ulp per quotient: 5 2^-52 < 2^-49) — and not both lie under kRcTiny, beneath which an exp or, with S' <= 1024, a
+// quotient may be subnormal and the relative bounds do not hold.
+constexpr double kRcRho = 0x1p-48, kRcTiny = 0x1p-1000;
+constexpr uint32_t kRcListCap = RG_OPE_RECALL_LIST_CAP, kRcListCapMax = 1u << 20;
 
 // entries of a wave's global list (0: no user can outgrow the LDS list)
 uint32_t lr_global_cap(uint32_t max_user_rows) { return max_user_rows > kLrLds ? max_user_rows : 0u; }
@@ -218,14 +229,17 @@ __global__ __launch_bounds__(256) void k_lr_check(const rg_event* __restrict__ r
     if (err) (void)__hip_atomic_fetch_or(&ws[kLrWsErr], err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Eg = OpeRecall (softmax form only): no ratio — the rank rule's verdict on the next organic view of every counted row (rg_ope_recall_logreg)
 template <bool kSoft, bool EG, typename... Eg>     // EG (argmax form only): pi is the EpsilonGreedy wrapper's round this act (rg_ope_replay_logreg_eg)
 __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
     rg_ope_logreg m, const rg_event* __restrict__ rows, const int64_t* __restrict__ offsets, uint64_t n_users, uint32_t ps_mode,
     const double* __restrict__ ps64, double ps_const, double* __restrict__ ratio, uint8_t* __restrict__ click,
     double* __restrict__ slots, uint32_t* __restrict__ gscr, uint32_t g_cap, lr_u64* __restrict__ ws, uint32_t n_waves,
     Eg... ega) {
-    static_assert(sizeof...(Eg) == (EG ? 1 : 0), "the EG instantiation takes an OpeEg, the plain one nothing");
+    constexpr bool kRecall = (std::is_same_v<Eg, OpeRecall> || ... || false);
+    static_assert(sizeof...(Eg) == ((EG || kRecall) ? 1 : 0), "the EG instantiation takes an OpeEg, the ranking one an OpeRecall, the plain one nothing");
     static_assert(!(kSoft && EG), "the wrapper's greedy action is the argmax form's");
+    static_assert(!kRecall || (kSoft && !EG), "the ranking form is the softmax form's");
     __shared__ uint32_t s_p[kOpeWaves][kLrLds];
     __shared__ uint32_t s_c[kOpeWaves][kLrLds];
     const uint32_t lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
@@ -238,6 +252,7 @@ __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
     const OpeLog log{rows, offsets, n_users, ps_mode, ps64, ps_const, ratio, click, slots, n_waves};
     OpeAcc acc;
     lr_u64 c_acts = 0, c_exact = 0, c_rows = 0, err = 0;
+    [[maybe_unused]] lr_u64 rc_counted = 0, rc_hits = 0;                           // (wave-uniform; the ranking form's)
 
     for (uint64_t user = wave; user < n_users; user += n_waves) {
         const int64_t b = offsets[user], e = offsets[user + 1];
@@ -255,6 +270,15 @@ __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
             const bool isb = ok && r.isb, iso = ok && r.iso;
             const lr_u64 omask = __ballot(iso), bmask = __ballot(isb);
             double pi = 0.0;
+            [[maybe_unused]] bool counted = false;
+            [[maybe_unused]] uint32_t vnext = 0;
+            [[maybe_unused]] uint8_t verdict = kRecallNotCounted;
+            if constexpr (kRecall) {
+                bool has_next;
+                const uint32_t next = ope_next_code(rows, r.row, e, r.x.z, lane, has_next);
+                vnext = next & RG_EV_INDEX_MASK;
+                counted = isb && vnext < P && ope_recall_counted(r.x.z, next, has_next);
+            }
             lr_u64 rem = omask | bmask;
             while (rem) {
                 const uint32_t k = static_cast<uint32_t>(__builtin_ctzll(rem));
@@ -318,7 +342,49 @@ __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
                 const lr_u64 next_o = omask & ~lanes_below(k);
                 const uint32_t end = next_o ? static_cast<uint32_t>(__builtin_ctzll(next_o)) : 64u;
                 const bool mine = isb && lane >= k && lane < end;
-                if (kSoft) {
+                if constexpr (kRecall) {
+                    // at most one row of the group is counted: the one in front of the next organic row
+                    const lr_u64 cm = __ballot(mine && counted);
+                    if (cm) {
+                        const OpeRecall& rc = ope_pack_arg(ega...);
+                        const uint32_t at = static_cast<uint32_t>(__builtin_ctzll(cm));
+                        const uint32_t v = lane_value(vnext, at);     // v < P <= 1024
+                        const uint32_t vq = v >> 6;
+                        double ev_v = 0.0;
+#pragma unroll
+                        for (int j = 0; j < kLrSoftBlocks; ++j) {
+                            if (64u * j < P) {
+                                const double t = __shfl(ev[j], static_cast<int>(v & 63));
+                                if (vq == static_cast<uint32_t>(j)) ev_v = t;
+                            }
+                        }
+                        // not_less: classes that may rank at or above v (v itself among them); greater: those that certainly rank above
+                        uint32_t not_less = 0, greater = 0;
+#pragma unroll
+                        for (int j = 0; j < kLrSoftBlocks; ++j) {
+                            if (64u * j < P) {
+                                const double x = ev[j];
+                                const bool on = 64u * j + lane < P;
+                                const bool near = fabs(x - ev_v) <= kRcRho * fmax(x, ev_v) || (x < kRcTiny && ev_v < kRcTiny);
+                                not_less += static_cast<uint32_t>(__popcll(__ballot(on && (near || x > ev_v))));
+                                greater += static_cast<uint32_t>(__popcll(__ballot(on && !near && x > ev_v)));
+                            }
+                        }
+                        const uint8_t out = not_less <= rc.k ? kRecallHit : greater >= rc.k ? kRecallMiss : kRecallUnresolved;
+                        if (lane == at) verdict = out;
+                        rc_counted += 1;
+                        rc_hits += out == kRecallHit ? 1 : 0;
+                        if (out == kRecallUnresolved && lane == 0) {
+                            const lr_u64 pos = __hip_atomic_fetch_add(&ws[kLrWsUnresolved], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            if (pos < rc.list_cap) {
+                                uint32_t* q = rc.list + 3 * static_cast<size_t>(pos);
+                                q[0] = static_cast<uint32_t>(user); q[1] = static_cast<uint32_t>(base - b) + at; q[2] = v;
+                            } else {
+                                (void)__hip_atomic_fetch_or(&ws[kLrWsOverflow], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            }
+                        }
+                    }
+                } else if constexpr (kSoft) {
                     const uint32_t al = idx & 63, aq = idx >> 6;      // idx < P <= 1024
                     double v = 0.0;
 #pragma unroll
@@ -334,11 +400,21 @@ __global__ __launch_bounds__(64 * kOpeWaves, kSoft ? 2 : 4) void k_ope_logreg(
                 }
                 rem &= end < 64 ? ~lanes_below(end) : 0ull;
             }
-            if (isb) acc.emit(log, r, pi);
+            if constexpr (kRecall) {
+                if (r.row < e) ope_pack_arg(ega...).hit[r.row] = verdict;
+            } else {
+                if (isb) acc.emit(log, r, pi);
+            }
         }
     }
-    acc.store(log, wave, lane);
+    if constexpr (!kRecall) acc.store(log, wave, lane);
     if (lane == 0) {
+        if constexpr (kRecall) {
+            const OpeRecall& rc = ope_pack_arg(ega...);
+            // (integer adds: the sums do not depend on their order)
+            if (rc_counted) (void)__hip_atomic_fetch_add(&rc.sums[0], rc_counted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (rc_hits) (void)__hip_atomic_fetch_add(&rc.sums[1], rc_hits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         if (c_acts) {
             (void)__hip_atomic_fetch_add(&ws[kLrWsActs], c_acts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             (void)__hip_atomic_fetch_add(&ws[kLrWsRowsRead], c_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -446,4 +522,56 @@ extern "C" int rg_ope_replay_logreg_eg(const rg_ope_logreg* m, const rg_ope_eg* 
     const OpeCall c{d_rows, d_offsets, n_users, max_user_rows, ps_mode, d_ps, ps_const, d_ratio, d_click, d_sums, d_workspace, workspace_bytes,
                     static_cast<hipStream_t>(stream)};
     return lr_replay<true>("rg_ope_replay_logreg_eg", m, &ega, c);
+}
+
+// ---- recall@k, the ranking form (the sampling model only): k_ope_logreg<true, false, OpeRecall> ----
+namespace {
+
+uint32_t rc_list_cap(uint32_t list_cap) { return list_cap ? list_cap : kRcListCap; }
+size_t rc_list_bytes(uint32_t cap) { return (static_cast<size_t>(cap) * 3 * sizeof(uint32_t) + 255) & ~size_t(255); }
+
+}  // namespace
+
+extern "C" size_t rg_ope_recall_logreg_workspace_bytes(const rg_ope_logreg* m, uint64_t n_users, uint32_t max_user_rows, uint32_t list_cap) {
+    if (!m) { fail(RG_EINVAL, "rg_ope_recall_logreg_workspace_bytes: null model"); return 0; }
+    if (list_cap > kRcListCapMax) { fail(RG_EINVAL, "rg_ope_recall_logreg_workspace_bytes: list_cap %u > %u", list_cap, kRcListCapMax); return 0; }
+    const uint32_t W = ope_waves(n_users, kLrMaxWaves);
+    return lr_head_bytes() + rc_list_bytes(rc_list_cap(list_cap)) + static_cast<size_t>(W) * 2 * lr_global_cap(max_user_rows) * sizeof(uint32_t);
+}
+
+extern "C" int rg_ope_recall_logreg(const rg_ope_logreg* m, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                                    uint32_t max_user_rows, uint32_t k, uint32_t list_cap, uint8_t* d_hit, int64_t* d_sums,
+                                    void* d_workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "rg_ope_recall_logreg";
+    if (int rc = lr_model_ok(m, who)) return rc;
+    if (!m->select_randomly) return fail(RG_EINVAL, "%s: the ranking form is the sampling model's (select_randomly != 0)", who);
+    if (k == 0 || k > m->num_products) return fail(RG_EINVAL, "%s: k %u outside 1 .. %u", who, k, m->num_products);
+    if (list_cap > kRcListCapMax) return fail(RG_EINVAL, "%s: list_cap %u > %u", who, list_cap, kRcListCapMax);
+    if (n_users && (!d_rows || !d_offsets || !d_hit)) return fail(RG_EINVAL, "%s: null rows / offsets / hit", who);
+    if (!d_sums || !d_workspace) return fail(RG_EINVAL, "%s: null sums / workspace", who);
+    const size_t need = rg_ope_recall_logreg_workspace_bytes(m, n_users, max_user_rows, list_cap);
+    if (workspace_bytes < need) return fail(RG_ENOMEM, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(d_rows) % 16) return fail(RG_EINVAL, "%s: rows not 16-byte aligned", who);
+    if (rg_device_count() <= 0) return fail(RG_ENODEV, "no HIP device");
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    int32_t cls[kLrSoftMax];
+    HIP_TRY(hipMemcpyAsync(cls, m->classes, m->n_classes * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint32_t c = 0; c < m->n_classes; ++c)
+        if (cls[c] != static_cast<int32_t>(c)) return fail(RG_EINVAL, "%s: needs classes[c] == c (classes[%u] = %d)", who, c, cls[c]);
+    const OpeCall c{d_rows, d_offsets, n_users, max_user_rows, RG_OPE_PS_ROW, nullptr, 0.0, nullptr, nullptr, nullptr, d_workspace,
+                    workspace_bytes, s};
+    const uint32_t W = ope_waves(n_users, kLrMaxWaves);
+    const uint32_t g_cap = lr_global_cap(max_user_rows), cap = rc_list_cap(list_cap);
+    lr_u64* ws = c.at<lr_u64>(0);
+    uint32_t* list = c.at<uint32_t>(lr_head_bytes());
+    uint32_t* gscr = g_cap ? c.at<uint32_t>(lr_head_bytes() + rc_list_bytes(cap)) : nullptr;
+    if (int rc = ope_check_log(who, c, m->num_products, ws)) return rc;
+    HIP_TRY(hipMemsetAsync(d_sums, 0, 2 * sizeof(int64_t), s));
+    const OpeRecall out{d_hit, reinterpret_cast<unsigned long long*>(d_sums), list, cap, k};
+    hipLaunchKernelGGL((k_ope_logreg<true, false, OpeRecall>), dim3(W / kOpeWaves), dim3(64 * kOpeWaves), 0, s, *m, d_rows, d_offsets, n_users,
+                       static_cast<uint32_t>(RG_OPE_PS_ROW), static_cast<const double*>(nullptr), 0.0, static_cast<double*>(nullptr),
+                       static_cast<uint8_t*>(nullptr), static_cast<double*>(nullptr), gscr, g_cap, ws, W, out);
+    HIP_TRY(hipGetLastError());
+    return RG_OK;
 }

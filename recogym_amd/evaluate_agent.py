@@ -14,7 +14,10 @@ the agent has a replay form (ope_policy_of; the likelihood agent's, which the ho
 qualifies, the rows are replayed on the device by one of the six entry points of the table _REPLAY_ENTRY — a plain policy, the
 frozen LogReg policy or the likelihood agent, each bare or under an EpsilonGreedy wrapper (`device_models` for a model inside).
 ope_replay is four steps: the log qualifies (_replay_users), the policy dict finds its entry point (_replay_target), one call,
-and the workspace's head decoded once from the layouts _abi names (_replay_head).  Otherwise the host loop below runs:
+and the workspace's head decoded once from the layouts _abi names (_replay_head).  recall@k has two device forms of its own
+(recall_replay): where `ps-a` is a function of the act, the top-k set of every act that occurs is built on the host by
+np.argpartition itself and the device tests membership (rg_ope_recall_hits); the sampling LogReg's softmax is ranked on the device
+(rg_ope_recall_logreg) and the rows inside its margin are decided on the host.  Otherwise the host loop below runs:
 the reference's loop made linear (one stable group-by instead of six frame filters per user), the same
 act() calls in the same order.
 
@@ -342,7 +345,8 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
     likelihood agent those of its unit: error, acts, table, lower, unresolved, overflow, rows_read (_abi.OPE_HEADS).  The likelihood agent's replay
     is None, after one RuntimeWarning, also where the host refutes an unresolved act or the device's list of them overflowed (under an
     EpsilonGreedy wrapper the listed acts are the GREEDY ones; with pure_new a wrong one changes pi on explored rows too).  `eg_out` (a
-    dict, EpsilonGreedy targets only) receives `greedy` (uint8) and `h0` (int32) of the same bandit rows (device tensors)."""
+    dict, EpsilonGreedy targets only) receives `greedy` (uint8) and `h0` (int32) of the same bandit rows (device tensors); where it
+    comes in with `per_row=True` also `greedy_rows` / `h0_rows`, one entry per row of the evaluated users (0 on organic rows)."""
     import torch
     pol = _replay_policy_of(agent) if pol is None else pol
     if pol is None or int(pol['num_products']) != int(dl.num_products):
@@ -402,6 +406,8 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
         c = _masked(((code & _abi.RG_EV_CLICK) != 0).to(torch.float64), is_b)
         if want:
             eg_out.update(greedy=_masked(greedy[:total], is_b), h0=_masked(h0[:total], is_b))
+            if eg_out.pop('per_row', False):   # (recall_replay: the two arrays as the device wrote them, one entry per row of the log)
+                eg_out.update(greedy_rows=greedy[:total], h0_rows=h0[:total])
     return r, c, sums
 
 
@@ -512,9 +518,189 @@ def verify_agents_SNIPS(reco_log, agents):
     return pd.DataFrame().from_dict(stat)
 
 
-def evaluate_recall_at_k(agent, reco_log, k=5):
-    """Hits of the next organic view in the top-k of `ps-a` after an unclicked bandit row (reference
-    evaluate_agent.py:832-870).  Host only: np.argpartition breaks ties in an order of its own."""
+# ------------------------------------------------------------------------------------------------
+# recall@k on the device
+# ------------------------------------------------------------------------------------------------
+# entries (distinct keys that occur x k) of the largest sets table recall_sets builds on the host: one np.argpartition over P
+# entries per key; beyond it the host loop is the better route
+RECALL_TABLE_MAX = 1 << 22
+_NO_FLIP = dict(epsilon=0.0, seed=0, pure_new=False)    # the wrapper that never explores: eg_threshold(0) = 0, every act greedy
+
+
+def _recall_form(pol):
+    """-> 'table' (the top-k set is a function of a key: rg_ope_recall_hits), 'rank' (the sampling LogReg's softmax:
+    rg_ope_recall_logreg) or None (OrganicUserEventCounter: `ps-a` depends on the whole count vector; a wrapper round it)."""
+    kind, eg = pol.get('kind'), pol.get('epsilon_greedy')
+    if (pol.get('logreg') or {}).get('select_randomly'):
+        return 'rank' if eg is None else None
+    if kind in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE, _abi.RG_POLICY_LOGREG_FROZEN, _abi.RG_POLICY_LOGREG_POLY):
+        return 'table'
+    return None
+
+
+def _recall_k_ok(pol, k):
+    return isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 1 <= k <= int(pol['num_products'])
+
+
+def recall_sets(agent_or_pol, keys, k):
+    """The top-k sets of a target whose `ps-a` is a function of a key -> int32 [len(keys), k], ascending within a key, or None
+    where len(keys) * k exceeds RECALL_TABLE_MAX.  key = 2 g + explored: g the (inner) agent's act, explored the EpsilonGreedy
+    flip (0 without a wrapper); a bare RandomAgent has the one key 0.  Per key the vector is built with the arithmetic and dtype
+    of the agent's host act — one-hot, (1 - eps) * one-hot or * (ones / P), eps * the normalised explore vector (epsilon_pure_new:
+    a zero at g), ones / P — and np.argpartition(vec, -k)[-k:] itself picks the set: NumPy's order among ties by construction."""
+    pol = agent_or_pol if isinstance(agent_or_pol, dict) else _replay_policy_of(agent_or_pol)
+    if pol is None or _recall_form(pol) != 'table' or not _recall_k_ok(pol, k):
+        raise ValueError('recall_sets: the target has no key form of `ps-a`, or k is outside 1 .. P')
+    keys = np.asarray(keys, dtype=np.int64).ravel()
+    if keys.size * int(k) > RECALL_TABLE_MAX:
+        return None
+    P, eg = int(pol['num_products']), pol.get('epsilon_greedy')
+    uniform = pol['kind'] == _abi.RG_POLICY_RANDOM_AGENT
+    sets = np.empty((keys.size, int(k)), dtype=np.int32)
+    for i, key in enumerate(keys):
+        g, explored = int(key) >> 1, bool(int(key) & 1)
+        if explored:
+            vec = np.ones(P)
+            if eg['pure_new']:
+                vec[g] = 0.0
+            vec = eg['epsilon'] * (vec / np.sum(vec))
+        else:
+            if uniform:
+                vec = np.ones(P) / P
+            else:
+                vec = np.zeros(P)
+                vec[g] = 1.0
+            if eg is not None:
+                vec = (1.0 - eg['epsilon']) * vec
+        sets[i] = np.sort(np.argpartition(vec, -k)[-k:])
+    return sets
+
+
+def _recall_resolve(dl, offsets, lr, listed, k):
+    """The rows the ranking form left inside its margin, one by one on the host: the act's view counts from the user's rows up to
+    the row, the agent's own proba (logreg_frozen.view_proba), np.argpartition -> (row index in the log, hit) per listed row."""
+    from .agents.logreg_frozen import view_proba
+    P = int(dl.num_products)
+    start = offsets.cpu().numpy()
+    out = []
+    for user, pos, v in listed:
+        b = int(start[user])
+        code = dl.rows[b:b + int(pos), 2].cpu().numpy().view(np.uint32)
+        organic = (code & _abi.RG_EV_BANDIT) == 0
+        views = np.bincount((code[organic] & _abi.RG_EV_INDEX_MASK).astype(np.int64), minlength=P)
+        proba = view_proba(lr['coef_t'], lr['intercept'], views)
+        out.append((b + int(pos), 1 if int(v) in set(np.argpartition(proba, -k)[-k:]) else 0))
+    return out
+
+
+def recall_replay(agent, dl, k=5, n_users=None, list_cap=None, stats=None):
+    """recall@k of `agent` over a DeviceLog on the device -> (hit uint8 over the counted rows of the log's first `n_users` users
+    (default: all but the last), in log order; counts int64 (counted, hits)), device tensors — or None: the host loop.  A bandit
+    row is counted when it has no click and the user's next row is organic.
+      table form  RandomAgent, the last-view tables, the frozen LogReg argmax, the likelihood agent (ope_policy_checked), and
+                  EpsilonGreedy round any of them where ope_replay accepts it: the rg_ope_replay_*_eg entry points write the
+                  act at every bandit row (`h0`) and the flip (`greedy`) — a bare target goes through them with epsilon = 0 —
+                  recall_sets builds the set of every key that occurs and rg_ope_recall_hits tests membership.
+      rank form   the sampling LogReg: rg_ope_recall_logreg; the rows inside its margin are decided on the host, and a list
+                  that overflowed gives the call up after one RuntimeWarning.  `list_cap`: the list's entries (default
+                  _abi.OPE_RECALL_LIST_CAP); `stats` (a dict) receives the head words (_abi.OPE_RECALL_HEAD).
+    None where the target has neither form (OrganicUserEventCounter, a wrapper round it), k is outside 1 .. P (before a device
+    is touched: the host loop keeps NumPy's behaviour there), the log does not qualify, or the sets table would exceed
+    RECALL_TABLE_MAX entries."""
+    pol = _replay_policy_of(agent)
+    if pol is None or not _recall_k_ok(pol, k):
+        return None
+    form = _recall_form(pol)
+    if form is None or int(pol['num_products']) != int(dl.num_products):
+        return None
+    import torch
+    k = int(k)
+    users = _replay_users(dl, pol, n_users)
+    if users is None:
+        return None
+    n_eval, offsets, max_rows = users
+    device = dl.rows.device
+    lib = _abi.load()
+    with torch.cuda.device(device):
+        total = int(offsets[-1].item()) if n_eval else 0
+        hit = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
+        counts = torch.empty(2, dtype=torch.int64, device=device)
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        if form == 'rank':
+            m, keep = _logreg_model(pol['logreg'], int(pol['num_products']), device)
+            cap = int(list_cap) if list_cap else _abi.OPE_RECALL_LIST_CAP
+            need = lib.rg_ope_recall_logreg_workspace_bytes(C.byref(m), n_eval, max_rows, cap)
+            if need == 0:
+                raise _abi.RecoGymHipError('rg_ope_recall_logreg workspace: ' + lib.rg_last_error().decode())
+            ws = torch.empty(need, dtype=torch.uint8, device=device)
+            _abi.check(lib.rg_ope_recall_logreg(C.byref(m), dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows, k, cap, hit.data_ptr(),
+                                                counts.data_ptr(), ws.data_ptr(), need, stream), 'rg_ope_recall_logreg')
+            head = _replay_head(ws, _abi.OPE_RECALL_HEAD)
+            if stats is not None:
+                stats.update(head)
+            if head['error']:
+                raise _abi.RecoGymHipError(f'rg_ope_recall_logreg: the replay reported error bits {head["error"]:#x} (a view history outgrew its list)')
+            if head['overflow']:
+                warnings.warn('recall@k: more rows inside the ranking margin than the device lists: the evaluation takes the host loop',
+                              RuntimeWarning, stacklevel=2)
+                return None
+            if head['unresolved']:
+                listed = ws[_abi.OPE_HEAD_BYTES:_abi.OPE_HEAD_BYTES + _abi.OPE_RECALL_LIST_ENTRY_BYTES * head['unresolved']]
+                listed = listed.view(torch.int32).cpu().numpy().view(np.uint32).reshape(-1, 3)
+                decided = _recall_resolve(dl, offsets, pol['logreg'], listed, k)
+                at = torch.tensor([r for r, _ in decided], dtype=torch.int64, device=device)
+                hit[at] = torch.tensor([h for _, h in decided], dtype=torch.uint8, device=device)
+                counts[1] += sum(h for _, h in decided)
+        else:
+            if pol['kind'] == _abi.RG_POLICY_RANDOM_AGENT and pol.get('epsilon_greedy') is None:
+                key = torch.zeros(max(total, 1), dtype=torch.int32, device=device)          # one constant vector: one key
+                present, sets_pol = np.zeros(1, dtype=np.int64), pol
+            else:
+                sets_pol = pol if pol.get('epsilon_greedy') is not None else dict(pol, epsilon_greedy=_NO_FLIP)
+                out = dict(per_row=True)
+                if ope_replay(agent, dl, sets_pol, n_users=n_eval, eg_out=out) is None:
+                    return None
+                raw = out['h0_rows'] * 2 + (1 - out['greedy_rows'].to(torch.int32))
+                is_b = (dl.rows[:total, 2] & _abi.RG_EV_BANDIT) != 0
+                uniq = torch.unique(_masked(raw, is_b))                                       # ascending; only this leaves the device
+                present = uniq.cpu().numpy().astype(np.int64)
+                if not present.size:
+                    present, uniq = np.zeros(1, dtype=np.int64), torch.zeros(1, dtype=torch.int32, device=device)
+                key = torch.searchsorted(uniq, raw).clamp_(max=present.size - 1).to(torch.int32)   # (organic rows: never read)
+                if key.numel() == 0:
+                    key = torch.zeros(1, dtype=torch.int32, device=device)
+            sets = recall_sets(sets_pol, present, k)
+            if sets is None:
+                return None
+            d_sets = torch.from_numpy(sets).to(device)
+            _abi.check(lib.rg_ope_recall_hits(dl.rows.data_ptr(), offsets.data_ptr(), n_eval, key.data_ptr(), int(present.size),
+                                              d_sets.data_ptr(), k, hit.data_ptr(), counts.data_ptr(), stream), 'rg_ope_recall_hits')
+            if stats is not None:
+                stats.update(keys=int(present.size))
+        hit = hit[:total]
+        return _masked(hit, hit != _abi.RG_RECALL_NOT_COUNTED), counts
+
+
+def _recall_device_or_none(agent, reco_log, k):
+    """-> (hit, counts, from_frame) from the device, or None (the host loop): _device_or_none's rules."""
+    dl = _as_device_log(reco_log)
+    if dl is None and not _device_present():
+        return None
+    pol = _replay_policy_of(agent)
+    if pol is None or not _recall_k_ok(pol, k) or _recall_form(pol) is None:
+        return None
+    if dl is None:
+        import torch
+        dl = _frame_to_device(reco_log, pol, torch.device(f'cuda:{torch.cuda.current_device()}'))
+        if dl is None:
+            return None
+        out = recall_replay(agent, dl, k, n_users=int(dl.offsets.numel()) - 1)    # (users 0 .. max(u) - 1 only)
+        return None if out is None else (*out, True)
+    out = recall_replay(agent, dl, k)
+    return None if out is None else (*out, False)
+
+
+def _host_recall(agent, reco_log, k):
     hits = []
 
     def visit(uid, idx, jj, prob_policy, cols):
@@ -526,12 +712,31 @@ def evaluate_recall_at_k(agent, reco_log, k=5):
     return hits
 
 
+def evaluate_recall_at_k(agent, reco_log, k=5):
+    """Hits (1 / 0) of the next organic view in the top-k of `ps-a`, for every unclicked bandit row of users 0 .. max(u)-1 that an
+    organic row of the same user follows (reference evaluate_agent.py:832-870): a list of ints for a DataFrame, an int64 device
+    tensor for a device log.  On the device (recall_replay) where the target's top-k set is a function of its act — built per
+    act by np.argpartition itself, whose order among ties no rank rule reproduces — or a softmax the device can rank;
+    OrganicUserEventCounter, whose `ps-a` is neither, and every k outside 1 .. P take the host loop."""
+    dev = _recall_device_or_none(agent, reco_log, k)
+    if dev is not None:
+        import torch
+        hit, _, from_frame = dev
+        return [int(h) for h in hit.cpu().numpy()] if from_frame else hit.to(torch.int64)
+    return _host_recall(agent, reco_log, k)
+
+
 def verify_agents_recall_at_k(reco_log, agents, k=5):
     stat = {'Agent': [], '0.025': [], '0.500': [], '0.975': []}
     for agent_id in agents:
         hits = evaluate_recall_at_k(agents[agent_id], reco_log, k=k)
-        mean_hits = np.mean(hits)
-        se_hits = np.std(hits) / np.sqrt(len(hits))
+        if isinstance(hits, list):
+            mean_hits = np.mean(hits)
+            se_hits = np.std(hits) / np.sqrt(len(hits))
+        else:
+            import torch
+            mean_hits, std_hits, n = _two_pass_std(hits.to(torch.float64))
+            se_hits = std_hits / np.sqrt(n)
         stat['Agent'].append(agent_id)
         stat['0.025'].append(mean_hits - 2 * se_hits)
         stat['0.500'].append(mean_hits)
