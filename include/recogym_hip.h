@@ -48,6 +48,9 @@ extern "C" {
 /* v14, additive since: rg_sim_set_epsilon_greedy_model (the EpsilonGreedy overlay round the frozen LogReg argmax and the likelihood
  * agent in the step loop) and rg_ope_replay_logreg_eg / rg_ope_replay_poly_eg (the off-policy replay of such a wrapper).  New
  * symbols only: nothing an existing caller sees has changed, and the version stays 14. */
+/* v14, additive since: rg_sim_set_weight_history, rg_sim_debug_set_timed_history, rg_sim_debug_weighted_acts and the counter
+ * RG_CNT_WH_CLOCK_RANGE (the likelihood agent's act on a time-weighted view history), and rg_weighted_feed_workspace_bytes /
+ * rg_weighted_feed (its training features from a sorted device log). */
 #define RG_ABI_VERSION 14
 
 /* error codes */
@@ -176,6 +179,9 @@ typedef struct rg_event {
 #define RG_CNT_POLY_TABLE 26     /* RG_POLICY_LOGREG_POLY: acts whose best decision lies on the expit step table (decided exactly there) */
 #define RG_CNT_POLY_UNRESOLVED 27 /* ... acts below the table with a lower-index decision inside the margin W of the best one: the action
                                    * taken is the first maximal decision; the act is listed for the host (rg_sim_read_poly_unresolved) */
+#define RG_CNT_WH_CLOCK_RANGE 28 /* RG_POLICY_LOGREG_POLY with a weight table: acts on a time-weighted history that met a clock value outside
+                                   * [0, 32767] — the act's own, a view's, a view after the act, or a difference beyond the table.  The
+                                   * weight was the table's at the clamped index; the caller discards the result */
 #define RG_CNT_N 32             /* out[] of rg_sim_read_counters; slots 16..23 are internal */
 
 typedef struct rg_sim rg_sim;
@@ -334,6 +340,23 @@ int rg_sim_set_logreg_fp16(rg_sim* sim, const uint16_t* d_coef16_t);
 int rg_sim_set_logreg_poly(rg_sim* sim, const double* d_wf, const double* d_wa, const double* d_wk_t, double intercept,
                            const double* d_expit_steps, uint32_t n_steps);
 
+/* RG_POLICY_LOGREG_POLY with the reference's weight_history_function: the act's features are not view counts but, per product,
+ * the sum of w(now - t_view) over the user's views.  The reference casts every clock value to int16 first, so inside the clock
+ * range [0, 32767] w is the table d_table[0 .. n) over the differences (float64 device array kept by pointer, n <= 32768; a float32
+ * table is passed widened, with accumulate_f32 = 1).  A product's feature is the sequential sum of its views' table entries in view
+ * order — in double, or with accumulate_f32 every add rounded to float32 with subnormals kept — rounded once to float32; a product
+ * whose feature is exactly 0 leaves the list; the decisions are rg_sim_set_logreg_poly's with these values as the counts c_j (an
+ * empty list is legal: z[a] = a wa[a] + intercept).  Legal after rg_sim_create and before rg_sim_reset_users, not together with
+ * the EpsilonGreedy overlay; allocates the users' timed history rows (n_cap x hist_cap x 8 bytes of device memory, freed by
+ * rg_sim_destroy).  The state is readable as option "weight_history".  With it on, a run is lock-step (no walk, no run-ahead, no
+ * tail kernel) and needs a log (rg_sim_set_log: the step's views are read back from their rows): every bandit event gets a fresh
+ * act at the clock value logged on its own row — the event index, or the NormalTimeGenerator's clock under time_mode = 1 — and so
+ * does the trailing row of a stopping user.  The history row holds VIEWS (rg_sim_debug_set_timed_history describes it), so
+ * RG_CNT_HIST_OVERFLOW counts views beyond hist_cap - 1 per user; RG_CNT_WH_CLOCK_RANGE counts clock values outside [0, 32767];
+ * unresolved acts are listed as ever (rg_sim_read_poly_unresolved), t being the event index of the act's own row: its history is
+ * the user's organic rows with a smaller index.  Launches count in the ledger family logreg_poly_w. */
+int rg_sim_set_weight_history(rg_sim* sim, const double* d_table, uint32_t n, uint32_t accumulate_f32);
+
 /* The unresolved acts of the run so far (since rg_sim_reset_users): out[3 i .. 3 i + 2] = (user id, t, action taken) for the first
  * min(listed, capacity) of them, in no particular order; t is the event index the act was computed at: its history is the user's
  * organic rows with index <= t.  *n_out = entries written, *overflow = 1 when the run had more unresolved acts than the device list
@@ -475,6 +498,39 @@ int rg_sim_debug_ouc_acts(rg_sim* sim, const double* d_u1, int32_t* d_action, do
  * the device function the step loop uses: d_action[i], d_flags[i] = bit 0: decided on the step table, bit 1: unresolved, bit 2: a
  * lower index than the first maximal decision won (a merge on a step).  Touches neither the counters nor the unresolved list. */
 int rg_sim_debug_poly_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, void* stream);
+/* rg_sim_debug_set_timed_history (after rg_sim_set_weight_history, right after rg_sim_reset_users): the TIMED view history of every
+ * user index — d_n[i] views (at most stride), view j of product d_products[i * stride + j] at clock value d_times16[i * stride + j],
+ * in view order (times never decreasing).  They go into the user's history row one at a time through the sorted insert that never
+ * merges: the row (hist_cap words, as RG_CNT_HIST_OVERFLOW describes it) holds a header (views kept << 32 | entries) and one word
+ * (product << 32 | time) per VIEW, ascending; a view that finds keep = hist_cap - 1 entries is dropped and adds one to
+ * RG_CNT_HIST_OVERFLOW.  Views of products outside [0, num_products) are skipped.
+ * rg_sim_debug_weighted_acts: the weighted act of every user index on its timed row at the clock value d_now16[i]: d_action / d_flags
+ * as rg_sim_debug_poly_acts, and beside them the feature list the act was taken on — d_list_n[i] products d_list_prod[i * stride + j]
+ * ascending with the float32 features d_list_val32[i * stride + j]; stride >= min(num_products, hist_cap - 1).  An act that met a
+ * clock value outside the range adds one to RG_CNT_WH_CLOCK_RANGE.  Counts as a launch of the ledger family logreg_poly_w. */
+int rg_sim_debug_set_timed_history(rg_sim* sim, const uint32_t* d_n, const uint32_t* d_products, const uint16_t* d_times16, uint32_t stride,
+                                   void* stream);
+int rg_sim_debug_weighted_acts(rg_sim* sim, const uint16_t* d_now16, int32_t* d_action, uint8_t* d_flags, uint32_t* d_list_n,
+                               uint32_t* d_list_prod, float* d_list_val32, uint32_t stride, void* stream);
+
+/*
+ * The training features of an agent with a weight_history_function from a sorted device log (AbstractFeatureProvider.train_data,
+ * reference agents/abstract.py:190-279): one row per bandit row, the trailing row included, holding per product the weighted sum
+ * of the user's views BEFORE that row at the row's clock value — rg_sim_set_weight_history's rule on the same table (d_table, n,
+ * accumulate_f32).  Stateless.  d_rows / d_offsets / n_users / max_user_rows as rg_ope_replay_logreg takes them, validated by the
+ * same rules before anything is written (a user that opens with a bandit row, more than max_user_rows rows, a product or an action
+ * >= num_products: RG_EINVAL).  d_t16[row] is the row's clock value after the int16 cast, 0xFFFF where it lies outside [0, 32767];
+ * d_brow[row] the ordinal of a bandit row among the log's bandit rows.  Two passes over the same arguments:
+ *   mode 0  d_len[ordinal] = the number of products whose feature is not 0 (the caller's prefix sum over it is d_crow);
+ *   mode 1  the products, ascending, into d_col[d_crow[ordinal] ..] and their float32 features into d_val at the same places.
+ * One wave per user carries the user's timed view list in the workspace (nothing is dropped).  The workspace's first int64 words
+ * after the call: 0 error bits of the validation, 1 rows whose d_t16 is outside [0, 32767] — not 0: the features are not the
+ * reference's, and the caller takes its host loop — 2 bandit rows walked. */
+size_t rg_weighted_feed_workspace_bytes(uint64_t n_users, uint32_t max_user_rows);
+int rg_weighted_feed(const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users, uint32_t max_user_rows, uint32_t num_products,
+                     const uint16_t* d_t16, const double* d_table, uint32_t n, uint32_t accumulate_f32, uint32_t mode,
+                     const int64_t* d_brow, int32_t* d_len, const int64_t* d_crow, int32_t* d_col, float* d_val, void* d_workspace,
+                     size_t workspace_bytes, void* stream);
 
 /*
  * Off-policy evaluation (evaluate_IPS / evaluate_SNIPS, reference evaluate_agent.py:753-810): replay a sorted log under a

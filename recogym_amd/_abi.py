@@ -31,6 +31,7 @@ RG_CNT_ANCHORED = 24
 RG_CNT_BAD_ACTION = 25
 RG_CNT_POLY_TABLE = 26
 RG_CNT_POLY_UNRESOLVED = 27
+RG_CNT_WH_CLOCK_RANGE = 28
 RG_CNT_N = 32
 
 RG_ERRORS = {-1: 'RG_EINVAL', -2: 'RG_ENODEV', -3: 'RG_ENOMEM', -4: 'RG_ESTATE', -5: 'RG_ELIMIT'}
@@ -154,6 +155,7 @@ SYMBOLS = {
     'rg_sim_set_logreg_fp32': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
     'rg_sim_set_logreg_fp16': (C.c_int, [_SIM, C.c_void_p]),
     'rg_sim_set_logreg_poly': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_uint32]),
+    'rg_sim_set_weight_history': (C.c_int, [_SIM, C.c_void_p, C.c_uint32, C.c_uint32]),
     'rg_sim_read_poly_unresolved': (C.c_int, [_SIM, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]),
     'rg_sim_set_log': (C.c_int, [_SIM, C.c_void_p, C.c_uint64]),
     'rg_sim_reset_users': (C.c_int, [_SIM, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
@@ -183,6 +185,12 @@ SYMBOLS = {
     'rg_sim_debug_set_history': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'rg_sim_debug_ouc_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rg_sim_debug_poly_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rg_sim_debug_set_timed_history': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    'rg_sim_debug_weighted_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                             C.c_void_p]),
+    'rg_weighted_feed_workspace_bytes': (C.c_size_t, [C.c_uint64, C.c_uint32]),
+    'rg_weighted_feed': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                   C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'rg_ope_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpePolicy), C.c_uint64, C.c_uint32]),
     'rg_ope_replay': (C.c_int, [C.POINTER(RgOpePolicy), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
                                 C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -99,6 +99,8 @@ class EpsilonGreedy(Agent):
             # opt-in; a sampling LogReg's act is a sampled action with a propensity of its own: host path
             if not getattr(c, 'device_models', False) or (pol.get('logreg') or {}).get('select_randomly'):
                 return None
+            if (pol.get('logreg_poly') or {}).get('weight_history') is not None:      # a time-weighted likelihood agent: host path
+                return None
         elif pol.get('policy') not in _DEVICE_INNER:
             return None
         if self._num_products() < 2 and c.epsilon_pure_new:

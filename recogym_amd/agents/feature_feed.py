@@ -13,7 +13,9 @@ CSR entry to every bandit row of its user that comes after its first view, and t
 is the number of the group's views before that row (one searchsorted on composite keys).
 
 With a `weight_history_function` the features are time-weighted float sums, not counts: that (rare) form takes the exact
-per-row construction of agents/views_history.train_data_weighted instead of the vectorised count path.
+per-row construction of agents/views_history.train_data_weighted instead of the vectorised count path — or, given a
+`Simulator.device_log()` and a function that stands for a table (views_history.weight_table), the device feed `rg_weighted_feed`
+(`weighted_train_data_device`), which returns the same tuple.
 """
 import numpy as np
 from scipy import sparse
@@ -46,6 +48,15 @@ def train_data_from_log(log, num_products, is_sparse=True, weight_history_functi
               when is_sparse is False), rows in log order (users ascending, t ascending);
     actions   int16; deltas int16 (the click column); pss float64.
     `log` must be in the reference's row order (every user's rows contiguous, t ascending)."""
+    if _is_device_log(log):
+        if weight_history_function is None:
+            raise TypeError('train_data_from_log takes a device log only with a weight_history_function (the count form: train_data_from_log_torch)')
+        from .views_history import weight_table
+        tabled = weight_table(weight_history_function)
+        out = weighted_train_data_device(log, num_products, *tabled, is_sparse=is_sparse) if tabled is not None else None
+        if out is not None:
+            return out
+        log = device_log_columns(log)       # no table, or a clock value outside [0, 32767]: the host loop on the same rows
     u, is_b, v, a, c, ps = _columns_of(log)
     if weight_history_function is not None:             # time-weighted views (agents/abstract.py:216-263): the exact per-row form
         from .views_history import train_data_weighted
@@ -98,6 +109,97 @@ def train_data_from_log(log, num_products, is_sparse=True, weight_history_functi
     if not is_sparse:
         return np.asarray(feats.todense(), dtype=np.float64), actions, deltas, pss
     return feats, actions, deltas, pss
+
+
+def _is_device_log(log):
+    return hasattr(log, 'rows') and hasattr(log, 'offsets') and hasattr(log, 'first_user')
+
+
+def _device_log_parts(dl):
+    """-> (is_bandit, index, click, t float32, ps float64 of the bandit rows) of a DeviceLog as torch tensors: what log_columns()
+    decodes, from the same words (`t` = the NormalTimeGenerator's clock where the log has one, else the event index, as float32)."""
+    import torch
+    from .. import _abi
+    code = dl.rows[:, 2]
+    is_b = (code & _abi.RG_EV_BANDIT) != 0
+    idx = code & _abi.RG_EV_INDEX_MASK
+    click = (code & _abi.RG_EV_CLICK) != 0
+    t32 = (dl.time if dl.time is not None else dl.rows[:, 1]).to(torch.float32)
+    if dl.ps is None:
+        ps = dl.rows[:, 3].contiguous().view(torch.float32).to(torch.float64)[is_b]
+    elif torch.is_tensor(dl.ps):
+        ps = dl.ps[is_b].to(torch.float64)
+    else:
+        ps = torch.full((int(is_b.sum().item()),), float(dl.ps), dtype=torch.float64, device=dl.rows.device)
+    return is_b, idx, click, t32, ps
+
+
+def device_log_columns(dl):
+    """A DeviceLog as the host dict Simulator.log_columns() gives (for the host loop of a weighted feed)."""
+    import torch
+    is_b, idx, click, t32, ps = _device_log_parts(dl)
+    ps_all = torch.full((is_b.numel(),), float('nan'), dtype=torch.float64, device=is_b.device)
+    ps_all[is_b] = ps
+    zero = torch.zeros((), dtype=idx.dtype, device=idx.device)
+    nan32 = torch.full((), float('nan'), dtype=torch.float32, device=idx.device)
+    cols = dict(t=t32, u=dl.rows[:, 0].contiguous(), is_bandit=is_b, v=torch.where(is_b, zero, idx), a=torch.where(is_b, idx, zero),
+                c=torch.where(is_b, click.to(torch.float32), nan32), ps=ps_all)
+    return {k: x.cpu().numpy() for k, x in cols.items()}
+
+
+def weighted_train_data_device(dl, num_products, table, is_f32, is_sparse=True):
+    """train_data_weighted on a DeviceLog, by rg_weighted_feed -> the same (features, actions, deltas, pss) tuple — features CSR
+    float32 with sorted indices — or None where a row's clock value lies outside [0, 32767] (the caller takes the host loop).
+    The int16 times are cast with torch from the float32 column log_columns() would give; the list lengths of the first pass become
+    `crow` by torch.cumsum; only the finished arrays cross to the host."""
+    import ctypes as C
+    import torch
+    from .. import _abi
+    lib = _abi.load()
+    P = int(num_products)
+    dev = dl.rows.device
+    is_b, idx, click, t32, ps = _device_log_parts(dl)
+    n_users = int(dl.offsets.numel()) - 1
+    nb = int(is_b.sum().item())
+    actions = idx[is_b].to(torch.int16).cpu().numpy()
+    deltas = click[is_b].to(torch.int16).cpu().numpy()
+    pss = ps.cpu().numpy()
+    if nb == 0 or n_users <= 0:
+        feats = sparse.csr_matrix((nb, P), dtype=np.float32)
+        return (feats if is_sparse else np.asarray(feats.todense(), dtype=float)), actions, deltas, pss
+    inside = (t32 >= 0) & (t32 < 32768)                                   # (NaN: outside)
+    t16 = torch.where(inside, t32, torch.full_like(t32, -1.0)).to(torch.int32).to(torch.int16).contiguous()      # -1 = 0xFFFF: outside
+    brow = (torch.cumsum(is_b.to(torch.int64), 0) - is_b.to(torch.int64)).contiguous()
+    offsets = dl.offsets.contiguous()
+    max_rows = int((offsets[1:] - offsets[:-1]).max().item())
+    wtab = torch.from_numpy(np.ascontiguousarray(table).astype(np.float64)).to(dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        need = lib.rg_weighted_feed_workspace_bytes(n_users, max_rows)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        lens = torch.zeros(nb, dtype=torch.int32, device=dev)
+
+        def call(mode, crow=None, col=None, val=None):
+            _abi.check(lib.rg_weighted_feed(dl.rows.data_ptr(), offsets.data_ptr(), n_users, max_rows, P, t16.data_ptr(), wtab.data_ptr(),
+                                            int(wtab.numel()), int(bool(is_f32)), mode, brow.data_ptr(), lens.data_ptr(),
+                                            None if crow is None else crow.data_ptr(), None if col is None else col.data_ptr(),
+                                            None if val is None else val.data_ptr(), ws.data_ptr(), need, stream), 'rg_weighted_feed')
+        call(0)
+        head = ws[:24].view(torch.int64).cpu().numpy()
+        if head[1]:
+            return None
+        assert head[2] == nb, (head, nb)
+        crow = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+        crow[1:] = torch.cumsum(lens.to(torch.int64), 0)
+        nnz = int(crow[-1].item())
+        col = torch.zeros(max(nnz, 1), dtype=torch.int32, device=dev)
+        val = torch.zeros(max(nnz, 1), dtype=torch.float32, device=dev)
+        call(1, crow, col, val)
+        torch.cuda.synchronize(dev)
+    # (the values leave the device as bytes: a float32 subnormal must not pass through an arithmetic conversion)
+    data = val[:nnz].view(torch.int32).cpu().numpy().view(np.float32)
+    feats = sparse.csr_matrix((data, col[:nnz].cpu().numpy(), crow.cpu().numpy()), shape=(nb, P), dtype=np.float32)
+    return (feats if is_sparse else np.asarray(feats.todense(), dtype=float)), actions, deltas, pss
 
 
 def train_data_from_log_torch(cols, num_products):

@@ -172,12 +172,18 @@ class LogregPolyFrozenAgent(Agent):
         """coef (1, 2P + P^2) / intercept (1,) as sklearn stores the fitted binary model."""
         super().__init__(config)
         self.wf, self.wa, self.wk, self.b = poly_split(coef, intercept, config.num_products)
-        # weight_history_function (ViewsFeaturesProvider with history): time-weighted float features instead of view counts — host
-        # path only
+        # weight_history_function (ViewsFeaturesProvider with history): time-weighted float features instead of view counts.  On the
+        # host path unless `device_weight_history` is set AND the function stands for a table over the int16 clock differences
+        # (views_history.weight_table; DESIGN.md 4g)
         self.history = None
+        self.weight_history = None
         if getattr(config, 'weight_history_function', None) is not None:
-            from .views_history import ViewsHistory
+            from .views_history import ViewsHistory, weight_table
             self.history = ViewsHistory(config.num_products, config.weight_history_function, is_sparse=True)
+            if getattr(config, 'device_weight_history', False):
+                tabled = weight_table(config.weight_history_function)
+                if tabled is not None:
+                    self.weight_history = dict(table=tabled[0], f32=tabled[1])
         self.reset()
 
     @classmethod
@@ -185,10 +191,12 @@ class LogregPolyFrozenAgent(Agent):
         return cls(config, logreg.coef_, logreg.intercept_)
 
     def device_policy(self):
-        if getattr(self.config, 'with_ps_all', False) or self.history is not None:
+        if getattr(self.config, 'with_ps_all', False) or (self.history is not None and self.weight_history is None):
             return None
-        return dict(policy=_abi.RG_POLICY_LOGREG_POLY, policy_seed=0, ouc=None,
-                    logreg_poly=dict(wf=self.wf, wa=self.wa, wk=self.wk, intercept=self.b))
+        model = dict(wf=self.wf, wa=self.wa, wk=self.wk, intercept=self.b)
+        if self.weight_history is not None:
+            model['weight_history'] = self.weight_history
+        return dict(policy=_abi.RG_POLICY_LOGREG_POLY, policy_seed=0, ouc=None, logreg_poly=model)
 
     def ope_policy(self):
         """None: `ope_policy` is the hook of replay forms that are exact without a host step; this agent's is `ope_policy_checked`."""
@@ -243,6 +251,16 @@ class LogregPolyAgent(LogregMulticlassIpsAgent):
 
     def ope_policy_checked(self):
         return self._ready().ope_policy_checked()
+
+    @property
+    def accepts_device_log(self):
+        """test_agent hands Simulator.device_log() to train_from_log exactly when the training features can be built where the log
+        lies: `device_weight_history` is set and the weight function stands for a table (feature_feed.weighted_train_data_device)."""
+        c = self.config
+        if not getattr(c, 'device_weight_history', False) or getattr(c, 'weight_history_function', None) is None:
+            return False
+        from .views_history import weight_table
+        return weight_table(c.weight_history_function) is not None
 
     def _sample_weights(self, clicks, pss):
         """The fit's sample weights, or None without with_ips.  As in the reference, clipping takes click / ps as the weight to

@@ -26,7 +26,9 @@ def evaluate_counts(env, agent, num_users, first_user_id=0):
     successes = sum of c over bandit rows, failures = bandit rows - successes; the phantom row
     of every user counts as a failure exactly as in the reference (bench_agents.py:203-206)."""
     rank, ws, _ = parallel.world()
-    if device_policy_of(agent) is not None:
+    pol = device_policy_of(agent)
+    # (a time-weighted likelihood agent reads its views back from the log and may be sent to the host route: generate_logs below)
+    if pol is not None and (pol.get('logreg_poly') or {}).get('weight_history') is None:
         first, count = parallel.shard_range(num_users, rank, ws)
         clicks = shown = 0
         dev = None

@@ -53,7 +53,7 @@
 // kernels), rg_exact.hip (float64 resolve), rg_draw_fp32.hip (fp32 / lean 16-bit sweeps), rg_draw_pipelined.hip (the pipelined sweep
 // + per-user cache kernels), rg_draw_wide.hip (wide-K sweep), rg_advance.hip (advance / tail / frozen LogReg), rg_walk.hip (the
 // user-major walk), rg_draw_exacthi.hip and rg_draw_lds.hip (the error-free and the tile-prefix sweeps), rg_ope.hip,
-// rg_ope_logreg.hip, rg_ope_eg.hip and rg_ope_poly.hip (off-policy replays), rg_count.hip (count agents' training), rg_evolve.hip (the exploration study), rg_logreg_poly.hip (the likelihood agent's act) — compiled in parallel and
+// rg_ope_logreg.hip, rg_ope_eg.hip and rg_ope_poly.hip (off-policy replays), rg_count.hip (count agents' training), rg_evolve.hip (the exploration study), rg_logreg_poly.hip (the likelihood agent's act), rg_weight_history.hip (its act on a time-weighted history) — compiled in parallel and
 // linked by __graft_entry__.build(); recogym_hip.hip includes all of them (a one-unit build).  This header holds what they
 // share: types, the workspace layout, device helpers (namespace rgk, identical in every unit); a unit hands its kernels to the
 // host code through the *_kernel_for functions declared here.  rg_ope_common.hpp adds what the four replay units share.
@@ -74,6 +74,7 @@ constexpr int kMaxGrid = 4096;
 constexpr uint32_t kDefaultHistoryCap = 256;
 constexpr uint32_t kPolyListCap = 4096;        // unresolved acts of a run the device lists (RG_POLICY_LOGREG_POLY)
 constexpr uint32_t kPolySteps = 1024;          // expit steps the table holds at most (8 KB of LDS)
+constexpr uint32_t kPolyHist = 256;            // history entries a wave of the likelihood agent's act keeps in LDS (the default history row); beyond: read from the source
 // the policies that act on the view history through the lr_* act list (k_logreg_select)
 inline bool lr_family(uint32_t policy) { return policy == RG_POLICY_LOGREG_FROZEN || policy == RG_POLICY_LOGREG_POLY; }
 constexpr uint64_t kRepackMinUsers = 1ull << 18;   // runs smaller than this keep slot == user index throughout (RECOGYM_REPACK_MIN overrides: tests)
@@ -383,7 +384,7 @@ struct RunOpts {
     X(draw_f64) X(draw_fp32) X(draw16_fused) X(draw16_sliced) X(search) X(draw_tp) X(pick) X(draw_cached) \
     X(sweep_xh) X(exact_m) X(exact_tile) X(exact_h) X(walk) X(walk2) X(walk_solo) \
     X(advance) X(advance_run) X(tail) X(repack) X(env0) X(logreg_screen) X(logreg_acts) X(logreg_sample) X(logreg_poly) \
-    X(sort_tiled) X(sort_plain)
+    X(logreg_poly_w) X(sort_tiled) X(sort_plain)
 struct Ledger {
 #define RG_LEDGER_FIELD(f) uint64_t f = 0;
     RG_LEDGER_FAMILIES(RG_LEDGER_FIELD)
@@ -394,10 +395,29 @@ struct Ledger {
 enum ProfClass { kProfSweep, kProfSearch /* + finalize */, kProfResolve /* float64 */, kProfLogreg, kProfAdvance,
                  kProfWalk1, kProfWalk2 /* every later round */, kProfTail, kProfNone /* closes an interval, opens none */ };
 
+// the weight table of a time-weighted view history as the kernels take it (rg_sim_set_weight_history; rg_wh_common.hpp): a
+// caller-owned device array kept by pointer
+struct WhTable {
+    const double* tab;
+    uint32_t n;              // entries (<= 32768); a difference beyond it is clamped and counted
+    uint32_t f32;            // every add rounds to float32 (the table's dtype was float32)
+};
+
+// what the kernels of a time-weighted run take beside DevSim (rg_weight_history.hip): the table, the users' TIMED history rows
+// ([n_cap][hist_cap], by user index; rg_wh_common.hpp has the layout) and, where a feature list can outgrow a wave's LDS rows
+// (min(P, hist_cap - 1) > 256), room for it per wave of the act kernel's grid — both allocated by rg_sim_set_weight_history
+struct WhRun {
+    WhTable wt;
+    unsigned long long* rows;
+    uint32_t* spill;          // [kWhGridBlocks * 4 waves][2][spill_cap], or null
+    uint32_t spill_cap;
+};
+
 struct rg_sim {
     rg_config cfg;
     Ledger led;
     DevSim d;
+    WhRun wh;                 // wt.tab != nullptr: the likelihood agent acts on time-weighted features (no kernel but rg_weight_history.hip's reads it)
     RunOpts opt;
     void* workspace;
     size_t workspace_bytes;
@@ -491,6 +511,11 @@ search_kernel_t logreg_decide_kernel();
 search_kernel_t logreg_sample_kernel();
 search_kernel_t poly_acts_kernel();                        // rg_logreg_poly.hip
 void (*poly_debug_kernel())(DevSim, int32_t*, uint8_t*);
+void (*wh_insert_kernel())(DevSim, WhRun, uint32_t);      // rg_weight_history.hip
+void (*wh_acts_kernel())(DevSim, WhRun, uint32_t, uint32_t);
+void (*wh_debug_set_kernel())(DevSim, WhRun, const uint32_t*, const uint32_t*, const uint16_t*, uint32_t);
+void (*wh_debug_acts_kernel())(DevSim, WhRun, const uint16_t*, int32_t*, uint8_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t);
+constexpr int kWhGridBlocks = 512;                         // k_poly_acts_w's grid at most (its waves own WhRun::spill)
 advance_kernel_t advance_kernel(bool eg);                  // eg: the instantiation that carries the EpsilonGreedy overlay
 advance_run_kernel_t advance_run_kernel(bool eg);
 round_rows_kernel_t round_rows_kernel();

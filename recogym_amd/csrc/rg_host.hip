@@ -777,6 +777,9 @@ int sweep_grid(rg_sim* sim, uint64_t work_items) {
     return grid;
 }
 
+// k_poly_acts_w: a wave per act, at most kWhGridBlocks blocks (its waves own the rows of WhRun::spill)
+constexpr int wh_grid(uint64_t acts) { return grid_for(acts, kBlock / 64) < kWhGridBlocks ? grid_for(acts, kBlock / 64) : kWhGridBlocks; }
+
 int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
     if (sim->t >= kMaxSteps) return fail(RG_ELIMIT, "more than %u steps", kMaxSteps);
     const DevSim& d = sim->d;
@@ -850,7 +853,14 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         if (int rc = prof_mark(sim, st, kProfResolve)) return rc;
         launch_exact(sim, t, 0, upper, st);
     }
-    if (d.policy == RG_POLICY_LOGREG_FROZEN) {
+    if (sim->wh.wt.tab) {
+        // a time-weighted history: the step's views into the timed rows, a fresh act per bandit event (rg_weight_history.hip)
+        if (int rc = prof_mark(sim, st, kProfLogreg)) return rc;
+        if (!d.log) return fail(RG_ESTATE, "a run on a time-weighted history reads the step's views from the log: attach one (rg_sim_set_log)");
+        hipLaunchKernelGGL(wh_insert_kernel(), dim3(grid_for(upper)), dim3(kBlock), 0, st, d, sim->wh, t);
+        hipLaunchKernelGGL(wh_acts_kernel(), dim3(wh_grid(upper)), dim3(kBlock), 0, st, d, sim->wh, t, 0u);
+        sim->led.logreg_poly_w += 1;
+    } else if (d.policy == RG_POLICY_LOGREG_FROZEN) {
         if (int rc = prof_mark(sim, st, kProfLogreg)) return rc;
         // acts of the users whose view history changed since their last one (frozen LogReg at scale)
         hipLaunchKernelGGL(logreg_select_kernel(), dim3(grid_for(upper)), dim3(kBlock), 0, st, d, t);
@@ -892,6 +902,11 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
     if (d.sigma_omega != 0.0)
         hipLaunchKernelGGL(drift_kernel(), dim3(grid_for(static_cast<uint64_t>(upper) * ((d.K + 1) / 2))), dim3(kBlock), 0, st, d, t);
     if (d.run_ahead) hipLaunchKernelGGL(round_rows_kernel(), dim3(1), dim3(1), 0, st, d, t, 0u);
+    // a time-weighted history: the trailing rows this step wrote are acted at their own clock value (k_advance set it) and patched
+    if (sim->wh.wt.tab) {
+        if (int rc = prof_mark(sim, st, kProfLogreg)) return rc;
+        hipLaunchKernelGGL(wh_acts_kernel(), dim3(wh_grid(upper)), dim3(kBlock), 0, st, d, sim->wh, t, 1u);
+    }
     HIP_TRY(hipGetLastError());
     if (int rc = prof_mark(sim, st, kProfNone)) return rc;
     if (sim->profiling) sim->prof_launches += 1;
@@ -1370,6 +1385,8 @@ int rg_sim_create(rg_sim** out, const rg_config* cfg, uint64_t n_users, void* d_
 
 int rg_sim_destroy(rg_sim* sim) {
     if (!sim) return RG_OK;
+    if (sim->wh.rows) (void)hipFree(sim->wh.rows);
+    if (sim->wh.spill) (void)hipFree(sim->wh.spill);
     if (sim->h_pinned) (void)hipHostFree(sim->h_pinned);
     if (sim->h_step) (void)hipHostFree(sim->h_step);
     for (hipEvent_t e : sim->prof_events) (void)hipEventDestroy(e);
@@ -1420,6 +1437,7 @@ const Option kOptions[] = {
     RG_OPT_R("use_cache", s->d.use_cache) RG_OPT_R("fin_in_sweep", s->fin_in_sweep) RG_OPT_R("handover_auto", s->handover_auto)
     RG_OPT_R("draw_smem", s->bf16_smem) RG_OPT_R("mfma_smem", s->mfma_smem) RG_OPT_R("xh_smem", s->xh_smem) RG_OPT_R("tp_smem", s->tp_smem)
     RG_OPT_R("tp_nts", s->tp_nts) RG_OPT_R("tp_cpt", s->d.tp_cpt) RG_OPT_R("draw_threads", s->draw_threads)
+    RG_OPT_R("weight_history", s->wh.wt.tab ? 1 : 0)           // rg_sim_set_weight_history was called
     RG_OPT_R("exact_rows", s->d.exact_rows) RG_OPT_R("hist_cap", s->d.hist_cap) RG_OPT_R("repack_min", s->opt.repack_min) RG_OPT_R("ablate", s->d.ablate)
 };
 const Option* find_option(const char* name) {
@@ -1561,6 +1579,7 @@ int rg_sim_set_epsilon_greedy_model(rg_sim* sim, double epsilon, uint64_t eg_see
         return fail(RG_EINVAL, "rg_sim_set_epsilon_greedy_model wraps the frozen LogReg argmax or the likelihood agent (policy %u)", sim->cfg.policy);
     if (sim->d.lr_sample)
         return fail(RG_EINVAL, "rg_sim_set_epsilon_greedy_model: a LogReg with lr_select_randomly samples its act (propensity != 1): host path");
+    if (sim->wh.wt.tab) return fail(RG_EINVAL, "EpsilonGreedy round a time-weighted likelihood agent: host path");
     if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(RG_EINVAL, "epsilon %g outside [0, 1]", epsilon);
     if (pure_new && sim->d.P < 2u) return fail(RG_EINVAL, "epsilon_pure_new needs at least 2 products");
     if (!d_cdf) return fail(RG_EINVAL, "the explore table is NULL");
@@ -1629,6 +1648,34 @@ int rg_sim_set_logreg_poly(rg_sim* sim, const double* d_wf, const double* d_wa, 
     if (!(intercept == intercept)) return fail(RG_EINVAL, "the intercept is NaN");
     sim->d.pl_wf = d_wf; sim->d.pl_wa = d_wa; sim->d.pl_wk_t = d_wk_t; sim->d.pl_b = intercept;
     sim->d.pl_th = d_expit_steps; sim->d.pl_nth = n_steps;
+    return RG_OK;
+}
+
+int rg_sim_set_weight_history(rg_sim* sim, const double* d_table, uint32_t n, uint32_t accumulate_f32) {
+    if (!sim) return fail(RG_EINVAL, "sim is NULL");
+    if (sim->cfg.policy != RG_POLICY_LOGREG_POLY) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY");
+    if (sim->users_reset) return fail(RG_ESTATE, "rg_sim_set_weight_history comes before rg_sim_reset_users");
+    if (sim->d.eg_on) return fail(RG_EINVAL, "EpsilonGreedy round a time-weighted likelihood agent: host path");
+    if (!d_table) return fail(RG_EINVAL, "the weight table is NULL");
+    if (n == 0 || n > 32768u) return fail(RG_EINVAL, "the weight table has %u entries (1 .. 32768)", n);
+    if (rg_device_count() <= 0) return fail(RG_ENODEV, "no HIP device");
+    const DevSim& d = sim->d;
+    // (each of the two on its own: a call repeated after one of them failed must not pass with the other missing)
+    if (!sim->wh.rows &&
+        hipMalloc(reinterpret_cast<void**>(&sim->wh.rows), sizeof(unsigned long long) * static_cast<size_t>(d.n_cap) * d.hist_cap) != hipSuccess) {
+        sim->wh.rows = nullptr;
+        return fail(RG_ENOMEM, "no device memory for the timed history rows");
+    }
+    const uint32_t longest = d.P < d.hist_cap - 1 ? d.P : d.hist_cap - 1;
+    if (!sim->wh.spill && longest > kPolyHist) {
+        if (hipMalloc(reinterpret_cast<void**>(&sim->wh.spill), sizeof(uint32_t) * 2 * static_cast<size_t>(kWhGridBlocks) * (kBlock / 64) * longest) != hipSuccess) {
+            sim->wh.spill = nullptr;
+            return fail(RG_ENOMEM, "no device memory for the feature lists beyond a wave's LDS rows");
+        }
+        sim->wh.spill_cap = longest;
+    }
+    sim->wh.wt.tab = d_table; sim->wh.wt.n = n; sim->wh.wt.f32 = accumulate_f32 ? 1u : 0u;
+    sim->walk = sim->walk2 = false;            // lock-step (as rg_sim_set_epsilon_greedy): an act per bandit event, at the event's clock value
     return RG_OK;
 }
 
@@ -1705,6 +1752,8 @@ int rg_sim_reset_users(rg_sim* sim, uint64_t first_user_id, uint64_t n, uint64_t
     if (d.lr_dirty) HIP_TRY(hipMemsetAsync(d.lr_cnt, 0, sizeof(uint32_t) * (kMaxSteps + 2), st));
     if (d.sigma_omega != 0.0) HIP_TRY(hipMemsetAsync(d.drift_cnt, 0, sizeof(uint32_t) * (kMaxSteps + 2), st));
     HIP_TRY(hipMemsetAsync(d.counters, 0, sizeof(unsigned long long) * RG_CNT_N, st));
+    if (sim->wh.rows)      // the timed rows' headers (rg_wh_common.hpp): every user starts without a view
+        HIP_TRY(hipMemset2DAsync(sim->wh.rows, sizeof(unsigned long long) * d.hist_cap, 0, sizeof(unsigned long long), n, st));
     HIP_TRY(hipMemsetAsync(d.tp_hist, 0, sizeof(uint32_t) * (kTpBins * kTpShards + 4), st));
     if (d.debug_row_base && d.log) {       // test hook: the raw log starts at that row; what lies below is marked unused
         if (d.debug_row_base > d.log_cap) return fail(RG_EINVAL, "debug row base %llu beyond the log capacity %llu",
@@ -1775,7 +1824,8 @@ int rg_sim_run(rg_sim* sim, uint32_t max_steps, void* stream) {
     // To the end from a fresh reset, nothing that moves omega inside a bandit run: run-ahead rounds (k_advance_run) — a user's whole
     // bandit run per round instead of a lock-step launch per event.  Everything else (partial runs, the step API, the sum cache of a
     // sigma_omega == 0 run without the walk) stays lock-step: event index == step number.
-    if (sim->t == 0 && max_steps >= kMaxSteps && sim->run_ahead && !sim->d.change_omega_for_bandits && !sim->d.use_cache && !sim->d.u_override) {
+    if (sim->t == 0 && max_steps >= kMaxSteps && sim->run_ahead && !sim->d.change_omega_for_bandits && !sim->d.use_cache && !sim->d.u_override &&
+        !sim->wh.wt.tab) {
         sim->d.run_ahead = sim->run_ahead;
         hipLaunchKernelGGL(round_rows_kernel(), dim3(1), dim3(1), 0, st, sim->d, 0u, 1u);
     }
@@ -1795,7 +1845,7 @@ int rg_sim_run(rg_sim* sim, uint32_t max_steps, void* stream) {
         if (live == 0) break;
         // few users left: finish them user by user (k_tail) instead of ~1 000 more latency-bound steps
         const size_t tail_smem = sizeof(double) * (((sim->d.K + 1) & ~1u) + ((sim->d.PT / 64 + 3) & ~3u));
-        if (live <= sim->tail_below && max_steps >= kMaxSteps && tail_smem <= 48 * 1024 && sim->t + 2 < kMaxSteps) {
+        if (live <= sim->tail_below && !sim->wh.wt.tab && max_steps >= kMaxSteps && tail_smem <= 48 * 1024 && sim->t + 2 < kMaxSteps) {
             if (int rc = prof_mark(sim, st, kProfTail)) return rc;
             const int grid = static_cast<int>(live < 2048 ? live : 2048);
             hipLaunchKernelGGL(tail_kernel(sim->d.eg_on != 0u), dim3(grid), dim3(kBlock), tail_smem, st, sim->d, sim->t);
@@ -1963,6 +2013,32 @@ int rg_sim_debug_poly_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, voi
     if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
     hipLaunchKernelGGL(poly_debug_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        sim->d, d_action, d_flags);
+    HIP_TRY(hipGetLastError());
+    return RG_OK;
+}
+
+int rg_sim_debug_set_timed_history(rg_sim* sim, const uint32_t* d_n, const uint32_t* d_products, const uint16_t* d_times16, uint32_t stride,
+                                   void* stream) {
+    if (!sim || !d_n || !d_products || !d_times16) return fail(RG_EINVAL, "NULL argument");
+    if (!sim->wh.wt.tab) return fail(RG_ESTATE, "rg_sim_set_weight_history must be called first");
+    if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users");
+    hipLaunchKernelGGL(wh_debug_set_kernel(), dim3(grid_for(sim->d.n_users)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), sim->d,
+                       sim->wh, d_n, d_products, d_times16, stride);
+    HIP_TRY(hipGetLastError());
+    return RG_OK;
+}
+
+int rg_sim_debug_weighted_acts(rg_sim* sim, const uint16_t* d_now16, int32_t* d_action, uint8_t* d_flags, uint32_t* d_list_n,
+                               uint32_t* d_list_prod, float* d_list_val32, uint32_t stride, void* stream) {
+    if (!sim || !d_now16 || !d_action || !d_flags || !d_list_n || !d_list_prod || !d_list_val32) return fail(RG_EINVAL, "NULL argument");
+    if (!sim->wh.wt.tab) return fail(RG_ESTATE, "rg_sim_set_weight_history must be called first");
+    if (!sim->d.pl_wk_t) return fail(RG_ESTATE, "rg_sim_set_logreg_poly must be called first");
+    if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
+    const uint32_t longest = sim->d.P < sim->d.hist_cap - 1 ? sim->d.P : sim->d.hist_cap - 1;
+    if (stride < longest) return fail(RG_EINVAL, "stride %u is below the longest feature list (%u)", stride, longest);
+    hipLaunchKernelGGL(wh_debug_acts_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+                       sim->d, sim->wh, d_now16, d_action, d_flags, d_list_n, d_list_prod, reinterpret_cast<uint32_t*>(d_list_val32), stride);
+    sim->led.logreg_poly_w += 1;
     HIP_TRY(hipGetLastError());
     return RG_OK;
 }

@@ -26,15 +26,15 @@
 // Two template parameters keep the function one for both callers:
 //   M  the model: members P, pl_nth, pl_wf, pl_wa, pl_wk_t ([viewed product][action]), pl_b — DevSim has them; PolyModel is the
 //      replay's;
-//   H  the history, ascending by product: size(), prod(i), cnt(i), get(i, p, c) for 0 <= i < size() — PolyRowHist over a
-//      step-loop history row, PolyListHist over the replay's (product, count) list.
+//   H  the history, ascending by product: size(), prod(i), cnt(i), get(i, p, c) for 0 <= i < size(), val_t the type of a value —
+//      PolyRowHist over a step-loop history row, PolyListHist over the replay's (product, count) list (integer counts), WhListHist
+//      (rg_wh_common.hpp) over a time-weighted feature list (doubles that hold float32 values).
 #pragma once
 
 #include "rg_common.hpp"
 
 namespace rgk {
 
-constexpr uint32_t kPolyHist = 256;       // history entries a wave keeps in LDS (the default history row); beyond: read from the source
 constexpr uint32_t kPolyNone = 0xFFFFFFFFu;
 constexpr double kPolyFloor = -700.0;     // z* below this: outside the domain of the margin's proof (poly_act)
 
@@ -47,6 +47,7 @@ struct PolyModel {
 
 // the entries of a step-loop history row after its header
 struct PolyRowHist {
+    typedef uint32_t val_t;
     const hent_t* hr;
     uint32_t nd;
     __device__ __forceinline__ uint32_t size() const { return nd; }
@@ -57,6 +58,7 @@ struct PolyRowHist {
 
 // a (product, count) list in two arrays (LDS or global)
 struct PolyListHist {
+    typedef uint32_t val_t;
     const uint32_t* lp;
     const uint32_t* lc;
     uint32_t nd;
@@ -137,7 +139,8 @@ __device__ __forceinline__ uint32_t poly_act(const M& d, const H& h, int lane, c
                                              uint32_t* flags) {
     const uint32_t nd = h.size();
     for (uint32_t i = lane; i < nd && i < kPolyHist; i += 64) {
-        uint32_t p, c;
+        uint32_t p;
+        typename H::val_t c;
         h.get(i, p, c);
         s_cnt[i] = static_cast<double>(c);
         s_prod[i] = p;
@@ -150,7 +153,8 @@ __device__ __forceinline__ uint32_t poly_act(const M& d, const H& h, int lane, c
         const uint32_t i = i0 + lane;
         double term = 0.0;
         if (i < nd) {
-            uint32_t p, c;
+            uint32_t p;
+            typename H::val_t c;
             h.get(i, p, c);
             term = __dmul_rn(static_cast<double>(c), d.pl_wf[p]);
         }

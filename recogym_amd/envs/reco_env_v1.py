@@ -92,6 +92,13 @@ def _gym_surface():
 _EnvBase, Discrete = _gym_surface()
 
 
+WH_VIEW_CEILING = 4095      # views a timed history row holds at most (simulate's retry doubles the row up to here)
+
+
+class HistoryOverflow(_abi.RecoGymHipError):
+    """simulate(): a user's view history outgrew the longest row the retry allows."""
+
+
 def device_policy_of(agent):
     """-> dict(policy, policy_seed, ouc) if `agent` can run inside the batched device loop."""
     if agent is None:
@@ -429,8 +436,12 @@ class RecoEnv1(_EnvBase):
                 # a user viewed more distinct products than its history row holds (default 255): run again with
                 # rows twice as long, the way a log overflow is retried with a larger buffer
                 cap = 2 * max(int((pol.get('ouc') or {}).get('history_cap', 0) or pol.get('history_cap', 0) or 255), 255) + 1
-                if cap > 4 * self.config.num_products + 512:
-                    raise _abi.RecoGymHipError('per-user view history overflowed ouc_history_cap')
+                # the ceiling: distinct products for a count row; VIEWS for the timed row of a time-weighted likelihood agent
+                # (WH_VIEW_CEILING: 32 KB per user at most — a user of the reference's parameter ranges has tens of views)
+                weighted = (pol.get('logreg_poly') or {}).get('weight_history') is not None
+                if cap > (WH_VIEW_CEILING if weighted else 4 * self.config.num_products + 512):
+                    sim.close()
+                    raise HistoryOverflow('per-user view history overflowed ouc_history_cap')
                 sim.close()
                 pol = dict(pol, ouc=dict(pol.get('ouc') or {}, history_cap=cap))
                 sim = self.make_simulator(total, agent, log=log, device=device, policy=pol)
@@ -539,12 +550,21 @@ class RecoEnv1(_EnvBase):
         (an extension; the reference always starts at 0) selects which addressed users are simulated."""
         use = agent if agent else self.agent
         pol = device_policy_of(use)
+        weighted = pol is not None and (pol.get('logreg_poly') or {}).get('weight_history') is not None
         if pol is not None:
-            cnt, sim = self.simulate(num_offline_users, use, num_organic_offline_users, first_user_id=first_user_id)
+            try:
+                cnt, sim = self.simulate(num_offline_users, use, num_organic_offline_users, first_user_id=first_user_id)
+            except HistoryOverflow:
+                if not weighted:
+                    raise
+                cnt = sim = None      # a user with more views than WH_VIEW_CEILING: the host route, which has no row to overflow
+        if pol is not None and sim is not None:
             cols = sim.log_columns()
             # the likelihood agent: the few acts its device rule lists as unresolved are recomputed on the host; a refuted one
-            # (or more of them than the list holds) sends the whole call to the host route below
+            # (or more of them than the list holds) sends the whole call to the host route below — and so does, for its
+            # time-weighted form, a clock value outside the int16 range the weight table covers
             stands = pol.get('policy') != _abi.RG_POLICY_LOGREG_POLY or not cnt.get('poly_unresolved') or sim.poly_verify(cols)
+            stands = stands and not (weighted and cnt.get('wh_clock_range'))
             sim.close()
             if stands:
                 with_all = bool(getattr(self.config, 'with_ps_all', False)) and use is None
@@ -552,8 +572,10 @@ class RecoEnv1(_EnvBase):
                 if pol.get('ps_all') is not None:              # the agent's whole distribution per bandit row
                     df['ps-a'] = pd.Series(pol['ps_all'](df), dtype=object, copy=False)
                 return df
+        if pol is not None:
             warnings.warn('LogregPolyAgent: the host refuted an act the device could not resolve (or the list of such acts '
-                          'overflowed); generate_logs repeats the call on the host route', RuntimeWarning)
+                          'overflowed' + ('; or a clock value left [0, 32767], or a user had more than WH_VIEW_CEILING views'
+                                          if weighted else '') + '); generate_logs repeats the call on the host route', RuntimeWarning)
         if self._time_mode or getattr(use, 'per_user_path', False) or getattr(self.config, 'per_user_path', False) or \
                 not batch_safe(use):
             return self._generate_logs_per_user(num_offline_users, use, num_organic_offline_users, first_user_id)

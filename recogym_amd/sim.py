@@ -122,6 +122,24 @@ def poly_host_act(views, model):
     return int(np.argmax(expit(poly_decisions(prods, cnts, *model))))
 
 
+def weighted_host_act(prods, times, now, weight_history, model):
+    """The likelihood agent's act on a time-weighted history, on the host: views_history.weighted_list on the int16 casts of the
+    clock values, the decisions in the contract's order, scipy's expit, first maximum.  -> the action, or -1 where a clock value
+    lies outside [0, 32767] (no act of the device form stands there)."""
+    from scipy.special import expit
+    from .agents.logreg_poly import poly_decisions
+    from .agents.views_history import weighted_list
+    times, now = np.asarray(times, dtype=np.float64), np.asarray(now, dtype=np.float64).reshape(-1)
+    if len(now) != 1 or not (0 <= now[0] < 32768) or (len(times) and not ((times >= 0) & (times < 32768)).all()):
+        return -1
+    try:
+        p, val = weighted_list(prods, np.trunc(times).astype(np.int64), int(np.trunc(now[0])), weight_history['table'],
+                               weight_history['f32'])
+    except ValueError:
+        return -1
+    return int(np.argmax(expit(poly_decisions(p, val.astype(np.float64), *model))))
+
+
 def poly_replay_verify(dl, acts, overflow, model):
     """The host's confirmation of the acts rg_ope_replay_poly could not resolve (Simulator.poly_verify's counterpart for a
     replay).  `dl`: the replayed DeviceLog; `acts`: (n, 3) array of (user index, position of the bandit row the act was computed
@@ -161,6 +179,9 @@ class Simulator:
     logreg_poly  dict(wf (P,), wa (P,), wk (P, P) [action][product], intercept): the likelihood agent's fitted model
                  (RG_POLICY_LOGREG_POLY; agents/logreg_poly.py) — the table of expit's top steps is built and uploaded here.
                  After a run, `poly_verify(columns)` recomputes the acts the device could not resolve on the host.
+                 An optional entry `weight_history = dict(table=, f32=)` (agents/views_history.weight_table) makes the act's
+                 features the time-weighted ones: a fresh act per bandit event at the event's clock value; such a
+                 run is lock-step and needs a log.  debug_set_timed_history / debug_weighted_acts reach the device function.
     """
 
     def __init__(self, config, n_users, policy=_abi.RG_POLICY_UNIFORM_ENV, policy_seed=None,
@@ -265,11 +286,21 @@ class Simulator:
                             and float(self.logreg[0].abs().max().item()) < 6.0e4):
                         self.logreg16 = self.logreg[0].to(torch.float16).contiguous()
                         _abi.check(self.lib.rg_sim_set_logreg_fp16(self._h, self.logreg16.data_ptr()), 'rg_sim_set_logreg_fp16')
+            self.weight_history = None
             if policy == _abi.RG_POLICY_LOGREG_POLY:
                 self.logreg_poly_host, self.logreg_poly = poly_device_model(logreg_poly, int(config.num_products), self.device)
                 _abi.check(self.lib.rg_sim_set_logreg_poly(self._h, *[t.data_ptr() for t in self.logreg_poly[:3]],
                                                            C.c_double(self.logreg_poly_host[3]), self.logreg_poly[3].data_ptr(),
                                                            int(self.logreg_poly[3].numel())), 'rg_sim_set_logreg_poly')
+                # logreg_poly['weight_history'] = dict(table=, f32=) (agents/views_history.weight_table): the act's features are
+                # time-weighted sums, not counts — the table goes up widened to float64
+                self.weight_history = logreg_poly.get('weight_history')
+                if self.weight_history is not None:
+                    table = np.ascontiguousarray(self.weight_history['table'])
+                    assert table.dtype == (np.float32 if self.weight_history['f32'] else np.float64), table.dtype
+                    self.wh_table = torch.from_numpy(table.astype(np.float64)).to(self.device)
+                    _abi.check(self.lib.rg_sim_set_weight_history(self._h, self.wh_table.data_ptr(), int(self.wh_table.numel()),
+                                                                  int(bool(self.weight_history['f32']))), 'rg_sim_set_weight_history')
             self.poly_unresolved = self.poly_refuted = None
             self.poly_overflow = False
             if log_capacity is None:
@@ -391,7 +422,43 @@ class Simulator:
         res['bad_actions'] = int(out[_abi.RG_CNT_BAD_ACTION])        # external actions outside [0, P) that reached the device
         res['poly_table'] = int(out[_abi.RG_CNT_POLY_TABLE])         # likelihood agent: acts decided on the expit step table
         res['poly_unresolved'] = int(out[_abi.RG_CNT_POLY_UNRESOLVED])   # ... acts listed for the host (poly_verify)
+        res['wh_clock_range'] = int(out[_abi.RG_CNT_WH_CLOCK_RANGE])     # ... weighted acts that met a clock value outside [0, 32767]
         return res
+
+    def debug_set_timed_history(self, n_views, products, times16):
+        """rg_sim_debug_set_timed_history: per user index of the reset range, n_views[i] views (products[i, j] at clock value
+        times16[i, j], in view order) as its time-weighted history."""
+        products = np.ascontiguousarray(products, dtype=np.uint32)
+        times16 = np.ascontiguousarray(times16, dtype=np.uint16)
+        assert products.shape == times16.shape and products.shape[0] == self.n_active == len(n_views)
+        with torch.cuda.device(self.device):
+            d = [torch.from_numpy(np.ascontiguousarray(n_views, dtype=np.uint32).view(np.int32)).to(self.device),
+                 torch.from_numpy(products.view(np.int32)).to(self.device), torch.from_numpy(times16.view(np.int16)).to(self.device)]
+            _abi.check(self.lib.rg_sim_debug_set_timed_history(self._h, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(),
+                                                               int(products.shape[1]), self._stream()), 'rg_sim_debug_set_timed_history')
+            torch.cuda.synchronize(self.device)
+
+    def debug_weighted_acts(self, now16, stride=None):
+        """rg_sim_debug_weighted_acts at the clock values now16 -> (actions, flags, list lengths, list products (n, stride), list
+        values (n, stride) float32): the weighted act of every user index and the feature list it was taken on."""
+        n = self.n_active
+        now16 = np.ascontiguousarray(now16, dtype=np.uint16)
+        assert now16.shape == (n,)
+        stride = int(stride or max(1, min(int(self.config.num_products), self.get_option('hist_cap') - 1)))
+        with torch.cuda.device(self.device):
+            now = torch.from_numpy(now16.view(np.int16)).to(self.device)
+            act = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+            fl = torch.full((n,), 255, dtype=torch.uint8, device=self.device)
+            ln = torch.zeros(n, dtype=torch.int32, device=self.device)
+            lp = torch.full((n, stride), -1, dtype=torch.int32, device=self.device)
+            lv = torch.zeros((n, stride), dtype=torch.float32, device=self.device)
+            _abi.check(self.lib.rg_sim_debug_weighted_acts(self._h, now.data_ptr(), act.data_ptr(), fl.data_ptr(), ln.data_ptr(),
+                                                           lp.data_ptr(), lv.data_ptr(), stride, self._stream()),
+                       'rg_sim_debug_weighted_acts')
+            torch.cuda.synchronize(self.device)
+        # (the values leave the device as bytes: a float32 subnormal must not pass through an arithmetic conversion)
+        return (act.cpu().numpy().astype(np.int64), fl.cpu().numpy().astype(np.int64), ln.cpu().numpy().astype(np.int64),
+                lp.cpu().numpy().astype(np.int64), lv.view(torch.int32).cpu().numpy().view(np.float32))
 
     def poly_unresolved_acts(self):
         """The acts of the run the likelihood agent's device rule could not resolve -> ((n, 3) uint32 array of (user id, t, action
@@ -420,11 +487,27 @@ class Simulator:
             first = np.flatnonzero(np.r_[True, u[1:] != u[:-1]])
             t = np.arange(len(u)) - np.repeat(first, np.diff(np.r_[first, len(u)]))
             bad = []
+            clock = self._clock64(cols) if self.weight_history is not None else None
             for user, t_act, a in acts:
-                if poly_host_act(v[organic & (u == user) & (t <= t_act)], self.logreg_poly_host) != int(a):
+                if clock is not None:
+                    # a time-weighted act: the user's views before the listed row, their clock values and the row's own
+                    mine = u == user
+                    host = weighted_host_act(v[mine & organic & (t < t_act)], clock[mine & organic & (t < t_act)],
+                                             clock[mine & (t == t_act)], self.weight_history, self.logreg_poly_host)
+                else:
+                    host = poly_host_act(v[organic & (u == user) & (t <= t_act)], self.logreg_poly_host)
+                if host != int(a):
                     bad.append((user, t_act, a))
             self.poly_refuted = np.asarray(bad, dtype=np.uint32).reshape(-1, 3)
         return not self.poly_overflow and len(self.poly_refuted) == 0
+
+    def _clock64(self, cols):
+        """The clock value of every row of log_columns() as the device holds it: float64 under a NormalTimeGenerator (the `t`
+        column is its float32 rounding, which can cross an integer), the event index otherwise."""
+        if not self.time_mode:
+            return np.asarray(cols['t'], dtype=np.float64)
+        out, offsets = self.sorted_log()
+        return self.sorted_time(offsets, int(out.shape[0])).cpu().numpy().astype(np.float64)
 
     def set_profiling(self, on=True):
         _abi.check(self.lib.rg_sim_set_profiling(self._h, int(on)), 'rg_sim_set_profiling')
