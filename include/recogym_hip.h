@@ -51,6 +51,9 @@ extern "C" {
 /* v14, additive since: rg_sim_set_weight_history, rg_sim_debug_set_timed_history, rg_sim_debug_weighted_acts and the counter
  * RG_CNT_WH_CLOCK_RANGE (the likelihood agent's act on a time-weighted view history), and rg_weighted_feed_workspace_bytes /
  * rg_weighted_feed (its training features from a sorted device log). */
+/* v14, additive since: RG_POLICY_BAYES_VB with rg_sim_set_bayes_vb and rg_sim_debug_bayes_acts (the posterior-sample act of
+ * BayesianAgentVB in the step loop) and the counter RG_CNT_BAYES_SATURATED; its unresolved acts share the likelihood agent's list,
+ * counter and reader (RG_CNT_POLY_UNRESOLVED, rg_sim_read_poly_unresolved). */
 #define RG_ABI_VERSION 14
 
 /* error codes */
@@ -81,6 +84,11 @@ extern "C" {
                                      the maximum of predict_proba[:, 1] = expit(decision) over one decision per action, on the
                                      polynomial features of the user's view counts — rg_sim_set_logreg_poly has the contract; ps = 1.
                                      Routed like RG_POLICY_LOGREG_FROZEN (lock-step / rounds, no tail kernel). */
+/* (7 is not assigned and stays refused as an unknown policy: the recorded create plan, tests/golden/create_plan.json, holds
+ * policy 7 as its refused policy number) */
+#define RG_POLICY_BAYES_VB 8      /* frozen BayesianAgentVB, agents/bayesian_poly_vb.py:71-91: a = the first index of the maximum over the
+                                     actions of mean_s expit(sum_p views[p] Lambda[s][p P + a]) over the posterior samples s —
+                                     rg_sim_set_bayes_vb has the contract; ps = 1.  Routed like RG_POLICY_LOGREG_POLY. */
 
 /*
  * Everything the step loop needs from `env.config` (a Configuration built from env_1_args,
@@ -182,6 +190,7 @@ typedef struct rg_event {
 #define RG_CNT_WH_CLOCK_RANGE 28 /* RG_POLICY_LOGREG_POLY with a weight table: acts on a time-weighted history that met a clock value outside
                                    * [0, 32767] — the act's own, a view's, a view after the act, or a difference beyond the table.  The
                                    * weight was the table's at the clamped index; the caller discards the result */
+#define RG_CNT_BAYES_SATURATED 29 /* RG_POLICY_BAYES_VB: acts decided in the saturated zone (some action's decisions all >= RG_BAYES_ZSAT) */
 #define RG_CNT_N 32             /* out[] of rg_sim_read_counters; slots 16..23 are internal */
 
 typedef struct rg_sim rg_sim;
@@ -357,6 +366,25 @@ int rg_sim_set_logreg_poly(rg_sim* sim, const double* d_wf, const double* d_wa, 
  * the user's organic rows with a smaller index.  Launches count in the ledger family logreg_poly_w. */
 int rg_sim_set_weight_history(rg_sim* sim, const double* d_table, uint32_t n, uint32_t accumulate_f32);
 
+/* RG_POLICY_BAYES_VB: the posterior samples of BayesianAgentVB, one float64 device array kept by pointer: d_lam_t[(p P + a) S + s] =
+ * Lambda[s][p P + a], S = num_samples >= 1 (the sample axis contiguous: the 64 lanes of a wave read 512 contiguous bytes per (p, a)).
+ * The decisions of action a over the n distinct viewed products p_0 < ... < p_(n-1) with counts c_j, float64, multiply then add, in
+ * exactly this order:   z[a][s] = 0;  for j: z[a][s] += c_j lam_t[p_j][a][s];   beside them m[a][s] = sum_j |c_j lam_t[p_j][a][s]| in
+ * the same order and M = max m.  q[a] = (sum_s 1 / (1 + exp(-z[a][s]))) / S, the sum taken per lane over s = lane, lane + 64, ... and
+ * then over the lanes by a fixed xor butterfly (two runs give the same bits).  ez = (2 n + 4) 2^-53 M and W = ez / 4 +
+ * (2 S + 44) 2^-53 bound the distance of q[a] from the reference's value in ANY summation order.  The rule:
+ *   n = 0                      action 0;
+ *   ez >= 1                    the first maximum of q, UNRESOLVED;
+ *   A1 = {a: min_s z[a][s] >= RG_BAYES_ZSAT} not empty:  a_c = min A1, RG_BAYES_SATURATED (RG_CNT_BAYES_SATURATED), and UNRESOLVED
+ *                              when some a < a_c has 1 - q[a] <= W (the reference's mean is exactly 1.0 at a_c, and may be at a);
+ *   else                       a* = the first maximum of q, UNRESOLVED when another action has q[a*] - q[a] <= 2 W.
+ * Unresolved acts are counted and listed as the likelihood agent's (RG_CNT_POLY_UNRESOLVED, rg_sim_read_poly_unresolved).
+ * The EpsilonGreedy model overlay on this policy is RG_EINVAL. */
+#define RG_BAYES_ZSAT 40.0
+#define RG_BAYES_SATURATED 1u
+#define RG_BAYES_UNRESOLVED 2u
+int rg_sim_set_bayes_vb(rg_sim* sim, const double* d_lam_t, uint32_t num_samples);
+
 /* The unresolved acts of the run so far (since rg_sim_reset_users): out[3 i .. 3 i + 2] = (user id, t, action taken) for the first
  * min(listed, capacity) of them, in no particular order; t is the event index the act was computed at: its history is the user's
  * organic rows with index <= t.  *n_out = entries written, *overflow = 1 when the run had more unresolved acts than the device list
@@ -498,6 +526,10 @@ int rg_sim_debug_ouc_acts(rg_sim* sim, const double* d_u1, int32_t* d_action, do
  * the device function the step loop uses: d_action[i], d_flags[i] = bit 0: decided on the step table, bit 1: unresolved, bit 2: a
  * lower index than the first maximal decision won (a merge on a step).  Touches neither the counters nor the unresolved list. */
 int rg_sim_debug_poly_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, void* stream);
+/* rg_sim_debug_bayes_acts: the RG_POLICY_BAYES_VB act of every user index on its current history (rg_sim_debug_set_history), by the
+ * device function the step loop uses: d_action[i], d_flags[i] (RG_BAYES_SATURATED | RG_BAYES_UNRESOLVED) and the device's means
+ * d_q[i * num_products + a] (with an empty history no mean is computed: 0.5 is written).  Touches neither the counters nor the list. */
+int rg_sim_debug_bayes_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, double* d_q, void* stream);
 /* rg_sim_debug_set_timed_history (after rg_sim_set_weight_history, right after rg_sim_reset_users): the TIMED view history of every
  * user index — d_n[i] views (at most stride), view j of product d_products[i * stride + j] at clock value d_times16[i * stride + j],
  * in view order (times never decreasing).  They go into the user's history row one at a time through the sorted insert that never

@@ -18,6 +18,7 @@ RG_POLICY_EXTERNAL = 3
 RG_POLICY_LAST_VIEW_TABLE = 4
 RG_POLICY_LOGREG_FROZEN = 5
 RG_POLICY_LOGREG_POLY = 6
+RG_POLICY_BAYES_VB = 8      # (7 is not assigned: include/recogym_hip.h)
 
 RG_EV_BANDIT = 0x80000000
 RG_EV_CLICK = 0x40000000
@@ -32,6 +33,7 @@ RG_CNT_BAD_ACTION = 25
 RG_CNT_POLY_TABLE = 26
 RG_CNT_POLY_UNRESOLVED = 27
 RG_CNT_WH_CLOCK_RANGE = 28
+RG_CNT_BAYES_SATURATED = 29
 RG_CNT_N = 32
 
 RG_ERRORS = {-1: 'RG_EINVAL', -2: 'RG_ENODEV', -3: 'RG_ENOMEM', -4: 'RG_ESTATE', -5: 'RG_ELIMIT'}
@@ -155,6 +157,7 @@ SYMBOLS = {
     'rg_sim_set_logreg_fp32': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),
     'rg_sim_set_logreg_fp16': (C.c_int, [_SIM, C.c_void_p]),
     'rg_sim_set_logreg_poly': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_uint32]),
+    'rg_sim_set_bayes_vb': (C.c_int, [_SIM, C.c_void_p, C.c_uint32]),
     'rg_sim_set_weight_history': (C.c_int, [_SIM, C.c_void_p, C.c_uint32, C.c_uint32]),
     'rg_sim_read_poly_unresolved': (C.c_int, [_SIM, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]),
     'rg_sim_set_log': (C.c_int, [_SIM, C.c_void_p, C.c_uint64]),
@@ -185,6 +188,7 @@ SYMBOLS = {
     'rg_sim_debug_set_history': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'rg_sim_debug_ouc_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rg_sim_debug_poly_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rg_sim_debug_bayes_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rg_sim_debug_set_timed_history': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'rg_sim_debug_weighted_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                              C.c_void_p]),

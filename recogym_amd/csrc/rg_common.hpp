@@ -53,7 +53,7 @@
 // kernels), rg_exact.hip (float64 resolve), rg_draw_fp32.hip (fp32 / lean 16-bit sweeps), rg_draw_pipelined.hip (the pipelined sweep
 // + per-user cache kernels), rg_draw_wide.hip (wide-K sweep), rg_advance.hip (advance / tail / frozen LogReg), rg_walk.hip (the
 // user-major walk), rg_draw_exacthi.hip and rg_draw_lds.hip (the error-free and the tile-prefix sweeps), rg_ope.hip,
-// rg_ope_logreg.hip, rg_ope_eg.hip and rg_ope_poly.hip (off-policy replays), rg_count.hip (count agents' training), rg_evolve.hip (the exploration study), rg_logreg_poly.hip (the likelihood agent's act), rg_weight_history.hip (its act on a time-weighted history) — compiled in parallel and
+// rg_ope_logreg.hip, rg_ope_eg.hip and rg_ope_poly.hip (off-policy replays), rg_count.hip (count agents' training), rg_evolve.hip (the exploration study), rg_logreg_poly.hip (the likelihood agent's act), rg_weight_history.hip (its act on a time-weighted history), rg_bayes_vb.hip (BayesianAgentVB's act) — compiled in parallel and
 // linked by __graft_entry__.build(); recogym_hip.hip includes all of them (a one-unit build).  This header holds what they
 // share: types, the workspace layout, device helpers (namespace rgk, identical in every unit); a unit hands its kernels to the
 // host code through the *_kernel_for functions declared here.  rg_ope_common.hpp adds what the four replay units share.
@@ -76,7 +76,12 @@ constexpr uint32_t kPolyListCap = 4096;        // unresolved acts of a run the d
 constexpr uint32_t kPolySteps = 1024;          // expit steps the table holds at most (8 KB of LDS)
 constexpr uint32_t kPolyHist = 256;            // history entries a wave of the likelihood agent's act keeps in LDS (the default history row); beyond: read from the source
 // the policies that act on the view history through the lr_* act list (k_logreg_select)
-inline bool lr_family(uint32_t policy) { return policy == RG_POLICY_LOGREG_FROZEN || policy == RG_POLICY_LOGREG_POLY; }
+inline bool lr_family(uint32_t policy) { return policy == RG_POLICY_LOGREG_FROZEN || policy == RG_POLICY_LOGREG_POLY || policy == RG_POLICY_BAYES_VB; }
+// the policies whose unresolved acts go to pl_list (rg_sim_read_poly_unresolved)
+inline bool lists_unresolved(uint32_t policy) { return policy == RG_POLICY_LOGREG_POLY || policy == RG_POLICY_BAYES_VB; }
+// the transposed model of RG_POLICY_BAYES_VB, P x P x S doubles, at most: what one raw buffer resource of the library spans (2 GiB,
+// raw_buffer_rsrc), which also keeps every element offset of the act below 2^28
+constexpr uint64_t kBayesModelBytes = 1ull << 31;
 constexpr uint64_t kRepackMinUsers = 1ull << 18;   // runs smaller than this keep slot == user index throughout (RECOGYM_REPACK_MIN overrides: tests)
 
 inline thread_local char g_err[512] = "";
@@ -317,6 +322,10 @@ struct DevSim {
     const double* pl_wf; const double* pl_wa; const double* pl_wk_t; const double* pl_th;
     double pl_b;
     uint32_t* pl_list;
+    // RG_POLICY_BAYES_VB (rg_sim_set_bayes_vb; rg_bayes_vb.hip): routed the same way, lr_poly = 2 selects k_bayes_acts, unresolved acts
+    // go to pl_list too.  Its model travels in two of the slots above, which that policy leaves unused — pl_wk_t = lam_t [viewed
+    // product][action][sample], caller-owned, pl_nth = the number of samples — so this record, a by-value argument of every kernel,
+    // keeps its size and every other kernel its code.
 };
 
 }  // namespace rgk
@@ -384,7 +393,7 @@ struct RunOpts {
     X(draw_f64) X(draw_fp32) X(draw16_fused) X(draw16_sliced) X(search) X(draw_tp) X(pick) X(draw_cached) \
     X(sweep_xh) X(exact_m) X(exact_tile) X(exact_h) X(walk) X(walk2) X(walk_solo) \
     X(advance) X(advance_run) X(tail) X(repack) X(env0) X(logreg_screen) X(logreg_acts) X(logreg_sample) X(logreg_poly) \
-    X(logreg_poly_w) X(sort_tiled) X(sort_plain)
+    X(logreg_poly_w) X(sort_tiled) X(sort_plain) X(bayes_vb)
 struct Ledger {
 #define RG_LEDGER_FIELD(f) uint64_t f = 0;
     RG_LEDGER_FAMILIES(RG_LEDGER_FIELD)
@@ -511,6 +520,8 @@ search_kernel_t logreg_decide_kernel();
 search_kernel_t logreg_sample_kernel();
 search_kernel_t poly_acts_kernel();                        // rg_logreg_poly.hip
 void (*poly_debug_kernel())(DevSim, int32_t*, uint8_t*);
+search_kernel_t bayes_acts_kernel();                       // rg_bayes_vb.hip
+void (*bayes_debug_kernel())(DevSim, int32_t*, uint8_t*, double*);
 void (*wh_insert_kernel())(DevSim, WhRun, uint32_t);      // rg_weight_history.hip
 void (*wh_acts_kernel())(DevSim, WhRun, uint32_t, uint32_t);
 void (*wh_debug_set_kernel())(DevSim, WhRun, const uint32_t*, const uint32_t*, const uint16_t*, uint32_t);
@@ -738,7 +749,7 @@ inline size_t carve_all(const rg_config& c, uint64_t n, const Geom& g, void* bas
     double* lr_ps2 = w.take<double>(lrs ? n : 1);
     // the screen's scratch: a row per act of a STEP, not per user — a step lists the users whose history changed and who act now
     // (a quarter of the organic users at the default transition matrix); what a step lists beyond the rows goes through k_logreg_acts
-    const size_t lr_part_cap = lr && c.policy != RG_POLICY_LOGREG_POLY ? (n / 2 + 4096 < n ? n / 2 + 4096 : n) : 0;
+    const size_t lr_part_cap = lr && !lists_unresolved(c.policy) ? (n / 2 + 4096 < n ? n / 2 + 4096 : n) : 0;
     uint32_t* lr_part = w.take<uint32_t>(lr_part_cap ? lr_part_cap * static_cast<size_t>(8 * (4 + 2 * 8)) : 1);       // kLrSplit x kLrPartWords
     // round 1's list (the users + kParkSlack for the blocks its waves leave part-used), then round 2's hand-overs (kParkSlack)
     uint32_t* park_list = w.take<uint32_t>(g.cache ? n + 128 + static_cast<size_t>(2) * kParkSlack : 1);
@@ -758,7 +769,7 @@ inline size_t carve_all(const rg_config& c, uint64_t n, const Geom& g, void* bas
     const uint32_t tp_tiles = g.F16 == 2 ? kTpBins : g.n_chunks / 4;
     const uint32_t tp_sh = g.F16 == 2 ? kTpShards : tp_shards_of(tp_tiles);
     uint32_t* tp_order = w.take<uint32_t>(g.tp ? static_cast<size_t>(tp_tiles) * tp_sh * tp_shard_cap(n, tp_sh) : 1);
-    uint32_t* pl_list = w.take<uint32_t>(c.policy == RG_POLICY_LOGREG_POLY ? 3 * static_cast<size_t>(kPolyListCap) : 1);
+    uint32_t* pl_list = w.take<uint32_t>(lists_unresolved(c.policy) ? 3 * static_cast<size_t>(kPolyListCap) : 1);
     if (d) {
         d->pl_list = pl_list;
         d->tp_rec = g.tp ? tp_rec : nullptr; d->tp_hist = tp_hist; d->tp_order = tp_order; d->tp_cap = tp_shard_cap(n, tp_sh); d->tp_shards = tp_sh; d->tp_cpt = 4;
@@ -804,7 +815,7 @@ inline int validate(const rg_config* c, uint64_t n) {
     if (sizeof(double) * (static_cast<size_t>(c->K) * 64 + 64 + 16 * c->K) > 64 * 1024)
         return fail(RG_EINVAL, "K %u exceeds the float64 draw kernel's LDS budget", c->K);
     if (n == 0 || n >= (1ull << 31)) return fail(RG_EINVAL, "n_users %llu out of range", (unsigned long long)n);
-    if (c->policy > RG_POLICY_LOGREG_POLY) return fail(RG_EINVAL, "unknown policy %u", c->policy);
+    if (c->policy > RG_POLICY_BAYES_VB || c->policy == 7u /* not assigned: recogym_hip.h */) return fail(RG_EINVAL, "unknown policy %u", c->policy);
     if (c->time_mode > 1) return fail(RG_EINVAL, "unknown time_mode %u", c->time_mode);
     if (c->env_kind > 1) return fail(RG_EINVAL, "unknown env_kind %u", c->env_kind);
     if (c->lr_select_randomly && (c->policy != RG_POLICY_LOGREG_FROZEN || c->num_products > 1024))

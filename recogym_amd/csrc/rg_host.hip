@@ -864,7 +864,10 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         if (int rc = prof_mark(sim, st, kProfLogreg)) return rc;
         // acts of the users whose view history changed since their last one (frozen LogReg at scale)
         hipLaunchKernelGGL(logreg_select_kernel(), dim3(grid_for(upper)), dim3(kBlock), 0, st, d, t);
-        if (d.lr_poly) {           // the likelihood agent: a wave per act, float64 throughout (rg_logreg_poly.hip)
+        if (d.lr_poly == 2u) {     // BayesianAgentVB: a wave per act, lanes over the posterior samples (rg_bayes_vb.hip)
+            hipLaunchKernelGGL(bayes_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), 0, st, d, t);
+            sim->led.bayes_vb += 1;
+        } else if (d.lr_poly) {    // the likelihood agent: a wave per act, float64 throughout (rg_logreg_poly.hip)
             hipLaunchKernelGGL(poly_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), 0, st, d, t);
             sim->led.logreg_poly += 1;
         } else if (d.lr_sample) {  // select_randomly: a softmax and a draw per act (a wave each)
@@ -1138,8 +1141,8 @@ void plan_config(rg_sim* s, const rg_config* cfg, uint64_t n_users, const Switch
     d.cdf_b0 = cfg->trans_cdf[1][0]; d.cdf_b1 = cfg->trans_cdf[1][1];
     d.sigma0 = cfg->sigma_omega_initial; d.sigma_omega = cfg->sigma_omega; d.change_omega_for_bandits = cfg->change_omega_for_bandits;
     // the likelihood agent runs wherever the frozen LogReg policy does, through the same act list: one policy for the kernels
-    d.policy = cfg->policy == RG_POLICY_LOGREG_POLY ? RG_POLICY_LOGREG_FROZEN : cfg->policy;
-    d.lr_poly = cfg->policy == RG_POLICY_LOGREG_POLY ? 1u : 0u;
+    d.policy = lists_unresolved(cfg->policy) ? RG_POLICY_LOGREG_FROZEN : cfg->policy;
+    d.lr_poly = cfg->policy == RG_POLICY_LOGREG_POLY ? 1u : cfg->policy == RG_POLICY_BAYES_VB ? 2u : 0u;   // (2: k_bayes_acts)
     d.ouc_select_randomly = cfg->ouc_select_randomly; d.ouc_exploit_explore = cfg->ouc_exploit_explore;
     d.ouc_reverse_pop = cfg->ouc_reverse_pop; d.ouc_epsilon = cfg->ouc_epsilon;
     d.time_mode = cfg->time_mode; d.time_mu = cfg->time_mu; d.time_sigma = cfg->time_sigma; d.env_kind = cfg->env_kind;
@@ -1577,6 +1580,7 @@ int rg_sim_set_epsilon_greedy_model(rg_sim* sim, double epsilon, uint64_t eg_see
     if (sim->users_reset) return fail(RG_ESTATE, "rg_sim_set_epsilon_greedy_model must be called before rg_sim_reset_users");
     if (sim->d.policy != RG_POLICY_LOGREG_FROZEN)
         return fail(RG_EINVAL, "rg_sim_set_epsilon_greedy_model wraps the frozen LogReg argmax or the likelihood agent (policy %u)", sim->cfg.policy);
+    if (sim->cfg.policy == RG_POLICY_BAYES_VB) return fail(RG_EINVAL, "EpsilonGreedy round RG_POLICY_BAYES_VB: host path");
     if (sim->d.lr_sample)
         return fail(RG_EINVAL, "rg_sim_set_epsilon_greedy_model: a LogReg with lr_select_randomly samples its act (propensity != 1): host path");
     if (sim->wh.wt.tab) return fail(RG_EINVAL, "EpsilonGreedy round a time-weighted likelihood agent: host path");
@@ -1651,6 +1655,18 @@ int rg_sim_set_logreg_poly(rg_sim* sim, const double* d_wf, const double* d_wa, 
     return RG_OK;
 }
 
+int rg_sim_set_bayes_vb(rg_sim* sim, const double* d_lam_t, uint32_t num_samples) {
+    if (!sim) return fail(RG_EINVAL, "sim is NULL");
+    if (sim->cfg.policy != RG_POLICY_BAYES_VB) return fail(RG_ESTATE, "policy is not RG_POLICY_BAYES_VB");
+    if (!d_lam_t) return fail(RG_EINVAL, "the model array is NULL");
+    if (num_samples == 0) return fail(RG_EINVAL, "num_samples is 0");
+    const uint64_t P = sim->d.P;
+    if (P * P * num_samples > kBayesModelBytes / sizeof(double))
+        return fail(RG_EINVAL, "the model (%u x %u x %u doubles) exceeds %llu bytes", sim->d.P, sim->d.P, num_samples, (unsigned long long)kBayesModelBytes);
+    sim->d.pl_wk_t = d_lam_t; sim->d.pl_nth = num_samples;       // (the likelihood agent's slots: DevSim, RG_POLICY_BAYES_VB)
+    return RG_OK;
+}
+
 int rg_sim_set_weight_history(rg_sim* sim, const double* d_table, uint32_t n, uint32_t accumulate_f32) {
     if (!sim) return fail(RG_EINVAL, "sim is NULL");
     if (sim->cfg.policy != RG_POLICY_LOGREG_POLY) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY");
@@ -1681,7 +1697,7 @@ int rg_sim_set_weight_history(rg_sim* sim, const double* d_table, uint32_t n, ui
 
 int rg_sim_read_poly_unresolved(rg_sim* sim, uint32_t* out, uint32_t capacity, uint32_t* n_out, uint32_t* overflow, void* stream) {
     if (!sim || !n_out || !overflow || (capacity && !out)) return fail(RG_EINVAL, "NULL argument");
-    if (sim->cfg.policy != RG_POLICY_LOGREG_POLY) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY");
+    if (!lists_unresolved(sim->cfg.policy)) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY or RG_POLICY_BAYES_VB");
     if (!sim->users_reset) return fail(RG_ESTATE, "no reset range");
     hipStream_t st = static_cast<hipStream_t>(stream);
     unsigned long long listed = 0;
@@ -1730,6 +1746,8 @@ int rg_sim_reset_users(rg_sim* sim, uint64_t first_user_id, uint64_t n, uint64_t
         return fail(RG_ESTATE, "rg_sim_set_logreg must be called first");
     if (sim->cfg.policy == RG_POLICY_LOGREG_POLY && !sim->d.pl_wk_t)
         return fail(RG_ESTATE, "rg_sim_set_logreg_poly must be called first");
+    if (sim->cfg.policy == RG_POLICY_BAYES_VB && !sim->d.pl_wk_t)
+        return fail(RG_ESTATE, "rg_sim_set_bayes_vb must be called first");
     if (n == 0 || n > sim->d.n_cap) return fail(RG_EINVAL, "n %llu exceeds the %u users the workspace was sized for",
                                                  (unsigned long long)n, sim->d.n_cap);
     if (first_user_id + n > (1ull << 32)) return fail(RG_EINVAL, "user ids must fit 32 bits");
@@ -2013,6 +2031,18 @@ int rg_sim_debug_poly_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, voi
     if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
     hipLaunchKernelGGL(poly_debug_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        sim->d, d_action, d_flags);
+    HIP_TRY(hipGetLastError());
+    return RG_OK;
+}
+
+int rg_sim_debug_bayes_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, double* d_q, void* stream) {
+    if (!sim || !d_action || !d_flags || !d_q) return fail(RG_EINVAL, "NULL argument");
+    if (sim->cfg.policy != RG_POLICY_BAYES_VB) return fail(RG_ESTATE, "policy is not RG_POLICY_BAYES_VB");
+    if (!sim->d.pl_wk_t) return fail(RG_ESTATE, "rg_sim_set_bayes_vb must be called first");
+    if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
+    hipLaunchKernelGGL(bayes_debug_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+                       sim->d, d_action, d_flags, d_q);
+    sim->led.bayes_vb += 1;
     HIP_TRY(hipGetLastError());
     return RG_OK;
 }

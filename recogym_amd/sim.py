@@ -113,6 +113,23 @@ def poly_device_model(logreg_poly, num_products, device):
     return (wf, wa, wk, float(logreg_poly['intercept'])), dev
 
 
+def bayes_device_model(bayes_vb, num_products, device):
+    """A policy dict's `bayes_vb` entry (lam (S, P^2): BayesianAgentVB's posterior draws) -> (Lambda on the host, lam_t (P, P, S)
+    float64 tensor on `device`): the model transposed to [viewed product][action][sample], the sample axis contiguous (the 64 lanes
+    of a wave read 512 contiguous bytes per (p, a)) — what rg_sim_set_bayes_vb takes."""
+    from .agents.bayesian_poly_vb import bayes_transpose
+    lam = np.ascontiguousarray(bayes_vb['lam'], dtype=np.float64)
+    return lam, torch.from_numpy(bayes_transpose(lam, num_products)).to(device)
+
+
+def bayes_host_act(views, num_products, Lambda):
+    """The host act of BayesianAgentVB on the organic views `views` (product ids, any order): the reference's expression on the
+    dense int16 counts — what the device's unresolved acts are judged by."""
+    from .agents.bayesian_poly_vb import reference_act
+    X = np.bincount(np.asarray(views, dtype=np.int64), minlength=int(num_products)).astype(np.int16).reshape(1, -1)
+    return reference_act(X, Lambda)[0]
+
+
 def poly_host_act(views, model):
     """The host act of the likelihood agent on the organic views `views` (product ids, any order) under model = (wf, wa, wk, b):
     the decisions in the contract's order, scipy's expit, first maximum — what the device's unresolved acts are judged by."""
@@ -182,12 +199,15 @@ class Simulator:
                  An optional entry `weight_history = dict(table=, f32=)` (agents/views_history.weight_table) makes the act's
                  features the time-weighted ones: a fresh act per bandit event at the event's clock value; such a
                  run is lock-step and needs a log.  debug_set_timed_history / debug_weighted_acts reach the device function.
+    bayes_vb     dict(lam (S, P^2)): BayesianAgentVB's posterior draws (RG_POLICY_BAYES_VB; agents/bayesian_poly_vb.py), transposed
+                 and uploaded here.  Its unresolved acts share the likelihood agent's list, counter (`poly_unresolved`) and
+                 `poly_verify`, which judges them by the reference's own expression.
     """
 
     def __init__(self, config, n_users, policy=_abi.RG_POLICY_UNIFORM_ENV, policy_seed=None,
                  ouc=None, epoch=0, log_capacity=None, device=None, tables=None, policy_table=None,
                  policy_ps=None, logreg=None, ps_float64=None, p_click=False, env0=None, policy_ps64=False,
-                 epsilon_greedy=None, logreg_poly=None):
+                 epsilon_greedy=None, logreg_poly=None, bayes_vb=None):
         if policy == _abi.RG_POLICY_LOGREG_FROZEN and ((logreg or {}).get('int8') or os.environ.get('RECOGYM_LOGREG') == 'int8'):
             # (refused, not ignored: a caller that labels the act's bytes from this switch would report 1 B per weight for an fp16 run)
             raise ValueError("the 8-bit LogReg screen is retired (measured slower than the fp16 screen): drop logreg['int8'] / RECOGYM_LOGREG=int8")
@@ -301,6 +321,11 @@ class Simulator:
                     self.wh_table = torch.from_numpy(table.astype(np.float64)).to(self.device)
                     _abi.check(self.lib.rg_sim_set_weight_history(self._h, self.wh_table.data_ptr(), int(self.wh_table.numel()),
                                                                   int(bool(self.weight_history['f32']))), 'rg_sim_set_weight_history')
+            self.bayes_vb_host = None
+            if policy == _abi.RG_POLICY_BAYES_VB:
+                self.bayes_vb_host, self.bayes_vb = bayes_device_model(bayes_vb, int(config.num_products), self.device)
+                _abi.check(self.lib.rg_sim_set_bayes_vb(self._h, self.bayes_vb.data_ptr(), int(self.bayes_vb.shape[2])),
+                           'rg_sim_set_bayes_vb')
             self.poly_unresolved = self.poly_refuted = None
             self.poly_overflow = False
             if log_capacity is None:
@@ -423,7 +448,32 @@ class Simulator:
         res['poly_table'] = int(out[_abi.RG_CNT_POLY_TABLE])         # likelihood agent: acts decided on the expit step table
         res['poly_unresolved'] = int(out[_abi.RG_CNT_POLY_UNRESOLVED])   # ... acts listed for the host (poly_verify)
         res['wh_clock_range'] = int(out[_abi.RG_CNT_WH_CLOCK_RANGE])     # ... weighted acts that met a clock value outside [0, 32767]
+        res['bayes_saturated'] = int(out[_abi.RG_CNT_BAYES_SATURATED])   # BayesianAgentVB: acts decided in the saturated zone
         return res
+
+    def debug_set_history(self, nd, products, counts):
+        """rg_sim_debug_set_history: per user index of the reset range, nd[i] distinct products products[i, j] (ascending) with
+        view counts counts[i, j]."""
+        products, counts = np.ascontiguousarray(products, dtype=np.uint32), np.ascontiguousarray(counts, dtype=np.uint32)
+        assert products.shape == counts.shape and products.shape[0] == self.n_active == len(nd)
+        with torch.cuda.device(self.device):
+            d = [torch.from_numpy(np.ascontiguousarray(x, dtype=np.uint32).view(np.int32)).to(self.device) for x in (nd, products, counts)]
+            _abi.check(self.lib.rg_sim_debug_set_history(self._h, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(),
+                                                         int(products.shape[1]), self._stream()), 'rg_sim_debug_set_history')
+            torch.cuda.synchronize(self.device)
+
+    def debug_bayes_acts(self):
+        """rg_sim_debug_bayes_acts -> (actions, flags, q (n, P)): BayesianAgentVB's act of every user index on its current history
+        and the device's means."""
+        n, P = self.n_active, int(self.config.num_products)
+        with torch.cuda.device(self.device):
+            act = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+            fl = torch.full((n,), 255, dtype=torch.uint8, device=self.device)
+            q = torch.full((n, P), float('nan'), dtype=torch.float64, device=self.device)
+            _abi.check(self.lib.rg_sim_debug_bayes_acts(self._h, act.data_ptr(), fl.data_ptr(), q.data_ptr(), self._stream()),
+                       'rg_sim_debug_bayes_acts')
+            torch.cuda.synchronize(self.device)
+        return act.cpu().numpy().astype(np.int64), fl.cpu().numpy().astype(np.int64), q.cpu().numpy()
 
     def debug_set_timed_history(self, n_views, products, times16):
         """rg_sim_debug_set_timed_history: per user index of the reset range, n_views[i] views (products[i, j] at clock value
@@ -494,6 +544,8 @@ class Simulator:
                     mine = u == user
                     host = weighted_host_act(v[mine & organic & (t < t_act)], clock[mine & organic & (t < t_act)],
                                              clock[mine & (t == t_act)], self.weight_history, self.logreg_poly_host)
+                elif self.bayes_vb_host is not None:
+                    host = bayes_host_act(v[organic & (u == user) & (t <= t_act)], self.config.num_products, self.bayes_vb_host)
                 else:
                     host = poly_host_act(v[organic & (u == user) & (t <= t_act)], self.logreg_poly_host)
                 if host != int(a):
