@@ -227,7 +227,8 @@ int rg_sim_destroy(rg_sim* sim);
  * (k_draw_mfma), draw16_fused / draw16_sliced (k_draw_bf16 / k_draw_bf16p / k_draw_f16w as one sweep with the search fused in /
  * over product slices), search (k_draw_search behind the slices), draw_tp (k_draw_tp / k_draw_tpw), pick (k_pick), draw_cached
  * (k_draw_cached), sweep_xh (k_sweep_xh), exact_m / exact_tile / exact_h (the float64 sums: a user per lane / a product per lane /
- * the walk's mixed batch), walk (k_walk), walk2 (k_walk2), walk_solo (k_walk_solo), advance (k_advance), advance_run
+ * the walk's mixed batch), walk (k_walk), walk2 (k_walk2), walk_solo (k_walk_solo), park_compact (k_park_compact: round 1's list
+ * made dense, between round 1 and the float64 batch of a walked run with device-side list lengths), advance (k_advance), advance_run
  * (k_advance_run), tail (k_tail), repack, env0 (k_draw_env0), logreg_screen, logreg_acts, logreg_sample, logreg_poly (k_poly_acts), sort_tiled / sort_plain
  * (the ordered log's scatter).  What rg_sim_create chose for the fast draw: draw_kh, draw_n1 (the class: KH, k-steps N1),
  * draw_split (0 none, 1 three-way bf16, 2 two-way fp16, 3 two-way fp16 wide), draw_kernel (0 float64 only, 1 fp32 MFMA, 2 a 16-bit
@@ -239,6 +240,11 @@ int rg_sim_destroy(rg_sim* sim);
  * sweep, k_draw_mfma, k_sweep_xh, k_draw_tp / k_draw_tpw), tp_nts (LDS row stride of a user's tile prefixes), tp_cpt (chunks per tile
  * of the wide sweep), draw_threads (block size of the draw kernel), exact_rows (rows of the float64 chunk-sum scratch), hist_cap
  * (history entries per user row), repack_min (users below which slot == user index), ablate (timing-experiment bits).
+ * The last walked run's round-1 list, from the run's one read-back (0 before any): park_slots (the entries its waves reserved,
+ * 64 at a time: users and padding), park_users (the users parked at an uncertified draw), handed_over (the users its draining
+ * waves handed on), batch_users (the list entries the float64 batch swept for: park_users + handed_over, the dense list
+ * k_park_compact made of them).  A run with host-side list lengths (pipe_groups = 0, or fewer than pipe_min_users) counts no kinds
+ * and makes no dense list: park_users = handed_over = -1, batch_users = park_slots = the list it read back.
  * Setting any of them fails like an unknown name.
  * RG_EINVAL for an unknown name or a value out of range. */
 int rg_sim_set_option(rg_sim* sim, const char* name, int64_t value);

@@ -243,7 +243,8 @@ struct DevSim {
     uint32_t* list;           // [2 parity][2 state][n_users]
     uint32_t* step_cnt;       // [kMaxSteps+2][2]: users in organic / bandit state at step t
     uint64_t* log_base;       // [kMaxSteps+2]: first log row of step t
-    uint32_t* exact_list;     // [n_users] organic users whose draw needs the float64 path
+    uint32_t* exact_list;     // [n_users] organic users whose draw needs the float64 path (a lock-step step's); run_walk_pipe: the
+                              // dense list of the users round 1 parked or handed over (k_park_compact, kDenseList)
     uint32_t* exact_cnt;      // [kMaxSteps+2]
     // Run-ahead rounds (rg_sim_run to the end without the user-major walk; k_advance_run): a lock-step "step" becomes a ROUND — every
     // listed user's next organic event, or its whole bandit run up to the next organic event / stop / possible click — so users sit
@@ -391,7 +392,7 @@ struct RunOpts {
 // to prove that the named kernel served the run (with the float64 resolve behind every draw a run on another kernel still passes).
 #define RG_LEDGER_FAMILIES(X) \
     X(draw_f64) X(draw_fp32) X(draw16_fused) X(draw16_sliced) X(search) X(draw_tp) X(pick) X(draw_cached) \
-    X(sweep_xh) X(exact_m) X(exact_tile) X(exact_h) X(walk) X(walk2) X(walk_solo) \
+    X(sweep_xh) X(exact_m) X(exact_tile) X(exact_h) X(walk) X(walk2) X(walk_solo) X(park_compact) \
     X(advance) X(advance_run) X(tail) X(repack) X(env0) X(logreg_screen) X(logreg_acts) X(logreg_sample) X(logreg_poly) \
     X(logreg_poly_w) X(sort_tiled) X(sort_plain) X(bayes_vb)
 struct Ledger {
@@ -450,10 +451,14 @@ struct rg_sim {
     double prof_pipe_ms;      // profiling: wall time of those runs (first to last mark of each)
     // rg_sim_debug_walk_fate: where the last walked run left the list of its last round (null: there was none)
     uint32_t fate_base; const unsigned long long* fate_count;
+    // the last walked run's round-1 list as its one read-back reported it (options park_slots, park_users, handed_over,
+    // batch_users): reserved entries, users with the pend bit, users handed over, list entries the float64 batch was given.
+    // run_walk reads no per-kind count: there park_users and handed_over are -1
+    int64_t park_slots, park_users, handed_over, batch_users;
     uint32_t repack_every;    // steps between repacks (RECOGYM_REPACK, 0 = never)
     bool sort_plain;          // rg_sim_sort_log scatters without the LDS tiles (RECOGYM_SORT_PLAIN: A/B)
     uint32_t tail_below;      // rg_sim_run hands the run to k_tail once at most this many users live (RECOGYM_TAIL, 0 = never)
-    uint32_t* h_pinned;       // 4 x u32 staging for the live-count readback
+    uint32_t* h_pinned;       // staging of the host's read-backs: the live counts of a step, the words that close a run
     char* h_step;             // 128 pinned bytes of rg_sim_step_user: the action going down, the packed result coming back
     size_t mfma_smem, bf16_smem;
     void (*bf16_kernel)(DevSim, uint32_t, uint32_t);
@@ -537,6 +542,7 @@ typedef void (*solo_kernel_t)(DevSim, uint32_t, uint32_t, uint32_t);
 solo_kernel_t solo_kernel_for(const DevSim& d);            // (nullptr: the last round is k_walk2's too)
 void (*cache_prefix_kernel())(DevSim, int);
 void (*exact_prefix_kernel())(DevSim, uint32_t);
+void (*park_compact_kernel())(DevSim);
 
 // ------------------------------------------------------------------------------------------
 // workspace carving (host)
@@ -568,11 +574,18 @@ constexpr int kCntTailRows = 16, kCntTailOrganic = 17, kCntTailBandit = 18, kCnt
 constexpr int kCntWalkHits = RG_CNT_MEMO_HITS;
 // the walked run: park_list holds round 1's list — the users plus the 64-entry blocks its waves leave part-used (<= 2 per wave:
 // parked users, hand-over) — and behind it the last round's list: kParkSlack entries (a wave of round 2 hands over once: <= 2
-// blocks).  run_walk_pipe's walk_ctl = 8 counters {round-1 ticket, round-1 list length, float64 batch ticket, round-2 ticket, -...}
-// and 8 more {last round's list length, last round's ticket}.  Walk grids are capped at kMaxWalkWaves waves.
+// blocks).  run_walk_pipe reads that list once: k_park_compact copies its users — no unused entry — into the DENSE list, which
+// lives in exact_list (idle in a walked run: only a lock-step step's search lists draws there).  The float64 batch,
+// k_exact_prefix and round 2 (in_base == kDenseList) take the dense list.  walk_ctl = 8 counters {round-1 ticket, round-1 list
+// length in reserved entries, float64 batch ticket, round-2 ticket, users of the dense list (kCtlAll), the handed-over ones
+// among them (kCtlHanded), the run's step-limit word (kCtlLimit: k_walk_finish's copy, so that the run's one read-back takes
+// words 1 .. 6), -} and 8 more {last round's list length, last round's ticket}.  Walk grids are capped at kMaxWalkWaves waves.
 constexpr uint32_t kMaxWalkWaves = 4096;
 constexpr uint32_t kParkSlack = 2u * 64u * kMaxWalkWaves;
 constexpr uint32_t kWalkCtlWords = 16;
+constexpr uint32_t kCtlAll = 4, kCtlHanded = 5, kCtlLimit = 6;
+constexpr uint32_t kDenseList = 0xFFFFFFFFu;     // k_walk2's in_base of a round that reads the dense list
+constexpr uint32_t kCompactTile = 4096;          // list entries a block of k_park_compact takes per atomic on either count
 
 // the draw kernels' classes and tile shapes for a configuration, and the sizing decisions that follow from them and the switches: cache (the
 // per-user sum cache exists), all_f64 (every draw a float64 sweep), repack (a second copy of the per-user state), tp (k_draw_tp's records)

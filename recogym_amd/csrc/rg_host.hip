@@ -179,6 +179,7 @@ __global__ void k_walk_finish(DevSim d) {
     d.step_cnt[0] = 0; d.step_cnt[1] = 0; d.step_cnt[2] = 0; d.step_cnt[3] = 0;
     d.log_base[0] = d.debug_row_base;
     d.log_base[1] = d.counters[kCntTailRows];
+    d.walk_ctl[kCtlLimit] = d.counters[kCntTailLimit];      // (run_walk_pipe's read-back: one copy of walk_ctl's words)
 }
 
 // totals that are sums over the per-step counts
@@ -920,11 +921,14 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
 // A run that ended on the device (a walked run, k_tail): the step limit read back — the one host read-back of such a run,
 // it synchronises the stream — and the host's books closed at step t_end.  wall_from: the mark from which the run's wall time
 // (to the last mark; run_walk_pipe's) is taken, now that every mark has passed
+// `words` device words from `from`, the step limit the last of them, come back in h_pinned (kPinnedWords hold them)
 constexpr size_t kNoWall = ~static_cast<size_t>(0);
-int close_run(rg_sim* sim, hipStream_t st, uint32_t t_end, size_t wall_from = kNoWall) {
+constexpr size_t kPinnedWords = 8;
+int close_run(rg_sim* sim, hipStream_t st, uint32_t t_end, size_t wall_from = kNoWall, const unsigned long long* from = nullptr, size_t words = 1) {
     unsigned long long* h64 = reinterpret_cast<unsigned long long*>(sim->h_pinned);
-    HIP_TRY(hipMemcpyAsync(h64, sim->d.counters + kCntTailLimit, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h64, from ? from : sim->d.counters + kCntTailLimit, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    h64 += words - 1;
     if (sim->profiling && wall_from != kNoWall) {
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, sim->prof_events[wall_from], sim->prof_events[sim->prof_used - 1]));
@@ -943,13 +947,24 @@ int walk_begin(rg_sim* sim, hipStream_t st) {
         HIP_TRY(hipMemcpyAsync(sim->d.counters + kCntTailRows, &sim->d.debug_row_base, sizeof(unsigned long long), hipMemcpyHostToDevice, st));
     return RG_OK;
 }
-int walk_end(rg_sim* sim, hipStream_t st, size_t wall_from = kNoWall) {
+// (dense: run_walk_pipe — the same read-back also brings what k_park_compact counted of round 1's list)
+int walk_end(rg_sim* sim, hipStream_t st, size_t wall_from = kNoWall, bool dense = false) {
     if (int rc = prof_mark(sim, st, kProfNone)) return rc;       // the last round ends here ...
     hipLaunchKernelGGL(k_walk_finish, dim3(1), dim3(1), 0, st, sim->d);
     HIP_TRY(hipGetLastError());
     if (int rc = prof_mark(sim, st, kProfNone)) return rc;       // ... and the run here
     if (sim->profiling) sim->prof_launches += 1;
-    return close_run(sim, st, 1u, wall_from);
+    if (!dense) return close_run(sim, st, 1u, wall_from);
+    static_assert(kCtlLimit <= kPinnedWords, "walk_ctl's words 1 .. kCtlLimit fit the pinned staging");
+    const int rc = close_run(sim, st, 1u, wall_from, sim->d.walk_ctl + 1, kCtlLimit);
+    const unsigned long long* h64 = reinterpret_cast<const unsigned long long*>(sim->h_pinned);
+    if (rc == RG_OK || rc == RG_ELIMIT) {
+        sim->park_slots = static_cast<int64_t>(h64[0]);
+        sim->batch_users = static_cast<int64_t>(h64[kCtlAll - 1]);
+        sim->handed_over = static_cast<int64_t>(h64[kCtlHanded - 1]);
+        sim->park_users = sim->batch_users - sim->handed_over;
+    }
+    return rc;
 }
 
 // rg_sim_run "to the end" of a sigma_omega == 0 run: sweep (fills the per-user cache) -> k_walk round 1 ->
@@ -958,6 +973,7 @@ int run_walk(rg_sim* sim, hipStream_t st) {
     const DevSim& d = sim->d;
     if (int rc = walk_begin(sim, st)) return rc;
     sim->fate_count = nullptr;
+    sim->park_slots = sim->batch_users = 0; sim->park_users = sim->handed_over = -1;
     bool fused_prefix = false;
     // 1. every user's first product sweep: only the per-user sums are kept (no search, no rows)
     if (int rc = prof_mark(sim, st, kProfSweep)) return rc;
@@ -995,6 +1011,7 @@ int run_walk(rg_sim* sim, hipStream_t st) {
     HIP_TRY(hipMemcpyAsync(h64, d.counters + kCntParkCnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const uint32_t n_park = static_cast<uint32_t>(*h64);
+    sim->park_slots = sim->batch_users = n_park;
     if (sim->opt.debug) {
         unsigned long long ev2[2] = {0, 0};
         HIP_TRY(hipMemcpy(ev2, d.counters + kCntTailOrganic, sizeof(ev2), hipMemcpyDeviceToHost));
@@ -1097,10 +1114,20 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, dw, n, 1, walk_chunk_rows(n, blocks), 0u, region);
         sim->led.walk2 += 1;
     }
-    // ---- the users it parked: float64 sums, prefixes, round 2 (what it hands over: the last round's list) ----
+    // ---- its list made dense (k_park_compact): the float64 batch works per list ENTRY, and an unused one costs what a user costs ----
+    {
+        DevSim dc = dg;
+        dc.list_in = region;
+        uint32_t cgrid = (n + kParkSlack + kCompactTile - 1) / kCompactTile;
+        if (cgrid > 1024u) cgrid = 1024u;
+        if (int rc = prof_mark(sim, st, kProfResolve)) return rc;
+        hipLaunchKernelGGL(park_compact_kernel(), dim3(cgrid), dim3(kBlock), 0, st, dc);
+        sim->led.park_compact += 1;
+    }
+    // ---- the users it parked (or handed over): float64 sums, prefixes, round 2 (what it hands over: the last round's list) ----
     {
         DevSim dx = dg;
-        dx.q_ticket = ctl + 2; dx.q_count = ctl + 1; dx.list_in = region;
+        dx.q_ticket = ctl + 2; dx.q_count = ctl + kCtlAll; dx.park_list = d.exact_list; dx.list_in = 0;      // the dense list
         const uint32_t est = n / 3 + 4096u;                  // launch shapes only: the lengths are read on the device
         uint32_t xgrid = (n + 255u) / 256u;
         if (xgrid > static_cast<uint32_t>(sim->pipe_xblocks)) xgrid = static_cast<uint32_t>(sim->pipe_xblocks);
@@ -1109,10 +1136,10 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         sim->led.exact_h += 1;
         hipLaunchKernelGGL(exact_prefix_kernel(), dim3(grid_for(est, kBlock / 64)), dim3(kBlock), 0, st, dx, n);
         DevSim dr = dg;
-        dr.q_ticket = ctl + 3; dr.q_park = ctl_last + 0; dr.q_count = ctl + 1;
+        dr.q_ticket = ctl + 3; dr.q_park = ctl_last + 0; dr.q_count = ctl + kCtlAll;
         const int blocks = walk_blocks(est, sim->pipe_occ2, n_cus);
         if (int rc = prof_mark(sim, st, kProfWalk2)) return rc;
-        hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, dr, n, 2, walk_chunk_rows(est, blocks), region, base_solo);
+        hipLaunchKernelGGL(wk, dim3(blocks), dim3(kBlock), smem, st, dr, n, 2, walk_chunk_rows(est, blocks), kDenseList, base_solo);
         sim->led.walk2 += 1;
     }
     // ---- last round: a wave per user (k_walk_solo) over what round 2 handed over ----
@@ -1124,7 +1151,7 @@ int run_walk_pipe(rg_sim* sim, hipStream_t st) {
         hipLaunchKernelGGL(sk, dim3(sh.blocks), dim3(kBlock), 0, st, dl, n, sh.chunk_rows, base_solo);
         sim->led.walk_solo += 1;
     }
-    return walk_end(sim, st, first_mark);
+    return walk_end(sim, st, first_mark, true);
 }
 
 
@@ -1305,6 +1332,7 @@ void plan_pipe(rg_sim* s, const Switches& w) {
     s->fin_in_sweep = !w.fin_in_sweep.is('0');
     s->d.fin_in_sweep = 0;
     s->fate_base = 0; s->fate_count = nullptr;
+    s->park_slots = s->park_users = s->handed_over = s->batch_users = 0;
 }
 void plan_logreg_run_ahead(rg_sim* s, const Switches& w) {
     s->run_ahead = w.run_ahead.set ? w.run_ahead.u32() : 32;   // events a round of a run to the end may take a user through (0: lock-step, an event per launch)
@@ -1441,6 +1469,7 @@ const Option kOptions[] = {
     RG_OPT_R("draw_smem", s->bf16_smem) RG_OPT_R("mfma_smem", s->mfma_smem) RG_OPT_R("xh_smem", s->xh_smem) RG_OPT_R("tp_smem", s->tp_smem)
     RG_OPT_R("tp_nts", s->tp_nts) RG_OPT_R("tp_cpt", s->d.tp_cpt) RG_OPT_R("draw_threads", s->draw_threads)
     RG_OPT_R("weight_history", s->wh.wt.tab ? 1 : 0)           // rg_sim_set_weight_history was called
+    RG_OPT_R("park_slots", s->park_slots) RG_OPT_R("park_users", s->park_users) RG_OPT_R("handed_over", s->handed_over) RG_OPT_R("batch_users", s->batch_users)
     RG_OPT_R("exact_rows", s->d.exact_rows) RG_OPT_R("hist_cap", s->d.hist_cap) RG_OPT_R("repack_min", s->opt.repack_min) RG_OPT_R("ablate", s->d.ablate)
 };
 const Option* find_option(const char* name) {
@@ -1828,7 +1857,7 @@ int rg_sim_run(rg_sim* sim, uint32_t max_steps, void* stream) {
     if (!sim->users_reset) return fail(RG_ESTATE, "rg_sim_reset_users must be called first");
     if (sim->d.policy == RG_POLICY_EXTERNAL) return fail(RG_ESTATE, "rg_sim_run needs a device policy");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!sim->h_pinned) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sim->h_pinned), 4 * sizeof(uint32_t)));
+    if (!sim->h_pinned) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sim->h_pinned), kPinnedWords * sizeof(unsigned long long)));
     if (sim->walk && sim->t == 0 && max_steps >= kMaxSteps) {
         // the pipelined form where its kernels exist (k_walk2 behind the fused-prefix fp16 sweep, k_walk_solo, the mixed float64
         // batch) and the reset range fills an unsliced sweep; else the serial chain with its list lengths read back by the host

@@ -673,6 +673,60 @@ __global__ void __launch_bounds__(kBlock) k_exact_prefix(DevSim d, uint32_t n_li
     }
 }
 
+// Round 1's list (park_list + list_in, walk_ctl[1] reserved entries: the blocks of 64 its waves left part-used are padded with
+// 0xFFFFFFFF) -> the DENSE list in exact_list: its users and nothing else, walk_ctl[kCtlAll] of them; how many of them are
+// handed-over ones (no pend bit in park_t: the others are parked at an uncertified draw) is counted in walk_ctl[kCtlHanded].  A
+// user is listed once, so the n_cap entries of exact_list hold them.  A block takes kCompactTile entries at a time and reserves
+// their room with ONE atomic per count (a hot address sustains ~6 M atomics/s); a tile keeps the list's order, the order of the
+// tiles follows the blocks' scheduling, as the list's own order follows that of round 1's waves.
+__global__ void __launch_bounds__(kBlock) k_park_compact(DevSim d) {
+    constexpr int kPer = kCompactTile / kBlock;
+    __shared__ uint32_t s_wave[kBlock / 64];
+    __shared__ uint32_t s_base;
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const uint32_t n = static_cast<uint32_t>(d.walk_ctl[1]);
+    const uint32_t* src = d.park_list + d.list_in;
+    for (uint32_t t0 = blockIdx.x * kCompactTile; t0 < n; t0 += gridDim.x * kCompactTile) {
+        uint32_t slot[kPer];
+        uint32_t n_u = 0u, n_h = 0u;                       // users / handed-over users among this thread's entries
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            // (kPer CONSECUTIVE entries per thread — a 64-byte run —, so that a tile keeps the list's order: the users a wave of
+            // round 1 listed together have neighbouring indices, and the batch and round 2 gather their rows together)
+            const uint32_t idx = t0 + threadIdx.x * static_cast<uint32_t>(kPer) + static_cast<uint32_t>(j);
+            slot[j] = idx < n ? src[idx] : 0xFFFFFFFFu;
+        }
+#pragma unroll
+        for (int j = 0; j < kPer; ++j)
+            if (slot[j] != 0xFFFFFFFFu) {
+                n_u += 1u;
+                n_h += ((d.park_t[slot[j]] >> 27) & 1u) ^ 1u;
+            }
+        // exclusive prefix over the block of both counts at once (each <= kCompactTile < 2^16): users low, handed-over high
+        const uint32_t mine = n_u | (n_h << 16);
+        uint32_t incl = mine;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = static_cast<uint32_t>(__shfl_up(static_cast<int>(incl), o));
+            if (lane >= o) incl += y;
+        }
+        __syncthreads();                                   // (the previous tile's s_wave / s_base are read)
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0u, total = 0u;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) { if (w < wave) before += s_wave[w]; total += s_wave[w]; }
+        if (threadIdx.x == 0) {
+            s_base = (total & 0xFFFFu) ? static_cast<uint32_t>(atomicAdd(d.walk_ctl + kCtlAll, static_cast<unsigned long long>(total & 0xFFFFu))) : 0u;
+            if (total >> 16) atomicAdd(d.walk_ctl + kCtlHanded, static_cast<unsigned long long>(total >> 16));
+        }
+        __syncthreads();
+        uint32_t at = s_base + ((before + incl - mine) & 0xFFFFu);
+#pragma unroll
+        for (int j = 0; j < kPer; ++j)
+            if (slot[j] != 0xFFFFFFFFu) d.exact_list[at++] = slot[j];
+    }
+}
+
 // (the float64 pick as a noinline CALL freed ~40 registers of the walk's loop, but at four blocks per CU — 128 VGPRs, the loop
 // spilling around the call — the kernel no longer reproduced the oracle: measured, dropped; inlined at three blocks per CU
 // the loop holds everything in 168 registers)
@@ -827,7 +881,10 @@ __global__ void __launch_bounds__(kBlock, (KH <= 10 ? 3 : 2)) k_walk2(DevSim d_a
                     if (mine) {
                         const uint32_t idx = res_next + r;
                         uint32_t s2 = d.grp_lo + idx;
-                        if (round >= 2) s2 = d.park_list[in_base + idx];
+                        if (round >= 2) {
+                            const uint32_t* lst = in_base == kDenseList ? d.exact_list : d.park_list + in_base;     // (the dense list: rg_common.hpp)
+                            s2 = lst[idx];
+                        }
                         if (s2 != 0xFFFFFFFFu) {
                             // (round 1: a new user, t = 0, and every writer of the hot row — the sweeps' finalize, k_cache_prefix — has
                             // just left its memo empty: the first draw cannot be answered by it and goes straight to the search,
@@ -2135,6 +2192,7 @@ walk_kernel_t walk2_kernel_for(const DevSim& d, int occ) {
 }
 void (*cache_prefix_kernel())(DevSim, int) { return k_cache_prefix; }
 void (*exact_prefix_kernel())(DevSim, uint32_t) { return k_exact_prefix; }
+void (*park_compact_kernel())(DevSim) { return k_park_compact; }
 
 // blocks per CU the kernel is compiled for (register budget 512 / OCC per lane): KH <= 16 at 2, 3 or 4, KH = 32 at 1
 walk_kernel_t walk_kernel_for(const DevSim& d, int occ) {
