@@ -54,6 +54,9 @@ extern "C" {
 /* v14, additive since: RG_POLICY_BAYES_VB with rg_sim_set_bayes_vb and rg_sim_debug_bayes_acts (the posterior-sample act of
  * BayesianAgentVB in the step loop) and the counter RG_CNT_BAYES_SATURATED; its unresolved acts share the likelihood agent's list,
  * counter and reader (RG_CNT_POLY_UNRESOLVED, rg_sim_read_poly_unresolved). */
+/* v14, additive since: RG_POLICY_NN_IPS with rg_sim_set_nn_ips and rg_sim_debug_nn_acts (the three-layer perceptron act of NnIpsAgent
+ * in the step loop, the first argmax policy whose logged propensity is a model output) and the flag RG_NN_UNRESOLVED; its unresolved
+ * acts share the same list, counter and reader. */
 #define RG_ABI_VERSION 14
 
 /* error codes */
@@ -89,6 +92,10 @@ extern "C" {
 #define RG_POLICY_BAYES_VB 8      /* frozen BayesianAgentVB, agents/bayesian_poly_vb.py:71-91: a = the first index of the maximum over the
                                      actions of mean_s expit(sum_p views[p] Lambda[s][p P + a]) over the posterior samples s —
                                      rg_sim_set_bayes_vb has the contract; ps = 1.  Routed like RG_POLICY_LOGREG_POLY. */
+/* (9 is not assigned either and stays refused: tests/test_bayes_vb_host.py holds policy 9 as a refused number) */
+#define RG_POLICY_NN_IPS 10       /* frozen NnIpsAgent, agents/nn_ips.py:43-63,111-137: prob = softmax(W3 sigmoid(W2 sigmoid(W1 x + b1) + b2) + b3)
+                                     over the user's view counts x, a = the first index of the maximum, ps = prob[a] (not 1) —
+                                     rg_sim_set_nn_ips has the contract.  Routed like RG_POLICY_LOGREG_POLY. */
 
 /*
  * Everything the step loop needs from `env.config` (a Configuration built from env_1_args,
@@ -391,6 +398,26 @@ int rg_sim_set_weight_history(rg_sim* sim, const double* d_table, uint32_t n, ui
 #define RG_BAYES_UNRESOLVED 2u
 int rg_sim_set_bayes_vb(rg_sim* sim, const double* d_lam_t, uint32_t num_samples);
 
+/* RG_POLICY_NN_IPS: the net of NnIpsAgent, six float64 device arrays kept by pointer that hold the model's fp32 values widened, the
+ * matrices transposed so that the row of a viewed product or hidden unit is contiguous: d_w1t[p H + h] = W1[h][p], d_b1[h],
+ * d_w2t[h H + k] = W2[k][h], d_b2[k], d_w3t[k P + a] = W3[a][k], d_b3[a]; H = num_hidden in [1, 1024], num_products <= 4000, every
+ * value finite (else RG_EINVAL).  The call reads the arrays once (the absolute row sums A2, A3 below) and synchronises.
+ * The act over the n distinct viewed products p_0 < ... < p_(n-1) with counts c_j, float64, multiply then add, in exactly this order:
+ *   s1[h] = 0; for j: s1[h] += c_j w1t[p_j][h];  s1[h] += b1[h];  h1 = sg(s1)     m1[h] = sum_j |c_j w1t[p_j][h]| + |b1[h]|, M1 = max m1
+ *   s2[k] = 0; for h: s2[k] += w2t[h][k] h1[h];  s2[k] += b2[k];  h2 = sg(s2)
+ *   z[a]  = 0; for k: z[a]  += w3t[k][a] h2[k];  z[a]  += b3[a]
+ *   a* = the first index of max z;  e[a] = ex(z[a] - z[a*]);  ps = e[a*] / sum, the sum taken per lane over a = lane, lane + 64, ...
+ *   and then over the 64 lanes by a fixed xor butterfly.  sg(x) = 1 / (1 + ex(-x)); ex is an exponential made of IEEE operations
+ *   only (rg_nn_common.hpp: nn_exp), so that a host restatement gives the same bits (agents/nn_ips.py).
+ * W(n, M1, H, A2, A3) (A2 = max_k sum_h |w2t[h][k]| + |b2[k]|, A3 likewise) bounds the distance of every z[a] from the
+ * logit of torch's fp32 forward in ANY summation order, plus half the gap below which an fp32 softmax can tie or reorder two logits.
+ * The act is RG_NN_UNRESOLVED when some other action has z[a*] - z[a] <= 2 W, or a count exceeds 2^24 (not an fp32 value): counted
+ * and listed as the likelihood agent's (RG_CNT_POLY_UNRESOLVED, rg_sim_read_poly_unresolved).  ps goes to the policy's rows.
+ * The EpsilonGreedy model overlay on this policy is RG_EINVAL. */
+#define RG_NN_UNRESOLVED 2u
+int rg_sim_set_nn_ips(rg_sim* sim, const double* d_w1t, const double* d_b1, const double* d_w2t, const double* d_b2,
+                      const double* d_w3t, const double* d_b3, uint32_t num_hidden);
+
 /* The unresolved acts of the run so far (since rg_sim_reset_users): out[3 i .. 3 i + 2] = (user id, t, action taken) for the first
  * min(listed, capacity) of them, in no particular order; t is the event index the act was computed at: its history is the user's
  * organic rows with index <= t.  *n_out = entries written, *overflow = 1 when the run had more unresolved acts than the device list
@@ -536,6 +563,10 @@ int rg_sim_debug_poly_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, voi
  * device function the step loop uses: d_action[i], d_flags[i] (RG_BAYES_SATURATED | RG_BAYES_UNRESOLVED) and the device's means
  * d_q[i * num_products + a] (with an empty history no mean is computed: 0.5 is written).  Touches neither the counters nor the list. */
 int rg_sim_debug_bayes_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, double* d_q, void* stream);
+/* rg_sim_debug_nn_acts: the RG_POLICY_NN_IPS act of every user index on its current history (rg_sim_debug_set_history), by the device
+ * function the step loop uses: d_action[i], d_flags[i] (RG_NN_UNRESOLVED), the logits d_z[i * num_products + a] and d_ps[i].
+ * Touches neither the counters nor the list. */
+int rg_sim_debug_nn_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, double* d_z, double* d_ps, void* stream);
 /* rg_sim_debug_set_timed_history (after rg_sim_set_weight_history, right after rg_sim_reset_users): the TIMED view history of every
  * user index — d_n[i] views (at most stride), view j of product d_products[i * stride + j] at clock value d_times16[i * stride + j],
  * in view order (times never decreasing).  They go into the user's history row one at a time through the sorted insert that never

@@ -19,6 +19,7 @@ RG_POLICY_LAST_VIEW_TABLE = 4
 RG_POLICY_LOGREG_FROZEN = 5
 RG_POLICY_LOGREG_POLY = 6
 RG_POLICY_BAYES_VB = 8      # (7 is not assigned: include/recogym_hip.h)
+RG_POLICY_NN_IPS = 10       # (9 is not assigned: include/recogym_hip.h)
 
 RG_EV_BANDIT = 0x80000000
 RG_EV_CLICK = 0x40000000
@@ -158,6 +159,7 @@ SYMBOLS = {
     'rg_sim_set_logreg_fp16': (C.c_int, [_SIM, C.c_void_p]),
     'rg_sim_set_logreg_poly': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_uint32]),
     'rg_sim_set_bayes_vb': (C.c_int, [_SIM, C.c_void_p, C.c_uint32]),
+    'rg_sim_set_nn_ips': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     'rg_sim_set_weight_history': (C.c_int, [_SIM, C.c_void_p, C.c_uint32, C.c_uint32]),
     'rg_sim_read_poly_unresolved': (C.c_int, [_SIM, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]),
     'rg_sim_set_log': (C.c_int, [_SIM, C.c_void_p, C.c_uint64]),
@@ -189,6 +191,7 @@ SYMBOLS = {
     'rg_sim_debug_ouc_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rg_sim_debug_poly_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rg_sim_debug_bayes_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rg_sim_debug_nn_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rg_sim_debug_set_timed_history': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'rg_sim_debug_weighted_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                              C.c_void_p]),

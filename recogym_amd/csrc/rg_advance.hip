@@ -557,7 +557,7 @@ __global__ void __launch_bounds__(kAdvBlock) k_advance(DevSim d, uint32_t t, con
                     ps = __builtin_nan("");
                 }
                 else if constexpr (EG) a = model_act_overlay(d, slot, user, t, lr_a, &ps);      // (lr_a: the greedy action of a model)
-                else if (d.policy == RG_POLICY_LOGREG_FROZEN) { a = lr_a; ps = d.lr_sample ? d.lr_ps[uidx] : 1.0; }
+                else if (d.policy == RG_POLICY_LOGREG_FROZEN) { a = lr_a; ps = d.lr_sample || lr_logs_ps(d) ? d.lr_ps[uidx] : 1.0; }
                 else a = policy_act_eg<EG>(d, slot, user, t, &ps);
                 // beta[a] . omega, k ascending (the oracle's association); loads are issued eight
                 // k at a time — a plain loop leaves one HBM round trip per k on the critical path
@@ -641,7 +641,7 @@ __global__ void __launch_bounds__(kAdvBlock) k_advance(DevSim d, uint32_t t, con
                     uint32_t a;
                     if constexpr (EG) a = model_act_overlay(d, slot, user, t + 1, lr_a, &ps);
                     else if (d.policy != RG_POLICY_LOGREG_FROZEN) a = policy_act_eg<EG>(d, slot, user, t + 1, &ps);
-                    else if (!d.lr_sample) a = lr_a;
+                    else if (!d.lr_sample) { a = lr_a; if (lr_logs_ps(d)) ps = d.lr_ps[uidx]; }
                     else if (is_org) { a = lr_a; ps = d.lr_ps[uidx]; }                       // k_logreg_sample drew it for event t + 1
                     else { a = d.lr_action2[uidx]; ps = d.lr_ps2[uidx]; }
                     rg_event e;
@@ -751,7 +751,7 @@ __device__ __forceinline__ bool run_bandit_event(const DevSim& d, uint32_t slot,
     uint32_t a = 0;
     if (RG_ADV_ABL(25)) {}
     else if constexpr (EG) a = model_act_overlay(d, slot, user, te, lr_a, &ps);     // (every event of the run flips its own coin)
-    else if (d.policy == RG_POLICY_LOGREG_FROZEN) a = lr_a;
+    else if (d.policy == RG_POLICY_LOGREG_FROZEN) { a = lr_a; if (lr_logs_ps(d)) ps = d.lr_ps[d.uid[slot]]; }
     else a = policy_act_eg<EG>(d, slot, user, te, &ps);
     double ctr = 0.0;
     bool click = false;
@@ -926,7 +926,8 @@ k_advance_run(DevSim d, uint32_t t, uint32_t hops) {
                 double ps = 1.0;
                 uint32_t a;
                 if constexpr (EG) a = model_act_overlay(d, slot, user, t_last + 1, lr_a, &ps);
-                else a = d.policy == RG_POLICY_LOGREG_FROZEN ? lr_a : policy_act_eg<EG>(d, slot, user, t_last + 1, &ps);
+                else if (d.policy == RG_POLICY_LOGREG_FROZEN) { a = lr_a; if (lr_logs_ps(d)) ps = d.lr_ps[uidx]; }
+                else a = policy_act_eg<EG>(d, slot, user, t_last + 1, &ps);
                 rg_event e;
                 e.u = user; e.t = t_last + 1; e.code = RG_EV_BANDIT | RG_EV_PHANTOM | a;
                 e.ps = static_cast<float>(ps);

@@ -53,7 +53,7 @@
 // kernels), rg_exact.hip (float64 resolve), rg_draw_fp32.hip (fp32 / lean 16-bit sweeps), rg_draw_pipelined.hip (the pipelined sweep
 // + per-user cache kernels), rg_draw_wide.hip (wide-K sweep), rg_advance.hip (advance / tail / frozen LogReg), rg_walk.hip (the
 // user-major walk), rg_draw_exacthi.hip and rg_draw_lds.hip (the error-free and the tile-prefix sweeps), rg_ope.hip,
-// rg_ope_logreg.hip, rg_ope_eg.hip and rg_ope_poly.hip (off-policy replays), rg_count.hip (count agents' training), rg_evolve.hip (the exploration study), rg_logreg_poly.hip (the likelihood agent's act), rg_weight_history.hip (its act on a time-weighted history), rg_bayes_vb.hip (BayesianAgentVB's act) — compiled in parallel and
+// rg_ope_logreg.hip, rg_ope_eg.hip and rg_ope_poly.hip (off-policy replays), rg_count.hip (count agents' training), rg_evolve.hip (the exploration study), rg_logreg_poly.hip (the likelihood agent's act), rg_weight_history.hip (its act on a time-weighted history), rg_bayes_vb.hip (BayesianAgentVB's act), rg_nn_ips.hip (NnIpsAgent's act) — compiled in parallel and
 // linked by __graft_entry__.build(); recogym_hip.hip includes all of them (a one-unit build).  This header holds what they
 // share: types, the workspace layout, device helpers (namespace rgk, identical in every unit); a unit hands its kernels to the
 // host code through the *_kernel_for functions declared here.  rg_ope_common.hpp adds what the four replay units share.
@@ -76,12 +76,19 @@ constexpr uint32_t kPolyListCap = 4096;        // unresolved acts of a run the d
 constexpr uint32_t kPolySteps = 1024;          // expit steps the table holds at most (8 KB of LDS)
 constexpr uint32_t kPolyHist = 256;            // history entries a wave of the likelihood agent's act keeps in LDS (the default history row); beyond: read from the source
 // the policies that act on the view history through the lr_* act list (k_logreg_select)
-inline bool lr_family(uint32_t policy) { return policy == RG_POLICY_LOGREG_FROZEN || policy == RG_POLICY_LOGREG_POLY || policy == RG_POLICY_BAYES_VB; }
+inline bool lr_family(uint32_t policy) { return policy == RG_POLICY_LOGREG_FROZEN || policy == RG_POLICY_LOGREG_POLY || policy == RG_POLICY_BAYES_VB || policy == RG_POLICY_NN_IPS; }
 // the policies whose unresolved acts go to pl_list (rg_sim_read_poly_unresolved)
-inline bool lists_unresolved(uint32_t policy) { return policy == RG_POLICY_LOGREG_POLY || policy == RG_POLICY_BAYES_VB; }
+inline bool lists_unresolved(uint32_t policy) { return policy == RG_POLICY_LOGREG_POLY || policy == RG_POLICY_BAYES_VB || policy == RG_POLICY_NN_IPS; }
 // the transposed model of RG_POLICY_BAYES_VB, P x P x S doubles, at most: what one raw buffer resource of the library spans (2 GiB,
 // raw_buffer_rsrc), which also keeps every element offset of the act below 2^28
 constexpr uint64_t kBayesModelBytes = 1ull << 31;
+// RG_POLICY_NN_IPS: hidden units at most (two layer vectors per wave in LDS: 16 KB a wave at the cap), products at most (the margin's
+// gamma terms use (k + 1) 2^-24 >= gamma_k, which holds up to k = 4095: DESIGN.md 4i), and the LDS a block spends on layer vectors
+// plus staged weights before the weights stay in global memory
+constexpr uint32_t kNnHidden = 1024;
+constexpr uint32_t kNnProducts = 4000;
+constexpr size_t kNnStageBytes = 48 * 1024;
+constexpr size_t kNnStaticLds = 16 * 1024;    // an upper bound of the static LDS of k_nn_acts / k_debug_nn_acts (kPolyHist rows of a block: 12.3 KB)
 constexpr uint64_t kRepackMinUsers = 1ull << 18;   // runs smaller than this keep slot == user index throughout (RECOGYM_REPACK_MIN overrides: tests)
 
 inline thread_local char g_err[512] = "";
@@ -327,6 +334,15 @@ struct DevSim {
     // go to pl_list too.  Its model travels in two of the slots above, which that policy leaves unused — pl_wk_t = lam_t [viewed
     // product][action][sample], caller-owned, pl_nth = the number of samples — so this record, a by-value argument of every kernel,
     // keeps its size and every other kernel its code.
+    // RG_POLICY_NN_IPS (rg_sim_set_nn_ips; rg_nn_ips.hip): lr_poly = 3 selects k_nn_acts, whose model is a kernel argument of its own
+    // (NnModel below), and makes the advance kernels log lr_ps instead of 1 (lr_logs_ps).
+};
+
+// the net of RG_POLICY_NN_IPS as k_nn_acts takes it (rg_sim_set_nn_ips has the layout); A2, A3: the absolute row sums the margin uses
+struct NnModel {
+    const double* w1t; const double* b1; const double* w2t; const double* b2; const double* w3t; const double* b3;
+    double A2, A3;
+    uint32_t H, staged;       // staged: the three matrices fit the block's LDS behind the layer vectors
 };
 
 }  // namespace rgk
@@ -394,7 +410,7 @@ struct RunOpts {
     X(draw_f64) X(draw_fp32) X(draw16_fused) X(draw16_sliced) X(search) X(draw_tp) X(pick) X(draw_cached) \
     X(sweep_xh) X(exact_m) X(exact_tile) X(exact_h) X(walk) X(walk2) X(walk_solo) X(park_compact) \
     X(advance) X(advance_run) X(tail) X(repack) X(env0) X(logreg_screen) X(logreg_acts) X(logreg_sample) X(logreg_poly) \
-    X(logreg_poly_w) X(sort_tiled) X(sort_plain) X(bayes_vb)
+    X(logreg_poly_w) X(sort_tiled) X(sort_plain) X(bayes_vb) X(nn_ips)
 struct Ledger {
 #define RG_LEDGER_FIELD(f) uint64_t f = 0;
     RG_LEDGER_FAMILIES(RG_LEDGER_FIELD)
@@ -427,6 +443,8 @@ struct rg_sim {
     rg_config cfg;
     Ledger led;
     DevSim d;
+    rgk::NnModel nn;          // RG_POLICY_NN_IPS: the model (w1t == nullptr: not set) and the dynamic LDS of k_nn_acts
+    size_t nn_smem;
     WhRun wh;                 // wt.tab != nullptr: the likelihood agent acts on time-weighted features (no kernel but rg_weight_history.hip's reads it)
     RunOpts opt;
     void* workspace;
@@ -527,6 +545,8 @@ search_kernel_t poly_acts_kernel();                        // rg_logreg_poly.hip
 void (*poly_debug_kernel())(DevSim, int32_t*, uint8_t*);
 search_kernel_t bayes_acts_kernel();                       // rg_bayes_vb.hip
 void (*bayes_debug_kernel())(DevSim, int32_t*, uint8_t*, double*);
+void (*nn_acts_kernel())(DevSim, NnModel, uint32_t);      // rg_nn_ips.hip
+void (*nn_debug_kernel())(DevSim, NnModel, int32_t*, uint8_t*, double*, double*);
 void (*wh_insert_kernel())(DevSim, WhRun, uint32_t);      // rg_weight_history.hip
 void (*wh_acts_kernel())(DevSim, WhRun, uint32_t, uint32_t);
 void (*wh_debug_set_kernel())(DevSim, WhRun, const uint32_t*, const uint32_t*, const uint16_t*, uint32_t);
@@ -757,7 +777,7 @@ inline size_t carve_all(const rg_config& c, uint64_t n, const Geom& g, void* bas
     uint32_t* lr_list = w.take<uint32_t>(lr ? n : 1);
     uint32_t* lr_cnt = w.take<uint32_t>(lr ? kMaxSteps + 2 : 1);
     const bool lrs = lr && c.lr_select_randomly;
-    double* lr_ps = w.take<double>(lrs ? n : 1);
+    double* lr_ps = w.take<double>(lrs || c.policy == RG_POLICY_NN_IPS ? n : 1);       // (RG_POLICY_NN_IPS logs a model output)
     uint32_t* lr_action2 = w.take<uint32_t>(lrs ? n : 1);
     double* lr_ps2 = w.take<double>(lrs ? n : 1);
     // the screen's scratch: a row per act of a STEP, not per user — a step lists the users whose history changed and who act now
@@ -828,7 +848,7 @@ inline int validate(const rg_config* c, uint64_t n) {
     if (sizeof(double) * (static_cast<size_t>(c->K) * 64 + 64 + 16 * c->K) > 64 * 1024)
         return fail(RG_EINVAL, "K %u exceeds the float64 draw kernel's LDS budget", c->K);
     if (n == 0 || n >= (1ull << 31)) return fail(RG_EINVAL, "n_users %llu out of range", (unsigned long long)n);
-    if (c->policy > RG_POLICY_BAYES_VB || c->policy == 7u /* not assigned: recogym_hip.h */) return fail(RG_EINVAL, "unknown policy %u", c->policy);
+    if (c->policy > RG_POLICY_NN_IPS || c->policy == 7u || c->policy == 9u /* not assigned: recogym_hip.h */) return fail(RG_EINVAL, "unknown policy %u", c->policy);
     if (c->time_mode > 1) return fail(RG_EINVAL, "unknown time_mode %u", c->time_mode);
     if (c->env_kind > 1) return fail(RG_EINVAL, "unknown env_kind %u", c->env_kind);
     if (c->lr_select_randomly && (c->policy != RG_POLICY_LOGREG_FROZEN || c->num_products > 1024))
@@ -1017,6 +1037,8 @@ __device__ __forceinline__ void bf16_split3(float x, unsigned short* sp) {
 
 
 
+// the cached act of the lr_* list carries its own propensity in lr_ps (RG_POLICY_NN_IPS: ps = prob[a], a model output)
+__device__ __forceinline__ bool lr_logs_ps(const DevSim& d) { return d.lr_poly == 3u; }
 typedef unsigned long long hent_t;
 __device__ __forceinline__ hent_t* hist_row(const DevSim& d, uint32_t slot) { return d.hist + static_cast<size_t>(slot) * d.hist_cap; }
 __device__ __forceinline__ uint32_t h_prod(hent_t e) { return static_cast<uint32_t>(e >> 32); }

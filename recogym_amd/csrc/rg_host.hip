@@ -865,7 +865,10 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         if (int rc = prof_mark(sim, st, kProfLogreg)) return rc;
         // acts of the users whose view history changed since their last one (frozen LogReg at scale)
         hipLaunchKernelGGL(logreg_select_kernel(), dim3(grid_for(upper)), dim3(kBlock), 0, st, d, t);
-        if (d.lr_poly == 2u) {     // BayesianAgentVB: a wave per act, lanes over the posterior samples (rg_bayes_vb.hip)
+        if (d.lr_poly == 3u) {     // NnIpsAgent: a wave per act, lanes over the hidden units, then the products (rg_nn_ips.hip)
+            hipLaunchKernelGGL(nn_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), sim->nn_smem, st, d, sim->nn, t);
+            sim->led.nn_ips += 1;
+        } else if (d.lr_poly == 2u) {     // BayesianAgentVB: a wave per act, lanes over the posterior samples (rg_bayes_vb.hip)
             hipLaunchKernelGGL(bayes_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), 0, st, d, t);
             sim->led.bayes_vb += 1;
         } else if (d.lr_poly) {    // the likelihood agent: a wave per act, float64 throughout (rg_logreg_poly.hip)
@@ -1169,7 +1172,7 @@ void plan_config(rg_sim* s, const rg_config* cfg, uint64_t n_users, const Switch
     d.sigma0 = cfg->sigma_omega_initial; d.sigma_omega = cfg->sigma_omega; d.change_omega_for_bandits = cfg->change_omega_for_bandits;
     // the likelihood agent runs wherever the frozen LogReg policy does, through the same act list: one policy for the kernels
     d.policy = lists_unresolved(cfg->policy) ? RG_POLICY_LOGREG_FROZEN : cfg->policy;
-    d.lr_poly = cfg->policy == RG_POLICY_LOGREG_POLY ? 1u : cfg->policy == RG_POLICY_BAYES_VB ? 2u : 0u;   // (2: k_bayes_acts)
+    d.lr_poly = cfg->policy == RG_POLICY_LOGREG_POLY ? 1u : cfg->policy == RG_POLICY_BAYES_VB ? 2u : cfg->policy == RG_POLICY_NN_IPS ? 3u : 0u;   // (2: k_bayes_acts, 3: k_nn_acts)
     d.ouc_select_randomly = cfg->ouc_select_randomly; d.ouc_exploit_explore = cfg->ouc_exploit_explore;
     d.ouc_reverse_pop = cfg->ouc_reverse_pop; d.ouc_epsilon = cfg->ouc_epsilon;
     d.time_mode = cfg->time_mode; d.time_mu = cfg->time_mu; d.time_sigma = cfg->time_sigma; d.env_kind = cfg->env_kind;
@@ -1610,6 +1613,7 @@ int rg_sim_set_epsilon_greedy_model(rg_sim* sim, double epsilon, uint64_t eg_see
     if (sim->d.policy != RG_POLICY_LOGREG_FROZEN)
         return fail(RG_EINVAL, "rg_sim_set_epsilon_greedy_model wraps the frozen LogReg argmax or the likelihood agent (policy %u)", sim->cfg.policy);
     if (sim->cfg.policy == RG_POLICY_BAYES_VB) return fail(RG_EINVAL, "EpsilonGreedy round RG_POLICY_BAYES_VB: host path");
+    if (sim->cfg.policy == RG_POLICY_NN_IPS) return fail(RG_EINVAL, "EpsilonGreedy round RG_POLICY_NN_IPS: host path");
     if (sim->d.lr_sample)
         return fail(RG_EINVAL, "rg_sim_set_epsilon_greedy_model: a LogReg with lr_select_randomly samples its act (propensity != 1): host path");
     if (sim->wh.wt.tab) return fail(RG_EINVAL, "EpsilonGreedy round a time-weighted likelihood agent: host path");
@@ -1696,6 +1700,53 @@ int rg_sim_set_bayes_vb(rg_sim* sim, const double* d_lam_t, uint32_t num_samples
     return RG_OK;
 }
 
+// max over the columns c < cols of (sum over the rows r < rows, ascending, of |wt[r cols + c]|) + |b[c]|: float64, one add per term
+// (agents/nn_ips.py: nn_abs_row_sums computes the same bits); -1 when a value is not finite
+static double nn_abs_row_sums(const std::vector<double>& wt, const std::vector<double>& b, size_t rows, size_t cols) {
+    double best = 0.0;
+    for (size_t c = 0; c < cols; ++c) {
+        double r = 0.0;
+        for (size_t k = 0; k < rows; ++k) r = r + std::fabs(wt[k * cols + c]);
+        r = r + std::fabs(b[c]);
+        if (!std::isfinite(r)) return -1.0;
+        best = r > best ? r : best;
+    }
+    return best;
+}
+
+int rg_sim_set_nn_ips(rg_sim* sim, const double* d_w1t, const double* d_b1, const double* d_w2t, const double* d_b2,
+                      const double* d_w3t, const double* d_b3, uint32_t num_hidden) {
+    if (!sim) return fail(RG_EINVAL, "sim is NULL");
+    if (sim->cfg.policy != RG_POLICY_NN_IPS) return fail(RG_ESTATE, "policy is not RG_POLICY_NN_IPS");
+    if (sim->users_reset) return fail(RG_ESTATE, "rg_sim_set_nn_ips must be called before rg_sim_reset_users");
+    if (!d_w1t || !d_b1 || !d_w2t || !d_b2 || !d_w3t || !d_b3) return fail(RG_EINVAL, "a model array is NULL");
+    if (num_hidden == 0 || num_hidden > kNnHidden) return fail(RG_EINVAL, "num_hidden %u outside [1, %u]", num_hidden, kNnHidden);
+    const size_t P = sim->d.P, H = num_hidden;
+    if (P > kNnProducts) return fail(RG_EINVAL, "RG_POLICY_NN_IPS serves at most %u products (%u)", kNnProducts, sim->d.P);
+    // the absolute row sums of the margin, once (the call synchronises); layer 1's values only have to be finite
+    std::vector<double> w1(P * H), b1(H), w2(H * H), b2(H), w3(H * P), b3(P);
+    HIP_TRY(hipMemcpy(w1.data(), d_w1t, sizeof(double) * P * H, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b1.data(), d_b1, sizeof(double) * H, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(w2.data(), d_w2t, sizeof(double) * H * H, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b2.data(), d_b2, sizeof(double) * H, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(w3.data(), d_w3t, sizeof(double) * H * P, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b3.data(), d_b3, sizeof(double) * P, hipMemcpyDeviceToHost));
+    const double A1 = nn_abs_row_sums(w1, b1, P, H), A2 = nn_abs_row_sums(w2, b2, H, H), A3 = nn_abs_row_sums(w3, b3, H, P);
+    if (A1 < 0.0 || A2 < 0.0 || A3 < 0.0) return fail(RG_EINVAL, "the model holds a value that is not finite");
+    NnModel& m = sim->nn;
+    m.w1t = d_w1t; m.b1 = d_b1; m.w2t = d_w2t; m.b2 = d_b2; m.w3t = d_w3t; m.b3 = d_b3;
+    m.A2 = A2; m.A3 = A3; m.H = num_hidden;
+    const size_t rows = sizeof(double) * 2 * (kBlock / 64) * H, mats = sizeof(double) * (2 * P * H + H * H);
+    m.staged = rows + mats <= kNnStageBytes ? 1u : 0u;
+    sim->nn_smem = rows + (m.staged ? mats : 0);
+    // the kernels hold 12.3 KB of static LDS besides (history rows, counters): from 64 KiB of the TOTAL on, the opt-in is needed
+    if (sim->nn_smem + kNnStaticLds > 64 * 1024) {
+        set_max_lds(nn_acts_kernel(), sim->nn_smem);
+        set_max_lds(nn_debug_kernel(), sim->nn_smem);
+    }
+    return RG_OK;
+}
+
 int rg_sim_set_weight_history(rg_sim* sim, const double* d_table, uint32_t n, uint32_t accumulate_f32) {
     if (!sim) return fail(RG_EINVAL, "sim is NULL");
     if (sim->cfg.policy != RG_POLICY_LOGREG_POLY) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY");
@@ -1726,7 +1777,7 @@ int rg_sim_set_weight_history(rg_sim* sim, const double* d_table, uint32_t n, ui
 
 int rg_sim_read_poly_unresolved(rg_sim* sim, uint32_t* out, uint32_t capacity, uint32_t* n_out, uint32_t* overflow, void* stream) {
     if (!sim || !n_out || !overflow || (capacity && !out)) return fail(RG_EINVAL, "NULL argument");
-    if (!lists_unresolved(sim->cfg.policy)) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY or RG_POLICY_BAYES_VB");
+    if (!lists_unresolved(sim->cfg.policy)) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY, RG_POLICY_BAYES_VB or RG_POLICY_NN_IPS");
     if (!sim->users_reset) return fail(RG_ESTATE, "no reset range");
     hipStream_t st = static_cast<hipStream_t>(stream);
     unsigned long long listed = 0;
@@ -1777,6 +1828,8 @@ int rg_sim_reset_users(rg_sim* sim, uint64_t first_user_id, uint64_t n, uint64_t
         return fail(RG_ESTATE, "rg_sim_set_logreg_poly must be called first");
     if (sim->cfg.policy == RG_POLICY_BAYES_VB && !sim->d.pl_wk_t)
         return fail(RG_ESTATE, "rg_sim_set_bayes_vb must be called first");
+    if (sim->cfg.policy == RG_POLICY_NN_IPS && !sim->nn.w1t)
+        return fail(RG_ESTATE, "rg_sim_set_nn_ips must be called first");
     if (n == 0 || n > sim->d.n_cap) return fail(RG_EINVAL, "n %llu exceeds the %u users the workspace was sized for",
                                                  (unsigned long long)n, sim->d.n_cap);
     if (first_user_id + n > (1ull << 32)) return fail(RG_EINVAL, "user ids must fit 32 bits");
@@ -2072,6 +2125,18 @@ int rg_sim_debug_bayes_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, do
     hipLaunchKernelGGL(bayes_debug_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        sim->d, d_action, d_flags, d_q);
     sim->led.bayes_vb += 1;
+    HIP_TRY(hipGetLastError());
+    return RG_OK;
+}
+
+int rg_sim_debug_nn_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, double* d_z, double* d_ps, void* stream) {
+    if (!sim || !d_action || !d_flags || !d_z || !d_ps) return fail(RG_EINVAL, "NULL argument");
+    if (sim->cfg.policy != RG_POLICY_NN_IPS) return fail(RG_ESTATE, "policy is not RG_POLICY_NN_IPS");
+    if (!sim->nn.w1t) return fail(RG_ESTATE, "rg_sim_set_nn_ips must be called first");
+    if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
+    hipLaunchKernelGGL(nn_debug_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), sim->nn_smem, static_cast<hipStream_t>(stream),
+                       sim->d, sim->nn, d_action, d_flags, d_z, d_ps);
+    sim->led.nn_ips += 1;
     HIP_TRY(hipGetLastError());
     return RG_OK;
 }

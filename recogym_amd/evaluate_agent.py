@@ -856,7 +856,7 @@ def _device_route(env, agent):
     pol = device_policy_of(agent)
     # the likelihood agent's device acts need the host's confirmation of the unresolved ones, which generate_logs
     # gives and this study's device loop does not: host route
-    return pol is not None and pol.get('policy') not in (_abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_BAYES_VB)
+    return pol is not None and pol.get('policy') not in (_abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_BAYES_VB, _abi.RG_POLICY_NN_IPS)
 
 
 def _new_rewards(num_products):

@@ -130,6 +130,23 @@ def bayes_host_act(views, num_products, Lambda):
     return reference_act(X, Lambda)[0]
 
 
+def nn_device_model(nn_ips, device):
+    """A policy dict's `nn_ips` entry (state: the six float32 arrays of NnIpsAgent's net) -> (the frozen host agent's net, NnModel on
+    the host, the six float64 tensors on `device` in rg_sim_set_nn_ips's order: the matrices transposed)."""
+    from .agents.nn_ips import NnIpsFrozenAgent, NnModel
+    from .envs.configuration import Configuration
+    m = NnModel(nn_ips['state'])
+    host = NnIpsFrozenAgent(Configuration({'num_products': m.P}), nn_ips['state'])
+    return host, m, [torch.from_numpy(x).to(device) for x in m.arrays()]
+
+
+def nn_host_act(views, num_products, agent):
+    """The host act of NnIpsAgent on the organic views `views` (product ids, any order): torch's fp32 forward on the dense float32
+    counts, first maximum — what the device's unresolved acts are judged by."""
+    x = np.bincount(np.asarray(views, dtype=np.int64), minlength=int(num_products))
+    return agent.act_on(np.flatnonzero(x), x[np.flatnonzero(x)])[0]
+
+
 def poly_host_act(views, model):
     """The host act of the likelihood agent on the organic views `views` (product ids, any order) under model = (wf, wa, wk, b):
     the decisions in the contract's order, scipy's expit, first maximum — what the device's unresolved acts are judged by."""
@@ -199,6 +216,9 @@ class Simulator:
                  An optional entry `weight_history = dict(table=, f32=)` (agents/views_history.weight_table) makes the act's
                  features the time-weighted ones: a fresh act per bandit event at the event's clock value; such a
                  run is lock-step and needs a log.  debug_set_timed_history / debug_weighted_acts reach the device function.
+    nn_ips       dict(state = dict(w1, b1, w2, b2, w3, b3)): NnIpsAgent's net (RG_POLICY_NN_IPS; agents/nn_ips.py), widened to float64,
+                 transposed and uploaded here; ps is the model's output, kept in float64.  Its unresolved acts share the likelihood
+                 agent's list, counter (`poly_unresolved`) and `poly_verify`, which judges them by torch's fp32 forward.
     bayes_vb     dict(lam (S, P^2)): BayesianAgentVB's posterior draws (RG_POLICY_BAYES_VB; agents/bayesian_poly_vb.py), transposed
                  and uploaded here.  Its unresolved acts share the likelihood agent's list, counter (`poly_unresolved`) and
                  `poly_verify`, which judges them by the reference's own expression.
@@ -207,7 +227,7 @@ class Simulator:
     def __init__(self, config, n_users, policy=_abi.RG_POLICY_UNIFORM_ENV, policy_seed=None,
                  ouc=None, epoch=0, log_capacity=None, device=None, tables=None, policy_table=None,
                  policy_ps=None, logreg=None, ps_float64=None, p_click=False, env0=None, policy_ps64=False,
-                 epsilon_greedy=None, logreg_poly=None, bayes_vb=None):
+                 epsilon_greedy=None, logreg_poly=None, bayes_vb=None, nn_ips=None):
         if policy == _abi.RG_POLICY_LOGREG_FROZEN and ((logreg or {}).get('int8') or os.environ.get('RECOGYM_LOGREG') == 'int8'):
             # (refused, not ignored: a caller that labels the act's bytes from this switch would report 1 B per weight for an fp16 run)
             raise ValueError("the 8-bit LogReg screen is retired (measured slower than the fp16 screen): drop logreg['int8'] / RECOGYM_LOGREG=int8")
@@ -226,7 +246,8 @@ class Simulator:
         # the loggers whose propensity is the constant 1 / P (its exact float64 value is filled in at decode time)
         self.uniform_ps = policy in (_abi.RG_POLICY_UNIFORM_ENV, _abi.RG_POLICY_RANDOM_AGENT) and epsilon_greedy is None
         self.ps_float64 = ((policy in (_abi.RG_POLICY_ORGANIC_USER_COUNT, _abi.RG_POLICY_LAST_VIEW_TABLE)
-                            or bool(logreg and logreg.get('select_randomly')) or epsilon_greedy is not None)
+                            or bool(logreg and logreg.get('select_randomly')) or epsilon_greedy is not None
+                            or policy == _abi.RG_POLICY_NN_IPS)
                            if ps_float64 is None else bool(ps_float64))
         self.keep_p_click = bool(p_click)
         host_tables = () if env0 is not None else (tables if tables is not None else draw_tables(config))
@@ -326,6 +347,11 @@ class Simulator:
                 self.bayes_vb_host, self.bayes_vb = bayes_device_model(bayes_vb, int(config.num_products), self.device)
                 _abi.check(self.lib.rg_sim_set_bayes_vb(self._h, self.bayes_vb.data_ptr(), int(self.bayes_vb.shape[2])),
                            'rg_sim_set_bayes_vb')
+            self.nn_ips_host = None
+            if policy == _abi.RG_POLICY_NN_IPS:
+                self.nn_ips_host, self.nn_ips_model, self.nn_ips = nn_device_model(nn_ips, self.device)
+                _abi.check(self.lib.rg_sim_set_nn_ips(self._h, *[x.data_ptr() for x in self.nn_ips], int(self.nn_ips_model.H)),
+                           'rg_sim_set_nn_ips')
             self.poly_unresolved = self.poly_refuted = None
             self.poly_overflow = False
             if log_capacity is None:
@@ -475,6 +501,20 @@ class Simulator:
             torch.cuda.synchronize(self.device)
         return act.cpu().numpy().astype(np.int64), fl.cpu().numpy().astype(np.int64), q.cpu().numpy()
 
+    def debug_nn_acts(self):
+        """rg_sim_debug_nn_acts -> (actions, flags, z (n, P), ps (n,)): NnIpsAgent's act of every user index on its current history,
+        the device's logits and propensity."""
+        n, P = self.n_active, int(self.config.num_products)
+        with torch.cuda.device(self.device):
+            act = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+            fl = torch.full((n,), 255, dtype=torch.uint8, device=self.device)
+            z = torch.full((n, P), float('nan'), dtype=torch.float64, device=self.device)
+            ps = torch.full((n,), float('nan'), dtype=torch.float64, device=self.device)
+            _abi.check(self.lib.rg_sim_debug_nn_acts(self._h, act.data_ptr(), fl.data_ptr(), z.data_ptr(), ps.data_ptr(), self._stream()),
+                       'rg_sim_debug_nn_acts')
+            torch.cuda.synchronize(self.device)
+        return act.cpu().numpy().astype(np.int64), fl.cpu().numpy().astype(np.int64), z.cpu().numpy(), ps.cpu().numpy()
+
     def debug_set_timed_history(self, n_views, products, times16):
         """rg_sim_debug_set_timed_history: per user index of the reset range, n_views[i] views (products[i, j] at clock value
         times16[i, j], in view order) as its time-weighted history."""
@@ -544,6 +584,8 @@ class Simulator:
                     mine = u == user
                     host = weighted_host_act(v[mine & organic & (t < t_act)], clock[mine & organic & (t < t_act)],
                                              clock[mine & (t == t_act)], self.weight_history, self.logreg_poly_host)
+                elif self.nn_ips_host is not None:
+                    host = nn_host_act(v[organic & (u == user) & (t <= t_act)], self.config.num_products, self.nn_ips_host)
                 elif self.bayes_vb_host is not None:
                     host = bayes_host_act(v[organic & (u == user) & (t <= t_act)], self.config.num_products, self.bayes_vb_host)
                 else:

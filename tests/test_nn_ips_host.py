@@ -1,0 +1,293 @@
+"""NnIpsAgent on the host: the device rule restated in numpy (nn_rule on nn_forward) and the host act against the unmodified
+reference's own logs (tests/golden/nn_ips_*.npz, tests/make_golden_nn_ips.py), the port's build() against the reference's own,
+the margin's ingredients, the host routes and where the agent has a device form.  No device."""
+import math
+import sys
+
+import numpy as np
+import pytest
+
+import golden_util as gu
+import nn_ips_util as nu
+import ref_harness as rh
+from make_golden_ope import log_frame
+from recogym_amd import _abi
+from recogym_amd import agents
+from recogym_amd.agents.nn_ips import (HIDDEN_CAP, UNRESOLVED, NnIpsAgent, NnIpsFrozenAgent, NnModel, nn_abs_row_sums, nn_exp, nn_forward,
+                                       nn_ips_args, nn_logit_bound, nn_margin, nn_ps_bound, nn_rule)
+from recogym_amd.envs.configuration import Configuration
+from recogym_amd.envs.context import DefaultContext
+from recogym_amd.envs.observation import Observation
+from recogym_amd.envs.session import OrganicSessions
+
+
+def random_state(P, H, seed, scale=0.5):
+    rng = np.random.RandomState(seed)
+    shapes = dict(w1=(H, P), b1=(H,), w2=(H, H), b2=(H,), w3=(P, H), b3=(P,))
+    return {k: (rng.standard_normal(s) * scale).astype(np.float32) for k, s in shapes.items()}
+
+
+def training_log():
+    cols = gu.load('nn_ips_p10')[1]
+    return {k[len('trainlog_'):]: v for k, v in cols.items() if k.startswith('trainlog_')}
+
+
+def test_agent_is_exported_with_the_reference_arguments():
+    assert agents.NnIpsAgent is NnIpsAgent and agents.nn_ips_args is nn_ips_args and agents.NnIpsFrozenAgent is NnIpsFrozenAgent
+    want = dict(num_products=10, number_of_flips=1, select_randomly=False, M=111, learning_rate=0.01, num_epochs=100, num_hidden=20,
+                lambda_val=0.01, with_ps_all=False)
+    assert {k: v for k, v in nn_ips_args.items() if k != 'random_seed'} == want and 'random_seed' in nn_ips_args
+    assert _abi.RG_POLICY_NN_IPS == 10 and _abi.RG_ABI_VERSION == 14 and UNRESOLVED == 2
+
+
+def test_the_policy_is_accepted_with_a_propensity_row():
+    """rg_sim_create is host code: the policy sizes a workspace with a history row, the unresolved list and lr_ps (a double per
+    user more than the Bayes agent's workspace, give or take the alignment); the numbers around it stay refused."""
+    import ctypes as C
+    import __graft_entry__ as graft
+    import make_golden_create_plan as plan
+    graft.build()
+    lib = _abi.load()
+    n = 100000
+    need = lib.rg_sim_workspace_bytes(C.byref(plan.rg_config(plan._c(policy=_abi.RG_POLICY_NN_IPS))), n)
+    bayes = lib.rg_sim_workspace_bytes(C.byref(plan.rg_config(plan._c(policy=_abi.RG_POLICY_BAYES_VB))), n)
+    assert 8 * n - 4096 <= need - bayes <= 8 * n + 4096
+    for refused in (7, 9, 11):
+        assert lib.rg_sim_workspace_bytes(C.byref(plan.rg_config(plan._c(policy=refused))), n) == 0
+
+
+def test_nn_exp_is_an_exponential():
+    x = np.r_[np.linspace(-720.0, 720.0, 20001), 0.0, -0.0, 1e-300, -1e-300]
+    want = np.exp(np.clip(x, -700.0, 700.0))
+    assert np.abs(nn_exp(x) / want - 1.0).max() <= 4 * 2.0 ** -53
+    assert nn_exp(np.array([0.0]))[0] == 1.0
+
+
+@pytest.mark.parametrize('name', nu.FIXTURES)
+def test_rule_reproduces_the_reference_actions_and_ps(name):
+    """nn_rule on each fixture's histories: the fixture's action wherever it reports "resolved", the restated ps within nn_ps_bound of
+    the fixture's (both asserted per row by check_log_against_rule), the census the generator recorded, and the resolved share."""
+    meta, cols = gu.load(name)
+    P = meta['env_args']['num_products']
+    acts, unresolved, distinct = nu.check_log_against_rule(cols, P, nu.fixture_state(meta, cols), name)
+    assert dict(acts=len(acts), unresolved=unresolved, distinct_actions=distinct) == meta['census']
+    assert len(acts) > 200 and 10 * unresolved <= len(acts)
+    if name.endswith('_loaded'):
+        assert 2 * distinct >= P
+
+
+@pytest.mark.parametrize('name', ['nn_ips_p10', 'nn_ips_p40_loaded'])
+def test_host_act_reproduces_the_reference_rows(name):
+    """The frozen agent driven like generate_logs drives it: the reference's action on every row of an act the rule resolves (the
+    only ones another BLAS build cannot flip) and its ps within twice nn_ps_bound (two fp32 forwards, each within the bound of the
+    float64 value)."""
+    meta, cols = gu.load(name)
+    P = meta['env_args']['num_products']
+    ag = NnIpsFrozenAgent(Configuration({'num_products': P, 'with_ps_all': True}), nu.fixture_state(meta, cols))
+    u, z, v, a, t = cols['u'], cols['z'], cols['v'], cols['a'], cols['t']
+    keep = u < 40
+    by_row = {i: act for act in nu.rule_over_log(cols, P, nu.fixture_state(meta, cols)) for i in act['rows']}
+    cur, session, n_acts = None, None, 0
+    for i in np.flatnonzero(keep):
+        if u[i] != cur:
+            cur, session = u[i], OrganicSessions()
+            ag.reset()
+        if z[i] == 0:
+            session.next(DefaultContext(int(t[i]), int(u[i])), int(v[i]))
+        else:
+            act = ag.act(Observation(DefaultContext(int(t[i]), int(u[i])), session), 0, False)
+            if by_row[i]['flags'] & UNRESOLVED:
+                session = OrganicSessions()
+                continue
+            assert act['a'] == a[i], (name, i, act['a'], int(a[i]))
+            assert abs(act['ps'] / cols['ps'][i] - 1.0) <= 2.0 * by_row[i]['bound'], (name, i, act['ps'], cols['ps'][i])
+            assert act['ps-a'].sum() == 1.0 and act['ps-a'][a[i]] == 1.0
+            session = OrganicSessions()
+            n_acts += 1
+    assert n_acts > 500
+
+
+_REF_ROOTS = ('gym', 'numba', 'recogym')
+
+
+@pytest.fixture
+def reference(monkeypatch):
+    """The reference package imported against tests/ref_shims, isolated from the rest of the session (as in test_ope_host.py): a
+    `gym` another test left in sys.modules must not shadow the shims, and the modules imported here are dropped again."""
+    if not rh.reference_available():
+        pytest.skip('reference package not present')
+    for k in [k for k in sys.modules if k.split('.')[0] in _REF_ROOTS]:
+        monkeypatch.delitem(sys.modules, k)
+    monkeypatch.syspath_prepend(rh.SHIMS)
+    try:
+        yield rh.import_reference()
+    finally:
+        for k in [k for k in sys.modules if k.split('.')[0] in _REF_ROOTS]:
+            sys.modules.pop(k, None)
+
+
+def reference_log_frame(train):
+    import pandas as pd
+    return pd.DataFrame(dict(t=train['t'], u=train['u'], z=np.where(train['z'] == 1, 'bandit', 'organic'), v=train['v'], a=train['a'],
+                             c=train['c'], ps=train['ps']))
+
+
+def port_state(train, **over):
+    import torch
+    from make_golden_nn_ips import AGENT_SEED
+    ag = NnIpsAgent(Configuration({**nn_ips_args, 'num_products': 10, 'random_seed': AGENT_SEED, **over}))
+    ag.train_from_log(log_frame(train))
+    assert ag.frozen is None                                  # the model is built at the first act
+    torch.manual_seed(AGENT_SEED)
+    return ag._ready().state()
+
+
+def test_build_equals_the_reference_build_bit_for_bit(reference):
+    """Both run live on the reference's training log under the same torch.manual_seed, at the reference's defaults.  With M = 111
+    the reference's Threshold replaces every ratio prob / ps of a uniform log (at most 10) by the constant M and the loss has no
+    gradient: this case pins the initialisation, the one below the training steps."""
+    from make_golden_nn_ips import reference_agent, state_of
+    train = training_log()
+    want = state_of(reference_agent(10, reference_log_frame(train)))
+    got = port_state(train)
+    for k in nu.KEYS:
+        assert np.array_equal(got[k].view(np.uint32), want[k].view(np.uint32)), k
+    stored = nu.fixture_state(*gu.load('nn_ips_p10'))
+    assert all(np.allclose(got[k], stored[k], rtol=1e-4, atol=1e-6) for k in nu.KEYS)      # (the fixture's net, on its machine's BLAS)
+    untrained = port_state(train, num_epochs=0)
+    assert all(np.array_equal(got[k], untrained[k]) for k in nu.KEYS)                      # the defaults do not train: see above
+
+
+@pytest.mark.parametrize('over', [dict(M=0.5, num_epochs=30), dict(M=0.5, num_epochs=12, learning_rate=0.5, lambda_val=0.3, num_hidden=7)])
+def test_training_steps_equal_the_reference_bit_for_bit(reference, over):
+    """M below the ratios prob / ps: the loss has a gradient, and the loss itself (the clipped ratio, the negated deltas broadcast
+    over the products, the variance term under lambda_val), the learning rate and the optimiser all show in the result.  The port
+    and the reference, both live on the same log under the same seed, end at the same bits, and those are not the initial net's."""
+    from make_golden_nn_ips import reference_agent, state_of
+    train = training_log()
+    want = state_of(reference_agent(10, reference_log_frame(train), **over))
+    got = port_state(train, **over)
+    untrained = port_state(train, **{**over, 'num_epochs': 0})
+    for k in nu.KEYS:
+        assert np.array_equal(got[k].view(np.uint32), want[k].view(np.uint32)), k
+    moved = [k for k in nu.KEYS if not np.array_equal(got[k], untrained[k])]
+    print(over, 'moved', moved)
+    # (at the default learning rate the first layer's steps stay below half an fp32 ulp of its weights; at 0.5 every array moves)
+    assert {'w3', 'b3'} <= set(moved) and (over.get('learning_rate', 0.01) < 0.5 or moved == list(nu.KEYS)), moved
+    fewer = port_state(train, **{**over, 'num_epochs': over['num_epochs'] - 1})
+    assert not np.array_equal(got['w3'], fewer['w3'])                                      # ... and the last step still moves it
+
+
+def test_train_from_log_equals_call_by_call_train():
+    """(M = 0.5: with the reference's default M = 111 its Threshold replaces every ratio prob / ps of this log by the constant M, the
+    loss has no gradient and the net stays at its initialisation, whatever the log.)"""
+    import torch
+    train = training_log()
+    keep = train['u'] < 20
+    train = {k: v[keep] for k, v in train.items()}
+    cfg = Configuration({**nn_ips_args, 'num_products': 10, 'random_seed': 7, 'num_epochs': 5, 'M': 0.5})
+    a = NnIpsAgent(cfg)
+    a.train_from_log(log_frame(train))
+    b = NnIpsAgent(cfg)
+    u, z, v, t = train['u'], train['z'], train['v'], train['t']
+    cur, session = None, None
+    for i in range(len(u)):
+        if u[i] != cur:
+            cur, session = u[i], OrganicSessions()
+        if z[i] == 0:
+            session.next(DefaultContext(int(t[i]), int(u[i])), int(v[i]))
+        else:
+            b.train(Observation(DefaultContext(int(t[i]), int(u[i])), session),
+                    dict(t=int(t[i]), u=int(u[i]), a=int(train['a'][i]), ps=float(train['ps'][i])), int(train['c'][i]), False)
+            session = OrganicSessions()
+    states = []
+    for ag in (a, b):
+        torch.manual_seed(11)
+        states.append(ag._ready().state())
+    for k in nu.KEYS:
+        assert np.array_equal(states[0][k].view(np.uint32), states[1][k].view(np.uint32)), k
+    init = NnIpsAgent(Configuration({**nn_ips_args, 'num_products': 10, 'random_seed': 7, 'num_epochs': 0, 'M': 0.5}))
+    init.train_from_log(log_frame(train))
+    torch.manual_seed(11)
+    assert not np.array_equal(init._ready().state()['w3'], states[0]['w3'])      # the five steps moved the net
+
+
+def test_margin_ingredients():
+    st = random_state(6, 5, 3)
+    m = NnModel(st)
+    w2, w3 = st['w2'].astype(np.float64), st['w3'].astype(np.float64)
+    assert m.w1t.shape == (6, 5) and m.w3t.shape == (5, 6) and m.w2t[1, 3] == w2[3, 1]
+    assert math.isclose(m.A2, (np.abs(w2).sum(axis=1) + np.abs(st['b2'].astype(np.float64))).max(), rel_tol=1e-14)
+    assert math.isclose(m.A3, (np.abs(w3).sum(axis=1) + np.abs(st['b3'].astype(np.float64))).max(), rel_tol=1e-14)
+    assert nn_abs_row_sums(np.array([[1.0, -2.0], [-3.0, 0.5]]), np.array([0.25, -4.0])) == 6.5
+    u = 2.0 ** -24
+    E1 = 8 * u * 3.0
+    E2 = 2.0 * (10 * u + (E1 / 4 + 2.0 ** -21))
+    E3 = 1.5 * (10 * u + (E2 / 4 + 2.0 ** -21))
+    assert nn_logit_bound(3, 3.0, 5, 2.0, 1.5) == E3 and nn_margin(3, 3.0, 5, 2.0, 1.5) == E3 + 2.0 ** -20
+    assert nn_ps_bound(3, 3.0, 5, 2.0, 1.5, 6) == math.expm1(2 * E3 + (math.log(6) + 6 + 24) * u)
+    assert nn_ps_bound(3, 1e300, 5, 1.0, 1.0, 6) == math.inf
+    # the rule: a tie and a count that is not an fp32 value are unresolved; an empty history acts on the biases alone
+    tie = {k: v.copy() for k, v in st.items()}
+    tie['w3'][4] = tie['w3'][1]
+    tie['b3'][4] = tie['b3'][1] = 50.0
+    a, fl, z, ps = nn_rule([2], [1], NnModel(tie))
+    assert z[1] == z[4] and (a, fl) == (1, UNRESOLVED)
+    assert nn_rule([2], [(1 << 24) + 1], m)[1] == UNRESOLVED
+    z0, ps0, a0, M1 = nn_forward([], [], m)
+    assert M1 == np.abs(m.b1).max() and 0.0 < ps0 < 1.0 and a0 == int(np.argmax(z0))
+
+
+def test_select_randomly_act_is_the_addressed_draw():
+    from recogym_amd import rng
+    st = random_state(10, 20, 8, 1.0)
+    ag = NnIpsFrozenAgent(Configuration({'num_products': 10, 'select_randomly': True, 'random_seed': 5, 'with_ps_all': True}), st)
+    session = OrganicSessions()
+    session.next(DefaultContext(0, 3), 4)
+    act = ag.act(Observation(DefaultContext(1, 3), session), 0, False)
+    prob = act['ps-a']
+    assert prob.dtype == np.float32 and abs(prob.sum() - 1.0) < 1e-6
+    cdf = prob.astype(np.float64).cumsum()
+    cdf /= cdf[-1]
+    _, _, u1 = rng.policy_uniforms(5, 3, 1)
+    assert act['a'] == int(cdf.searchsorted(u1, side='right')) and act['ps'] == float(prob[act['a']])
+
+
+def test_batch_copies_of_the_frozen_agent_are_distinct_objects():
+    """The frozen agent is a plain Agent that holds its net as a member: the per-slot copies of the batched host route are
+    distinct agents with their own view counts, and share the net."""
+    import torch
+    from copy import deepcopy
+    from recogym_amd.envs.reco_env_v1 import _shared_state_memo
+    agent = NnIpsFrozenAgent(Configuration({'num_products': 10}), random_state(10, 20, 1))
+    assert not isinstance(agent, torch.nn.Module) and isinstance(agent.net, torch.nn.Module)
+    shared = _shared_state_memo(agent)
+    copies = [deepcopy(agent, dict(shared)) for _ in range(3)]
+    assert len({id(c) for c in copies} | {id(agent)}) == 4 and len({id(c.views) for c in copies} | {id(agent.views)}) == 4
+    assert all(c.net is agent.net for c in copies)
+    session = OrganicSessions()
+    session.next(DefaultContext(0, 0), 7)
+    copies[0].act(Observation(DefaultContext(1, 0), session), 0, False)
+    assert copies[0].views[7] == 1 and copies[1].views.sum() == 0 and agent.views.sum() == 0
+
+
+def test_device_policy_refusals():
+    st = random_state(10, 20, 2)
+    ok = NnIpsFrozenAgent(Configuration({'num_products': 10}), st)
+    pol = ok.device_policy()
+    assert pol['policy'] == _abi.RG_POLICY_NN_IPS and pol['ouc'] is None and set(pol['nn_ips']['state']) == set(nu.KEYS)
+    assert ok.ope_policy() is None and ok.ope_policy_checked() is None
+    for over in (dict(with_ps_all=True), dict(weight_history_function=lambda dt: np.exp(-0.2 * dt)), dict(select_randomly=True)):
+        assert NnIpsFrozenAgent(Configuration({'num_products': 10, **over}), st).device_policy() is None, over
+    bad = {k: v.copy() for k, v in st.items()}
+    bad['w2'][3, 4] = np.inf
+    assert NnIpsFrozenAgent(Configuration({'num_products': 10}), bad).device_policy() is None
+    bad['w2'][3, 4] = np.nan
+    assert NnIpsFrozenAgent(Configuration({'num_products': 10}), bad).device_policy() is None
+    wide = random_state(4, HIDDEN_CAP + 1, 3, 0.01)
+    assert NnIpsFrozenAgent(Configuration({'num_products': 4}), wide).device_policy() is None
+    assert NnIpsFrozenAgent(Configuration({'num_products': 4}), random_state(4, HIDDEN_CAP, 3, 0.01)).device_policy() is not None
+    # the training agent asks its frozen one
+    ag = NnIpsAgent(Configuration({**nn_ips_args, 'num_products': 10, 'random_seed': 7, 'num_epochs': 1, 'with_ps_all': True}))
+    ag.train_from_log(log_frame({k: v[training_log()['u'] < 5] for k, v in training_log().items()}))
+    assert ag.device_policy() is None and ag.ope_policy() is None and ag.ope_policy_checked() is None
