@@ -1,4 +1,4 @@
-// rg_common.hpp — librecogym_hip.so: the reco-gym-v1 step loop as batched CDNA4 (gfx950) kernels (shared part of its sixteen units).
+// rg_common.hpp — librecogym_hip.so: the reco-gym-v1 step loop as batched CDNA4 (gfx950) kernels (shared part of its twenty units).
 //
 // What runs here (reference file:line each kernel takes over; see DESIGN.md for the data layout
 // and the roofline of each kernel):
@@ -48,8 +48,9 @@
 
 #include "../../include/recogym_hip.h"
 #include "../../include/recogym_rng.h"
+#include "rg_exp64.hpp"
 
-// Translation units.  The library is built from sixteen units, one per kernel family — rg_host.hip (host code, the C ABI, small
+// Translation units.  The library is built from twenty units, one per kernel family — rg_host.hip (host code, the C ABI, small
 // kernels), rg_exact.hip (float64 resolve), rg_draw_fp32.hip (fp32 / lean 16-bit sweeps), rg_draw_pipelined.hip (the pipelined sweep
 // + per-user cache kernels), rg_draw_wide.hip (wide-K sweep), rg_advance.hip (advance / tail / frozen LogReg), rg_walk.hip (the
 // user-major walk), rg_draw_exacthi.hip and rg_draw_lds.hip (the error-free and the tile-prefix sweeps), rg_ope.hip,
@@ -1506,35 +1507,8 @@ __device__ __forceinline__ double exp64(double x) {
     return ldexp(p, static_cast<int>(kf));
 }
 
-// Table variant for the kernel that spends its time in exp: exp(x) = 2^e * T[j] * exp(r) with
-// n = rint(x * 32/ln 2) = 32 e + j and |r| <= ln 2 / 64, so a degree-6 polynomial is enough
-// (remainder r^7/5040 < 4e-18) — ~15 float64 instructions instead of ~35.  T[j] = 2^(j/32),
-// correctly rounded; `tab` is the block's LDS copy (32 doubles, one bank pair each: conflict-free).
-static __device__ const double kExp2Tab32[32] = {
-    0x1.0000000000000p+0, 0x1.059b0d3158574p+0, 0x1.0b5586cf9890fp+0, 0x1.11301d0125b51p+0,
-    0x1.172b83c7d517bp+0, 0x1.1d4873168b9aap+0, 0x1.2387a6e756238p+0, 0x1.29e9df51fdee1p+0,
-    0x1.306fe0a31b715p+0, 0x1.371a7373aa9cbp+0, 0x1.3dea64c123422p+0, 0x1.44e086061892dp+0,
-    0x1.4bfdad5362a27p+0, 0x1.5342b569d4f82p+0, 0x1.5ab07dd485429p+0, 0x1.6247eb03a5585p+0,
-    0x1.6a09e667f3bcdp+0, 0x1.71f75e8ec5f74p+0, 0x1.7a11473eb0187p+0, 0x1.82589994cce13p+0,
-    0x1.8ace5422aa0dbp+0, 0x1.93737b0cdc5e5p+0, 0x1.9c49182a3f090p+0, 0x1.a5503b23e255dp+0,
-    0x1.ae89f995ad3adp+0, 0x1.b7f76f2fb5e47p+0, 0x1.c199bdd85529cp+0, 0x1.cb720dcef9069p+0,
-    0x1.d5818dcfba487p+0, 0x1.dfc97337b9b5fp+0, 0x1.ea4afa2a490dap+0, 0x1.f50765b6e4540p+0};
-
-__device__ __forceinline__ double exp64t(double x, const double* tab) {
-    x = fmax(x, -750.0);                                   // e^-750 underflows to exactly 0 (also takes -inf)
-    const double nf = rint(x * 0x1.71547652b82fep+5);      // 32 / ln 2
-    double r = fma(nf, -0x1.62e42fe000000p-6, x);          // ln 2 / 32, high part (29 bits: nf * hi is exact)
-    r = fma(nf, -0x1.f473de6af278fp-35, r);                // low part
-    const int n = static_cast<int>(nf);
-    double p = 1.3888888888888889e-03;                     // 1/6!
-    p = fma(p, r, 8.3333333333333332e-03);                 // 1/5!
-    p = fma(p, r, 4.1666666666666664e-02);                 // 1/4!
-    p = fma(p, r, 1.6666666666666666e-01);                 // 1/3!
-    p = fma(p, r, 0.5);
-    p = fma(p, r, 1.0);
-    p = fma(p, r, 1.0);
-    return ldexp(tab[n & 31] * p, n >> 5);
-}
+// The table variant for the kernels that spend their time in exp (exp64t_parts / exp64t_add / exp64t and the table kExp2Tab32):
+// rg_exp64.hpp, a header of its own that a host compiler takes too.
 
 // inclusive scan of x over the 64 lanes of the wave
 __device__ __forceinline__ double wave_scan(double x, int lane) {
@@ -1596,9 +1570,10 @@ constexpr int kExactUsers = 4 * kUPW;        // users per block
 //   D[product i][user j] += Gamma[i][4s..4s+3] . omega_j[4s..4s+3]        16 products x 16 users x 4 k per MFMA
 // A = the Gamma rows of a 64-product chunk staged in LDS by the block (a straight copy of gamma_rm, mu in the last
 // column), B = omega of 16 users (register resident for the work item), 4 (K <= 32) or 2 groups of 16 users per wave
-// so that every A fragment read from LDS feeds 4 / 2 MFMAs; the VALU only adds mu, subtracts the reference and takes
-// the exp of the 4 logits a lane gets per group and tile.  The matrix unit's accumulation order differs from the
-// k-ascending chain (as the oracle's differs from OpenBLAS'): a 1e-16-level difference, decisions unchanged.
+// so that every A fragment read from LDS feeds 4 / 2 MFMAs; the accumulators start from mu - reference, so the VALU only takes
+// the exp of the 4 logits a lane gets per group and tile (the unit is compiled with the MFMA's VGPR form: the exps read
+// them in place).  The matrix unit's accumulation order differs from the k-ascending chain (as the oracle's differs from
+// OpenBLAS'): a 1e-16-level difference, decisions unchanged.
 // C/D layout of the f64 MFMA: column = lane & 15, row = (lane >> 4) + 4 * reg.
 // ------------------------------------------------------------------------------------------
 using f64x4 = __attribute__((ext_vector_type(4))) double;

@@ -126,8 +126,8 @@ __global__ void __launch_bounds__(kBlock) k_exact_sums_m(DevSim d, uint32_t t, i
     constexpr int NLD = (TILE / 2 + kBlock - 1) / kBlock;            // 16-byte pieces of a chunk per thread
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     double* tiles = reinterpret_cast<double*>(smem_raw);             // [2][TILE]
-    double* exp_tab = tiles + 2 * TILE;
-    if (threadIdx.x < 32) exp_tab[threadIdx.x] = kExp2Tab32[threadIdx.x];
+    uint32_t* exp_tab = reinterpret_cast<uint32_t*>(tiles + 2 * TILE);   // 32 entries of two words (exp64t_entry)
+    if (threadIdx.x < 32) exp64t_entry(kExp2Tab32[threadIdx.x], threadIdx.x, exp_tab);
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int q = lane >> 4, jl = lane & 15;
     const uint32_t n_cc = d.PT / 64;
@@ -202,9 +202,15 @@ __global__ void __launch_bounds__(kBlock) k_exact_sums_m(DevSim d, uint32_t t, i
             for (int g = 0; g < G; ++g) sum[g] = mode == 0 ? -INFINITY : 0.0;
 #pragma unroll 1
             for (int tt = 0; tt < 4; ++tt) {
+                // the accumulators start from mu - M (M = 0 in mode 0), so what the matrix pipe hands back is the exp's argument
+                double mu[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mu[r] = A[static_cast<size_t>(tt * 16 + q + 4 * r) * RSd + 4 * KB];   // -inf for products >= P
                 f64x4 acc[G];
 #pragma unroll
-                for (int g = 0; g < G; ++g) acc[g] = f64x4{0.0, 0.0, 0.0, 0.0};
+                for (int g = 0; g < G; ++g)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[g][r] = mu[r] - M[g];
                 const double* arow = A + static_cast<size_t>(tt * 16 + jl) * RSd + q;
 #pragma unroll
                 for (int s2 = 0; s2 < KB; ++s2) {
@@ -212,16 +218,11 @@ __global__ void __launch_bounds__(kBlock) k_exact_sums_m(DevSim d, uint32_t t, i
 #pragma unroll
                     for (int g = 0; g < G; ++g) acc[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[g][s2], acc[g], 0, 0, 0);
                 }
-                double mu[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) mu[r] = A[static_cast<size_t>(tt * 16 + q + 4 * r) * RSd + 4 * KB];   // -inf for products >= P
 #pragma unroll
                 for (int g = 0; g < G; ++g)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const double l = acc[g][r] + mu[r];
-                        sum[g] = mode == 0 ? fmax(sum[g], l) : sum[g] + exp64t(l - M[g], exp_tab);
-                    }
+                    for (int r = 0; r < 4; ++r)
+                        sum[g] = mode == 0 ? fmax(sum[g], acc[g][r]) : exp64t_add(sum[g], acc[g][r], exp_tab);
             }
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -256,9 +257,9 @@ __global__ void __launch_bounds__(kBlock) k_exact_sums_h(DevSim d, uint32_t n, u
     constexpr int NLD = (TILE / 2 + kBlock - 1) / kBlock;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     double* tiles = reinterpret_cast<double*>(smem_raw);             // [2][TILE]
-    double* exp_tab = tiles + 2 * TILE;
+    uint32_t* exp_tab = reinterpret_cast<uint32_t*>(tiles + 2 * TILE);   // 32 entries of two words (exp64t_entry)
     __shared__ uint32_t s_grp;
-    if (threadIdx.x < 32) exp_tab[threadIdx.x] = kExp2Tab32[threadIdx.x];
+    if (threadIdx.x < 32) exp64t_entry(kExp2Tab32[threadIdx.x], threadIdx.x, exp_tab);
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int q = lane >> 4, jl = lane & 15;
     const uint32_t n_cc = d.PT / 64;
@@ -327,9 +328,14 @@ __global__ void __launch_bounds__(kBlock) k_exact_sums_h(DevSim d, uint32_t n, u
                 for (int g = 0; g < G; ++g) sum[g] = 0.0;
 #pragma unroll 1
                 for (int tt = 0; tt < 4; ++tt) {
-                    f64x4 acc[G];
+                    double mu[4];
 #pragma unroll
-                    for (int g = 0; g < G; ++g) acc[g] = f64x4{0.0, 0.0, 0.0, 0.0};
+                    for (int r = 0; r < 4; ++r) mu[r] = A[static_cast<size_t>(tt * 16 + q + 4 * r) * RSd + 4 * KB];
+                    f64x4 acc[G];                      // started from mu - M: the matrix pipe hands back the exp's argument
+#pragma unroll
+                    for (int g = 0; g < G; ++g)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) acc[g][r] = mu[r] - M[g];
                     const double* arow = A + static_cast<size_t>(tt * 16 + jl) * RSd + q;
 #pragma unroll
                     for (int s2 = 0; s2 < KB; ++s2) {
@@ -337,13 +343,10 @@ __global__ void __launch_bounds__(kBlock) k_exact_sums_h(DevSim d, uint32_t n, u
 #pragma unroll
                         for (int g = 0; g < G; ++g) acc[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[g][s2], acc[g], 0, 0, 0);
                     }
-                    double mu[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) mu[r] = A[static_cast<size_t>(tt * 16 + q + 4 * r) * RSd + 4 * KB];
 #pragma unroll
                     for (int g = 0; g < G; ++g)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) sum[g] += exp64t(acc[g][r] + mu[r] - M[g], exp_tab);
+                        for (int r = 0; r < 4; ++r) sum[g] = exp64t_add(sum[g], acc[g][r], exp_tab);
                 }
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
@@ -357,6 +360,8 @@ __global__ void __launch_bounds__(kBlock) k_exact_sums_h(DevSim d, uint32_t n, u
         } else {
             // ================= vector form (k_exact_sums_u's body): wave = 64 users of the group =================
             constexpr int UPL = UPB / (kBlock / 64) / 64;          // users per lane: 1 (256-user groups)
+            constexpr int RW = 4 * KB + 1;                         // doubles of a gamma_rm row in use: Gamma[p][0 .. 4 KB), mu[p]
+            constexpr bool kTwoRows = 4 * RW <= 84;                // two rows' scalar registers beside the kernel's own: K <= 20
             uint32_t w_row[UPL];
             bool act[UPL];
             double om[UPL][4 * KB], M[UPL];
@@ -372,29 +377,78 @@ __global__ void __launch_bounds__(kBlock) k_exact_sums_h(DevSim d, uint32_t n, u
                     om[j][k] = (act[j] && static_cast<uint32_t>(k) < d.K) ? d.omega[static_cast<size_t>(slot) * d.OMS + k] : 0.0;
                 M[j] = act[j] ? static_cast<double>(d.exact_ref[slot]) * 0.69314718055994530942 : 0.0;
             }
-            for (uint32_t cc = cc_lo; cc < cc_hi; ++cc) {
-                double acc[UPL];
+            // One product: the logit's FMA chain starts from mu - M and the exp comes back as scale * poly for one FMA into acc.
+            auto dot_exp = [&](const double (&r)[RW], double (&scale)[UPL], double (&poly)[UPL]) {
 #pragma unroll
-                for (int j = 0; j < UPL; ++j) acc[j] = 0.0;
-                const uint32_t p1 = cc * 64 + 64;
-#pragma unroll 2
-                for (uint32_t p = cc * 64; p < p1; ++p) {
-                    kdouble* row = (kdouble*)(d.gamma_rm) + static_cast<size_t>(p) * RSd;
-                    double l[UPL];
+                for (int j = 0; j < UPL; ++j) {
+                    double l = r[4 * KB] - M[j];
 #pragma unroll
-                    for (int j = 0; j < UPL; ++j) l[j] = 0.0;
+                    for (int k = 0; k < 4 * KB; ++k) l = fma(r[k], om[j][k], l);
+                    exp64t_parts(l, exp_tab, scale[j], poly[j]);
+                }
+            };
+            auto load_row = [&](double (&r)[RW], uint32_t p) {
+                kdouble* row = (kdouble*)(d.gamma_rm) + static_cast<size_t>(p) * RSd;
 #pragma unroll
-                    for (int k = 0; k < 4 * KB; ++k) {
-                        const double g = row[k];
+                for (int k = 0; k < RW; ++k) r[k] = row[k];
+            };
+            if constexpr (kTwoRows) {
+                // Two rows in scalar registers, each fetched one product ahead.  Scalar loads and the LDS read of the exp table
+                // share a counter and scalar loads return out of order, so waiting for a table value waits for every row in flight.
+                // Hence a row's loads are issued right AFTER the table value of the product that used its registers has arrived:
+                // they then have the rest of that exp and the whole next product to land before the next such wait.
+                const uint32_t p_last = cc_hi * 64 - 1;        // the rows fetched past the item's end are not used: clamped (cc_lo < cc_hi: S <= n_cc)
+                double ra[RW], rb[RW];
+                load_row(ra, cc_lo * 64);
+                load_row(rb, cc_lo * 64 + 1);
+                // Both rows are used here (empty statements that take a value of every four: every load instruction's), so the
+                // compiler waits for them here.  Without it the wait sits at the loop's head, where in every turn it also waits
+                // for the row just asked for.
 #pragma unroll
-                        for (int j = 0; j < UPL; ++j) l[j] += g * om[j][k];
+                for (int k = 0; k < RW; k += 4) asm volatile("" ::"s"(ra[k]), "s"(rb[k]));
+                auto step = [&](double (&r)[RW], uint32_t p_next, double (&acc)[UPL]) {
+                    double scale[UPL], poly[UPL];
+                    dot_exp(r, scale, poly);
+                    __builtin_amdgcn_sched_barrier(0);
+                    load_row(r, min(p_next, p_last));
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int j = 0; j < UPL; ++j) acc[j] = fma(scale[j], poly[j], acc[j]);
+                };
+                for (uint32_t cc = cc_lo; cc < cc_hi; ++cc) {
+                    double acc[UPL];
+#pragma unroll
+                    for (int j = 0; j < UPL; ++j) acc[j] = 0.0;
+                    const uint32_t p1 = cc * 64 + 64;
+#pragma unroll 1
+                    for (uint32_t p = cc * 64; p < p1; p += 2) {
+                        step(ra, p + 2, acc);
+                        step(rb, p + 3, acc);
                     }
 #pragma unroll
-                    for (int j = 0; j < UPL; ++j) acc[j] += exp64t(l[j] + row[4 * KB] - M[j], exp_tab);
+                    for (int j = 0; j < UPL; ++j)
+                        if (act[j]) d.exact_sums[static_cast<size_t>(w_row[j]) * n_cc + cc] = acc[j];
                 }
+            } else {
+                for (uint32_t cc = cc_lo; cc < cc_hi; ++cc) {
+                    double acc[UPL];
 #pragma unroll
-                for (int j = 0; j < UPL; ++j)
-                    if (act[j]) d.exact_sums[static_cast<size_t>(w_row[j]) * n_cc + cc] = acc[j];
+                    for (int j = 0; j < UPL; ++j) acc[j] = 0.0;
+                    const uint32_t p1 = cc * 64 + 64;
+#pragma unroll 1
+                    for (uint32_t p = cc * 64; p < p1; p += 2)     // two products a turn, written out
+#pragma unroll
+                        for (uint32_t h = 0; h < 2; ++h) {
+                            double r[RW], scale[UPL], poly[UPL];
+                            load_row(r, p + h);
+                            dot_exp(r, scale, poly);
+#pragma unroll
+                            for (int j = 0; j < UPL; ++j) acc[j] = fma(scale[j], poly[j], acc[j]);
+                        }
+#pragma unroll
+                    for (int j = 0; j < UPL; ++j)
+                        if (act[j]) d.exact_sums[static_cast<size_t>(w_row[j]) * n_cc + cc] = acc[j];
+                }
             }
         }
     }
