@@ -224,7 +224,8 @@ int rg_sim_destroy(rg_sim* sim);
  * the pair of calls); after that the library never reads the environment.  Names: walk_bias, walk_refill,
  * walk_handover, walk_click_batch, walk_search_batch, walk_helpers (0 .. 7), walk_click_join, walk_line64, pipe_groups (1: the walked
  * run keeps its list lengths on the device; 0: the host reads them back), pipe_occ1, pipe_occ2, pipe_xblocks,
- * pipe_min_users, exact_mix, exact_tile, slices (-1 = by population), sweep_prefix_off, tail_below,
+ * pipe_min_users, exact_mix, exact_tile, slices (-1 = by population), sweep_prefix_off, tail_below (a value above 0 is
+ * refused where rg_sim_create keeps it 0: the LogReg family of policies and per-user clocks),
  * repack_every, run_ahead (events a round of a run to the end may take a user through, 0 = an event per launch), lr_part_cap (acts
  * of a step the frozen-LogReg fp16 screen takes; can only be lowered), sweep_lds (1: the unsliced sweep of a run whose draws are
  * not cached keeps its tile prefixes in LDS and searches them there, k_draw_tp; 0: k_draw_bf16p's scratch + search), debug.

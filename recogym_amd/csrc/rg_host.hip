@@ -1493,6 +1493,12 @@ int rg_sim_set_option(rg_sim* sim, const char* name, int64_t value) {
     if (!strcmp(name, "run_ahead") && value && sim->d.env_kind) return fail(RG_EINVAL, "env_kind 1 (reco-gym-v0) runs lock-step (run_ahead = 0)");
     if (!strcmp(name, "lr_part_cap") && static_cast<uint64_t>(value) > sim->lr_part_rows)
         return fail(RG_EINVAL, "lr_part_cap can only be lowered (the workspace holds %u rows)", sim->lr_part_rows);
+    // plan_repack_tail's rule, held after create too: k_tail acts through policy_act's scalar frozen-LogReg loop (a model a
+    // LOGREG_POLY / BAYES_VB / NN_IPS handle does not have) and keeps no per-user clock
+    if (!strcmp(name, "tail_below") && value && sim->d.policy == RG_POLICY_LOGREG_FROZEN)
+        return fail(RG_EINVAL, "tail_below must stay 0 under the LogReg family of policies (frozen LogReg, LOGREG_POLY, BAYES_VB, NN_IPS): the tail kernel has no wave-cooperative act");
+    if (!strcmp(name, "tail_below") && value && sim->d.time_mode)
+        return fail(RG_EINVAL, "tail_below must stay 0 with a per-user clock (time_mode): the tail kernel keeps none");
     if (!strcmp(name, "walk_search_batch") && value < 1) value = 1;
     if (!strcmp(name, "walk_handover")) sim->handover_auto = false;
     o->set(sim, value);

@@ -281,7 +281,8 @@ WALK_CASES = ([('default', K, P) for K in (3, 10, 13, 21, 27) for P in (640, 545
 # ---------------------------------------------------------------------------------------------------------------------------
 FAMILIES = ('draw_f64', 'draw_fp32', 'draw16_fused', 'draw16_sliced', 'search', 'draw_tp', 'pick', 'draw_cached', 'sweep_xh',
             'exact_m', 'exact_tile', 'exact_h', 'walk', 'walk2', 'walk_solo', 'advance', 'advance_run', 'tail', 'repack', 'env0',
-            'logreg_screen', 'logreg_acts', 'logreg_sample', 'sort_tiled', 'sort_plain')
+            'logreg_screen', 'logreg_acts', 'logreg_sample', 'sort_tiled', 'sort_plain', 'logreg_poly', 'logreg_poly_w', 'bayes_vb',
+            'nn_ips')
 DESCRIPTORS = ('draw_kh', 'draw_n1', 'draw_split', 'draw_kernel', 'draw_pipelined', 'xh_class', 'xh_waves', 'sweep_lds_kernel')
 DRAW_FAMILIES = ('draw_f64', 'draw_fp32', 'draw16_fused', 'draw16_sliced', 'draw_tp', 'draw_cached', 'sweep_xh', 'env0')
 

@@ -38,18 +38,24 @@ def acts_of_log(cols, P):
 
 
 def rule_over_log(cols, P, state):
-    """nn_rule on every act of a log -> list of dict(rows, user, t, action, flags, ps, bound): `bound` is nn_ps_bound of the act,
-    (user, t) the entry the device lists for an unresolved act (the event index of the last organic row before the act)."""
+    """nn_rule on every act of a log -> list of dict(rows, user, t, t_lockstep, action, flags, ps, bound): `bound` is nn_ps_bound of
+    the act, (user, t) the entry the device lists for an unresolved act in run-ahead rounds (the event index of the last organic row
+    before the act: a round lists the user at that event), (user, t_lockstep) the entry of a run with an event per launch — DESIGN.md
+    4f: "an organic user is listed at the event that completes the history, a bandit user at the act's own event": the same index
+    where the act serves nothing but the trailing row of a user that stops from the organic state, one more (the act's first bandit
+    row) everywhere else."""
     m = NnModel(state)
-    first = {}
+    first, last = {}, {}
     for i, uu in enumerate(cols['u']):
         first.setdefault(int(uu), i)
+        last[int(uu)] = i
     out = []
     for rows, prods, cnts in acts_of_log(cols, P):
         action, flags, z, ps = nn_rule(prods, cnts, m)
         M1 = nn_forward(prods, cnts, m)[3]
         user = int(cols['u'][rows[0]])
-        out.append(dict(rows=rows, user=user, t=rows[0] - first[user] - 1, action=action, flags=flags, ps=float(ps),
+        t = rows[0] - first[user] - 1
+        out.append(dict(rows=rows, user=user, t=t, t_lockstep=t if rows == [last[user]] else t + 1, action=action, flags=flags, ps=float(ps),
                         bound=nn_ps_bound(len(prods), M1, m.H, m.A2, m.A3, P)))
     return out
 

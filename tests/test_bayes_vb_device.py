@@ -7,6 +7,7 @@ import warnings
 import numpy as np
 import pytest
 
+import adversarial_util as au
 import bayes_util as bu
 import golden_util as gu
 from device_util import assert_frames_equal, make_env
@@ -21,25 +22,28 @@ from recogym_amd.envs.reco_env_v1 import env_1_args
 pytestmark = pytest.mark.gpu
 
 
-def run_fixture(name):
+def run_fixture(name, first_user=0, n_users=None, organic_only_below=0, ledger=False):
+    """-> meta, cols, rows, counters, the raw sorted log, launches of k_bayes_acts[, the launch ledger, poly_verify's outcome and
+    the unresolved list]"""
     from recogym_amd.sim import Simulator
     meta, cols = gu.load(name)
-    P, n = meta['env_args']['num_products'], meta['n_users']
+    P, n = meta['env_args']['num_products'], meta['n_users'] if n_users is None else n_users
     frozen = BayesianVBFrozenAgent(Configuration({'num_products': P}), bu.fixture_lambda(meta, cols))
     sim = Simulator(gu.env_config(meta), n, device='cuda:0', **frozen.device_policy())
-    sim.reset_users(0, n)
+    sim.reset_users(first_user, n, organic_only_below=organic_only_below)
     sim.run()
     rows, cnt, raw = sim.rows(), sim.counters(), sim.sorted_log_host()[0]
     launched = sim.get_option('launched_bayes_vb')
+    extra = ()
+    if ledger:
+        stands = sim.poly_verify()
+        extra = (au.ledger(sim), stands, sim.poly_unresolved.copy())
     sim.close()
-    return meta, cols, rows, cnt, raw, launched
+    return (meta, cols, rows, cnt, raw, launched) + extra
 
 
-@pytest.mark.parametrize('name', bu.FIXTURES)
-def test_device_log_equals_the_reference(name):
-    """P = 4 with all 1000 draws, P = 10 with 120 draws (a masked last stride) under sigma_omega > 0 (lock-step rounds) and = 0,
-    and the shifted model whose acts all saturate with the lowest index winning."""
-    meta, cols, rows, cnt, _, launched = run_fixture(name)
+def assert_log_equals_the_reference(name, meta, cols, rows, cnt, launched):
+    """The rows and counters of a run of the fixture's users (of several runs: rows concatenated, counters summed) held to it."""
     gu.assert_rows_equal(rows, cols, ps_rtol=0, what=name)
     census = meta['census']
     print(name, {k: cnt[k] for k in ('lr_acts', 'lr_rows', 'bayes_saturated', 'poly_unresolved')}, census)
@@ -48,17 +52,31 @@ def test_device_log_equals_the_reference(name):
     assert cnt['live'] == 0 and cnt['log_dropped'] == 0 and cnt['hist_overflow'] == 0
 
 
+@pytest.mark.parametrize('name', bu.FIXTURES)
+def test_device_log_equals_the_reference(name):
+    """P = 4 with all 1000 draws, P = 10 with 120 draws (a masked last stride) under sigma_omega > 0 (lock-step rounds) and = 0,
+    and the shifted model whose acts all saturate with the lowest index winning."""
+    meta, cols, rows, cnt, _, launched = run_fixture(name)
+    assert_log_equals_the_reference(name, meta, cols, rows, cnt, launched)
+
+
 def test_two_runs_give_the_same_log():
     a, b = run_fixture('bayes_p10_s120'), run_fixture('bayes_p10_s120')
     assert np.array_equal(a[4], b[4]) and a[3] == b[3]
 
 
-def test_generate_logs_with_the_trained_agent_equals_the_host_route():
+def trained_agent():
+    """-> the meta of bayes_p4, BayesianAgentVB trained on the fixture's training log"""
     meta, cols = gu.load('bayes_p4')
     train = {k[len('trainlog_'):]: v for k, v in cols.items() if k.startswith('trainlog_')}
     from make_golden_ope import log_frame
     agent = BayesianAgentVB(Configuration({**bayesian_poly_args, 'num_products': 4, 'random_seed': 7}))
     agent.train_from_log(log_frame(train))
+    return meta, agent
+
+
+def test_generate_logs_with_the_trained_agent_equals_the_host_route():
+    meta, agent = trained_agent()
     env = make_env(meta['env_args'])
     with warnings.catch_warnings():
         warnings.simplefilter('error', RuntimeWarning)

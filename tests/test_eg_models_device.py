@@ -34,20 +34,20 @@ MODES = (dict(tail_below=0, run_ahead=0), dict(tail_below=0, run_ahead=32), dict
 EG = dict(epsilon=0.3, random_seed=7)
 
 
-def run(cfg, n, pol, options=()):
+def run(cfg, n, pol, options=(), first_user=0, organic_only_below=0):
     sim = Simulator(cfg, n, device=DEV, **{k: v for k, v in pol.items() if k != 'ps_all'})
     for k, v in dict(options).items():
         sim.set_option(k, v)
-    sim.reset_users(0, n)
+    sim.reset_users(first_user, n, organic_only_below=organic_only_below)
     sim.run()
     return sim
 
 
-def run_fixture(name, options=()):
+def run_fixture(name, options=(), first_user=0, n_users=None, organic_only_below=0):
     meta, cols, P = mu.load(name)
     pol = mu.wrapper(meta, cols, P).device_policy()
     assert pol is not None and pol['epsilon_greedy']['epsilon'] == meta['eg_args']['epsilon']
-    return meta, cols, P, run(gu.env_config(meta), meta['n_users'], pol, options)
+    return meta, cols, P, run(gu.env_config(meta), meta['n_users'] if n_users is None else n_users, pol, options, first_user, organic_only_below)
 
 
 def same(a, b):
@@ -55,26 +55,28 @@ def same(a, b):
 
 
 # ---- (a) the device log against the fixture --------------------------------------------------------------------------------
+def assert_log_is_the_fixture(what, meta, cols, rows, cnt):
+    """The rows and counters of a run of the fixture's users (of several runs: rows concatenated, counters summed) held to it."""
+    is_b = cols['z'] == 1
+    last = np.r_[cols['u'][1:] != cols['u'][:-1], True]
+    gu.assert_rows_equal(rows, cols, ps_rtol=0, what=what)
+    assert np.array_equal(eu.bits(rows['ps'][is_b]), eu.bits(cols['ps'][is_b])), f'{what}: ps bits'
+    assert np.array_equal(rows['phantom'] != 0, is_b & last), 'the phantom row is every user\'s last'
+    census = meta['census']
+    print(what, {k: cnt[k] for k in ('lr_acts', 'lr_rows', 'poly_table', 'poly_unresolved')}, census)
+    assert cnt['lr_acts'] == census['acts'], what
+    if meta['inner'] == 'poly':
+        assert cnt['poly_table'] == census['table'] and cnt['poly_unresolved'] == census['unresolved'] == 0, what
+    assert cnt['live'] == 0 and cnt['log_dropped'] == 0 and cnt['hist_overflow'] == 0, what
+
+
 @pytest.mark.parametrize('name', mu.LOG_FIXTURES)
 def test_device_log_equals_the_reference_fixture(name):
-    is_b = last = None
     for options in MODES:
         meta, cols, P, sim = run_fixture(name, options)
-        if is_b is None:
-            is_b = cols['z'] == 1
-            last = np.r_[cols['u'][1:] != cols['u'][:-1], True]
         rows, cnt = sim.rows(), sim.counters()
         sim.close()
-        what = f'{name} {options}'
-        gu.assert_rows_equal(rows, cols, ps_rtol=0, what=what)
-        assert np.array_equal(eu.bits(rows['ps'][is_b]), eu.bits(cols['ps'][is_b])), f'{what}: ps bits'
-        assert np.array_equal(rows['phantom'] != 0, is_b & last), 'the phantom row is every user\'s last'
-        census = meta['census']
-        print(what, {k: cnt[k] for k in ('lr_acts', 'lr_rows', 'poly_table', 'poly_unresolved')}, census)
-        assert cnt['lr_acts'] == census['acts'], what
-        if meta['inner'] == 'poly':
-            assert cnt['poly_table'] == census['table'] and cnt['poly_unresolved'] == census['unresolved'] == 0, what
-        assert cnt['live'] == 0 and cnt['log_dropped'] == 0 and cnt['hist_overflow'] == 0, what
+        assert_log_is_the_fixture(f'{name} {options}', meta, cols, rows, cnt)
 
 
 # ---- (b) the branches ------------------------------------------------------------------------------------------------------

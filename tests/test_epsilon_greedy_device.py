@@ -28,39 +28,50 @@ DEV = 'cuda:0'
 MODES = (dict(tail_below=0, run_ahead=0), dict(tail_below=0, run_ahead=32), dict())
 
 
-def run(cfg, n, pol, options=(), first=0, n_users=None):
+def run(cfg, n, pol, options=(), first=0, n_users=None, organic_only_below=0):
     sim = Simulator(cfg, n, device=DEV, **{k: v for k, v in pol.items() if k != 'ps_all'})
     for k, v in dict(options).items():
         sim.set_option(k, v)
-    sim.reset_users(first, n if n_users is None else n_users)
+    sim.reset_users(first, n if n_users is None else n_users, organic_only_below=organic_only_below)
     sim.run()
     return sim
 
 
-@pytest.mark.parametrize('name', eu.LOG_FIXTURES)
-def test_device_log_equals_the_reference_fixture(name):
+def run_fixture(name, options=(), first_user=0, n_users=None, organic_only_below=0):
+    """-> meta, cols, the Simulator after its run (the caller closes it)"""
     meta, cols, P = eu.load(name)
-    cfg = gu.env_config(meta)
     pol = eu.wrapper(meta, cols, P).device_policy()
     assert pol is not None and pol['epsilon_greedy']['epsilon'] == meta['eg_args']['epsilon']
+    n = meta['n_users'] if n_users is None else n_users
+    return meta, cols, run(gu.env_config(meta), n, pol, options, first_user, organic_only_below=organic_only_below)
+
+
+def assert_log_is_the_fixture(what, meta, cols, rows, sims):
+    """The rows of a run of the fixture's users held to it (`sims`: the Simulators that ran them; of several: their rows concatenated)."""
     is_b = cols['z'] == 1
     last = np.r_[cols['u'][1:] != cols['u'][:-1], True]
-    for options in MODES:
-        sim = run(cfg, meta['n_users'], pol, options)
-        rows = sim.rows()
-        gu.assert_rows_equal(rows, cols, ps_rtol=0, what=f'{name} {options}')
-        assert np.array_equal(eu.bits(rows['ps'][is_b]), eu.bits(cols['ps'][is_b])), f'{name} {options}: ps bits'
-        assert np.array_equal(rows['phantom'] != 0, is_b & last), 'the phantom row is every user\'s last'
+    gu.assert_rows_equal(rows, cols, ps_rtol=0, what=what)
+    assert np.array_equal(eu.bits(rows['ps'][is_b]), eu.bits(cols['ps'][is_b])), f'{what}: ps bits'
+    assert np.array_equal(rows['phantom'] != 0, is_b & last), 'the phantom row is every user\'s last'
+    for sim in sims:
         assert sim.aux_ps is not None and not sim.uniform_ps            # the float64 side array is on by default
         if meta['env_args']['sigma_omega'] == 0.0:
             # the overlay has no walked form: the run stayed in the lock-step kernels
             with pytest.raises(_abi.RecoGymHipError, match='no walked run'):
                 sim.walk_fate()
             assert sim.counters()['memo_hits'] == 0
+
+
+@pytest.mark.parametrize('name', eu.LOG_FIXTURES)
+def test_device_log_equals_the_reference_fixture(name):
+    for options in MODES:
+        meta, cols, sim = run_fixture(name, options)
+        assert_log_is_the_fixture(f'{name} {options}', meta, cols, sim.rows(), [sim])
         sim.close()
     if name == 'eg_p1000_k20_table_sigma0':
         # (the same inner policy alone IS walked at this shape — BASELINE config 2's table: the check above means something)
-        plain = run(cfg, meta['n_users'], {k: v for k, v in pol.items() if k != 'epsilon_greedy'})
+        pol = eu.wrapper(meta, cols, meta['env_args']['num_products']).device_policy()
+        plain = run(gu.env_config(meta), meta['n_users'], {k: v for k, v in pol.items() if k != 'epsilon_greedy'})
         plain.walk_fate()
         plain.close()
 

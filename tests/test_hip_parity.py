@@ -41,13 +41,19 @@ def n_super_chunks(P):
     return (n_chunks + sc_chunks - 1) // sc_chunks
 
 
-@pytest.mark.parametrize('name', gu.fixtures('philox_'))
-def test_hip_reproduces_reference_fixture(name):
-    """The committed logs of the unmodified reference (counter RNG injected), row for row."""
+def run_fixture(name, first_user=0, n_users=None, organic_only_below=None, with_ledger=False):
+    """A philox_ fixture's users (or n_users of them from first_user on, the ids below organic_only_below organic only; default: the
+    fixture's warm-up users) -> meta, cols, rows, counters[, the launch ledger]"""
     meta, cols = gu.load(name)
     extra = {} if gu.env0_tables(meta) is None else dict(env0=gu.env0_tables(meta))      # reco-gym-v0 fixtures: env_kind = 1
-    rows, cnt = run_sim(gu.env_config(meta), meta['n_users'], meta['n_organic'],
-                        **gu.policy_args(meta, cols), **extra)
+    total = meta['n_users'] + meta['n_organic'] if n_users is None else n_users
+    n_org = meta['n_organic'] if organic_only_below is None else max(0, min(total, organic_only_below - first_user))
+    return (meta, cols) + run_sim(gu.env_config(meta), total - n_org, n_org, first_user, with_ledger,
+                                  **gu.policy_args(meta, cols), **extra)
+
+
+def assert_rows_are_the_reference_fixture(name, meta, cols, rows, cnt):
+    """The rows and counters of a run of the fixture's users held to it."""
     # ps: float64 on both sides (BanditMF logs a float32 torch logit: compared at float32 resolution)
     gu.assert_rows_equal(rows, cols, ps_rtol=1e-5 if meta['agent'] == 'bmf' else 1e-12, what=name)
     if 'p_click' in cols:          # every real bandit row's click probability vs the reference's own value
@@ -57,6 +63,12 @@ def test_hip_reproduces_reference_fixture(name):
     assert cnt['bandit'] + cnt['phantom'] == int((cols['z'] == 1).sum())
     assert cnt['clicks'] == int((cols['c'] == 1).sum())
     assert cnt['live'] == 0 and cnt['log_dropped'] == 0
+
+
+@pytest.mark.parametrize('name', gu.fixtures('philox_'))
+def test_hip_reproduces_reference_fixture(name):
+    """The committed logs of the unmodified reference (counter RNG injected), row for row."""
+    assert_rows_are_the_reference_fixture(name, *run_fixture(name))
 
 
 CASES = [

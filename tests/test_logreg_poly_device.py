@@ -10,6 +10,7 @@ import pytest
 import torch
 from scipy.special import expit
 
+import adversarial_util as au
 from device_util import assert_frames_equal, constant_agent, make_env
 import golden_util as gu
 import recogym_amd as recogym
@@ -34,16 +35,31 @@ def frozen_of(cols, P, **cfg):
     return LogregPolyFrozenAgent(Configuration({'num_products': P, **cfg}), cols['poly_coef'], cols['poly_intercept'])
 
 
-def run_fixture(name):
+def run_fixture(name, first_user=0, n_users=None, organic_only_below=0, ledger=False):
+    """-> meta, cols, rows, counters, the raw sorted log[, the launch ledger and the unresolved list (poly_verify's outcome)]"""
     from recogym_amd.sim import Simulator
     meta, cols = gu.load(name)
-    P, n = meta['env_args']['num_products'], meta['n_users']
+    P, n = meta['env_args']['num_products'], meta['n_users'] if n_users is None else n_users
     sim = Simulator(gu.env_config(meta), n, device='cuda:0', **frozen_of(cols, P).device_policy())
-    sim.reset_users(0, n)
+    sim.reset_users(first_user, n, organic_only_below=organic_only_below)
     sim.run()
     rows, cnt, raw = sim.rows(), sim.counters(), sim.sorted_log_host()[0]
+    extra = ()
+    if ledger:
+        stands = sim.poly_verify()
+        extra = (au.ledger(sim), stands, sim.poly_unresolved.copy())
     sim.close()
-    return meta, cols, rows, cnt, raw
+    return (meta, cols, rows, cnt, raw) + extra
+
+
+def assert_log_equals_the_reference(name, meta, cols, rows, cnt):
+    """The rows and counters of a run of the fixture's users (of several runs: rows concatenated, counters summed) held to it."""
+    gu.assert_rows_equal(rows, cols, ps_rtol=0, what=name)
+    census = meta['census']
+    print(name, {k: cnt[k] for k in ('lr_acts', 'lr_rows', 'poly_table', 'poly_unresolved')}, census)
+    assert cnt['poly_table'] == census['table'] and cnt['poly_unresolved'] == census['unresolved'] == 0
+    assert cnt['lr_acts'] == census['acts']
+    assert cnt['live'] == 0 and cnt['log_dropped'] == 0 and cnt['hist_overflow'] == 0
 
 
 @pytest.mark.parametrize('name', FIXTURES)
@@ -51,12 +67,7 @@ def test_device_log_equals_the_reference(name):
     """sigma_omega > 0 (lock-step rounds) and = 0, P = 10 and P = 40 (saturated acts), the IPS-weighted fit, and the shifted model
     whose acts all lie on the step table with lower indices winning merges."""
     meta, cols, rows, cnt, _ = run_fixture(name)
-    gu.assert_rows_equal(rows, cols, ps_rtol=0, what=name)
-    census = meta['census']
-    print(name, {k: cnt[k] for k in ('lr_acts', 'lr_rows', 'poly_table', 'poly_unresolved')}, census)
-    assert cnt['poly_table'] == census['table'] and cnt['poly_unresolved'] == census['unresolved'] == 0
-    assert cnt['lr_acts'] == census['acts']
-    assert cnt['live'] == 0 and cnt['log_dropped'] == 0 and cnt['hist_overflow'] == 0
+    assert_log_equals_the_reference(name, meta, cols, rows, cnt)
 
 
 def test_some_fixture_proves_the_table_and_a_merge():
@@ -69,12 +80,18 @@ def test_two_runs_give_the_same_log():
     assert np.array_equal(a[4], b[4]) and a[3] == b[3]
 
 
-def test_generate_logs_with_the_trained_agent_equals_the_host_route():
+def trained_agent():
+    """-> the meta of poly_p10, LogregPolyAgent trained on the fixture's training log"""
     meta, cols = gu.load('poly_p10')
     train = {k[len('trainlog_'):]: v for k, v in cols.items() if k.startswith('trainlog_')}
     from make_golden_ope import log_frame
     agent = LogregPolyAgent(Configuration({**logreg_poly_args, 'num_products': 10, 'random_seed': 7}))
     agent.train_from_log(log_frame(train))
+    return meta, agent
+
+
+def test_generate_logs_with_the_trained_agent_equals_the_host_route():
+    meta, agent = trained_agent()
     env = make_env(meta['env_args'])
     with warnings.catch_warnings():
         warnings.simplefilter('error', RuntimeWarning)

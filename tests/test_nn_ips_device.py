@@ -7,6 +7,7 @@ import warnings
 import numpy as np
 import pytest
 
+import adversarial_util as au
 import golden_util as gu
 import nn_ips_util as nu
 from device_util import make_env
@@ -26,27 +27,29 @@ def bits(x):
     return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
 
 
-def run_fixture(name):
+def run_fixture(name, first_user=0, n_users=None, organic_only_below=0, ledger=False):
     from recogym_amd.sim import Simulator
     meta, cols = gu.load(name)
-    P, n = meta['env_args']['num_products'], meta['n_users']
+    P, n = meta['env_args']['num_products'], meta['n_users'] if n_users is None else n_users
     state = nu.fixture_state(meta, cols)
     frozen = NnIpsFrozenAgent(Configuration({'num_products': P}), state)
     sim = Simulator(gu.env_config(meta), n, device='cuda:0', **frozen.device_policy())
-    sim.reset_users(0, n)
+    sim.reset_users(first_user, n, organic_only_below=organic_only_below)
     sim.run()
     rows, cnt, raw = sim.rows(), sim.counters(), sim.sorted_log_host()[0]
     stands = sim.poly_verify()
     listed, refuted, overflow = sim.poly_unresolved.copy(), sim.poly_refuted.copy(), sim.poly_overflow
     launched = sim.get_option('launched_nn_ips')
+    led = au.ledger(sim) if ledger else None
     sim.close()
     return dict(meta=meta, cols=cols, state=state, rows=rows, cnt=cnt, raw=raw, stands=stands, listed=listed, refuted=refuted,
-                overflow=overflow, launched=launched)
+                overflow=overflow, launched=launched, ledger=led)
 
 
-@pytest.mark.parametrize('name', nu.FIXTURES)
-def test_device_log_equals_the_fixture(name):
-    r = run_fixture(name)
+def assert_run_equals_the_fixture(name, r, lockstep=False):
+    """The results of a run of the fixture's users (run_fixture's dict; of several runs: rows and lists concatenated, counters
+    summed) held to the fixture.  `lockstep`: the run took an event per launch (not the run-ahead rounds of the default form), where
+    the device lists an unresolved act of a bandit user under the act's own event (nu.rule_over_log's t_lockstep)."""
     rows, cols, P = r['rows'], r['cols'], r['meta']['env_args']['num_products']
     no_ps = rows.copy()
     no_ps['ps'] = cols['ps']                                 # the integer columns here; ps below, against its own bound
@@ -59,7 +62,7 @@ def test_device_log_equals_the_fixture(name):
             err = abs(rows['ps'][i] / cols['ps'][i] - 1.0)
             worst = max(worst, err / act['bound'])
             assert err <= act['bound'], (name, i, rows['ps'][i], cols['ps'][i], act['bound'])
-    want = {(a['user'], a['t']) for a in acts if a['flags'] & UNRESOLVED}
+    want = {(a['user'], a['t_lockstep' if lockstep else 't']) for a in acts if a['flags'] & UNRESOLVED}
     got = {(int(u), int(t)) for u, t, _ in r['listed']}
     print(name, {k: r['cnt'][k] for k in ('lr_acts', 'lr_rows', 'poly_unresolved')}, r['meta']['census'], 'worst ps error / bound', worst)
     assert r['stands'] and not r['overflow'] and len(r['refuted']) == 0
@@ -67,6 +70,11 @@ def test_device_log_equals_the_fixture(name):
     assert r['cnt']['lr_acts'] == len(acts) and r['launched'] > 0
     assert 10 * len(want) <= len(acts)                      # at least 90 % of the acts are resolved on the device
     assert r['cnt']['live'] == 0 and r['cnt']['log_dropped'] == 0 and r['cnt']['hist_overflow'] == 0
+
+
+@pytest.mark.parametrize('name', nu.FIXTURES)
+def test_device_log_equals_the_fixture(name):
+    assert_run_equals_the_fixture(name, run_fixture(name))
 
 
 def test_two_runs_give_the_same_log():
@@ -229,7 +237,8 @@ def assert_frames_equal_ps_bounded(got, want, P, state):
     assert np.array_equal(np.isnan(g), np.isnan(w))
 
 
-def test_generate_logs_with_the_trained_agent_equals_the_host_route():
+def trained_agent():
+    """-> the meta of nn_ips_p10, NnIpsAgent trained on the fixture's training log"""
     import torch
     from make_golden_ope import log_frame
     meta, cols = gu.load('nn_ips_p10')
@@ -238,6 +247,11 @@ def test_generate_logs_with_the_trained_agent_equals_the_host_route():
     agent.train_from_log(log_frame(train))
     torch.manual_seed(7)
     agent.build()
+    return meta, agent
+
+
+def test_generate_logs_with_the_trained_agent_equals_the_host_route():
+    meta, agent = trained_agent()
     env = make_env(meta['env_args'])
     with warnings.catch_warnings():
         warnings.simplefilter('error', RuntimeWarning)
