@@ -57,6 +57,8 @@ extern "C" {
 /* v14, additive since: RG_POLICY_NN_IPS with rg_sim_set_nn_ips and rg_sim_debug_nn_acts (the three-layer perceptron act of NnIpsAgent
  * in the step loop, the first argmax policy whose logged propensity is a model output) and the flag RG_NN_UNRESOLVED; its unresolved
  * acts share the same list, counter and reader. */
+/* v14, additive since: rg_ope_nn_workspace_bytes / rg_ope_replay_nn / rg_ope_replay_nn_eg and rg_ope_bayes_workspace_bytes /
+ * rg_ope_replay_bayes / rg_ope_replay_bayes_eg (the off-policy replay of those two agents, plain and under EpsilonGreedy). */
 #define RG_ABI_VERSION 14
 
 /* error codes */
@@ -758,6 +760,65 @@ int rg_ope_replay_poly_eg(const rg_ope_poly* model, const rg_ope_eg* eg, const r
                           uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const,
                           double* d_ratio, uint8_t* d_click, double* d_sums, uint8_t* d_greedy, int32_t* d_h0,
                           void* d_workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Off-policy evaluation of NnIpsAgent's argmax form (NnIpsFrozenAgent, reference agents/nn_ips.py:111-137 with with_ps_all = True,
+ * select_randomly off) and of BayesianAgentVB (BayesianVBFrozenAgent, reference agents/bayesian_poly_vb.py:71-91 with with_ps_all =
+ * True): replay a sorted log under the model.  Stateless (no rg_sim handle).  The arrays are device arrays laid out as
+ * rg_sim_set_nn_ips / rg_sim_set_bayes_vb take them.  The policy sees the user's cumulative view counts (all organic rows so far,
+ * across sessions); the act is the step loop's (k_nn_acts / k_bayes_acts: the same order of operations, margin and flags),
+ * pi = [action == a], r = pi / ps.  The sampling NN has no replay form (its `ps-a` is torch's fp32 softmax).
+ */
+typedef struct rg_ope_nn {
+    uint32_t num_products;          /* P, 1 .. 4000 */
+    uint32_t num_hidden;            /* H, 1 .. 1024 */
+    const double* w1t;              /* [P][H] */
+    const double* b1;               /* [H] */
+    const double* w2t;              /* [H][H] */
+    const double* b2;               /* [H] */
+    const double* w3t;              /* [H][P] */
+    const double* b3;               /* [P] */
+} rg_ope_nn;
+
+typedef struct rg_ope_bayes {
+    uint32_t num_products;          /* P <= RG_EV_INDEX_MASK */
+    uint32_t num_samples;           /* S >= 1; P P S doubles within 2 GiB */
+    const double* lam_t;            /* [P][P][S], [viewed product][action][sample] */
+} rg_ope_bayes;
+
+/* rg_ope_nn_workspace_bytes / rg_ope_bayes_workspace_bytes: device workspace the unit's replay needs for n_users users the longest
+ * of which has max_user_rows rows (0 = error, see rg_last_error).
+ * rg_ope_replay_nn / rg_ope_replay_bayes: argument for argument rg_ope_replay_poly after the model, with its validation of the log
+ * (RG_EINVAL before anything is written), its unresolved list from byte 256 — up to 4096 entries of three uint32 (user index,
+ * position of the bandit row the act was computed at within the user's rows, action taken), in no fixed order: the acts flagged
+ * RG_NN_UNRESOLVED (a count above 2^24 among them) / RG_BAYES_UNRESOLVED — and its rule that the ratios are written with the
+ * device's action; a caller that needs the reference's action on such acts recomputes them on the host
+ * (recogym_amd.sim.replay_verify).  RG_EINVAL also for a null model or array, num_hidden outside 1 .. 1024, num_products above 4000
+ * (NN) or RG_EV_INDEX_MASK, num_samples == 0 or a model beyond 2 GiB, and an NN value that is not finite; RG_ENOMEM for a workspace
+ * too small.  The first int64 words of the workspace afterwards:
+ *   NN     [0] error bits (0), [1] acts computed, [2] unresolved acts, [3] non-zero when more than 4096 were, [4] w1t rows read;
+ *   Bayes  [0] error bits (0), [1] acts computed, [2] acts decided in the saturated zone, [3] unresolved acts, [4] non-zero when
+ *          more than 4096 were, [5] lam_t rows read.
+ * d_sums holds the same bits on every run.  The Bayes unit synchronises `stream` once (the validation's verdict); the NN unit once
+ * more before it: the library downloads the net for the margin's absolute row sums and the finiteness check, as rg_sim_set_nn_ips does.
+ * rg_ope_replay_nn_eg / rg_ope_replay_bayes_eg: the EpsilonGreedy target round the model, argument for argument
+ * rg_ope_replay_poly_eg after the model (the act is the wrapper's greedy action g; d_greedy / d_h0 as there). */
+size_t rg_ope_nn_workspace_bytes(const rg_ope_nn* model, uint64_t n_users, uint32_t max_user_rows);
+int rg_ope_replay_nn(const rg_ope_nn* model, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                     uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
+                     uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream);
+int rg_ope_replay_nn_eg(const rg_ope_nn* model, const rg_ope_eg* eg, const rg_event* d_rows, const int64_t* d_offsets,
+                        uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const,
+                        double* d_ratio, uint8_t* d_click, double* d_sums, uint8_t* d_greedy, int32_t* d_h0,
+                        void* d_workspace, size_t workspace_bytes, void* stream);
+size_t rg_ope_bayes_workspace_bytes(const rg_ope_bayes* model, uint64_t n_users, uint32_t max_user_rows);
+int rg_ope_replay_bayes(const rg_ope_bayes* model, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                        uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
+                        uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream);
+int rg_ope_replay_bayes_eg(const rg_ope_bayes* model, const rg_ope_eg* eg, const rg_event* d_rows, const int64_t* d_offsets,
+                           uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const,
+                           double* d_ratio, uint8_t* d_click, double* d_sums, uint8_t* d_greedy, int32_t* d_h0,
+                           void* d_workspace, size_t workspace_bytes, void* stream);
 
 /*
  * recall@k (evaluate_recall_at_k, reference evaluate_agent.py:832-870) over a sorted log.  A bandit row i of user u is COUNTED

@@ -101,6 +101,17 @@ class RgOpePoly(C.Structure):
                 ('th', C.c_void_p), ('intercept', C.c_double)]
 
 
+class RgOpeNn(C.Structure):
+    """struct rg_ope_nn: NnIpsAgent's net of rg_ope_replay_nn (device arrays, rg_sim_set_nn_ips's layout)."""
+    _fields_ = [('num_products', C.c_uint32), ('num_hidden', C.c_uint32), ('w1t', C.c_void_p), ('b1', C.c_void_p), ('w2t', C.c_void_p),
+                ('b2', C.c_void_p), ('w3t', C.c_void_p), ('b3', C.c_void_p)]
+
+
+class RgOpeBayes(C.Structure):
+    """struct rg_ope_bayes: BayesianAgentVB's posterior samples of rg_ope_replay_bayes (a device array, rg_sim_set_bayes_vb's layout)."""
+    _fields_ = [('num_products', C.c_uint32), ('num_samples', C.c_uint32), ('lam_t', C.c_void_p)]
+
+
 class RgOpeEg(C.Structure):
     """struct rg_ope_eg: the EpsilonGreedy wrapper of rg_ope_replay_eg."""
     _fields_ = [('epsilon', C.c_double), ('seed', C.c_uint64), ('pure_new', C.c_uint32), ('reserved', C.c_uint32),
@@ -113,7 +124,9 @@ class RgOpeEg(C.Structure):
 # the bandit row within the user's rows, action taken).
 OPE_HEAD_BYTES = 256
 OPE_HEADS = {'logreg': ('error', 'acts', 'exact', 'rows_read'),
-             'poly': ('error', 'acts', 'table', 'lower', 'unresolved', 'overflow', 'rows_read')}
+             'poly': ('error', 'acts', 'table', 'lower', 'unresolved', 'overflow', 'rows_read'),
+             'nn': ('error', 'acts', 'unresolved', 'overflow', 'rows_read'),
+             'bayes': ('error', 'acts', 'saturated', 'unresolved', 'overflow', 'rows_read')}
 OPE_POLY_LIST_CAP = 4096
 OPE_POLY_LIST_ENTRY_BYTES = 12
 # recall@k (rg_ope_recall_hits, rg_ope_recall_logreg): the values of d_hit; the ranking form's head words and, from byte
@@ -219,6 +232,16 @@ SYMBOLS = {
     'rg_ope_replay_poly_eg': (C.c_int, [C.POINTER(RgOpePoly), C.POINTER(RgOpeEg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
                                         C.c_uint32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    **{name.format(unit): (res, [C.POINTER(model), *args])
+       for unit, model in (('nn', RgOpeNn), ('bayes', RgOpeBayes))
+       for name, res, args in (
+           ('rg_ope_{}_workspace_bytes', C.c_size_t, [C.c_uint64, C.c_uint32]),
+           # (after the model: rg_ope_replay_poly's / rg_ope_replay_poly_eg's arguments)
+           ('rg_ope_replay_{}', C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_double, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+           ('rg_ope_replay_{}_eg', C.c_int, [C.POINTER(RgOpeEg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
+                                             C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_size_t, C.c_void_p]))},
     'rg_ope_recall_hits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     'rg_ope_recall_logreg_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpeLogreg), C.c_uint64, C.c_uint32, C.c_uint32]),

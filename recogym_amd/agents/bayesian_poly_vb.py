@@ -186,8 +186,16 @@ class BayesianVBFrozenAgent(Agent):
         return None
 
     def ope_policy_checked(self):
-        """None: off-policy evaluation of this agent takes the host loop."""
-        return None
+        """The replay form of the act (rg_ope_replay_bayes; `ps-a` is one-hot at the act), which lists the acts its margin cannot
+        resolve for the host's confirmation (evaluate_agent.ope_replay, sim.replay_verify).  Opt-in: the configuration key
+        `device_replay`.  None — the host loop — without it, without with_ps_all, with a weight function, with a model beyond
+        MODEL_BYTES_CAP or one that is not finite."""
+        c = self.config
+        if not getattr(c, 'with_ps_all', False) or not getattr(c, 'device_replay', False) or self.history is not None:
+            return None
+        if self.Lambda.size * 8 > MODEL_BYTES_CAP or not np.isfinite(self.Lambda).all():
+            return None
+        return dict(kind=_abi.RG_POLICY_BAYES_VB, num_products=int(c.num_products), policy_seed=0, bayes_vb=dict(lam=self.Lambda))
 
     def reset(self):
         self.views = np.zeros((1, self.config.num_products), dtype=np.int16)     # the reference's dense int16 counts

@@ -229,8 +229,17 @@ class NnIpsFrozenAgent(Agent):
         return None
 
     def ope_policy_checked(self):
-        """None: off-policy evaluation of this agent takes the host loop."""
-        return None
+        """The replay form of the argmax act (rg_ope_replay_nn; `ps-a` is one-hot at the act), which lists the acts its margin cannot
+        resolve for the host's confirmation (evaluate_agent.ope_replay, sim.replay_verify).  Opt-in: the configuration key
+        `device_replay`.  None — the host loop — without it, without with_ps_all, with a weight function, with select_randomly
+        (its `ps-a` is torch's fp32 softmax: no device value equals it), with a net beyond the kernel's caps or one that is not
+        finite."""
+        c = self.config
+        if not getattr(c, 'with_ps_all', False) or not getattr(c, 'device_replay', False) or self.history is not None or self.select_randomly:
+            return None
+        if self.model.H > HIDDEN_CAP or self.model.P > PRODUCTS_CAP or not self.model.finite():
+            return None
+        return dict(kind=_abi.RG_POLICY_NN_IPS, num_products=int(c.num_products), policy_seed=0, nn_ips=dict(state=self.state()))
 
     def reset(self):
         self.views = np.zeros(self.config.num_products, dtype=np.int64)

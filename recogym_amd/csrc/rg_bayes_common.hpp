@@ -1,5 +1,5 @@
 // rg_bayes_common.hpp — the act of BayesianAgentVB (RG_POLICY_BAYES_VB) on one history, by a whole wave: shared by the step loop
-// (rg_bayes_vb.hip) and, later, an off-policy replay (as rg_ope_poly.hip takes poly_act).  DESIGN.md 4h has the contract, the
+// (rg_bayes_vb.hip) and the off-policy replay (rg_ope_bayes.hip, as rg_ope_poly.hip takes poly_act).  DESIGN.md 4h has the contract, the
 // margin W term by term and the proof of the saturated zone.
 //
 // The reference's act (agents/bayesian_poly_vb.py:71-91) is argmax_a mean_s expit(sum_p views[p] Lambda[s][p P + a]) over the S

@@ -548,6 +548,17 @@ search_kernel_t bayes_acts_kernel();                       // rg_bayes_vb.hip
 void (*bayes_debug_kernel())(DevSim, int32_t*, uint8_t*, double*);
 void (*nn_acts_kernel())(DevSim, NnModel, uint32_t);      // rg_nn_ips.hip
 void (*nn_debug_kernel())(DevSim, NnModel, int32_t*, uint8_t*, double*, double*);
+// The net as a kernel takes it, from the six device arrays of rg_sim_set_nn_ips (rg_host.hip; who: the caller's name for the error
+// text): downloads them (the call synchronises), computes the margin's absolute row sums A2, A3, refuses a value that is not finite
+// (RG_EINVAL), and decides the staging for a block of `waves` waves — the matrices go to LDS behind the 2 H doubles per wave of layer
+// vectors where both stay within kNnStageBytes.  *smem: the block's dynamic LDS bytes.  Shared by the step loop and the replay
+// (rg_ope_nn.hip): neither takes A2 / A3 from its caller.
+int nn_host_model(const char* who, uint32_t P, uint32_t H, const double* d_w1t, const double* d_b1, const double* d_w2t, const double* d_b2,
+                  const double* d_w3t, const double* d_b3, int waves, NnModel* m, size_t* smem);
+// more than 64 KiB of LDS needs an explicit opt-in per kernel instantiation (set_max_lds: whatever the size)
+template <class Kernel> void set_max_lds(Kernel kernel, size_t bytes) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+}
 void (*wh_insert_kernel())(DevSim, WhRun, uint32_t);      // rg_weight_history.hip
 void (*wh_acts_kernel())(DevSim, WhRun, uint32_t, uint32_t);
 void (*wh_debug_set_kernel())(DevSim, WhRun, const uint32_t*, const uint32_t*, const uint16_t*, uint32_t);

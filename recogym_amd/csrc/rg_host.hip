@@ -670,12 +670,44 @@ static_assert(sweep_slices(2000, 256, -1, 32) == SweepSlices{8, 32} && sweep_sli
 // (the fused-prefix sweep of a walked run, k_sweep_xh, k_draw_tp, run_walk_pipe)
 bool f16_pipelined(const rg_sim* sim) { return sim->bf16_kernel == bf16p_kernel_for(sim->d) && sim->d.f16 && !sim->d.wide; }
 
-// more than 64 KiB of dynamic LDS needs an explicit opt-in per kernel instantiation (set_max_lds: whatever the size)
-template <class Kernel> void set_max_lds(Kernel kernel, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-}
+// (set_max_lds: rg_common.hpp)
 template <class Kernel> void opt_in_lds(Kernel kernel, size_t bytes) {
     if (bytes > 64 * 1024) set_max_lds(kernel, bytes);
+}
+
+// max over the columns c < cols of (sum over the rows r < rows, ascending, of |wt[r cols + c]|) + |b[c]|: float64, one add per term
+// (agents/nn_ips.py: nn_abs_row_sums computes the same bits); -1 when a value is not finite
+static double nn_abs_row_sums(const std::vector<double>& wt, const std::vector<double>& b, size_t rows, size_t cols) {
+    double best = 0.0;
+    for (size_t c = 0; c < cols; ++c) {
+        double r = 0.0;
+        for (size_t k = 0; k < rows; ++k) r = r + std::fabs(wt[k * cols + c]);
+        r = r + std::fabs(b[c]);
+        if (!std::isfinite(r)) return -1.0;
+        best = r > best ? r : best;
+    }
+    return best;
+}
+
+int nn_host_model(const char* who, uint32_t num_products, uint32_t num_hidden, const double* d_w1t, const double* d_b1, const double* d_w2t,
+                  const double* d_b2, const double* d_w3t, const double* d_b3, int waves, NnModel* m, size_t* smem) {
+    const size_t P = num_products, H = num_hidden;
+    // the absolute row sums of the margin, once (the call synchronises); layer 1's values only have to be finite
+    std::vector<double> w1(P * H), b1(H), w2(H * H), b2(H), w3(H * P), b3(P);
+    HIP_TRY(hipMemcpy(w1.data(), d_w1t, sizeof(double) * P * H, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b1.data(), d_b1, sizeof(double) * H, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(w2.data(), d_w2t, sizeof(double) * H * H, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b2.data(), d_b2, sizeof(double) * H, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(w3.data(), d_w3t, sizeof(double) * H * P, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b3.data(), d_b3, sizeof(double) * P, hipMemcpyDeviceToHost));
+    const double A1 = nn_abs_row_sums(w1, b1, P, H), A2 = nn_abs_row_sums(w2, b2, H, H), A3 = nn_abs_row_sums(w3, b3, H, P);
+    if (A1 < 0.0 || A2 < 0.0 || A3 < 0.0) return fail(RG_EINVAL, "%sthe model holds a value that is not finite", who);
+    m->w1t = d_w1t; m->b1 = d_b1; m->w2t = d_w2t; m->b2 = d_b2; m->w3t = d_w3t; m->b3 = d_b3;
+    m->A2 = A2; m->A3 = A3; m->H = num_hidden;
+    const size_t rows = sizeof(double) * 2 * static_cast<size_t>(waves) * H, mats = sizeof(double) * (2 * P * H + H * H);
+    m->staged = rows + mats <= kNnStageBytes ? 1u : 0u;
+    *smem = rows + (m->staged ? mats : 0);
+    return RG_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1706,20 +1738,6 @@ int rg_sim_set_bayes_vb(rg_sim* sim, const double* d_lam_t, uint32_t num_samples
     return RG_OK;
 }
 
-// max over the columns c < cols of (sum over the rows r < rows, ascending, of |wt[r cols + c]|) + |b[c]|: float64, one add per term
-// (agents/nn_ips.py: nn_abs_row_sums computes the same bits); -1 when a value is not finite
-static double nn_abs_row_sums(const std::vector<double>& wt, const std::vector<double>& b, size_t rows, size_t cols) {
-    double best = 0.0;
-    for (size_t c = 0; c < cols; ++c) {
-        double r = 0.0;
-        for (size_t k = 0; k < rows; ++k) r = r + std::fabs(wt[k * cols + c]);
-        r = r + std::fabs(b[c]);
-        if (!std::isfinite(r)) return -1.0;
-        best = r > best ? r : best;
-    }
-    return best;
-}
-
 int rg_sim_set_nn_ips(rg_sim* sim, const double* d_w1t, const double* d_b1, const double* d_w2t, const double* d_b2,
                       const double* d_w3t, const double* d_b3, uint32_t num_hidden) {
     if (!sim) return fail(RG_EINVAL, "sim is NULL");
@@ -1727,24 +1745,8 @@ int rg_sim_set_nn_ips(rg_sim* sim, const double* d_w1t, const double* d_b1, cons
     if (sim->users_reset) return fail(RG_ESTATE, "rg_sim_set_nn_ips must be called before rg_sim_reset_users");
     if (!d_w1t || !d_b1 || !d_w2t || !d_b2 || !d_w3t || !d_b3) return fail(RG_EINVAL, "a model array is NULL");
     if (num_hidden == 0 || num_hidden > kNnHidden) return fail(RG_EINVAL, "num_hidden %u outside [1, %u]", num_hidden, kNnHidden);
-    const size_t P = sim->d.P, H = num_hidden;
-    if (P > kNnProducts) return fail(RG_EINVAL, "RG_POLICY_NN_IPS serves at most %u products (%u)", kNnProducts, sim->d.P);
-    // the absolute row sums of the margin, once (the call synchronises); layer 1's values only have to be finite
-    std::vector<double> w1(P * H), b1(H), w2(H * H), b2(H), w3(H * P), b3(P);
-    HIP_TRY(hipMemcpy(w1.data(), d_w1t, sizeof(double) * P * H, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(b1.data(), d_b1, sizeof(double) * H, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(w2.data(), d_w2t, sizeof(double) * H * H, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(b2.data(), d_b2, sizeof(double) * H, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(w3.data(), d_w3t, sizeof(double) * H * P, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(b3.data(), d_b3, sizeof(double) * P, hipMemcpyDeviceToHost));
-    const double A1 = nn_abs_row_sums(w1, b1, P, H), A2 = nn_abs_row_sums(w2, b2, H, H), A3 = nn_abs_row_sums(w3, b3, H, P);
-    if (A1 < 0.0 || A2 < 0.0 || A3 < 0.0) return fail(RG_EINVAL, "the model holds a value that is not finite");
-    NnModel& m = sim->nn;
-    m.w1t = d_w1t; m.b1 = d_b1; m.w2t = d_w2t; m.b2 = d_b2; m.w3t = d_w3t; m.b3 = d_b3;
-    m.A2 = A2; m.A3 = A3; m.H = num_hidden;
-    const size_t rows = sizeof(double) * 2 * (kBlock / 64) * H, mats = sizeof(double) * (2 * P * H + H * H);
-    m.staged = rows + mats <= kNnStageBytes ? 1u : 0u;
-    sim->nn_smem = rows + (m.staged ? mats : 0);
+    if (sim->d.P > kNnProducts) return fail(RG_EINVAL, "RG_POLICY_NN_IPS serves at most %u products (%u)", kNnProducts, sim->d.P);
+    if (int rc = nn_host_model("", sim->d.P, num_hidden, d_w1t, d_b1, d_w2t, d_b2, d_w3t, d_b3, kBlock / 64, &sim->nn, &sim->nn_smem)) return rc;
     // the kernels hold 12.3 KB of static LDS besides (history rows, counters): from 64 KiB of the TOTAL on, the opt-in is needed
     if (sim->nn_smem + kNnStaticLds > 64 * 1024) {
         set_max_lds(nn_acts_kernel(), sim->nn_smem);

@@ -1,5 +1,6 @@
 // rg_nn_common.hpp — the act of NnIpsAgent (RG_POLICY_NN_IPS) on one history, by a whole wave: used by the step loop and the debug
-// entry (rg_nn_ips.hip).  DESIGN.md 4i has the contract, the margin W term by term and its proof.
+// entry (rg_nn_ips.hip) and by the off-policy replay (rg_ope_nn.hip), with the block's dynamic LDS they share (NnLds, nn_lds).
+// DESIGN.md 4i has the contract, the margin W term by term and its proof.
 //
 // The reference's act (agents/nn_ips.py:43-63, 111-137) is a = argmax prob, ps = prob[a] with
 //     prob = softmax(W3 sigmoid(W2 sigmoid(W1 x + b1) + b2) + b3)            x the user's view counts,
@@ -157,6 +158,29 @@ __device__ __forceinline__ uint32_t nn_act(const NnModel& m, uint32_t P, const H
     __builtin_amdgcn_wave_barrier();                      // the LDS rows are the next act's from here
     *flags = resolved ? 0u : RG_NN_UNRESOLVED;
     return a1;
+}
+
+// The block's dynamic LDS (nn_host_model sizes it on the host): two layer vectors of H doubles per wave, then — where m.staged —
+// the three matrices, copied once per block.  kWaves: the waves of the block (the step loop's kBlock / 64, the replay's kOpeWaves).
+struct NnLds {
+    double* rows;
+    const double* w1t; const double* w2t; const double* w3t;
+};
+
+template <int kWaves>
+__device__ __forceinline__ NnLds nn_lds(const NnModel& m, uint32_t P, char* smem) {
+    NnLds l;
+    l.rows = reinterpret_cast<double*>(smem);
+    l.w1t = m.w1t; l.w2t = m.w2t; l.w3t = m.w3t;
+    if (m.staged) {
+        double* s_w = l.rows + static_cast<size_t>(2) * kWaves * m.H;
+        const uint32_t n1 = P * m.H, n2 = m.H * m.H;
+        for (uint32_t i = threadIdx.x; i < n1; i += 64 * kWaves) { s_w[i] = m.w1t[i]; s_w[n1 + n2 + i] = m.w3t[i]; }
+        for (uint32_t i = threadIdx.x; i < n2; i += 64 * kWaves) s_w[n1 + i] = m.w2t[i];
+        l.w1t = s_w; l.w2t = s_w + n1; l.w3t = s_w + n1 + n2;
+    }
+    __syncthreads();
+    return l;
 }
 
 }  // namespace rgk

@@ -5,28 +5,6 @@
 
 namespace rgk {
 
-// The block's dynamic LDS (nn_lds_bytes on the host): two layer vectors of H doubles per wave, then — where m.staged — the three
-// matrices, copied once per block.
-struct NnLds {
-    double* rows;
-    const double* w1t; const double* w2t; const double* w3t;
-};
-
-__device__ __forceinline__ NnLds nn_lds(const NnModel& m, uint32_t P, char* smem) {
-    NnLds l;
-    l.rows = reinterpret_cast<double*>(smem);
-    l.w1t = m.w1t; l.w2t = m.w2t; l.w3t = m.w3t;
-    if (m.staged) {
-        double* s_w = l.rows + static_cast<size_t>(2) * (kBlock / 64) * m.H;
-        const uint32_t n1 = P * m.H, n2 = m.H * m.H;
-        for (uint32_t i = threadIdx.x; i < n1; i += kBlock) { s_w[i] = m.w1t[i]; s_w[n1 + n2 + i] = m.w3t[i]; }
-        for (uint32_t i = threadIdx.x; i < n2; i += kBlock) s_w[n1 + i] = m.w2t[i];
-        l.w1t = s_w; l.w2t = s_w + n1; l.w3t = s_w + n1 + n2;
-    }
-    __syncthreads();
-    return l;
-}
-
 // The act of the user in `slot` (wave-uniform), by the whole wave: nn_act on the user's history row.
 __device__ uint32_t nn_act_wave(const DevSim& d, const NnModel& m, const NnLds& l, uint32_t slot, int lane, int wave, double* s_cnt,
                                 uint32_t* s_prod, uint32_t* flags, double* ps_out, double* z_out) {
@@ -46,7 +24,7 @@ __global__ void __launch_bounds__(kBlock) k_nn_acts(DevSim d, NnModel m, uint32_
     const uint32_t n = d.lr_cnt[t];
     if (blockIdx.x * (kBlock / 64) >= n) return;          // (the whole block: no act of the grid-stride loop is its)
     if (threadIdx.x < 2) s_sum[threadIdx.x] = 0ull;
-    const NnLds l = nn_lds(m, d.P, smem_raw);
+    const NnLds l = nn_lds<kBlock / 64>(m, d.P, smem_raw);
     const uint32_t waves_total = gridDim.x * (kBlock / 64);
     unsigned long long c_acts = 0, c_rows = 0;
     for (uint32_t w = blockIdx.x * (kBlock / 64) + wave; w < n; w += waves_total) {
@@ -87,7 +65,7 @@ __global__ void __launch_bounds__(kBlock) k_debug_nn_acts(DevSim d, NnModel m, i
     __shared__ uint32_t s_prod[kBlock / 64][kPolyHist];
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     if (blockIdx.x * (kBlock / 64) >= d.n_users) return;
-    const NnLds l = nn_lds(m, d.P, smem_raw);
+    const NnLds l = nn_lds<kBlock / 64>(m, d.P, smem_raw);
     const uint32_t waves_total = gridDim.x * (kBlock / 64);
     for (uint32_t i = blockIdx.x * (kBlock / 64) + wave; i < d.n_users; i += waves_total) {
         uint32_t fl = 0;

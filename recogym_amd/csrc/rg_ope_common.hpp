@@ -1,6 +1,6 @@
-// rg_ope_common.hpp — the skeleton the off-policy replay units share (rg_ope.hip, rg_ope_logreg.hip, rg_ope_eg.hip, rg_ope_poly.hip;
-// DESIGN.md §4b), and what the two units that keep a sorted view history share besides: the list insert (ope_list_add) and the
-// validation of the log (ope_check_log).
+// rg_ope_common.hpp — the skeleton the off-policy replay units share (rg_ope.hip, rg_ope_logreg.hip, rg_ope_eg.hip, rg_ope_poly.hip,
+// rg_ope_nn.hip, rg_ope_bayes.hip), and what the units that keep a sorted view history share besides: the list
+// insert (ope_list_add) and the validation of the log (ope_check_log).
 //
 // One wave per user, users assigned statically (wave w takes users w, w + W, ...).  A user's rows stream in coalesced 64-row
 // chunks (16-byte rg_event per lane + the row's float64 ps); a unit computes the target policy's pi of every bandit lane, the

@@ -10,9 +10,10 @@ verify_agents_IPS, verify_agents_SNIPS, evaluate_recall_at_k, verify_agents_reca
 `reco_log` is a DataFrame with the reference's columns (t, u, z, v, a, c, ps), a Simulator or a
 Simulator.device_log().  Users 0 .. max(u) - 1 are evaluated (the reference's range(max(reco_log.u)):
 the user with the largest id is not), each user's rows in frame order.  Where a HIP device is present,
-the agent has a replay form (ope_policy_of; the likelihood agent's, which the host confirms: ope_checked_policy_of) and the log
-qualifies, the rows are replayed on the device by one of the six entry points of the table _REPLAY_ENTRY — a plain policy, the
-frozen LogReg policy or the likelihood agent, each bare or under an EpsilonGreedy wrapper (`device_models` for a model inside).
+the agent has a replay form (ope_policy_of; the likelihood agent's and, with `device_replay`, NnIpsAgent's and BayesianAgentVB's, which
+the host confirms: ope_checked_policy_of) and the log qualifies, the rows are replayed on the device by one of the ten entry points of
+the table _REPLAY_ENTRY — a plain policy, the frozen LogReg policy, the likelihood agent, the NN or the Bayes agent, each bare or under
+an EpsilonGreedy wrapper (`device_models` for a model inside).
 ope_replay is four steps: the log qualifies (_replay_users), the policy dict finds its entry point (_replay_target), one call,
 and the workspace's head decoded once from the layouts _abi names (_replay_head).  recall@k has two device forms of its own
 (recall_replay): where `ps-a` is a function of the act, the top-k set of every act that occurs is built on the host by
@@ -154,8 +155,8 @@ def ope_policy_of(agent):
 
 def ope_checked_policy_of(agent):
     """-> the policy dict of an agent whose replay form needs a host step before its result stands (`ope_policy_checked()`: the
-    likelihood agent, whose device rule lists the acts it cannot resolve — ope_replay confirms them with sim.poly_replay_verify),
-    else None.  Kept apart from ope_policy_of, whose forms are exact as the device leaves them.  The dict's `logreg_poly` entry
+    likelihood agent and, behind the configuration key `device_replay`, NnIpsAgent and BayesianAgentVB, whose device rules list the
+    acts they cannot resolve — ope_replay confirms them with sim.replay_verify and the unit's host act), else None.  Kept apart from ope_policy_of, whose forms are exact as the device leaves them.  The dict's `logreg_poly` entry
     holds wf, wa, wk, intercept (host arrays) and may carry two optional keys: `expit_steps` (a step table other than
     expit_steps()) and `device_model` (sim.poly_device_model's result for the log's device: a caller that replays several logs
     under one model keeps it there instead of moving it per call; ope_replay asserts the device)."""
@@ -268,10 +269,24 @@ _REPLAY_ENTRY = {
     ('logreg', True): ('rg_ope_logreg_workspace_bytes', 'rg_ope_replay_logreg_eg'),       # (the wrapper round a model: the plain
     ('poly', False): ('rg_ope_poly_workspace_bytes', 'rg_ope_replay_poly'),               # unit's workspace, list and head words)
     ('poly', True): ('rg_ope_poly_workspace_bytes', 'rg_ope_replay_poly_eg'),
+    ('nn', False): ('rg_ope_nn_workspace_bytes', 'rg_ope_replay_nn'),
+    ('nn', True): ('rg_ope_nn_workspace_bytes', 'rg_ope_replay_nn_eg'),
+    ('bayes', False): ('rg_ope_bayes_workspace_bytes', 'rg_ope_replay_bayes'),
+    ('bayes', True): ('rg_ope_bayes_workspace_bytes', 'rg_ope_replay_bayes_eg'),
+}
+# the one warning of a replay that is given up: the host refuted an unresolved act, or the device's list of them overflowed
+_REFUTED = {
+    'poly': 'the likelihood agent\'s replay has acts the host does not confirm (or more unresolved acts than the '
+            'device lists): the off-policy evaluation takes the host loop',
+    'nn': 'the replay of NnIpsAgent has acts that torch\'s forward on the host does not confirm (or more unresolved acts than the '
+          'device lists): the off-policy evaluation takes the host loop',
+    'bayes': 'the replay of BayesianAgentVB has acts that the reference\'s expression on the host does not confirm (or more unresolved '
+             'acts than the device lists): the off-policy evaluation takes the host loop',
 }
 # structs: what leads the argument list (the policy or model, then the wrapper); keep: the tensors they point into; size_fn / replay_fn /
-# what: the entry point and its name; head: the word names of the workspace's head or None; poly_host: the likelihood agent's host model
-_ReplayTarget = namedtuple('_ReplayTarget', 'structs keep size_fn replay_fn what head poly_host')
+# what: the entry point and its name; unit / head: the unit and the word names of its workspace's head or None; host_act: where the unit
+# lists unresolved acts, the agent's act on the host, host_act(views) -> action (sim.replay_verify), else None
+_ReplayTarget = namedtuple('_ReplayTarget', 'structs keep size_fn replay_fn what unit head host_act')
 
 
 def _replay_target(pol, device):
@@ -279,19 +294,35 @@ def _replay_target(pol, device):
     what it wraps (an inner policy that samples its act)."""
     import torch
     P = int(pol['num_products'])
-    eg, poly_host = pol.get('epsilon_greedy'), None
+    eg, host_act = pol.get('epsilon_greedy'), None
     if eg is not None and (pol.get('kind') not in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE, _abi.RG_POLICY_LOGREG_FROZEN,
-                                                    _abi.RG_POLICY_LOGREG_POLY) or (pol.get('logreg') or {}).get('select_randomly')):
+                                                    _abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_BAYES_VB) or (pol.get('logreg') or {}).get('select_randomly')):
         return None
     if pol.get('logreg_poly') is not None:
         # the likelihood agent: the model and the step table move to the log's device as the step loop's do (sim.poly_device_model)
         # (`device_model`, optional: that function's result for this device, where the caller keeps the model there between calls)
-        from .sim import poly_device_model
+        from . import sim
         unit, poly = 'poly', pol['logreg_poly']
-        poly_host, keep = poly.get('device_model') or poly_device_model(poly, P, device)
+        poly_host, keep = poly.get('device_model') or sim.poly_device_model(poly, P, device)
         assert all(t.device == device and t.dtype == torch.float64 for t in keep), 'device_model lies on another device than the log'
         cp = _abi.RgOpePoly(num_products=P, n_steps=int(keep[3].numel()), wf=keep[0].data_ptr(), wa=keep[1].data_ptr(),
                             wk_t=keep[2].data_ptr(), th=keep[3].data_ptr(), intercept=poly_host[3])
+        host_act = lambda views: sim.poly_host_act(views, poly_host)                    # noqa: E731
+    elif pol.get('nn_ips') is not None:
+        # NnIpsAgent's argmax form: the six arrays move to the log's device as the step loop's do (sim.nn_device_model)
+        from . import sim
+        unit = 'nn'
+        nn_host, nn, keep = sim.nn_device_model(pol['nn_ips'], device)
+        assert nn.P == P, (nn.P, P)
+        cp = _abi.RgOpeNn(P, nn.H, *[t.data_ptr() for t in keep])
+        host_act = lambda views: sim.nn_host_act(views, P, nn_host)                     # noqa: E731
+    elif pol.get('bayes_vb') is not None:
+        # BayesianAgentVB: the posterior samples move transposed, as the step loop's do (sim.bayes_device_model)
+        from . import sim
+        unit = 'bayes'
+        lam, lam_t = sim.bayes_device_model(pol['bayes_vb'], P, device)
+        cp, keep = _abi.RgOpeBayes(P, int(lam.shape[0]), lam_t.data_ptr()), [lam_t]
+        host_act = lambda views: sim.bayes_host_act(views, P, lam)                      # noqa: E731
     elif pol.get('logreg') is not None:
         # the frozen LogReg policy: the model moves to the log's device once per call
         unit = 'logreg'
@@ -312,7 +343,7 @@ def _replay_target(pol, device):
                                     reserved=0, prob_explore=explore_table(P, pure_new)[1]))
     lib = _abi.load()
     size_name, what = _REPLAY_ENTRY[unit, eg is not None]
-    return _ReplayTarget(structs, keep, getattr(lib, size_name), getattr(lib, what), what, _abi.OPE_HEADS.get(unit), poly_host)
+    return _ReplayTarget(structs, keep, getattr(lib, size_name), getattr(lib, what), what, unit, _abi.OPE_HEADS.get(unit), host_act)
 
 
 def _replay_users(dl, pol, n_users):
@@ -342,7 +373,7 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
     sums = float64 tensor (n, sum c r, sum r).  None where the agent has no replay form or the log does not qualify (a user
     that opens with a bandit row; a float clock under a policy that draws).  `stats` (a dict, frozen LogReg policies only)
     receives the head words of the LogReg unit's workspace: error, acts, exact (acts decided by float64 scores), rows_read; under the
-    likelihood agent those of its unit: error, acts, table, lower, unresolved, overflow, rows_read (_abi.OPE_HEADS).  The likelihood agent's replay
+    likelihood agent, NnIpsAgent and BayesianAgentVB those of their units (_abi.OPE_HEADS: 'poly', 'nn', 'bayes').  Their replay
     is None, after one RuntimeWarning, also where the host refutes an unresolved act or the device's list of them overflowed (under an
     EpsilonGreedy wrapper the listed acts are the GREEDY ones; with pure_new a wrong one changes pi on explored rows too).  `eg_out` (a
     dict, EpsilonGreedy targets only) receives `greedy` (uint8) and `h0` (int32) of the same bandit rows (device tensors); where it
@@ -392,13 +423,12 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
                 raise _abi.RecoGymHipError(f'{target.what}: the replay reported error bits {head["error"]:#x} (a view history outgrew its list)')
             if head.get('unresolved'):
                 # the acts the device's rule could not resolve: confirmed on the host, or the whole replay is given up (no patching)
-                from .sim import poly_replay_verify
+                from .sim import replay_verify
                 n_listed = min(head['unresolved'], _abi.OPE_POLY_LIST_CAP)
                 listed = ws[_abi.OPE_HEAD_BYTES:_abi.OPE_HEAD_BYTES + _abi.OPE_POLY_LIST_ENTRY_BYTES * n_listed]
                 listed = listed.view(torch.int32).cpu().numpy().view(np.uint32).reshape(-1, 3)
-                if not poly_replay_verify(dl, listed, head['overflow'], target.poly_host):
-                    warnings.warn('the likelihood agent\'s replay has acts the host does not confirm (or more unresolved acts than the '
-                                  'device lists): the off-policy evaluation takes the host loop', RuntimeWarning, stacklevel=2)
+                if not replay_verify(dl, listed, head['overflow'], target.host_act):
+                    warnings.warn(_REFUTED[target.unit], RuntimeWarning, stacklevel=2)
                     return None
         code = dl.rows[:total, 2]
         is_b = (code & _abi.RG_EV_BANDIT) != 0
@@ -533,7 +563,8 @@ def _recall_form(pol):
     kind, eg = pol.get('kind'), pol.get('epsilon_greedy')
     if (pol.get('logreg') or {}).get('select_randomly'):
         return 'rank' if eg is None else None
-    if kind in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE, _abi.RG_POLICY_LOGREG_FROZEN, _abi.RG_POLICY_LOGREG_POLY):
+    if kind in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE, _abi.RG_POLICY_LOGREG_FROZEN, _abi.RG_POLICY_LOGREG_POLY,
+                _abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_BAYES_VB):
         return 'table'
     return None
 
@@ -597,7 +628,8 @@ def recall_replay(agent, dl, k=5, n_users=None, list_cap=None, stats=None):
     """recall@k of `agent` over a DeviceLog on the device -> (hit uint8 over the counted rows of the log's first `n_users` users
     (default: all but the last), in log order; counts int64 (counted, hits)), device tensors — or None: the host loop.  A bandit
     row is counted when it has no click and the user's next row is organic.
-      table form  RandomAgent, the last-view tables, the frozen LogReg argmax, the likelihood agent (ope_policy_checked), and
+      table form  RandomAgent, the last-view tables, the frozen LogReg argmax, the likelihood agent, NnIpsAgent and BayesianAgentVB
+                  (ope_policy_checked), and
                   EpsilonGreedy round any of them where ope_replay accepts it: the rg_ope_replay_*_eg entry points write the
                   act at every bandit row (`h0`) and the flip (`greedy`) — a bare target goes through them with epsilon = 0 —
                   recall_sets builds the set of every key that occurs and rg_ope_recall_hits tests membership.

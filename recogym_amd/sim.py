@@ -175,9 +175,15 @@ def weighted_host_act(prods, times, now, weight_history, model):
 
 
 def poly_replay_verify(dl, acts, overflow, model):
-    """The host's confirmation of the acts rg_ope_replay_poly could not resolve (Simulator.poly_verify's counterpart for a
-    replay).  `dl`: the replayed DeviceLog; `acts`: (n, 3) array of (user index, position of the bandit row the act was computed
-    at within the user's rows, action taken); `overflow`: the list did not hold them all; `model`: (wf, wa, wk, b) on the host.
+    """replay_verify for the likelihood agent: `model`: (wf, wa, wk, b) on the host, the host act poly_host_act."""
+    return replay_verify(dl, acts, overflow, lambda views: poly_host_act(views, model))
+
+
+def replay_verify(dl, acts, overflow, host_act):
+    """The host's confirmation of the acts a replay unit could not resolve (rg_ope_replay_poly, rg_ope_replay_nn,
+    rg_ope_replay_bayes: Simulator.poly_verify's counterpart for a replay).  `dl`: the replayed DeviceLog; `acts`: (n, 3) array of
+    (user index, position of the bandit row the act was computed at within the user's rows, action taken); `overflow`: the list did
+    not hold them all; `host_act(views)`: the agent's action on the organic views `views` (product ids in log order) on the host.
     The history of a listed act is the user's organic rows BEFORE that position; only the listed users' rows leave the device.
     -> True when the replay stands: every listed act confirmed, no overflow."""
     if overflow:
@@ -191,7 +197,7 @@ def poly_replay_verify(dl, acts, overflow, model):
     code = {int(u): dl.rows[int(b):int(e), 2].contiguous().cpu().numpy().view(np.uint32) for u, b, e in zip(users, begin, end)}
     for user, pos, a in acts:
         c = code[int(user)][:int(pos)]
-        if poly_host_act(c[(c & _abi.RG_EV_BANDIT) == 0] & _abi.RG_EV_INDEX_MASK, model) != int(a):
+        if int(host_act(c[(c & _abi.RG_EV_BANDIT) == 0] & _abi.RG_EV_INDEX_MASK)) != int(a):
             return False
     return True
 
