@@ -59,6 +59,8 @@ extern "C" {
  * acts share the same list, counter and reader. */
 /* v14, additive since: rg_ope_nn_workspace_bytes / rg_ope_replay_nn / rg_ope_replay_nn_eg and rg_ope_bayes_workspace_bytes /
  * rg_ope_replay_bayes / rg_ope_replay_bayes_eg (the off-policy replay of those two agents, plain and under EpsilonGreedy). */
+/* v14, additive since: rg_sim_set_epsilon_greedy_model_ps (the EpsilonGreedy overlay round NnIpsAgent and BayesianAgentVB in the
+ * step loop; the greedy row of the former logs (1 - epsilon) times the model's own propensity). */
 #define RG_ABI_VERSION 14
 
 /* error codes */
@@ -315,6 +317,17 @@ int rg_sim_set_epsilon_greedy(rg_sim* sim, double epsilon, uint64_t eg_seed, uin
  * overlay.  Arguments, the other checks and the call window are rg_sim_set_epsilon_greedy's. */
 int rg_sim_set_epsilon_greedy_model(rg_sim* sim, double epsilon, uint64_t eg_seed, uint32_t pure_new, const double* d_cdf,
                                     double ps_explore, double one_minus_eps);
+
+/* The same overlay round the two models whose handle is RG_POLICY_NN_IPS or RG_POLICY_BAYES_VB, and round nothing else (any other
+ * policy: RG_EINVAL; rg_sim_set_epsilon_greedy_model keeps refusing these two).  The greedy action g of an act is the cached act of
+ * k_nn_acts / k_bayes_acts.  Its inner propensity is the act's own: 1.0 for BayesianAgentVB, and for NnIpsAgent the model output
+ * prob[g] the act kernel cached beside the action — a greedy row logs one_minus_eps * prob[g], one float64 product (the reference's
+ * (1.0 - epsilon) * greedy_action['ps']), an explored one ps_explore.  The act kernels, the view history and the unresolved list are
+ * what they are without the overlay: the list holds the GREEDY act of every listed act, and with pure_new a wrong greedy act moves
+ * explored actions too, so a caller confirms the listed acts on the host as it does without the overlay (rg_sim_read_poly_unresolved).
+ * Arguments, the other checks and the call window are rg_sim_set_epsilon_greedy's. */
+int rg_sim_set_epsilon_greedy_model_ps(rg_sim* sim, double epsilon, uint64_t eg_seed, uint32_t pure_new, const double* d_cdf,
+                                       double ps_explore, double one_minus_eps);
 
 /* The overlay's explore action on caller-supplied uniforms (stateless; the part rg_sim_debug_ouc_acts plays for
  * OrganicUserEventCounter): d_out[i] = what rng.choice(P, p = product_probas) returns for the uniform d_u1[i] in [0, 1) when the

@@ -166,6 +166,7 @@ SYMBOLS = {
     'rg_sim_set_policy_table_f64': (C.c_int, [_SIM, C.c_void_p, C.c_void_p]),
     'rg_sim_set_epsilon_greedy': (C.c_int, [_SIM, C.c_double, C.c_uint64, C.c_uint32, C.c_void_p, C.c_double, C.c_double]),
     'rg_sim_set_epsilon_greedy_model': (C.c_int, [_SIM, C.c_double, C.c_uint64, C.c_uint32, C.c_void_p, C.c_double, C.c_double]),
+    'rg_sim_set_epsilon_greedy_model_ps': (C.c_int, [_SIM, C.c_double, C.c_uint64, C.c_uint32, C.c_void_p, C.c_double, C.c_double]),
     'rg_eg_explore_actions': (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     'rg_sim_set_logreg': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     'rg_sim_set_logreg_fp32': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float]),

@@ -18,6 +18,12 @@ reference's).  The rows and ratios are the same bits on either route; the key ch
 `device_policy()` returns the model's dict plus `epsilon_greedy=`, `ope_policy()` the LogReg argmax replay dict and
 `ope_policy_checked()` the likelihood agent's checked dict (the host confirms the acts the device cannot resolve), each plus
 `epsilon_greedy=`.
+
+NnIpsAgent (argmax form) and BayesianAgentVB take the same key: `device_policy()` returns their dict plus `epsilon_greedy=`
+(rg_sim_set_epsilon_greedy_model_ps: a greedy NnIpsAgent row logs (1 - epsilon) * prob[a]) and `ope_policy_checked()` their checked
+replay dict (rg_ope_replay_nn_eg / rg_ope_replay_bayes_eg), where the inner agent carries with_ps_all and `device_replay`.  The acts
+either device rule lists as unresolved are the GREEDY ones, and generate_logs / ope_replay confirm them on the host as they do
+without the wrapper.
 """
 import numpy as np
 
@@ -37,7 +43,9 @@ epsilon_greedy_args = {
 _DEVICE_INNER = (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_ORGANIC_USER_COUNT, _abi.RG_POLICY_LAST_VIEW_TABLE)
 _REPLAY_INNER = (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE)
 # with `device_models`: the agents whose act is a model's, computed once per change of the view history (its action is greedy, ps = 1)
-_MODEL_INNER = (_abi.RG_POLICY_LOGREG_FROZEN, _abi.RG_POLICY_LOGREG_POLY)
+_MODEL_INNER = (_abi.RG_POLICY_LOGREG_FROZEN, _abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_BAYES_VB)
+# ... whose replay lists the greedy acts the device cannot resolve, for the host's confirmation (ope_policy_checked)
+_CHECKED_INNER = (_abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_BAYES_VB)
 # what the wrapper passes on to the inner agent only where that agent has it (test_agent asks with hasattr / getattr)
 _DELEGATED = ('train_from_log', 'train_online_from_log', 'accepts_device_log', 'needs_training')
 
@@ -86,8 +94,8 @@ class EpsilonGreedy(Agent):
 
     def device_policy(self):
         """The inner agent's device policy plus `epsilon_greedy=dict(epsilon, seed, pure_new)`; None where the inner agent has no
-        device form of the kinds the overlay serves (the two model kinds only with `device_models`, and never a sampling
-        LogReg), with epsilon_select_worse and with with_ps_all."""
+        device form of the kinds the overlay serves (the model kinds — LogReg argmax, likelihood agent, NnIpsAgent, BayesianAgentVB —
+        only with `device_models`, and never a sampling LogReg), with epsilon_select_worse and with with_ps_all."""
         c = self.config
         if getattr(c, 'epsilon_select_worse', False) or getattr(c, 'with_ps_all', False):
             return None
@@ -134,8 +142,10 @@ class EpsilonGreedy(Agent):
         return dict(pol, epsilon_greedy=self._overlay())
 
     def ope_policy_checked(self):
-        """With `device_models` and with_ps_all on the wrapper and the inner agent: the likelihood agent's checked replay dict
-        (rg_ope_replay_poly_eg; the host confirms the greedy acts the device lists as unresolved) plus `epsilon_greedy=`."""
+        """With `device_models` and with_ps_all on the wrapper and the inner agent: the checked replay dict of the likelihood agent,
+        NnIpsAgent or BayesianAgentVB (rg_ope_replay_poly_eg / _nn_eg / _bayes_eg; the host confirms the greedy acts the device lists
+        as unresolved) plus `epsilon_greedy=`.  None wherever the inner agent's own ope_policy_checked() is (the last two: without
+        their key `device_replay`)."""
         c = self.config
         if getattr(c, 'epsilon_select_worse', False) or not getattr(c, 'with_ps_all', False) or not getattr(c, 'device_models', False):
             return None
@@ -143,7 +153,7 @@ class EpsilonGreedy(Agent):
             return None
         from ..evaluate_agent import ope_checked_policy_of
         pol = ope_checked_policy_of(self.agent)
-        if pol is None or pol.get('kind') != _abi.RG_POLICY_LOGREG_POLY or pol.get('epsilon_greedy') is not None:
+        if pol is None or pol.get('kind') not in _CHECKED_INNER or pol.get('epsilon_greedy') is not None:
             return None
         if int(pol['num_products']) < 2 and c.epsilon_pure_new:
             return None

@@ -556,7 +556,7 @@ __global__ void __launch_bounds__(kAdvBlock) k_advance(DevSim d, uint32_t t, con
                     a = bad ? 0u : static_cast<uint32_t>(ai);
                     ps = __builtin_nan("");
                 }
-                else if constexpr (EG) a = model_act_overlay(d, slot, user, t, lr_a, &ps);      // (lr_a: the greedy action of a model)
+                else if constexpr (EG) a = model_act_overlay(d, slot, user, uidx, t, lr_a, &ps);      // (lr_a: the greedy action of a model)
                 else if (d.policy == RG_POLICY_LOGREG_FROZEN) { a = lr_a; ps = d.lr_sample || lr_logs_ps(d) ? d.lr_ps[uidx] : 1.0; }
                 else a = policy_act_eg<EG>(d, slot, user, t, &ps);
                 // beta[a] . omega, k ascending (the oracle's association); loads are issued eight
@@ -639,7 +639,7 @@ __global__ void __launch_bounds__(kAdvBlock) k_advance(DevSim d, uint32_t t, con
                     // final step_offline(done=True): one more act, reward 0 (abstract.py:223-233,311-316)
                     double ps = 1.0;
                     uint32_t a;
-                    if constexpr (EG) a = model_act_overlay(d, slot, user, t + 1, lr_a, &ps);
+                    if constexpr (EG) a = model_act_overlay(d, slot, user, uidx, t + 1, lr_a, &ps);
                     else if (d.policy != RG_POLICY_LOGREG_FROZEN) a = policy_act_eg<EG>(d, slot, user, t + 1, &ps);
                     else if (!d.lr_sample) { a = lr_a; if (lr_logs_ps(d)) ps = d.lr_ps[uidx]; }
                     else if (is_org) { a = lr_a; ps = d.lr_ps[uidx]; }                       // k_logreg_sample drew it for event t + 1
@@ -750,7 +750,7 @@ __device__ __forceinline__ bool run_bandit_event(const DevSim& d, uint32_t slot,
     double ps = 1.0;
     uint32_t a = 0;
     if (RG_ADV_ABL(25)) {}
-    else if constexpr (EG) a = model_act_overlay(d, slot, user, te, lr_a, &ps);     // (every event of the run flips its own coin)
+    else if constexpr (EG) a = model_act_overlay(d, slot, user, d.uid[slot], te, lr_a, &ps);     // (every event of the run flips its own coin)
     else if (d.policy == RG_POLICY_LOGREG_FROZEN) { a = lr_a; if (lr_logs_ps(d)) ps = d.lr_ps[d.uid[slot]]; }
     else a = policy_act_eg<EG>(d, slot, user, te, &ps);
     double ctr = 0.0;
@@ -925,7 +925,7 @@ k_advance_run(DevSim d, uint32_t t, uint32_t hops) {
                 // final step_offline(done=True): one more act, reward 0 (abstract.py:223-233,311-316)
                 double ps = 1.0;
                 uint32_t a;
-                if constexpr (EG) a = model_act_overlay(d, slot, user, t_last + 1, lr_a, &ps);
+                if constexpr (EG) a = model_act_overlay(d, slot, user, uidx, t_last + 1, lr_a, &ps);
                 else if (d.policy == RG_POLICY_LOGREG_FROZEN) { a = lr_a; if (lr_logs_ps(d)) ps = d.lr_ps[uidx]; }
                 else a = policy_act_eg<EG>(d, slot, user, t_last + 1, &ps);
                 rg_event e;

@@ -1314,8 +1314,9 @@ __device__ __attribute__((noinline)) uint32_t eg_explore_action(uint32_t P, bool
 
 // The overlay on a greedy action g whose propensity is *ps_out: the explore coin of (eg_seed, user, t) — an explored act takes the
 // table's action and the host's eps * (1 / n), a greedy one g and the inner propensity times the host's 1 - eps.  The inner act is
-// the caller's: policy_act (policy_act_eg), or the model's cached act lr_action[user] with propensity 1.0 at the sites that take it
-// (rg_sim_set_epsilon_greedy_model: the frozen LogReg argmax and the likelihood agent).
+// the caller's: policy_act (policy_act_eg), or the model's cached act lr_action[user] at the sites that take it, with propensity
+// 1.0 (rg_sim_set_epsilon_greedy_model: the frozen LogReg argmax and the likelihood agent; BayesianAgentVB) or the model's own
+// lr_ps[user] (NnIpsAgent: the greedy row logs (1 - eps) * prob[a], one float64 product) — model_act_overlay.
 __device__ __forceinline__ uint32_t eg_overlay(const DevSim& d, uint32_t user, uint32_t t, uint32_t g, double* ps_out) {
     const rg_u32x4 w = rg_draw(d.eg_seed, user, t, 0, RG_DRAW_POLICY);
     const double eps = d.eg_eps;
@@ -1338,12 +1339,17 @@ __device__ __forceinline__ uint32_t policy_act_eg(const DevSim& d, uint32_t slot
 }
 
 // The EG act at the sites that hold the cached model action lr_a (RG_POLICY_LOGREG_FROZEN without select_randomly — the only
-// LogReg form rg_sim_set_epsilon_greedy_model admits — the likelihood agent included): the model's action, propensity 1.0, is the
-// GREEDY one.  One overlay per site: a handle of any other policy takes policy_act for g.
-__device__ __forceinline__ uint32_t model_act_overlay(const DevSim& d, uint32_t slot, uint32_t user, uint32_t t, uint32_t lr_a, double* ps_out) {
+// LogReg form rg_sim_set_epsilon_greedy_model admits — the likelihood agent included; BayesianAgentVB and NnIpsAgent by
+// rg_sim_set_epsilon_greedy_model_ps): the model's action is the GREEDY one.  Its inner propensity is 1.0, or, where the act
+// kernel logs a model output (lr_logs_ps: NnIpsAgent's prob[a]), the cached lr_ps[uidx] — uidx the user's INDEX (uid[slot]), the
+// index k_nn_acts wrote it at; lr_ps has one element under every other policy, so the load stays behind lr_logs_ps.  One overlay
+// per site: a handle of any other policy takes policy_act for g.
+__device__ __forceinline__ uint32_t model_act_overlay(const DevSim& d, uint32_t slot, uint32_t user, uint32_t uidx, uint32_t t, uint32_t lr_a,
+                                                      double* ps_out) {
     uint32_t g = lr_a;
     *ps_out = 1.0;
     if (d.policy != RG_POLICY_LOGREG_FROZEN) g = policy_act(d, slot, user, t, ps_out);
+    else if (lr_logs_ps(d)) *ps_out = d.lr_ps[uidx];
     return eg_overlay(d, user, t, g, ps_out);
 }
 

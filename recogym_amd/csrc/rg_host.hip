@@ -1665,6 +1665,22 @@ int rg_sim_set_epsilon_greedy_model(rg_sim* sim, double epsilon, uint64_t eg_see
     return RG_OK;
 }
 
+int rg_sim_set_epsilon_greedy_model_ps(rg_sim* sim, double epsilon, uint64_t eg_seed, uint32_t pure_new, const double* d_cdf,
+                                       double ps_explore, double one_minus_eps) {
+    if (!sim) return fail(RG_EINVAL, "sim is NULL");
+    if (sim->users_reset) return fail(RG_ESTATE, "rg_sim_set_epsilon_greedy_model_ps must be called before rg_sim_reset_users");
+    if (sim->cfg.policy != RG_POLICY_NN_IPS && sim->cfg.policy != RG_POLICY_BAYES_VB)
+        return fail(RG_EINVAL, "rg_sim_set_epsilon_greedy_model_ps wraps NnIpsAgent or BayesianAgentVB (policy %u)", sim->cfg.policy);
+    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(RG_EINVAL, "epsilon %g outside [0, 1]", epsilon);
+    if (pure_new && sim->d.P < 2u) return fail(RG_EINVAL, "epsilon_pure_new needs at least 2 products");
+    if (!d_cdf) return fail(RG_EINVAL, "the explore table is NULL");
+    DevSim& d = sim->d;
+    d.eg_on = 1u; d.eg_pure_new = pure_new ? 1u : 0u; d.eg_seed = eg_seed;
+    d.eg_eps = epsilon; d.eg_ps_explore = ps_explore; d.eg_one_minus = one_minus_eps; d.eg_cdf = d_cdf;
+    sim->walk = sim->walk2 = false;            // (as rg_sim_set_epsilon_greedy)
+    return RG_OK;
+}
+
 int rg_eg_explore_actions(uint32_t num_products, uint32_t pure_new, const double* d_cdf, const double* d_u1, const int32_t* d_greedy,
                           uint64_t n, int32_t* d_out, void* stream) {
     if (num_products == 0 || num_products > RG_EV_INDEX_MASK || (pure_new && num_products < 2u))

@@ -215,7 +215,8 @@ class Simulator:
     p_click      also keep the click probability of every bandit row (parity checks)
     epsilon_greedy  dict(epsilon, seed, pure_new): the EpsilonGreedy overlay over `policy` (agents/epsilon_greedy.py;
                  rg_sim_set_epsilon_greedy, or rg_sim_set_epsilon_greedy_model where the policy is the frozen LogReg argmax or
-                 the likelihood agent) — the explore table and both propensity factors are NumPy's, built here
+                 the likelihood agent, or rg_sim_set_epsilon_greedy_model_ps where it is NnIpsAgent or BayesianAgentVB) — the
+                 explore table and both propensity factors are NumPy's, built here
     logreg_poly  dict(wf (P,), wa (P,), wk (P, P) [action][product], intercept): the likelihood agent's fitted model
                  (RG_POLICY_LOGREG_POLY; agents/logreg_poly.py) — the table of expit's top steps is built and uploaded here.
                  After a run, `poly_verify(columns)` recomputes the acts the device could not resolve on the host.
@@ -281,6 +282,8 @@ class Simulator:
                 # (a model inside — its cached act is the greedy action — has an entry point of its own)
                 model = policy in (_abi.RG_POLICY_LOGREG_FROZEN, _abi.RG_POLICY_LOGREG_POLY)
                 what = 'rg_sim_set_epsilon_greedy_model' if model else 'rg_sim_set_epsilon_greedy'
+                if policy in (_abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_BAYES_VB):
+                    what = 'rg_sim_set_epsilon_greedy_model_ps'       # (NnIpsAgent's greedy row logs (1 - eps) * the model's own ps)
                 _abi.check(getattr(self.lib, what)(self._h, eps, int(epsilon_greedy['seed']) & 0xFFFFFFFFFFFFFFFF,
                                                    int(pure_new), self.eg_cdf.data_ptr(), eps * prob, 1.0 - eps), what)
             if env0 is not None:
