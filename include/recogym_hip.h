@@ -61,6 +61,9 @@ extern "C" {
  * rg_ope_replay_bayes / rg_ope_replay_bayes_eg (the off-policy replay of those two agents, plain and under EpsilonGreedy). */
 /* v14, additive since: rg_sim_set_epsilon_greedy_model_ps (the EpsilonGreedy overlay round NnIpsAgent and BayesianAgentVB in the
  * step loop; the greedy row of the former logs (1 - epsilon) times the model's own propensity). */
+/* v14, additive since: RG_POLICY_MLR with rg_sim_set_mlr and rg_sim_debug_mlr_acts (the argmax act of PyTorchMLRAgent in the step
+ * loop) and the flag RG_MLR_UNRESOLVED; its unresolved acts share the same list, counter and reader; and rg_ope_mlr_workspace_bytes /
+ * rg_ope_replay_mlr / rg_ope_replay_mlr_eg (its off-policy replay). */
 #define RG_ABI_VERSION 14
 
 /* error codes */
@@ -100,6 +103,10 @@ extern "C" {
 #define RG_POLICY_NN_IPS 10       /* frozen NnIpsAgent, agents/nn_ips.py:43-63,111-137: prob = softmax(W3 sigmoid(W2 sigmoid(W1 x + b1) + b2) + b3)
                                      over the user's view counts x, a = the first index of the maximum, ps = prob[a] (not 1) —
                                      rg_sim_set_nn_ips has the contract.  Routed like RG_POLICY_LOGREG_POLY. */
+/* (11 is not assigned either and stays refused: tests/test_nn_ips_host.py holds policy 11 as a refused number) */
+#define RG_POLICY_MLR 12          /* frozen PyTorchMLRAgent, agents/pytorch_mlr.py:30-32,59-84: a = the first index of the maximum of x W^T
+                                     over the user's view counts x (fp32), ps = 1 — rg_sim_set_mlr has the contract.  Routed like
+                                     RG_POLICY_LOGREG_POLY. */
 
 /*
  * Everything the step loop needs from `env.config` (a Configuration built from env_1_args,
@@ -434,6 +441,19 @@ int rg_sim_set_bayes_vb(rg_sim* sim, const double* d_lam_t, uint32_t num_samples
 int rg_sim_set_nn_ips(rg_sim* sim, const double* d_w1t, const double* d_b1, const double* d_w2t, const double* d_b2,
                       const double* d_w3t, const double* d_b3, uint32_t num_hidden);
 
+/* RG_POLICY_MLR: the weight of PyTorchMLRAgent's one linear layer, one float64 device array kept by pointer that holds the model's
+ * fp32 values widened and transposed so that the row of a viewed product is contiguous: d_wt[p P + a] = W[a][p]; num_products in
+ * [1, 4000] (a 128 MB table at the most), every value finite (else RG_EINVAL).  The call reads the array once and synchronises.
+ * The act over the n distinct viewed products p_0 < ... < p_(n-1) with counts c_j, float64, multiply then add, in exactly this order:
+ *   z[a] = 0; for j: z[a] += c_j wt[p_j][a]        m1[a] = sum_j |c_j wt[p_j][a]| (the same order), M1 = max_a m1[a]
+ *   a* = the first index of max z
+ * E = (n + 5) 2^-24 M1 bounds the distance of every z[a] from the reference's fp32 dot in ANY summation order, fused
+ * or not.  The act is RG_MLR_UNRESOLVED unless z[a*] leads every other score by more than 2 E, no count exceeds 2^24 (not an fp32
+ * value), the history is not empty and M1 < 2^126 (no fp32 partial sum can overflow): counted and listed as the likelihood agent's
+ * (RG_CNT_POLY_UNRESOLVED, rg_sim_read_poly_unresolved).  ps = 1.  The EpsilonGreedy overlays on this policy are RG_EINVAL. */
+#define RG_MLR_UNRESOLVED 2u
+int rg_sim_set_mlr(rg_sim* sim, const double* d_wt);
+
 /* The unresolved acts of the run so far (since rg_sim_reset_users): out[3 i .. 3 i + 2] = (user id, t, action taken) for the first
  * min(listed, capacity) of them, in no particular order; t is the event index the act was computed at: its history is the user's
  * organic rows with index <= t.  *n_out = entries written, *overflow = 1 when the run had more unresolved acts than the device list
@@ -583,6 +603,10 @@ int rg_sim_debug_bayes_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, do
  * function the step loop uses: d_action[i], d_flags[i] (RG_NN_UNRESOLVED), the logits d_z[i * num_products + a] and d_ps[i].
  * Touches neither the counters nor the list. */
 int rg_sim_debug_nn_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, double* d_z, double* d_ps, void* stream);
+/* rg_sim_debug_mlr_acts: the RG_POLICY_MLR act of every user index on its current history (rg_sim_debug_set_history), by the device
+ * function the step loop uses: d_action[i], d_flags[i] (RG_MLR_UNRESOLVED) and the scores d_z[i * num_products + a].
+ * Touches neither the counters nor the list. */
+int rg_sim_debug_mlr_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, double* d_z, void* stream);
 /* rg_sim_debug_set_timed_history (after rg_sim_set_weight_history, right after rg_sim_reset_users): the TIMED view history of every
  * user index — d_n[i] views (at most stride), view j of product d_products[i * stride + j] at clock value d_times16[i * stride + j],
  * in view order (times never decreasing).  They go into the user's history row one at a time through the sorted insert that never
@@ -832,6 +856,33 @@ int rg_ope_replay_bayes_eg(const rg_ope_bayes* model, const rg_ope_eg* eg, const
                            uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const,
                            double* d_ratio, uint8_t* d_click, double* d_sums, uint8_t* d_greedy, int32_t* d_h0,
                            void* d_workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Off-policy evaluation of PyTorchMLRAgent (PyTorchMLRFrozenAgent, reference agents/pytorch_mlr.py:59-84): replay a sorted log under
+ * the model.  Stateless.  wt is a device array laid out as rg_sim_set_mlr takes it; the act is the step loop's (k_mlr_acts: the same
+ * order of operations, margin and flags), pi = [action == a], r = pi / ps.
+ * rg_ope_mlr_workspace_bytes / rg_ope_replay_mlr: argument for argument rg_ope_replay_nn after the model, with the same validation
+ * of the log, the same unresolved list from byte 256 (the acts flagged RG_MLR_UNRESOLVED) and the same rule that the ratios are
+ * written with the device's action.  RG_EINVAL also for a null model or array, num_products outside 1 .. 4000 and a value that is
+ * not finite.  Head words: [0] error bits (0), [1] acts computed, [2] unresolved acts, [3] non-zero when more than 4096 were,
+ * [4] wt rows read.  d_sums holds the same bits on every run.  Synchronises `stream` twice (the verdict of the finiteness
+ * check, which runs on the device, and the validation's verdict).
+ */
+typedef struct rg_ope_mlr {
+    uint32_t num_products;          /* P, 1 .. 4000 */
+    const double* wt;               /* [P][P], [viewed product][action] */
+} rg_ope_mlr;
+size_t rg_ope_mlr_workspace_bytes(const rg_ope_mlr* model, uint64_t n_users, uint32_t max_user_rows);
+int rg_ope_replay_mlr(const rg_ope_mlr* model, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                      uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
+                      uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream);
+/* rg_ope_replay_mlr_eg: argument for argument rg_ope_replay_nn_eg after the model (the act is the wrapper's greedy action g;
+ * d_greedy / d_h0 as there), but served for epsilon = 0 only — the wrapper that never explores, through which recall@k obtains the
+ * act of every bandit row (d_h0); any other epsilon is RG_EINVAL. */
+int rg_ope_replay_mlr_eg(const rg_ope_mlr* model, const rg_ope_eg* eg, const rg_event* d_rows, const int64_t* d_offsets,
+                         uint64_t n_users, uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const,
+                         double* d_ratio, uint8_t* d_click, double* d_sums, uint8_t* d_greedy, int32_t* d_h0,
+                         void* d_workspace, size_t workspace_bytes, void* stream);
 
 /*
  * recall@k (evaluate_recall_at_k, reference evaluate_agent.py:832-870) over a sorted log.  A bandit row i of user u is COUNTED

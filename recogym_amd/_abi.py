@@ -20,6 +20,7 @@ RG_POLICY_LOGREG_FROZEN = 5
 RG_POLICY_LOGREG_POLY = 6
 RG_POLICY_BAYES_VB = 8      # (7 is not assigned: include/recogym_hip.h)
 RG_POLICY_NN_IPS = 10       # (9 is not assigned: include/recogym_hip.h)
+RG_POLICY_MLR = 12           # (11 is not assigned: include/recogym_hip.h)
 
 RG_EV_BANDIT = 0x80000000
 RG_EV_CLICK = 0x40000000
@@ -112,6 +113,11 @@ class RgOpeBayes(C.Structure):
     _fields_ = [('num_products', C.c_uint32), ('num_samples', C.c_uint32), ('lam_t', C.c_void_p)]
 
 
+class RgOpeMlr(C.Structure):
+    """struct rg_ope_mlr: PyTorchMLRAgent's table of rg_ope_replay_mlr (a device array, rg_sim_set_mlr's layout)."""
+    _fields_ = [('num_products', C.c_uint32), ('wt', C.c_void_p)]
+
+
 class RgOpeEg(C.Structure):
     """struct rg_ope_eg: the EpsilonGreedy wrapper of rg_ope_replay_eg."""
     _fields_ = [('epsilon', C.c_double), ('seed', C.c_uint64), ('pure_new', C.c_uint32), ('reserved', C.c_uint32),
@@ -126,6 +132,7 @@ OPE_HEAD_BYTES = 256
 OPE_HEADS = {'logreg': ('error', 'acts', 'exact', 'rows_read'),
              'poly': ('error', 'acts', 'table', 'lower', 'unresolved', 'overflow', 'rows_read'),
              'nn': ('error', 'acts', 'unresolved', 'overflow', 'rows_read'),
+             'mlr': ('error', 'acts', 'unresolved', 'overflow', 'rows_read'),
              'bayes': ('error', 'acts', 'saturated', 'unresolved', 'overflow', 'rows_read')}
 OPE_POLY_LIST_CAP = 4096
 OPE_POLY_LIST_ENTRY_BYTES = 12
@@ -174,6 +181,7 @@ SYMBOLS = {
     'rg_sim_set_logreg_poly': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_uint32]),
     'rg_sim_set_bayes_vb': (C.c_int, [_SIM, C.c_void_p, C.c_uint32]),
     'rg_sim_set_nn_ips': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    'rg_sim_set_mlr': (C.c_int, [_SIM, C.c_void_p]),
     'rg_sim_set_weight_history': (C.c_int, [_SIM, C.c_void_p, C.c_uint32, C.c_uint32]),
     'rg_sim_read_poly_unresolved': (C.c_int, [_SIM, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]),
     'rg_sim_set_log': (C.c_int, [_SIM, C.c_void_p, C.c_uint64]),
@@ -206,6 +214,7 @@ SYMBOLS = {
     'rg_sim_debug_poly_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rg_sim_debug_bayes_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rg_sim_debug_nn_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rg_sim_debug_mlr_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'rg_sim_debug_set_timed_history': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     'rg_sim_debug_weighted_acts': (C.c_int, [_SIM, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                              C.c_void_p]),
@@ -243,6 +252,12 @@ SYMBOLS = {
            ('rg_ope_replay_{}_eg', C.c_int, [C.POINTER(RgOpeEg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
                                              C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_size_t, C.c_void_p]))},
+    'rg_ope_mlr_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpeMlr), C.c_uint64, C.c_uint32]),
+    'rg_ope_replay_mlr': (C.c_int, [C.POINTER(RgOpeMlr), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_double,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rg_ope_replay_mlr_eg': (C.c_int, [C.POINTER(RgOpeMlr), C.POINTER(RgOpeEg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
     'rg_ope_recall_hits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     'rg_ope_recall_logreg_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpeLogreg), C.c_uint64, C.c_uint32, C.c_uint32]),

@@ -7,6 +7,7 @@ from .logreg_ips import LogregMulticlassIpsAgent, logreg_multiclass_ips_args
 from .logreg_poly import LogregPolyAgent, LogregPolyFrozenAgent, logreg_poly_args
 from .bayesian_poly_vb import BayesianAgentVB, BayesianVBFrozenAgent, bayesian_poly_args
 from .nn_ips import NnIpsAgent, NnIpsFrozenAgent, nn_ips_args
+from .pytorch_mlr import PyTorchMLRAgent, PyTorchMLRFrozenAgent, pytorch_mlr_args
 from .feature_feed import train_data_from_log
 from .bandit_mf import BanditMFSquareAgent, bandit_mf_square_args
 from .organic_count import OrganicCount, organic_count_args

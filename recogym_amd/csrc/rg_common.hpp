@@ -54,7 +54,7 @@
 // kernels), rg_exact.hip (float64 resolve), rg_draw_fp32.hip (fp32 / lean 16-bit sweeps), rg_draw_pipelined.hip (the pipelined sweep
 // + per-user cache kernels), rg_draw_wide.hip (wide-K sweep), rg_advance.hip (advance / tail / frozen LogReg), rg_walk.hip (the
 // user-major walk), rg_draw_exacthi.hip and rg_draw_lds.hip (the error-free and the tile-prefix sweeps), rg_ope.hip,
-// rg_ope_logreg.hip, rg_ope_eg.hip and rg_ope_poly.hip (off-policy replays), rg_count.hip (count agents' training), rg_evolve.hip (the exploration study), rg_logreg_poly.hip (the likelihood agent's act), rg_weight_history.hip (its act on a time-weighted history), rg_bayes_vb.hip (BayesianAgentVB's act), rg_nn_ips.hip (NnIpsAgent's act) — compiled in parallel and
+// rg_ope_logreg.hip, rg_ope_eg.hip and rg_ope_poly.hip (off-policy replays), rg_count.hip (count agents' training), rg_evolve.hip (the exploration study), rg_logreg_poly.hip (the likelihood agent's act), rg_weight_history.hip (its act on a time-weighted history), rg_bayes_vb.hip (BayesianAgentVB's act), rg_nn_ips.hip (NnIpsAgent's act), rg_mlr.hip (PyTorchMLRAgent's act), rg_ope_mlr.hip (its replay) — compiled in parallel and
 // linked by __graft_entry__.build(); recogym_hip.hip includes all of them (a one-unit build).  This header holds what they
 // share: types, the workspace layout, device helpers (namespace rgk, identical in every unit); a unit hands its kernels to the
 // host code through the *_kernel_for functions declared here.  rg_ope_common.hpp adds what the four replay units share.
@@ -77,9 +77,9 @@ constexpr uint32_t kPolyListCap = 4096;        // unresolved acts of a run the d
 constexpr uint32_t kPolySteps = 1024;          // expit steps the table holds at most (8 KB of LDS)
 constexpr uint32_t kPolyHist = 256;            // history entries a wave of the likelihood agent's act keeps in LDS (the default history row); beyond: read from the source
 // the policies that act on the view history through the lr_* act list (k_logreg_select)
-inline bool lr_family(uint32_t policy) { return policy == RG_POLICY_LOGREG_FROZEN || policy == RG_POLICY_LOGREG_POLY || policy == RG_POLICY_BAYES_VB || policy == RG_POLICY_NN_IPS; }
+inline bool lr_family(uint32_t policy) { return policy == RG_POLICY_LOGREG_FROZEN || policy == RG_POLICY_LOGREG_POLY || policy == RG_POLICY_BAYES_VB || policy == RG_POLICY_NN_IPS || policy == RG_POLICY_MLR; }
 // the policies whose unresolved acts go to pl_list (rg_sim_read_poly_unresolved)
-inline bool lists_unresolved(uint32_t policy) { return policy == RG_POLICY_LOGREG_POLY || policy == RG_POLICY_BAYES_VB || policy == RG_POLICY_NN_IPS; }
+inline bool lists_unresolved(uint32_t policy) { return policy == RG_POLICY_LOGREG_POLY || policy == RG_POLICY_BAYES_VB || policy == RG_POLICY_NN_IPS || policy == RG_POLICY_MLR; }
 // the transposed model of RG_POLICY_BAYES_VB, P x P x S doubles, at most: what one raw buffer resource of the library spans (2 GiB,
 // raw_buffer_rsrc), which also keeps every element offset of the act below 2^28
 constexpr uint64_t kBayesModelBytes = 1ull << 31;
@@ -90,6 +90,9 @@ constexpr uint32_t kNnHidden = 1024;
 constexpr uint32_t kNnProducts = 4000;
 constexpr size_t kNnStageBytes = 48 * 1024;
 constexpr size_t kNnStaticLds = 16 * 1024;    // an upper bound of the static LDS of k_nn_acts / k_debug_nn_acts (kPolyHist rows of a block: 12.3 KB)
+// RG_POLICY_MLR: products at most (the margin's gamma term uses (n + 1) 2^-24 >= gamma_n, which holds up to n = 4095: DESIGN.md 4j;
+// the P x P float64 table is 128 MB there).  The table goes to the block's LDS where it stays within kNnStageBytes (P <= 78).
+constexpr uint32_t kMlrProducts = 4000;
 constexpr uint64_t kRepackMinUsers = 1ull << 18;   // runs smaller than this keep slot == user index throughout (RECOGYM_REPACK_MIN overrides: tests)
 
 inline thread_local char g_err[512] = "";
@@ -337,6 +340,8 @@ struct DevSim {
     // keeps its size and every other kernel its code.
     // RG_POLICY_NN_IPS (rg_sim_set_nn_ips; rg_nn_ips.hip): lr_poly = 3 selects k_nn_acts, whose model is a kernel argument of its own
     // (NnModel below), and makes the advance kernels log lr_ps instead of 1 (lr_logs_ps).
+    // RG_POLICY_MLR (rg_sim_set_mlr; rg_mlr.hip): lr_poly = 4 selects k_mlr_acts, whose model is a kernel argument of its own too
+    // (MlrModel below); ps = 1, as the frozen LogReg's argmax.
 };
 
 // the net of RG_POLICY_NN_IPS as k_nn_acts takes it (rg_sim_set_nn_ips has the layout); A2, A3: the absolute row sums the margin uses
@@ -344,6 +349,12 @@ struct NnModel {
     const double* w1t; const double* b1; const double* w2t; const double* b2; const double* w3t; const double* b3;
     double A2, A3;
     uint32_t H, staged;       // staged: the three matrices fit the block's LDS behind the layer vectors
+};
+
+// the table of RG_POLICY_MLR as k_mlr_acts takes it (rg_sim_set_mlr has the layout)
+struct MlrModel {
+    const double* wt;
+    uint32_t staged;          // the table fits the block's LDS
 };
 
 }  // namespace rgk
@@ -411,7 +422,7 @@ struct RunOpts {
     X(draw_f64) X(draw_fp32) X(draw16_fused) X(draw16_sliced) X(search) X(draw_tp) X(pick) X(draw_cached) \
     X(sweep_xh) X(exact_m) X(exact_tile) X(exact_h) X(walk) X(walk2) X(walk_solo) X(park_compact) \
     X(advance) X(advance_run) X(tail) X(repack) X(env0) X(logreg_screen) X(logreg_acts) X(logreg_sample) X(logreg_poly) \
-    X(logreg_poly_w) X(sort_tiled) X(sort_plain) X(bayes_vb) X(nn_ips)
+    X(logreg_poly_w) X(sort_tiled) X(sort_plain) X(bayes_vb) X(nn_ips) X(mlr)
 struct Ledger {
 #define RG_LEDGER_FIELD(f) uint64_t f = 0;
     RG_LEDGER_FAMILIES(RG_LEDGER_FIELD)
@@ -446,6 +457,8 @@ struct rg_sim {
     DevSim d;
     rgk::NnModel nn;          // RG_POLICY_NN_IPS: the model (w1t == nullptr: not set) and the dynamic LDS of k_nn_acts
     size_t nn_smem;
+    rgk::MlrModel mlr;        // RG_POLICY_MLR: the table (wt == nullptr: not set) and the dynamic LDS of k_mlr_acts
+    size_t mlr_smem;
     WhRun wh;                 // wt.tab != nullptr: the likelihood agent acts on time-weighted features (no kernel but rg_weight_history.hip's reads it)
     RunOpts opt;
     void* workspace;
@@ -555,6 +568,16 @@ void (*nn_debug_kernel())(DevSim, NnModel, int32_t*, uint8_t*, double*, double*)
 // (rg_ope_nn.hip): neither takes A2 / A3 from its caller.
 int nn_host_model(const char* who, uint32_t P, uint32_t H, const double* d_w1t, const double* d_b1, const double* d_w2t, const double* d_b2,
                   const double* d_w3t, const double* d_b3, int waves, NnModel* m, size_t* smem);
+void (*mlr_acts_kernel())(DevSim, MlrModel, uint32_t);    // rg_mlr.hip
+void (*mlr_debug_kernel())(DevSim, MlrModel, int32_t*, uint8_t*, double*);
+void (*mlr_finite_kernel())(const double*, size_t, uint32_t*);
+// The table as a kernel takes it, from the device array of rg_sim_set_mlr (rg_host.hip; who: the caller's name for the error text):
+// refuses a value that is not finite (RG_EINVAL) and decides the staging — the table goes to LDS where it stays within
+// kNnStageBytes.  *smem: the block's dynamic LDS bytes.  The finiteness check runs on the device (k_mlr_finite into the 4 bytes at
+// d_flag, device scratch of the caller's; 4 bytes come back and `st` is synchronised once): a replay call does not move up to
+// 128 MB to the host.  d_flag == nullptr: the table is downloaded and scanned here (rg_sim_set_mlr, once per handle).  Shared by
+// the step loop and the replay.
+int mlr_host_model(const char* who, uint32_t P, const double* d_wt, uint32_t* d_flag, hipStream_t st, MlrModel* m, size_t* smem);
 // more than 64 KiB of LDS needs an explicit opt-in per kernel instantiation (set_max_lds: whatever the size)
 template <class Kernel> void set_max_lds(Kernel kernel, size_t bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
@@ -860,7 +883,7 @@ inline int validate(const rg_config* c, uint64_t n) {
     if (sizeof(double) * (static_cast<size_t>(c->K) * 64 + 64 + 16 * c->K) > 64 * 1024)
         return fail(RG_EINVAL, "K %u exceeds the float64 draw kernel's LDS budget", c->K);
     if (n == 0 || n >= (1ull << 31)) return fail(RG_EINVAL, "n_users %llu out of range", (unsigned long long)n);
-    if (c->policy > RG_POLICY_NN_IPS || c->policy == 7u || c->policy == 9u /* not assigned: recogym_hip.h */) return fail(RG_EINVAL, "unknown policy %u", c->policy);
+    if (c->policy > RG_POLICY_MLR || c->policy == 7u || c->policy == 9u || c->policy == 11u /* not assigned: recogym_hip.h */) return fail(RG_EINVAL, "unknown policy %u", c->policy);
     if (c->time_mode > 1) return fail(RG_EINVAL, "unknown time_mode %u", c->time_mode);
     if (c->env_kind > 1) return fail(RG_EINVAL, "unknown env_kind %u", c->env_kind);
     if (c->lr_select_randomly && (c->policy != RG_POLICY_LOGREG_FROZEN || c->num_products > 1024))

@@ -710,6 +710,29 @@ int nn_host_model(const char* who, uint32_t num_products, uint32_t num_hidden, c
     return RG_OK;
 }
 
+int mlr_host_model(const char* who, uint32_t num_products, const double* d_wt, uint32_t* d_flag, hipStream_t st, MlrModel* m, size_t* smem) {
+    const size_t n = static_cast<size_t>(num_products) * num_products;
+    if (d_flag) {
+        uint32_t bad = 0;
+        HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), st));
+        const size_t blocks = (n + kBlock - 1) / kBlock;
+        hipLaunchKernelGGL(mlr_finite_kernel(), dim3(static_cast<uint32_t>(blocks < 1024 ? blocks : 1024)), dim3(kBlock), 0, st, d_wt, n, d_flag);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&bad, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (bad) return fail(RG_EINVAL, "%sthe model holds a value that is not finite", who);
+    } else {
+        std::vector<double> wt(n);
+        HIP_TRY(hipMemcpy(wt.data(), d_wt, sizeof(double) * n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(wt[i])) return fail(RG_EINVAL, "%sthe model holds a value that is not finite", who);
+    }
+    m->wt = d_wt;
+    m->staged = sizeof(double) * n <= kNnStageBytes ? 1u : 0u;
+    *smem = m->staged ? sizeof(double) * n : 0;
+    return RG_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // profiling: one timeline.  A mark records a pooled event; the stream's time from it to the next mark belongs to `cls`
 // (kProfNone: to nobody — it closes the timeline of a step or a run, and what is launched before the next mark is not timed)
@@ -897,7 +920,10 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         if (int rc = prof_mark(sim, st, kProfLogreg)) return rc;
         // acts of the users whose view history changed since their last one (frozen LogReg at scale)
         hipLaunchKernelGGL(logreg_select_kernel(), dim3(grid_for(upper)), dim3(kBlock), 0, st, d, t);
-        if (d.lr_poly == 3u) {     // NnIpsAgent: a wave per act, lanes over the hidden units, then the products (rg_nn_ips.hip)
+        if (d.lr_poly == 4u) {     // PyTorchMLRAgent: a wave per act, lanes over the actions (rg_mlr.hip)
+            hipLaunchKernelGGL(mlr_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), sim->mlr_smem, st, d, sim->mlr, t);
+            sim->led.mlr += 1;
+        } else if (d.lr_poly == 3u) {     // NnIpsAgent: a wave per act, lanes over the hidden units, then the products (rg_nn_ips.hip)
             hipLaunchKernelGGL(nn_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), sim->nn_smem, st, d, sim->nn, t);
             sim->led.nn_ips += 1;
         } else if (d.lr_poly == 2u) {     // BayesianAgentVB: a wave per act, lanes over the posterior samples (rg_bayes_vb.hip)
@@ -1204,7 +1230,7 @@ void plan_config(rg_sim* s, const rg_config* cfg, uint64_t n_users, const Switch
     d.sigma0 = cfg->sigma_omega_initial; d.sigma_omega = cfg->sigma_omega; d.change_omega_for_bandits = cfg->change_omega_for_bandits;
     // the likelihood agent runs wherever the frozen LogReg policy does, through the same act list: one policy for the kernels
     d.policy = lists_unresolved(cfg->policy) ? RG_POLICY_LOGREG_FROZEN : cfg->policy;
-    d.lr_poly = cfg->policy == RG_POLICY_LOGREG_POLY ? 1u : cfg->policy == RG_POLICY_BAYES_VB ? 2u : cfg->policy == RG_POLICY_NN_IPS ? 3u : 0u;   // (2: k_bayes_acts, 3: k_nn_acts)
+    d.lr_poly = cfg->policy == RG_POLICY_LOGREG_POLY ? 1u : cfg->policy == RG_POLICY_BAYES_VB ? 2u : cfg->policy == RG_POLICY_NN_IPS ? 3u : cfg->policy == RG_POLICY_MLR ? 4u : 0u;   // (2: k_bayes_acts, 3: k_nn_acts, 4: k_mlr_acts)
     d.ouc_select_randomly = cfg->ouc_select_randomly; d.ouc_exploit_explore = cfg->ouc_exploit_explore;
     d.ouc_reverse_pop = cfg->ouc_reverse_pop; d.ouc_epsilon = cfg->ouc_epsilon;
     d.time_mode = cfg->time_mode; d.time_mu = cfg->time_mu; d.time_sigma = cfg->time_sigma; d.env_kind = cfg->env_kind;
@@ -1652,6 +1678,7 @@ int rg_sim_set_epsilon_greedy_model(rg_sim* sim, double epsilon, uint64_t eg_see
         return fail(RG_EINVAL, "rg_sim_set_epsilon_greedy_model wraps the frozen LogReg argmax or the likelihood agent (policy %u)", sim->cfg.policy);
     if (sim->cfg.policy == RG_POLICY_BAYES_VB) return fail(RG_EINVAL, "EpsilonGreedy round RG_POLICY_BAYES_VB: host path");
     if (sim->cfg.policy == RG_POLICY_NN_IPS) return fail(RG_EINVAL, "EpsilonGreedy round RG_POLICY_NN_IPS: host path");
+    if (sim->cfg.policy == RG_POLICY_MLR) return fail(RG_EINVAL, "EpsilonGreedy round RG_POLICY_MLR: host path");
     if (sim->d.lr_sample)
         return fail(RG_EINVAL, "rg_sim_set_epsilon_greedy_model: a LogReg with lr_select_randomly samples its act (propensity != 1): host path");
     if (sim->wh.wt.tab) return fail(RG_EINVAL, "EpsilonGreedy round a time-weighted likelihood agent: host path");
@@ -1771,6 +1798,16 @@ int rg_sim_set_nn_ips(rg_sim* sim, const double* d_w1t, const double* d_b1, cons
     return RG_OK;
 }
 
+int rg_sim_set_mlr(rg_sim* sim, const double* d_wt) {
+    if (!sim) return fail(RG_EINVAL, "sim is NULL");
+    if (sim->cfg.policy != RG_POLICY_MLR) return fail(RG_ESTATE, "policy is not RG_POLICY_MLR");
+    if (sim->users_reset) return fail(RG_ESTATE, "rg_sim_set_mlr must be called before rg_sim_reset_users");
+    if (!d_wt) return fail(RG_EINVAL, "the model array is NULL");
+    if (sim->d.P == 0 || sim->d.P > kMlrProducts) return fail(RG_EINVAL, "RG_POLICY_MLR serves at most %u products (%u)", kMlrProducts, sim->d.P);
+    // (static + dynamic LDS stays below 64 KiB: 12.3 KB of history rows and at most kNnStageBytes of table — no opt-in)
+    return mlr_host_model("", sim->d.P, d_wt, nullptr, nullptr, &sim->mlr, &sim->mlr_smem);
+}
+
 int rg_sim_set_weight_history(rg_sim* sim, const double* d_table, uint32_t n, uint32_t accumulate_f32) {
     if (!sim) return fail(RG_EINVAL, "sim is NULL");
     if (sim->cfg.policy != RG_POLICY_LOGREG_POLY) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY");
@@ -1801,7 +1838,7 @@ int rg_sim_set_weight_history(rg_sim* sim, const double* d_table, uint32_t n, ui
 
 int rg_sim_read_poly_unresolved(rg_sim* sim, uint32_t* out, uint32_t capacity, uint32_t* n_out, uint32_t* overflow, void* stream) {
     if (!sim || !n_out || !overflow || (capacity && !out)) return fail(RG_EINVAL, "NULL argument");
-    if (!lists_unresolved(sim->cfg.policy)) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY, RG_POLICY_BAYES_VB or RG_POLICY_NN_IPS");
+    if (!lists_unresolved(sim->cfg.policy)) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY, RG_POLICY_BAYES_VB, RG_POLICY_NN_IPS or RG_POLICY_MLR");
     if (!sim->users_reset) return fail(RG_ESTATE, "no reset range");
     hipStream_t st = static_cast<hipStream_t>(stream);
     unsigned long long listed = 0;
@@ -1854,6 +1891,8 @@ int rg_sim_reset_users(rg_sim* sim, uint64_t first_user_id, uint64_t n, uint64_t
         return fail(RG_ESTATE, "rg_sim_set_bayes_vb must be called first");
     if (sim->cfg.policy == RG_POLICY_NN_IPS && !sim->nn.w1t)
         return fail(RG_ESTATE, "rg_sim_set_nn_ips must be called first");
+    if (sim->cfg.policy == RG_POLICY_MLR && !sim->mlr.wt)
+        return fail(RG_ESTATE, "rg_sim_set_mlr must be called first");
     if (n == 0 || n > sim->d.n_cap) return fail(RG_EINVAL, "n %llu exceeds the %u users the workspace was sized for",
                                                  (unsigned long long)n, sim->d.n_cap);
     if (first_user_id + n > (1ull << 32)) return fail(RG_EINVAL, "user ids must fit 32 bits");
@@ -2161,6 +2200,18 @@ int rg_sim_debug_nn_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, doubl
     hipLaunchKernelGGL(nn_debug_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), sim->nn_smem, static_cast<hipStream_t>(stream),
                        sim->d, sim->nn, d_action, d_flags, d_z, d_ps);
     sim->led.nn_ips += 1;
+    HIP_TRY(hipGetLastError());
+    return RG_OK;
+}
+
+int rg_sim_debug_mlr_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, double* d_z, void* stream) {
+    if (!sim || !d_action || !d_flags || !d_z) return fail(RG_EINVAL, "NULL argument");
+    if (sim->cfg.policy != RG_POLICY_MLR) return fail(RG_ESTATE, "policy is not RG_POLICY_MLR");
+    if (!sim->mlr.wt) return fail(RG_ESTATE, "rg_sim_set_mlr must be called first");
+    if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
+    hipLaunchKernelGGL(mlr_debug_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), sim->mlr_smem, static_cast<hipStream_t>(stream),
+                       sim->d, sim->mlr, d_action, d_flags, d_z);
+    sim->led.mlr += 1;
     HIP_TRY(hipGetLastError());
     return RG_OK;
 }

@@ -563,8 +563,8 @@ class RecoEnv1(_EnvBase):
             # the likelihood agent: the few acts its device rule lists as unresolved are recomputed on the host; a refuted one
             # (or more of them than the list holds) sends the whole call to the host route below — and so does, for its
             # time-weighted form, a clock value outside the int16 range the weight table covers
-            # (BayesianAgentVB and NnIpsAgent list their unresolved acts the same way: one protocol)
-            stands = pol.get('policy') not in (_abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_BAYES_VB, _abi.RG_POLICY_NN_IPS) or not cnt.get('poly_unresolved') \
+            # (BayesianAgentVB, NnIpsAgent and PyTorchMLRAgent list their unresolved acts the same way: one protocol)
+            stands = pol.get('policy') not in (_abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_BAYES_VB, _abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_MLR) or not cnt.get('poly_unresolved') \
                 or sim.poly_verify(cols)
             stands = stands and not (weighted and cnt.get('wh_clock_range'))
             sim.close()
@@ -575,7 +575,7 @@ class RecoEnv1(_EnvBase):
                     df['ps-a'] = pd.Series(pol['ps_all'](df), dtype=object, copy=False)
                 return df
         if pol is not None:
-            warnings.warn({_abi.RG_POLICY_BAYES_VB: 'BayesianAgentVB', _abi.RG_POLICY_NN_IPS: 'NnIpsAgent'}.get(pol.get('policy'), 'LogregPolyAgent') + ': the host refuted an act the device could not resolve (or the list of such acts '
+            warnings.warn({_abi.RG_POLICY_BAYES_VB: 'BayesianAgentVB', _abi.RG_POLICY_NN_IPS: 'NnIpsAgent', _abi.RG_POLICY_MLR: 'PyTorchMLRAgent'}.get(pol.get('policy'), 'LogregPolyAgent') + ': the host refuted an act the device could not resolve (or the list of such acts '
                           'overflowed' + ('; or a clock value left [0, 32767], or a user had more than WH_VIEW_CEILING views'
                                           if weighted else '') + '); generate_logs repeats the call on the host route', RuntimeWarning)
         if self._time_mode or getattr(use, 'per_user_path', False) or getattr(self.config, 'per_user_path', False) or \

@@ -271,6 +271,8 @@ _REPLAY_ENTRY = {
     ('poly', True): ('rg_ope_poly_workspace_bytes', 'rg_ope_replay_poly_eg'),
     ('nn', False): ('rg_ope_nn_workspace_bytes', 'rg_ope_replay_nn'),
     ('nn', True): ('rg_ope_nn_workspace_bytes', 'rg_ope_replay_nn_eg'),
+    ('mlr', False): ('rg_ope_mlr_workspace_bytes', 'rg_ope_replay_mlr'),
+    ('mlr', True): ('rg_ope_mlr_workspace_bytes', 'rg_ope_replay_mlr_eg'),                # (recall@k's way to the act of every row)
     ('bayes', False): ('rg_ope_bayes_workspace_bytes', 'rg_ope_replay_bayes'),
     ('bayes', True): ('rg_ope_bayes_workspace_bytes', 'rg_ope_replay_bayes_eg'),
 }
@@ -280,6 +282,8 @@ _REFUTED = {
             'device lists): the off-policy evaluation takes the host loop',
     'nn': 'the replay of NnIpsAgent has acts that torch\'s forward on the host does not confirm (or more unresolved acts than the '
           'device lists): the off-policy evaluation takes the host loop',
+    'mlr': 'the replay of PyTorchMLRAgent has acts that the reference\'s fp32 dot on the host does not confirm (or more unresolved acts '
+           'than the device lists): the off-policy evaluation takes the host loop',
     'bayes': 'the replay of BayesianAgentVB has acts that the reference\'s expression on the host does not confirm (or more unresolved '
              'acts than the device lists): the off-policy evaluation takes the host loop',
 }
@@ -296,7 +300,7 @@ def _replay_target(pol, device):
     P = int(pol['num_products'])
     eg, host_act = pol.get('epsilon_greedy'), None
     if eg is not None and (pol.get('kind') not in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE, _abi.RG_POLICY_LOGREG_FROZEN,
-                                                    _abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_BAYES_VB) or (pol.get('logreg') or {}).get('select_randomly')):
+                                                    _abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_BAYES_VB, _abi.RG_POLICY_MLR) or (pol.get('logreg') or {}).get('select_randomly')):
         return None
     if pol.get('logreg_poly') is not None:
         # the likelihood agent: the model and the step table move to the log's device as the step loop's do (sim.poly_device_model)
@@ -316,6 +320,16 @@ def _replay_target(pol, device):
         assert nn.P == P, (nn.P, P)
         cp = _abi.RgOpeNn(P, nn.H, *[t.data_ptr() for t in keep])
         host_act = lambda views: sim.nn_host_act(views, P, nn_host)                     # noqa: E731
+    elif pol.get('mlr') is not None and eg is not None and float(eg['epsilon']) != 0.0:
+        return None      # (rg_ope_replay_mlr_eg serves the wrapper that never explores only: recall@k's way to the acts)
+    elif pol.get('mlr') is not None:
+        # PyTorchMLRAgent: the table moves widened and transposed, as the step loop's does (sim.mlr_device_model)
+        from . import sim
+        unit = 'mlr'
+        mlr_host, wt = sim.mlr_device_model(pol['mlr'], device)
+        assert int(wt.shape[0]) == P, (wt.shape, P)
+        cp, keep = _abi.RgOpeMlr(P, wt.data_ptr()), [wt]
+        host_act = lambda views: sim.mlr_host_act(views, P, mlr_host)                   # noqa: E731
     elif pol.get('bayes_vb') is not None:
         # BayesianAgentVB: the posterior samples move transposed, as the step loop's do (sim.bayes_device_model)
         from . import sim
@@ -373,7 +387,8 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
     sums = float64 tensor (n, sum c r, sum r).  None where the agent has no replay form or the log does not qualify (a user
     that opens with a bandit row; a float clock under a policy that draws).  `stats` (a dict, frozen LogReg policies only)
     receives the head words of the LogReg unit's workspace: error, acts, exact (acts decided by float64 scores), rows_read; under the
-    likelihood agent, NnIpsAgent and BayesianAgentVB those of their units (_abi.OPE_HEADS: 'poly', 'nn', 'bayes').  Their replay
+    likelihood agent, NnIpsAgent, BayesianAgentVB and PyTorchMLRAgent those of their units (_abi.OPE_HEADS: 'poly', 'nn', 'bayes',
+    'mlr').  Their replay
     is None, after one RuntimeWarning, also where the host refutes an unresolved act or the device's list of them overflowed (under an
     EpsilonGreedy wrapper the listed acts are the GREEDY ones; with pure_new a wrong one changes pi on explored rows too).  `eg_out` (a
     dict, EpsilonGreedy targets only) receives `greedy` (uint8) and `h0` (int32) of the same bandit rows (device tensors); where it
@@ -564,7 +579,7 @@ def _recall_form(pol):
     if (pol.get('logreg') or {}).get('select_randomly'):
         return 'rank' if eg is None else None
     if kind in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE, _abi.RG_POLICY_LOGREG_FROZEN, _abi.RG_POLICY_LOGREG_POLY,
-                _abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_BAYES_VB):
+                _abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_BAYES_VB, _abi.RG_POLICY_MLR):
         return 'table'
     return None
 
@@ -888,7 +903,7 @@ def _device_route(env, agent):
     pol = device_policy_of(agent)
     # the likelihood agent's device acts need the host's confirmation of the unresolved ones, which generate_logs
     # gives and this study's device loop does not: host route
-    return pol is not None and pol.get('policy') not in (_abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_BAYES_VB, _abi.RG_POLICY_NN_IPS)
+    return pol is not None and pol.get('policy') not in (_abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_BAYES_VB, _abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_MLR)
 
 
 def _new_rewards(num_products):

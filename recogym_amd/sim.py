@@ -147,6 +147,23 @@ def nn_host_act(views, num_products, agent):
     return agent.act_on(np.flatnonzero(x), x[np.flatnonzero(x)])[0]
 
 
+def mlr_device_model(mlr, device):
+    """A policy dict's `mlr` entry (state: dict(W (P, P) float32, [action][viewed product])) -> (the frozen host agent, the float64
+    table [viewed product][action] on `device`, rg_sim_set_mlr's layout)."""
+    from .agents.pytorch_mlr import PyTorchMLRFrozenAgent, mlr_table
+    from .envs.configuration import Configuration
+    W = np.asarray(mlr['state']['W'], dtype=np.float32)
+    host = PyTorchMLRFrozenAgent(Configuration({'num_products': W.shape[0]}), W)
+    return host, torch.from_numpy(mlr_table(W)).to(device)
+
+
+def mlr_host_act(views, num_products, agent):
+    """The host act of PyTorchMLRAgent on the organic views `views` (product ids, any order): the reference's fp32 dot on the dense
+    float32 counts, first maximum — what the device's unresolved acts are judged by."""
+    x = np.bincount(np.asarray(views, dtype=np.int64), minlength=int(num_products))
+    return agent.act_on(np.flatnonzero(x), x[np.flatnonzero(x)])[0]
+
+
 def poly_host_act(views, model):
     """The host act of the likelihood agent on the organic views `views` (product ids, any order) under model = (wf, wa, wk, b):
     the decisions in the contract's order, scipy's expit, first maximum — what the device's unresolved acts are judged by."""
@@ -226,6 +243,9 @@ class Simulator:
     nn_ips       dict(state = dict(w1, b1, w2, b2, w3, b3)): NnIpsAgent's net (RG_POLICY_NN_IPS; agents/nn_ips.py), widened to float64,
                  transposed and uploaded here; ps is the model's output, kept in float64.  Its unresolved acts share the likelihood
                  agent's list, counter (`poly_unresolved`) and `poly_verify`, which judges them by torch's fp32 forward.
+    mlr          dict(state = dict(W (P, P) float32)): PyTorchMLRAgent's weight (RG_POLICY_MLR; agents/pytorch_mlr.py), widened to
+                 float64, transposed and uploaded here; ps = 1.  Its unresolved acts share the likelihood agent's list, counter
+                 (`poly_unresolved`) and `poly_verify`, which judges them by the reference's fp32 dot.
     bayes_vb     dict(lam (S, P^2)): BayesianAgentVB's posterior draws (RG_POLICY_BAYES_VB; agents/bayesian_poly_vb.py), transposed
                  and uploaded here.  Its unresolved acts share the likelihood agent's list, counter (`poly_unresolved`) and
                  `poly_verify`, which judges them by the reference's own expression.
@@ -234,7 +254,7 @@ class Simulator:
     def __init__(self, config, n_users, policy=_abi.RG_POLICY_UNIFORM_ENV, policy_seed=None,
                  ouc=None, epoch=0, log_capacity=None, device=None, tables=None, policy_table=None,
                  policy_ps=None, logreg=None, ps_float64=None, p_click=False, env0=None, policy_ps64=False,
-                 epsilon_greedy=None, logreg_poly=None, bayes_vb=None, nn_ips=None):
+                 epsilon_greedy=None, logreg_poly=None, bayes_vb=None, nn_ips=None, mlr=None):
         if policy == _abi.RG_POLICY_LOGREG_FROZEN and ((logreg or {}).get('int8') or os.environ.get('RECOGYM_LOGREG') == 'int8'):
             # (refused, not ignored: a caller that labels the act's bytes from this switch would report 1 B per weight for an fp16 run)
             raise ValueError("the 8-bit LogReg screen is retired (measured slower than the fp16 screen): drop logreg['int8'] / RECOGYM_LOGREG=int8")
@@ -361,6 +381,10 @@ class Simulator:
                 self.nn_ips_host, self.nn_ips_model, self.nn_ips = nn_device_model(nn_ips, self.device)
                 _abi.check(self.lib.rg_sim_set_nn_ips(self._h, *[x.data_ptr() for x in self.nn_ips], int(self.nn_ips_model.H)),
                            'rg_sim_set_nn_ips')
+            self.mlr_host = None
+            if policy == _abi.RG_POLICY_MLR:
+                self.mlr_host, self.mlr = mlr_device_model(mlr, self.device)
+                _abi.check(self.lib.rg_sim_set_mlr(self._h, self.mlr.data_ptr()), 'rg_sim_set_mlr')
             self.poly_unresolved = self.poly_refuted = None
             self.poly_overflow = False
             if log_capacity is None:
@@ -524,6 +548,19 @@ class Simulator:
             torch.cuda.synchronize(self.device)
         return act.cpu().numpy().astype(np.int64), fl.cpu().numpy().astype(np.int64), z.cpu().numpy(), ps.cpu().numpy()
 
+    def debug_mlr_acts(self):
+        """rg_sim_debug_mlr_acts -> (actions, flags, z (n, P)): PyTorchMLRAgent's act of every user index on its current history, the
+        device's scores."""
+        n, P = self.n_active, int(self.config.num_products)
+        with torch.cuda.device(self.device):
+            act = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+            fl = torch.full((n,), 255, dtype=torch.uint8, device=self.device)
+            z = torch.full((n, P), float('nan'), dtype=torch.float64, device=self.device)
+            _abi.check(self.lib.rg_sim_debug_mlr_acts(self._h, act.data_ptr(), fl.data_ptr(), z.data_ptr(), self._stream()),
+                       'rg_sim_debug_mlr_acts')
+            torch.cuda.synchronize(self.device)
+        return act.cpu().numpy().astype(np.int64), fl.cpu().numpy().astype(np.int64), z.cpu().numpy()
+
     def debug_set_timed_history(self, n_views, products, times16):
         """rg_sim_debug_set_timed_history: per user index of the reset range, n_views[i] views (products[i, j] at clock value
         times16[i, j], in view order) as its time-weighted history."""
@@ -595,6 +632,8 @@ class Simulator:
                                              clock[mine & (t == t_act)], self.weight_history, self.logreg_poly_host)
                 elif self.nn_ips_host is not None:
                     host = nn_host_act(v[organic & (u == user) & (t <= t_act)], self.config.num_products, self.nn_ips_host)
+                elif self.mlr_host is not None:
+                    host = mlr_host_act(v[organic & (u == user) & (t <= t_act)], self.config.num_products, self.mlr_host)
                 elif self.bayes_vb_host is not None:
                     host = bayes_host_act(v[organic & (u == user) & (t <= t_act)], self.config.num_products, self.bayes_vb_host)
                 else:

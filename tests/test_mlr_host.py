@@ -1,0 +1,309 @@
+"""PyTorchMLRAgent on the host: the port's build() against the unmodified reference's own, bit for bit; the host act against the
+reference's own logs (tests/golden/mlr_*.npz, tests/make_golden_mlr.py); the device rule restated in numpy (mlr_rule on
+mlr_forward) and its margin against the fp32 dot; where the agent has a device form.  No device."""
+import sys
+
+import numpy as np
+import pytest
+
+import golden_util as gu
+import mlr_util as mu
+import ref_harness as rh
+from make_golden_ope import log_frame
+from recogym_amd import _abi
+from recogym_amd import agents
+from recogym_amd.agents.pytorch_mlr import (COUNT_CAP, PRODUCTS_CAP, UNRESOLVED, PyTorchMLRAgent, PyTorchMLRFrozenAgent, host_act,
+                                            mlr_forward, mlr_margin, mlr_rule, mlr_table, pytorch_mlr_args)
+from recogym_amd.envs.configuration import Configuration
+from recogym_amd.envs.context import DefaultContext
+from recogym_amd.envs.observation import Observation
+from recogym_amd.envs.session import OrganicSessions
+
+AGENT_SEED = 7
+
+
+def test_agent_is_exported_with_the_reference_arguments():
+    assert agents.PyTorchMLRAgent is PyTorchMLRAgent and agents.pytorch_mlr_args is pytorch_mlr_args
+    assert agents.PyTorchMLRFrozenAgent is PyTorchMLRFrozenAgent
+    want = dict(n_epochs=30, learning_rate=0.01, logIPS=False, variance_penalisation_strength=.0, clip_weights=False, alpha=.0, ll_IPS=True)
+    assert {k: v for k, v in pytorch_mlr_args.items() if k != 'random_seed'} == want and 'random_seed' in pytorch_mlr_args
+    assert _abi.RG_POLICY_MLR == 12 and _abi.RG_ABI_VERSION == 14 and UNRESOLVED == 2
+
+
+def test_the_policy_is_accepted_and_its_neighbours_stay_refused():
+    """rg_sim_create is host code: the policy sizes the workspace of the other argmax policies with ps = 1 (BayesianAgentVB's: a
+    history row, the unresolved list, no propensity row); 11 and 13 stay refused."""
+    import ctypes as C
+    import __graft_entry__ as graft
+    import make_golden_create_plan as plan
+    graft.build()
+    lib = _abi.load()
+    n = 100000
+    need = lib.rg_sim_workspace_bytes(C.byref(plan.rg_config(plan._c(policy=_abi.RG_POLICY_MLR))), n)
+    assert need == lib.rg_sim_workspace_bytes(C.byref(plan.rg_config(plan._c(policy=_abi.RG_POLICY_BAYES_VB))), n) > 0
+    for refused in (11, 13):
+        assert lib.rg_sim_workspace_bytes(C.byref(plan.rg_config(plan._c(policy=refused))), n) == 0
+
+
+# ------------------------------------------------------------------------------------------------
+# 1. training equals the reference
+# ------------------------------------------------------------------------------------------------
+_REF_ROOTS = ('gym', 'numba', 'recogym')
+
+
+@pytest.fixture
+def reference(monkeypatch):
+    """The reference package imported against tests/ref_shims, isolated from the rest of the session (as in test_nn_ips_host.py)."""
+    if not rh.reference_available():
+        pytest.skip('reference package not present')
+    for k in [k for k in sys.modules if k.split('.')[0] in _REF_ROOTS]:
+        monkeypatch.delitem(sys.modules, k)
+    monkeypatch.syspath_prepend(rh.SHIMS)
+    try:
+        yield rh.import_reference()
+    finally:
+        for k in [k for k in sys.modules if k.split('.')[0] in _REF_ROOTS]:
+            sys.modules.pop(k, None)
+
+
+def reference_log_frame(train):
+    import pandas as pd
+    return pd.DataFrame(dict(t=train['t'], u=train['u'], z=np.where(train['z'] == 1, 'bandit', 'organic'), v=train['v'], a=train['a'],
+                             c=train['c'], ps=train['ps']))
+
+
+@pytest.fixture
+def one_thread():
+    """torch on one thread: with several, the backward of the binomial part's row gather (weight[a, :], an index_put_ that
+    accumulates) adds in the order the threads arrive, and the reference's own build() does not reproduce its own bits from run to
+    run for alpha > 0.  Bit equality of two builds is a statement about one thread."""
+    import torch
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(n)
+
+
+def port_weight(train, **over):
+    import torch
+    ag = PyTorchMLRAgent(Configuration({**pytorch_mlr_args, 'num_products': 10, 'random_seed': AGENT_SEED, **over}))
+    ag.train_from_log(log_frame(train))
+    assert ag.frozen is None                                  # the model is built at the first act
+    torch.manual_seed(AGENT_SEED)
+    return ag._ready().W
+
+
+CASES = [dict(alpha=0.0), dict(alpha=0.5), dict(alpha=1.0), dict(clip_weights=True), dict(clip_weights=3.0), dict(logIPS=True),
+         dict(variance_penalisation_strength=0.1), dict(alpha=0.5, ll_IPS=False)]
+
+
+@pytest.mark.parametrize('over', CASES, ids=lambda o: ','.join(f'{k}={v}' for k, v in o.items()))
+def test_build_equals_the_reference_build_bit_for_bit(reference, one_thread, over, capsys):
+    """Both run live on the training log of mlr_p10_a05 (150 users) from the same torch seed: 200 L-BFGS steps each, and the same
+    bits in W — the port's optimiser issues the reference optimiser's torch operations in its order.  (ll_IPS shows only where the
+    binomial part is on: that case runs at alpha = 0.5.)  The port prints nothing."""
+    from make_golden_mlr import reference_agent, weight_of
+    train = mu.training_log('mlr_p10_a05')
+    want = weight_of(reference_agent(10, reference_log_frame(train), **over))
+    capsys.readouterr()
+    got = port_weight(train, **over)
+    out = capsys.readouterr()
+    assert out.out == '' and out.err == ''
+    assert got.dtype == np.float32 and got.shape == (10, 10) and np.isfinite(got).all()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), np.abs(got - want).max()
+
+
+def test_training_moves_the_weight_and_depends_on_the_case(one_thread):
+    """Without the reference: the trained weight is not the initial one, and alpha changes it."""
+    import torch
+    from recogym_amd.agents.pytorch_mlr import make_models
+    train = mu.training_log('mlr_p10_a05')
+    torch.manual_seed(AGENT_SEED)
+    init = make_models(10)[0].weight.detach().numpy().copy()
+    a0, a1 = port_weight(train, alpha=0.0), port_weight(train, alpha=1.0)
+    assert not np.array_equal(a0, init) and not np.array_equal(a1, init) and not np.array_equal(a0, a1)
+    assert np.array_equal(a0, port_weight(train, alpha=0.0))
+
+
+def test_train_from_log_equals_call_by_call_train():
+    import torch
+    from recogym_amd.bench_agents import _train_from_dataframe
+    train = mu.training_log('mlr_p10_a05')
+    keep = train['u'] < 40
+    train = {k: v[keep] for k, v in train.items()}
+    a = PyTorchMLRAgent(Configuration({**pytorch_mlr_args, 'num_products': 10, 'random_seed': AGENT_SEED}))
+    a.train_from_log(log_frame(train))
+    b = PyTorchMLRAgent(Configuration({**pytorch_mlr_args, 'num_products': 10, 'random_seed': AGENT_SEED}))
+    _train_from_dataframe(b, log_frame(train))
+    fa, fb = a._training_set(), b._training_set()
+    for x, y in zip(fa, fb):
+        x = np.asarray(x.todense()) if hasattr(x, 'todense') else np.asarray(x)
+        y = np.asarray(y.todense()) if hasattr(y, 'todense') else np.asarray(y)
+        assert np.array_equal(x, y)
+
+
+# ------------------------------------------------------------------------------------------------
+# 2. the host act equals the reference's model
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', mu.FIXTURES)
+def test_host_act_reproduces_the_reference_rows(name):
+    """act_on on the history of every bandit row of the fixture is the reference's action there; the frozen agent driven like
+    generate_logs drives it (40 users) returns the same with ps = 1 and the one-hot `ps-a`, whatever with_ps_all says."""
+    meta, cols = gu.load(name)
+    P = meta['env_args']['num_products']
+    W = mu.fixture_weight(meta, cols)
+    ag = PyTorchMLRFrozenAgent(Configuration({'num_products': P}), W)
+    n_rows = 0
+    for act in mu.rule_over_log(cols, P, W):
+        a, ps = ag.act_on(act['prods'], act['cnts'])
+        assert ps == 1.0
+        for i in act['rows']:
+            assert a == cols['a'][i], (name, i, a, int(cols['a'][i]))
+            n_rows += 1
+    assert n_rows == int((cols['z'] == 1).sum()) > 5000
+    u, z, v, a, t = cols['u'], cols['z'], cols['v'], cols['a'], cols['t']
+    cur, session, n_acts = None, None, 0
+    for i in np.flatnonzero(u < 40):
+        if u[i] != cur:
+            cur, session = u[i], OrganicSessions()
+            ag.reset()
+        if z[i] == 0:
+            session.next(DefaultContext(int(t[i]), int(u[i])), int(v[i]))
+        else:
+            act = ag.act(Observation(DefaultContext(int(t[i]), int(u[i])), session), 0, False)
+            assert act['a'] == a[i] and act['ps'] == 1.0 and cols['ps'][i] == 1.0, (name, i)
+            assert act['ps-a'].shape == (P,) and act['ps-a'].sum() == 1.0 and act['ps-a'][a[i]] == 1.0
+            session = OrganicSessions()
+            n_acts += 1
+    assert n_acts > 500
+
+
+@pytest.mark.parametrize('name', mu.FIXTURES)
+def test_fixture_conditions(name):
+    """What the generator asserted: every act the rule resolves is the reference's; the recorded census; at least 5 distinct
+    actions and at most 1 % unresolved acts in a trained fixture, at least 20 % unresolved acts in mlr_p10_ties."""
+    meta, cols = gu.load(name)
+    P = meta['env_args']['num_products']
+    acts, unresolved, distinct = mu.check_log_against_rule(cols, P, mu.fixture_weight(meta, cols), name)
+    census = dict(acts=len(acts), unresolved=unresolved, distinct_actions=distinct)
+    assert census == meta['census'] and mu.census_ok(name, census) and len(acts) > 200
+    if name in mu.TRAINED:
+        assert distinct >= 5 and 100 * unresolved <= len(acts)
+        assert 10 * 1024 <= sum(v.nbytes for k, v in cols.items() if k.startswith('trainlog_'))
+    if name == 'mlr_p10_ties':
+        assert 5 * unresolved >= len(acts)
+
+
+# ------------------------------------------------------------------------------------------------
+# 3. the margin holds
+# ------------------------------------------------------------------------------------------------
+def check_margin(prods, cnts, W, wt):
+    """mlr_forward within E of the fp32 dot on this history, and a resolved act is the fp32 act -> resolved?"""
+    P = W.shape[0]
+    x = np.zeros(P, dtype=np.float32)
+    x[prods] = cnts
+    z32 = x.reshape(1, P).dot(W.T).reshape(P)
+    z, action, M1 = mlr_forward(prods, cnts, wt)
+    E = mlr_margin(len(prods), M1)
+    assert np.abs(z32.astype(np.float64) - z).max() <= E, (prods, cnts, np.abs(z32.astype(np.float64) - z).max(), E)
+    a, fl, _ = mlr_rule(prods, cnts, wt)
+    assert a == action
+    if not fl & UNRESOLVED:
+        assert a == int(np.argmax(z32)) == host_act(x, W), (prods, cnts, a)
+    return not fl & UNRESOLVED
+
+
+@pytest.mark.parametrize('name', mu.FIXTURES)
+def test_margin_holds_on_the_fixtures(name):
+    meta, cols = gu.load(name)
+    P = meta['env_args']['num_products']
+    W = mu.fixture_weight(meta, cols)
+    wt = mlr_table(W)
+    resolved = sum(check_margin(a['prods'], a['cnts'], W, wt) for a in mu.rule_over_log(cols, P, W))
+    assert (resolved == 0) == (name == 'mlr_p10_ties')
+
+
+@pytest.mark.parametrize('P', [2, 10, 65, 130])
+def test_margin_holds_on_random_histories(P):
+    """10^4 random histories per P, counts up to 2^24 (the largest the rule resolves), weights of three scales."""
+    rng = np.random.RandomState(P)
+    resolved = 0
+    for scale in (0.3, 1e-3, 1e4):
+        W = (rng.standard_normal((P, P)) * scale).astype(np.float32)
+        wt = mlr_table(W)
+        for k in range(3334):
+            n = rng.randint(1, P + 1)
+            prods = np.sort(rng.choice(P, n, replace=False))
+            kind = k % 3
+            cnts = rng.randint(1, 4, n) if kind == 0 else rng.randint(1, 301, n) if kind == 1 else rng.randint(1, COUNT_CAP + 1, n)
+            if kind == 2:
+                cnts[rng.randint(n)] = COUNT_CAP
+            resolved += check_margin(prods, cnts, W, wt)
+    assert resolved > 5000
+
+
+def test_rule_edges():
+    W = np.zeros((4, 4), dtype=np.float32)
+    W[2] = 1.0
+    wt = mlr_table(W)
+    assert mlr_rule([], [], wt)[:2] == (0, UNRESOLVED)                              # the empty history: all scores 0
+    assert mlr_rule([1], [3], wt)[:2] == (2, 0)
+    assert mlr_rule([1], [COUNT_CAP], wt)[:2] == (2, 0)
+    assert mlr_rule([1], [COUNT_CAP + 1], wt)[:2] == (2, UNRESOLVED)                # not an fp32 value
+    W[3] = 1.0
+    assert mlr_rule([1], [3], mlr_table(W))[:2] == (2, UNRESOLVED)                  # an exact tie: the lowest index, listed
+    W[3] = np.float32(1.0) + np.float32(2.0 ** -23)                                 # 2^-23 ahead; E = 6 * 2^-24 * c (1 + 2^-23)
+    assert mlr_rule([1], [3], mlr_table(W))[:2] == (3, UNRESOLVED)
+    assert mlr_margin(1, 3.0) == 6 * 2.0 ** -24 * 3.0
+    W[3] = 2.0
+    assert mlr_rule([1], [3], mlr_table(W))[:2] == (3, 0)
+    big = np.zeros((2, 2), dtype=np.float32)
+    big[1] = 3e38
+    assert mlr_rule([0], [1], mlr_table(big))[:2] == (1, UNRESOLVED)                # M1 >= 2^126: an fp32 sum could overflow
+
+
+# ------------------------------------------------------------------------------------------------
+# 4. refusals
+# ------------------------------------------------------------------------------------------------
+def test_device_policy_and_replay_refusals():
+    rng = np.random.RandomState(1)
+    W = rng.standard_normal((10, 10)).astype(np.float32)
+    ok = PyTorchMLRFrozenAgent(Configuration({'num_products': 10, 'device_replay': True}), W)
+    pol, rep = ok.device_policy(), ok.ope_policy_checked()
+    assert pol['policy'] == _abi.RG_POLICY_MLR and np.array_equal(pol['mlr']['state']['W'], W) and callable(pol['ps_all'])
+    assert rep['kind'] == _abi.RG_POLICY_MLR and rep['num_products'] == 10 and np.array_equal(rep['mlr']['state']['W'], W)
+    assert ok.ope_policy() is None
+    # the replay is opt-in; the step loop is not
+    plain = PyTorchMLRFrozenAgent(Configuration({'num_products': 10}), W)
+    assert plain.device_policy() is not None and plain.ope_policy_checked() is None
+    weighted = PyTorchMLRFrozenAgent(Configuration({'num_products': 10, 'device_replay': True, 'weight_history_function': lambda dt: np.exp(-dt)}), W)
+    assert weighted.device_policy() is None and weighted.ope_policy_checked() is None
+    for bad in (np.inf, np.nan):
+        Wb = W.copy()
+        Wb[3, 4] = bad
+        ag = PyTorchMLRFrozenAgent(Configuration({'num_products': 10, 'device_replay': True}), Wb)
+        assert ag.device_policy() is None and ag.ope_policy_checked() is None
+    P = PRODUCTS_CAP + 1
+    large = PyTorchMLRFrozenAgent(Configuration({'num_products': P, 'device_replay': True}), np.zeros((P, P), dtype=np.float32))
+    assert large.device_policy() is None and large.ope_policy_checked() is None
+    # the training agent hands both through once it is built
+    train = mu.training_log('mlr_p10_a05')
+    keep = train['u'] < 10
+    ag = PyTorchMLRAgent(Configuration({**pytorch_mlr_args, 'num_products': 10, 'random_seed': AGENT_SEED, 'device_replay': True}))
+    ag.train_from_log(log_frame({k: v[keep] for k, v in train.items()}))
+    assert ag.device_policy()['policy'] == _abi.RG_POLICY_MLR and ag.ope_policy_checked()['kind'] == _abi.RG_POLICY_MLR
+    assert ag.needs_training
+
+
+def test_ps_all_hook_is_one_hot_on_bandit_rows():
+    meta, cols = gu.load('mlr_p10_a05')
+    keep = cols['u'] < 5
+    df = log_frame({k: v[keep] for k, v in cols.items() if not k.startswith(('trainlog_', 'mlr_'))})
+    ag = PyTorchMLRFrozenAgent(Configuration({'num_products': 10}), mu.fixture_weight(meta, cols))
+    out = ag.ps_all_from_log(df)
+    is_b = (df['z'] == 'bandit').to_numpy()
+    assert all(x is None for x in out[~is_b])
+    for x, a in zip(out[is_b], df['a'][is_b]):
+        assert x.shape == (10,) and x.sum() == 1.0 and x[int(a)] == 1.0
