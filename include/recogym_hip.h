@@ -64,7 +64,8 @@ extern "C" {
 /* v14, additive since: RG_POLICY_MLR with rg_sim_set_mlr and rg_sim_debug_mlr_acts (the argmax act of PyTorchMLRAgent in the step
  * loop) and the flag RG_MLR_UNRESOLVED; its unresolved acts share the same list, counter and reader; and rg_ope_mlr_workspace_bytes /
  * rg_ope_replay_mlr / rg_ope_replay_mlr_eg (its off-policy replay). */
-#define RG_ABI_VERSION 14
+/* v15: rg_sim_debug_logreg_acts (the frozen LogReg's act kernels on placed histories). */
+#define RG_ABI_VERSION 15
 
 /* error codes */
 #define RG_OK 0
@@ -607,6 +608,13 @@ int rg_sim_debug_nn_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, doubl
  * function the step loop uses: d_action[i], d_flags[i] (RG_MLR_UNRESOLVED) and the scores d_z[i * num_products + a].
  * Touches neither the counters nor the list. */
 int rg_sim_debug_mlr_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, double* d_z, void* stream);
+/* rg_sim_debug_logreg_acts: the plain RG_POLICY_LOGREG_FROZEN act (argmax; not lr_select_randomly) of every user index on its current
+ * history (rg_sim_debug_set_history), right after rg_sim_reset_users, by the kernels the step loop launches, chosen as the step
+ * chooses them: k_logreg_screen + k_logreg_decide where the fp16 copy is attached (k_logreg_acts for what lies beyond lr_part_cap),
+ * k_logreg_acts otherwise.  Every slot is listed for an act at step 0 in place of k_logreg_select; d_action[i] = the act kept for
+ * user index i.  The counters (RG_CNT_LR_ACTS, RG_CNT_LR_ROWS, RG_CNT_LR_EXACT) and the launch ledger count as in a step.  The call
+ * leaves step 0's act list filled: rg_sim_step, rg_sim_run and every hook refuse (RG_ESTATE) until rg_sim_reset_users is called again. */
+int rg_sim_debug_logreg_acts(rg_sim* sim, int32_t* d_action, void* stream);
 /* rg_sim_debug_set_timed_history (after rg_sim_set_weight_history, right after rg_sim_reset_users): the TIMED view history of every
  * user index — d_n[i] views (at most stride), view j of product d_products[i * stride + j] at clock value d_times16[i * stride + j],
  * in view order (times never decreasing).  They go into the user's history row one at a time through the sorted insert that never

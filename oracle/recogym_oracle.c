@@ -162,6 +162,7 @@ typedef struct rgo_env {
     rgo_mt pol_mt;            /* agent.rng / agent.model.rng in MT mode */
     /* policy state: ViewsFeaturesProvider.views (agents/abstract.py:379-395) */
     int32_t* views;           /* (P) */
+    uint32_t* stored;         /* (P) scratch of the LogReg act: the viewed products, ascending */
     int32_t last_view;        /* BanditMFSquare.last_product_viewed (bandit_mf.py:60-65) */
     const int32_t* pol_table; /* RG_POLICY_LAST_VIEW_TABLE: action per last viewed product */
     const double* pol_ps;     /* and the ps logged with it (NULL = 1.0) */
@@ -178,6 +179,8 @@ typedef struct rgo_env {
     int64_t counters[4];      /* organic, bandit (real), clicks, phantom */
 } rgo_env;
 
+void rgo_env_destroy(rgo_env* e);
+
 rgo_env* rgo_env_create(const rg_config* cfg, int rng_mode, const double* gamma,
                         const double* mu_o, const double* beta, const double* mu_b) {
     rgo_env* e = (rgo_env*)calloc(1, sizeof(rgo_env));
@@ -187,9 +190,11 @@ rgo_env* rgo_env_create(const rg_config* cfg, int rng_mode, const double* gamma,
     e->gamma = gamma; e->mu_o = mu_o; e->beta = beta; e->mu_b = mu_b;
     e->omega = (double*)calloc(cfg->K, sizeof(double));
     e->views = (int32_t*)calloc(cfg->num_products, sizeof(int32_t));
+    e->stored = (uint32_t*)calloc(cfg->num_products ? cfg->num_products : 1, sizeof(uint32_t));
     e->buf = (double*)calloc(cfg->num_products, sizeof(double));
     e->zbuf = (double*)calloc(cfg->K, sizeof(double));
     e->cdfbuf = (double*)calloc(cfg->num_products, sizeof(double));   /* per-instance scratch: no malloc per draw */
+    if (!e->omega || !e->views || !e->stored || !e->buf || !e->zbuf || !e->cdfbuf) { rgo_env_destroy(e); return NULL; }
     e->state = RG_STATE_ORGANIC;
     e->first_step = 1;
     /* init_gym: reset_random_seed (abstract.py:88); agents seed their own RandomState at
@@ -201,7 +206,7 @@ rgo_env* rgo_env_create(const rg_config* cfg, int rng_mode, const double* gamma,
 
 void rgo_env_destroy(rgo_env* e) {
     if (!e) return;
-    free(e->omega); free(e->views); free(e->buf); free(e->zbuf); free(e->cdfbuf); free(e);
+    free(e->omega); free(e->views); free(e->stored); free(e->buf); free(e->zbuf); free(e->cdfbuf); free(e);
 }
 
 /* LogregMulticlassIpsAgent with a fitted model (agents/logreg_ips.py:60-87, select_randomly = False) */
@@ -505,10 +510,16 @@ int32_t rgo_env_policy_act(rgo_env* e, double* ps_out) {
          * plain expression below is that arithmetic.  argmax = first maximum (numpy). */
         uint32_t best = 0;
         double best_s = 0.0;
+        /* the stored products once per act, ascending (the same terms in the same order for every class: at 4 096 products and
+         * classes the scan of all P view counts per class was the whole time of a run) */
+        uint32_t* stored = e->stored;
+        uint32_t n_stored = 0;
+        for (uint32_t p = 0; p < P; ++p)
+            if (e->views[p]) stored[n_stored++] = p;
         for (uint32_t c = 0; c < e->lr_n; ++c) {
             double sc = 0.0;
-            for (uint32_t p = 0; p < P; ++p)
-                if (e->views[p]) sc = sc + (double)e->views[p] * e->lr_coef_t[(size_t)p * e->lr_n + c];
+            for (uint32_t i = 0; i < n_stored; ++i)
+                sc = sc + (double)e->views[stored[i]] * e->lr_coef_t[(size_t)stored[i] * e->lr_n + c];
             sc = sc + e->lr_intercept[c];
             if (e->cfg.lr_select_randomly && c < P) e->buf[c] = sc;
             if (c == 0 || sc > best_s) { best = c; best_s = sc; }

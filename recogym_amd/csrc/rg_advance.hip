@@ -296,6 +296,9 @@ __global__ void __launch_bounds__(kBlock, RG_LR_OCC) k_logreg_screen(DevSim d, u
                            static_cast<float>(nd + 3) * 5.9604644775390625e-08f * (d.lr_bmax + A)) * 1.02f;
         const float thr = 2.0f * B16 * 1.01f + 1e-30f;
         const uint32_t c_lo = r * RC, c_hi = min(c_lo + RC, C);
+        // what a lane outside the range reads instead (values unused): in bounds for an EMPTY range too (c_lo >= C where 7 RC >= C:
+        // C = 16, 56, 72, ...), where c_lo itself lies past intercept32 and the rows (C % 8 == 0 and C >= 8 with fp16 attached)
+        const uint32_t c_safe = min(c_lo, C - 8u);
         float rb = -INFINITY;
         uint32_t n_cand = 0;
         bool overflow = false;
@@ -335,7 +338,7 @@ __global__ void __launch_bounds__(kBlock, RG_LR_OCC) k_logreg_screen(DevSim d, u
         for (int e = 0; e < 8; ++e) rp[e] = d.lr_coef16_t + static_cast<size_t>(p8[e]) * C;
         auto fetch = [&](uint32_t c0, Batch& bt) {
             const uint32_t c = c0 + 8u * static_cast<uint32_t>(lane);
-            const uint32_t cl = c < c_hi ? c : c_lo;
+            const uint32_t cl = c < c_hi ? c : c_safe;
             bt.b0 = *reinterpret_cast<const float4*>(d.lr_intercept32 + cl);
             bt.b1 = *reinterpret_cast<const float4*>(d.lr_intercept32 + cl + 4);
 #pragma unroll
@@ -347,7 +350,7 @@ __global__ void __launch_bounds__(kBlock, RG_LR_OCC) k_logreg_screen(DevSim d, u
             const bool more = c0 + 512 < c_hi;
             const uint32_t c = c0 + 8u * static_cast<uint32_t>(lane);
             const bool in = c < c_hi;
-            const uint32_t cl = in ? c : c_lo;
+            const uint32_t cl = in ? c : c_safe;
             float acc[8] = {cur.b0.x, cur.b0.y, cur.b0.z, cur.b0.w, cur.b1.x, cur.b1.y, cur.b1.z, cur.b1.w};
 #pragma unroll
             for (int e = 0; e < 8; ++e) {                        // (rows beyond the history: count 0, no branch)

@@ -277,6 +277,11 @@ __global__ void __launch_bounds__(kBlock) k_debug_set_history(DevSim d, const ui
         hr[0] = (views << 32) | nd[i];
     }
 }
+// rg_sim_debug_logreg_acts: every slot of the reset range listed for an act at step 0, in place of k_logreg_select
+__global__ void __launch_bounds__(kBlock) k_debug_logreg_list(DevSim d) {
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < d.n_users; i += gridDim.x * kBlock) d.lr_list[i] = i;
+    if (blockIdx.x == 0 && threadIdx.x == 0) d.lr_cnt[0] = d.n_users;
+}
 // rg_sim_debug_ouc_acts: policy_act (OrganicUserEventCounter) with a caller-chosen second uniform, per user index
 __global__ void __launch_bounds__(kBlock) k_debug_ouc_acts(DevSim d, const double* u1, int32_t* action, double* ps, uint8_t* flags) {
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < d.n_users; i += gridDim.x * kBlock) {
@@ -836,6 +841,31 @@ int sweep_grid(rg_sim* sim, uint64_t work_items) {
 // k_poly_acts_w: a wave per act, at most kWhGridBlocks blocks (its waves own the rows of WhRun::spill)
 constexpr int wh_grid(uint64_t acts) { return grid_for(acts, kBlock / 64) < kWhGridBlocks ? grid_for(acts, kBlock / 64) : kWhGridBlocks; }
 
+// The plain frozen LogReg's acts of the slots lr_list[0 .. lr_cnt[t]) (at most `upper` of them): the step loop after k_logreg_select,
+// and rg_sim_debug_logreg_acts after listing every slot itself.
+void launch_logreg_acts(rg_sim* sim, uint32_t t, uint32_t upper, hipStream_t st) {
+    const DevSim& d = sim->d;
+    if (d.lr_coef16_t) {       // screen (a wave per act and class range), then decide (a wave per act)
+        // (the number of acts is only known on the device — at most a quarter of the live users, usually a fiftieth: the kernels
+        // walk their lists grid-stride, and the grids are capped at a few blocks per CU.  Sized for the worst case they were
+        // mostly blocks that start and leave — and k_logreg_decide's three counter atomics per WAVE, one act each, were all of
+        // its time: 41 of the 169 ms of C5's acts, profiles/r6/c5_fp16_kernel_stats_call31.csv)
+        const int cus = device_cus(sim);
+        auto capped = [&](uint64_t waves, int blocks_per_cu) { return capped_wave_grid(waves, blocks_per_cu, cus); };
+        hipLaunchKernelGGL(logreg_screen_kernel(), dim3(capped((static_cast<uint64_t>(upper) / 4 + 64) * kLrSplit, 16)),
+                           dim3(kBlock), 0, st, d, t);
+        sim->led.logreg_screen += 1;
+        hipLaunchKernelGGL(logreg_decide_kernel(), dim3(capped(static_cast<uint64_t>(upper) / 4 + 64, 8)), dim3(kBlock), 0, st, d, t);
+        if (upper > d.lr_part_cap) {   // the step may list more acts than the screen's scratch has rows: the rest in fp32 / float64
+            hipLaunchKernelGGL(logreg_acts_kernel(), dim3(capped(static_cast<uint64_t>(upper - d.lr_part_cap) / 4 + 64, 8)), dim3(kBlock), 0, st, d, t);
+            sim->led.logreg_acts += 1;
+        }
+    } else {
+        hipLaunchKernelGGL(logreg_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), 0, st, d, t);
+        sim->led.logreg_acts += 1;
+    }
+}
+
 int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
     if (sim->t >= kMaxSteps) return fail(RG_ELIMIT, "more than %u steps", kMaxSteps);
     const DevSim& d = sim->d;
@@ -935,25 +965,7 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         } else if (d.lr_sample) {  // select_randomly: a softmax and a draw per act (a wave each)
             hipLaunchKernelGGL(logreg_sample_kernel(), dim3(grid_for(static_cast<uint64_t>(upper) + 64, kBlock / 64)), dim3(kBlock), 0, st, d, t);
             sim->led.logreg_sample += 1;
-        } else if (d.lr_coef16_t) {       // screen (a wave per act and class range), then decide (a wave per act)
-            // (the number of acts is only known on the device — at most a quarter of the live users, usually a fiftieth: the kernels
-            // walk their lists grid-stride, and the grids are capped at a few blocks per CU.  Sized for the worst case they were
-            // mostly blocks that start and leave — and k_logreg_decide's three counter atomics per WAVE, one act each, were all of
-            // its time: 41 of the 169 ms of C5's acts, profiles/r6/c5_fp16_kernel_stats_call31.csv)
-            const int cus = device_cus(sim);
-            auto capped = [&](uint64_t waves, int blocks_per_cu) { return capped_wave_grid(waves, blocks_per_cu, cus); };
-            hipLaunchKernelGGL(logreg_screen_kernel(), dim3(capped((static_cast<uint64_t>(upper) / 4 + 64) * kLrSplit, 16)),
-                               dim3(kBlock), 0, st, d, t);
-            sim->led.logreg_screen += 1;
-            hipLaunchKernelGGL(logreg_decide_kernel(), dim3(capped(static_cast<uint64_t>(upper) / 4 + 64, 8)), dim3(kBlock), 0, st, d, t);
-            if (upper > d.lr_part_cap) {   // the step may list more acts than the screen's scratch has rows: the rest in fp32 / float64
-                hipLaunchKernelGGL(logreg_acts_kernel(), dim3(capped(static_cast<uint64_t>(upper - d.lr_part_cap) / 4 + 64, 8)), dim3(kBlock), 0, st, d, t);
-                sim->led.logreg_acts += 1;
-            }
-        } else {
-            hipLaunchKernelGGL(logreg_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), 0, st, d, t);
-            sim->led.logreg_acts += 1;
-        }
+        } else launch_logreg_acts(sim, t, upper, st);     // fp16 attached: screen + decide; otherwise the fp32 form
     }
     // 2. click draws, transitions, drift, next lists, bandit + phantom rows
     if (int rc = prof_mark(sim, st, kProfAdvance)) return rc;
@@ -2213,6 +2225,23 @@ int rg_sim_debug_mlr_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, doub
                        sim->d, sim->mlr, d_action, d_flags, d_z);
     sim->led.mlr += 1;
     HIP_TRY(hipGetLastError());
+    return RG_OK;
+}
+
+int rg_sim_debug_logreg_acts(rg_sim* sim, int32_t* d_action, void* stream) {
+    if (!sim || !d_action) return fail(RG_EINVAL, "NULL argument");
+    if (sim->cfg.policy != RG_POLICY_LOGREG_FROZEN || sim->d.lr_poly) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_FROZEN");
+    if (sim->d.lr_sample) return fail(RG_EINVAL, "a LogReg with lr_select_randomly samples its act: no argmax act to return");
+    if (!sim->d.lr_coef_t) return fail(RG_ESTATE, "rg_sim_set_logreg must be called first");
+    if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t n = sim->d.n_users;
+    hipLaunchKernelGGL(k_debug_logreg_list, dim3(grid_for(n)), dim3(kBlock), 0, st, sim->d);
+    launch_logreg_acts(sim, 0, n, st);
+    HIP_TRY(hipGetLastError());
+    static_assert(sizeof(*sim->d.lr_action) == sizeof(*d_action), "the acts are copied as they lie");
+    HIP_TRY(hipMemcpyAsync(d_action, sim->d.lr_action, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, st));
+    sim->users_reset = false;      // step 0's act list is filled and no act is dirty: step and run refuse until the users are reset again
     return RG_OK;
 }
 

@@ -561,6 +561,16 @@ class Simulator:
             torch.cuda.synchronize(self.device)
         return act.cpu().numpy().astype(np.int64), fl.cpu().numpy().astype(np.int64), z.cpu().numpy()
 
+    def debug_logreg_acts(self):
+        """rg_sim_debug_logreg_acts -> actions: the frozen LogReg's act of every user index on its current history, by the step loop's
+        kernels (the counters and the launch ledger count as in a step).  Reset the users again before a run."""
+        n = self.n_active
+        with torch.cuda.device(self.device):
+            act = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+            _abi.check(self.lib.rg_sim_debug_logreg_acts(self._h, act.data_ptr(), self._stream()), 'rg_sim_debug_logreg_acts')
+            torch.cuda.synchronize(self.device)
+        return act.cpu().numpy().astype(np.int64)
+
     def debug_set_timed_history(self, n_views, products, times16):
         """rg_sim_debug_set_timed_history: per user index of the reset range, n_views[i] views (products[i, j] at clock value
         times16[i, j], in view order) as its time-weighted history."""

@@ -24,7 +24,7 @@ def test_agent_is_exported_with_the_reference_arguments():
     assert agents.BayesianAgentVB is BayesianAgentVB and agents.bayesian_poly_args is bayesian_poly_args
     want = dict(num_products=10, poly_degree=2, max_iter=5000, aa=1., bb=1., with_ps_all=False, num_samples=1000)
     assert {k: v for k, v in bayesian_poly_args.items() if k != 'random_seed'} == want and 'random_seed' in bayesian_poly_args
-    assert _abi.RG_POLICY_BAYES_VB == 8 and _abi.RG_CNT_BAYES_SATURATED == 29 and _abi.RG_ABI_VERSION == 14
+    assert _abi.RG_POLICY_BAYES_VB == 8 and _abi.RG_CNT_BAYES_SATURATED == 29 and _abi.RG_ABI_VERSION == 15
     assert (ZSAT, SATURATED, UNRESOLVED) == (40.0, 1, 2)
 
 

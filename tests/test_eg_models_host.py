@@ -152,10 +152,10 @@ def declared_args(header, name):
     return [a.strip() for a in m.group(1).split(',')]
 
 
-def test_abi_declares_the_three_entry_points_and_stays_at_14():
+def test_abi_declares_the_three_entry_points_and_the_version():
     header = open(os.path.join(ROOT, 'include', 'recogym_hip.h')).read()
     S = _abi.SYMBOLS
-    assert int(re.search(r'#define RG_ABI_VERSION (\d+)', header).group(1)) == 14 == _abi.RG_ABI_VERSION
+    assert int(re.search(r'#define RG_ABI_VERSION (\d+)', header).group(1)) == 15 == _abi.RG_ABI_VERSION
     assert 'v14, additive since:' in header
     for name in ('rg_sim_set_epsilon_greedy_model', 'rg_ope_replay_logreg_eg', 'rg_ope_replay_poly_eg'):
         assert name in S and len(declared_args(header, name)) == len(S[name][1])

@@ -219,10 +219,10 @@ def declared_args(header, name):
     return [a.strip() for a in m.group(1).split(',')]
 
 
-def test_abi_declares_the_entry_point_and_stays_at_14():
+def test_abi_declares_the_entry_point_and_the_version():
     header = open(os.path.join(ROOT, 'include', 'recogym_hip.h')).read()
     S = _abi.SYMBOLS
-    assert int(re.search(r'#define RG_ABI_VERSION (\d+)', header).group(1)) == 14 == _abi.RG_ABI_VERSION
+    assert int(re.search(r'#define RG_ABI_VERSION (\d+)', header).group(1)) == 15 == _abi.RG_ABI_VERSION
     new = 'rg_sim_set_epsilon_greedy_model_ps'
     assert new in S and S[new] == S['rg_sim_set_epsilon_greedy'] == S['rg_sim_set_epsilon_greedy_model']
     assert declared_args(header, new) == declared_args(header, 'rg_sim_set_epsilon_greedy')

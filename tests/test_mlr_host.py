@@ -27,7 +27,7 @@ def test_agent_is_exported_with_the_reference_arguments():
     assert agents.PyTorchMLRFrozenAgent is PyTorchMLRFrozenAgent
     want = dict(n_epochs=30, learning_rate=0.01, logIPS=False, variance_penalisation_strength=.0, clip_weights=False, alpha=.0, ll_IPS=True)
     assert {k: v for k, v in pytorch_mlr_args.items() if k != 'random_seed'} == want and 'random_seed' in pytorch_mlr_args
-    assert _abi.RG_POLICY_MLR == 12 and _abi.RG_ABI_VERSION == 14 and UNRESOLVED == 2
+    assert _abi.RG_POLICY_MLR == 12 and _abi.RG_ABI_VERSION == 15 and UNRESOLVED == 2
 
 
 def test_the_policy_is_accepted_and_its_neighbours_stay_refused():

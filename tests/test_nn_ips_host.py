@@ -37,7 +37,7 @@ def test_agent_is_exported_with_the_reference_arguments():
     want = dict(num_products=10, number_of_flips=1, select_randomly=False, M=111, learning_rate=0.01, num_epochs=100, num_hidden=20,
                 lambda_val=0.01, with_ps_all=False)
     assert {k: v for k, v in nn_ips_args.items() if k != 'random_seed'} == want and 'random_seed' in nn_ips_args
-    assert _abi.RG_POLICY_NN_IPS == 10 and _abi.RG_ABI_VERSION == 14 and UNRESOLVED == 2
+    assert _abi.RG_POLICY_NN_IPS == 10 and _abi.RG_ABI_VERSION == 15 and UNRESOLVED == 2
 
 
 def test_the_policy_is_accepted_with_a_propensity_row():

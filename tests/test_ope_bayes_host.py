@@ -33,7 +33,7 @@ def model(**over):
 def test_the_mirror_matches_the_header_and_the_symbols_the_poly_unit(lib):
     th.check_mirror('rg_ope_bayes', _abi.RgOpeBayes)
     th.check_symbols_follow_the_poly_unit('bayes', _abi.RgOpeBayes)
-    th.check_abi_version_is_14(lib)
+    th.check_abi_version(lib)
     assert _abi.OPE_HEADS['bayes'] == ('error', 'acts', 'saturated', 'unresolved', 'overflow', 'rows_read')
     assert ev._REPLAY_ENTRY['bayes', False] == ('rg_ope_bayes_workspace_bytes', 'rg_ope_replay_bayes')
     assert ev._REPLAY_ENTRY['bayes', True] == ('rg_ope_bayes_workspace_bytes', 'rg_ope_replay_bayes_eg')

@@ -58,8 +58,8 @@ def check_symbols_follow_the_poly_unit(unit, mirror):
     assert f'#include "rg_ope_{unit}.hip"' in one_unit
 
 
-def check_abi_version_is_14(lib):
-    assert '#define RG_ABI_VERSION 14\n' in open(HEADER).read() and _abi.RG_ABI_VERSION == 14 and lib.rg_abi_version() == 14
+def check_abi_version(lib):
+    assert '#define RG_ABI_VERSION 15\n' in open(HEADER).read() and _abi.RG_ABI_VERSION == 15 and lib.rg_abi_version() == 15
 
 
 def refused(lib, unit, model, wrapped, over):
@@ -168,7 +168,7 @@ def model(**over):
 def test_the_mirror_matches_the_header_and_the_symbols_the_poly_unit(lib):
     check_mirror('rg_ope_nn', _abi.RgOpeNn)
     check_symbols_follow_the_poly_unit('nn', _abi.RgOpeNn)
-    check_abi_version_is_14(lib)
+    check_abi_version(lib)
     assert _abi.OPE_HEADS['nn'] == ('error', 'acts', 'unresolved', 'overflow', 'rows_read')
     assert ev._REPLAY_ENTRY['nn', False] == ('rg_ope_nn_workspace_bytes', 'rg_ope_replay_nn')
     assert ev._REPLAY_ENTRY['nn', True] == ('rg_ope_nn_workspace_bytes', 'rg_ope_replay_nn_eg')

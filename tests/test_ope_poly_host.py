@@ -88,12 +88,12 @@ def test_struct_layout_matches_header():
     assert _abi.SYMBOLS['rg_ope_poly_workspace_bytes'][1][1:] == _abi.SYMBOLS['rg_ope_logreg_workspace_bytes'][1][1:]
 
 
-def test_abi_version_is_14_in_its_three_places():
+def test_abi_version_is_the_same_in_its_three_places():
     header = open(os.path.join(ROOT, 'include', 'recogym_hip.h')).read()
     md = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
-    assert int(re.search(r'#define RG_ABI_VERSION (\d+)', header).group(1)) == 14
-    assert _abi.RG_ABI_VERSION == 14
-    assert int(re.search(r'rg_abi_version\(\) == (\d+)', md).group(1)) == 14
+    assert int(re.search(r'#define RG_ABI_VERSION (\d+)', header).group(1)) == 15
+    assert _abi.RG_ABI_VERSION == 15
+    assert int(re.search(r'rg_abi_version\(\) == (\d+)', md).group(1)) == 15
 
 
 # ---- the confirmation step ---------------------------------------------------------------------------------------------------
