@@ -135,6 +135,19 @@ __host__ __device__ constexpr uint32_t tp_rec_stride(uint32_t KH) { return (32u 
 // draws of one (tile, shard) list at most: every work item (128 users of k_draw_tp, 256 of k_draw_tpw) may put all its draws into one
 inline uint32_t tp_shard_cap(uint64_t n, uint32_t shards) { return static_cast<uint32_t>((((n + 255) / 256 + shards - 1) / shards) * 256); }
 
+// The model agent whose act kernel the step loop runs on the frozen LogReg's act list (DevSim::lr_poly; rg_act_common.hpp has the
+// skeleton its four kernels share).  act_kind_of: the kind of a configured policy.
+enum ActKind : uint32_t { kActNone = 0, kActPoly = 1, kActBayes = 2, kActNn = 3, kActMlr = 4 };
+inline ActKind act_kind_of(uint32_t policy) {
+    switch (policy) {
+        case RG_POLICY_LOGREG_POLY: return kActPoly;
+        case RG_POLICY_BAYES_VB: return kActBayes;
+        case RG_POLICY_NN_IPS: return kActNn;
+        case RG_POLICY_MLR: return kActMlr;
+        default: return kActNone;
+    }
+}
+
 // Everything a kernel needs, passed by value.
 struct DevSim {
     // configuration
@@ -329,18 +342,20 @@ struct DevSim {
     const double* eg_cdf;     // [P - 1] (pure_new) or [P]: cumsum(full(n, 1 / n)) / last, caller-owned
     // RG_POLICY_LOGREG_POLY (rg_sim_set_logreg_poly; rg_logreg_poly.hip): `policy` is RG_POLICY_LOGREG_FROZEN for such a handle too —
     // the act list, the view history and the hand-over of lr_action to the advance kernels are that policy's — and lr_poly selects
-    // k_poly_acts as the act kernel.  Caller-owned float64 arrays; pl_list [kPolyListCap][3] = (user id, t, action) of unresolved acts.
-    uint32_t lr_poly, pl_nth;
+    // the act kernel (ActKind above; kActPoly: k_poly_acts).  Caller-owned float64 arrays; pl_list [kPolyListCap][3] = (user id, t,
+    // action) of unresolved acts.
+    ActKind lr_poly;
+    uint32_t pl_nth;
     const double* pl_wf; const double* pl_wa; const double* pl_wk_t; const double* pl_th;
     double pl_b;
     uint32_t* pl_list;
-    // RG_POLICY_BAYES_VB (rg_sim_set_bayes_vb; rg_bayes_vb.hip): routed the same way, lr_poly = 2 selects k_bayes_acts, unresolved acts
+    // RG_POLICY_BAYES_VB (rg_sim_set_bayes_vb; rg_bayes_vb.hip): routed the same way, lr_poly = kActBayes selects k_bayes_acts, unresolved acts
     // go to pl_list too.  Its model travels in two of the slots above, which that policy leaves unused — pl_wk_t = lam_t [viewed
     // product][action][sample], caller-owned, pl_nth = the number of samples — so this record, a by-value argument of every kernel,
     // keeps its size and every other kernel its code.
-    // RG_POLICY_NN_IPS (rg_sim_set_nn_ips; rg_nn_ips.hip): lr_poly = 3 selects k_nn_acts, whose model is a kernel argument of its own
+    // RG_POLICY_NN_IPS (rg_sim_set_nn_ips; rg_nn_ips.hip): lr_poly = kActNn selects k_nn_acts, whose model is a kernel argument of its own
     // (NnModel below), and makes the advance kernels log lr_ps instead of 1 (lr_logs_ps).
-    // RG_POLICY_MLR (rg_sim_set_mlr; rg_mlr.hip): lr_poly = 4 selects k_mlr_acts, whose model is a kernel argument of its own too
+    // RG_POLICY_MLR (rg_sim_set_mlr; rg_mlr.hip): lr_poly = kActMlr selects k_mlr_acts, whose model is a kernel argument of its own too
     // (MlrModel below); ps = 1, as the frozen LogReg's argmax.
 };
 
@@ -1073,7 +1088,7 @@ __device__ __forceinline__ void bf16_split3(float x, unsigned short* sp) {
 
 
 // the cached act of the lr_* list carries its own propensity in lr_ps (RG_POLICY_NN_IPS: ps = prob[a], a model output)
-__device__ __forceinline__ bool lr_logs_ps(const DevSim& d) { return d.lr_poly == 3u; }
+__device__ __forceinline__ bool lr_logs_ps(const DevSim& d) { return d.lr_poly == kActNn; }
 typedef unsigned long long hent_t;
 __device__ __forceinline__ hent_t* hist_row(const DevSim& d, uint32_t slot) { return d.hist + static_cast<size_t>(slot) * d.hist_cap; }
 __device__ __forceinline__ uint32_t h_prod(hent_t e) { return static_cast<uint32_t>(e >> 32); }

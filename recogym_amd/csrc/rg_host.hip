@@ -866,6 +866,24 @@ void launch_logreg_acts(rg_sim* sim, uint32_t t, uint32_t upper, hipStream_t st)
     }
 }
 
+// A model agent's acts of the same list (DevSim::lr_poly; rg_act_common.hpp): a wave per act, grid-stride under the same cap.  Per
+// kind the kernel, its dynamic LDS, the model where it is a kernel argument of its own, and the ledger's counter.
+void launch_model_acts(rg_sim* sim, uint32_t t, uint32_t upper, hipStream_t st) {
+    const DevSim& d = sim->d;
+    const dim3 grid(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim)));
+    auto launch = [&](auto kernel, size_t smem, uint64_t& launched, auto... model) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kBlock), smem, st, d, model..., t);
+        launched += 1;
+    };
+    switch (d.lr_poly) {
+        case kActPoly: launch(poly_acts_kernel(), 0, sim->led.logreg_poly); break;         // float64 throughout (rg_logreg_poly.hip)
+        case kActBayes: launch(bayes_acts_kernel(), 0, sim->led.bayes_vb); break;          // lanes over the posterior samples (rg_bayes_vb.hip)
+        case kActNn: launch(nn_acts_kernel(), sim->nn_smem, sim->led.nn_ips, sim->nn); break;      // lanes over the hidden units, then the products (rg_nn_ips.hip)
+        case kActMlr: launch(mlr_acts_kernel(), sim->mlr_smem, sim->led.mlr, sim->mlr); break;     // lanes over the actions (rg_mlr.hip)
+        case kActNone: break;
+    }
+}
+
 int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
     if (sim->t >= kMaxSteps) return fail(RG_ELIMIT, "more than %u steps", kMaxSteps);
     const DevSim& d = sim->d;
@@ -950,19 +968,8 @@ int launch_step(rg_sim* sim, const int32_t* d_actions, hipStream_t st) {
         if (int rc = prof_mark(sim, st, kProfLogreg)) return rc;
         // acts of the users whose view history changed since their last one (frozen LogReg at scale)
         hipLaunchKernelGGL(logreg_select_kernel(), dim3(grid_for(upper)), dim3(kBlock), 0, st, d, t);
-        if (d.lr_poly == 4u) {     // PyTorchMLRAgent: a wave per act, lanes over the actions (rg_mlr.hip)
-            hipLaunchKernelGGL(mlr_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), sim->mlr_smem, st, d, sim->mlr, t);
-            sim->led.mlr += 1;
-        } else if (d.lr_poly == 3u) {     // NnIpsAgent: a wave per act, lanes over the hidden units, then the products (rg_nn_ips.hip)
-            hipLaunchKernelGGL(nn_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), sim->nn_smem, st, d, sim->nn, t);
-            sim->led.nn_ips += 1;
-        } else if (d.lr_poly == 2u) {     // BayesianAgentVB: a wave per act, lanes over the posterior samples (rg_bayes_vb.hip)
-            hipLaunchKernelGGL(bayes_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), 0, st, d, t);
-            sim->led.bayes_vb += 1;
-        } else if (d.lr_poly) {    // the likelihood agent: a wave per act, float64 throughout (rg_logreg_poly.hip)
-            hipLaunchKernelGGL(poly_acts_kernel(), dim3(capped_wave_grid(static_cast<uint64_t>(upper) / 4 + 64, 8, device_cus(sim))), dim3(kBlock), 0, st, d, t);
-            sim->led.logreg_poly += 1;
-        } else if (d.lr_sample) {  // select_randomly: a softmax and a draw per act (a wave each)
+        if (d.lr_poly) launch_model_acts(sim, t, upper, st);
+        else if (d.lr_sample) {    // select_randomly: a softmax and a draw per act (a wave each)
             hipLaunchKernelGGL(logreg_sample_kernel(), dim3(grid_for(static_cast<uint64_t>(upper) + 64, kBlock / 64)), dim3(kBlock), 0, st, d, t);
             sim->led.logreg_sample += 1;
         } else launch_logreg_acts(sim, t, upper, st);     // fp16 attached: screen + decide; otherwise the fp32 form
@@ -1242,7 +1249,7 @@ void plan_config(rg_sim* s, const rg_config* cfg, uint64_t n_users, const Switch
     d.sigma0 = cfg->sigma_omega_initial; d.sigma_omega = cfg->sigma_omega; d.change_omega_for_bandits = cfg->change_omega_for_bandits;
     // the likelihood agent runs wherever the frozen LogReg policy does, through the same act list: one policy for the kernels
     d.policy = lists_unresolved(cfg->policy) ? RG_POLICY_LOGREG_FROZEN : cfg->policy;
-    d.lr_poly = cfg->policy == RG_POLICY_LOGREG_POLY ? 1u : cfg->policy == RG_POLICY_BAYES_VB ? 2u : cfg->policy == RG_POLICY_NN_IPS ? 3u : cfg->policy == RG_POLICY_MLR ? 4u : 0u;   // (2: k_bayes_acts, 3: k_nn_acts, 4: k_mlr_acts)
+    d.lr_poly = act_kind_of(cfg->policy);
     d.ouc_select_randomly = cfg->ouc_select_randomly; d.ouc_exploit_explore = cfg->ouc_exploit_explore;
     d.ouc_reverse_pop = cfg->ouc_reverse_pop; d.ouc_epsilon = cfg->ouc_epsilon;
     d.time_mode = cfg->time_mode; d.time_mu = cfg->time_mu; d.time_sigma = cfg->time_sigma; d.env_kind = cfg->env_kind;
@@ -1430,6 +1437,41 @@ void plan_mfma_lds(rg_sim* s, const Switches& w) {
     }
     if (s->mfma_smem > 64 * 1024)
         for (uint32_t kh : {4u, 10u, 16u, 32u, 64u}) set_max_lds(mfma_kernel_for(kh), s->mfma_smem);
+}
+
+}  // namespace
+
+// helpers of the entry points below that share their body
+namespace {
+
+// What the three EpsilonGreedy setters share: the checks behind each one's own policy gate, and the overlay's fields.
+int set_eg_overlay(rg_sim* sim, double epsilon, uint64_t eg_seed, uint32_t pure_new, const double* d_cdf, double ps_explore,
+                   double one_minus_eps) {
+    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(RG_EINVAL, "epsilon %g outside [0, 1]", epsilon);
+    if (pure_new && sim->d.P < 2u) return fail(RG_EINVAL, "epsilon_pure_new needs at least 2 products");
+    if (!d_cdf) return fail(RG_EINVAL, "the explore table is NULL");
+    DevSim& d = sim->d;
+    d.eg_on = 1u; d.eg_pure_new = pure_new ? 1u : 0u; d.eg_seed = eg_seed;
+    d.eg_eps = epsilon; d.eg_ps_explore = ps_explore; d.eg_one_minus = one_minus_eps; d.eg_cdf = d_cdf;
+    sim->walk = sim->walk2 = false;            // the overlay lives in the lock-step kernels only (as time_mode / RECOGYM_WALK=0)
+    return RG_OK;
+}
+
+// What the four model agents' debug entry points check before they launch: the arguments (`outputs`: none of them null), the
+// policy (`name` as the header spells it), that the model is attached (`setter` names its entry point), and the reset state.
+int debug_acts_ok(const rg_sim* sim, bool outputs, uint32_t policy, const char* name, bool model_set, const char* setter) {
+    if (!sim || !outputs) return fail(RG_EINVAL, "NULL argument");
+    if (sim->cfg.policy != policy) return fail(RG_ESTATE, "policy is not %s", name);
+    if (!model_set) return fail(RG_ESTATE, "%s must be called first", setter);
+    if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
+    return RG_OK;
+}
+// ... and their launch: a wave per user index of the reset range
+template <class Kernel, class... Args>
+int launch_debug_acts(rg_sim* sim, Kernel kernel, size_t smem, void* stream, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), smem, static_cast<hipStream_t>(stream), sim->d, args...);
+    HIP_TRY(hipGetLastError());
+    return RG_OK;
 }
 
 }  // namespace
@@ -1672,14 +1714,7 @@ int rg_sim_set_epsilon_greedy(rg_sim* sim, double epsilon, uint64_t eg_seed, uin
     const uint32_t pol = sim->d.policy;
     if (pol != RG_POLICY_RANDOM_AGENT && pol != RG_POLICY_ORGANIC_USER_COUNT && pol != RG_POLICY_LAST_VIEW_TABLE)
         return fail(RG_EINVAL, "EpsilonGreedy wraps RandomAgent, OrganicUserEventCounter or a last-view table on the device (policy %u)", pol);
-    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(RG_EINVAL, "epsilon %g outside [0, 1]", epsilon);
-    if (pure_new && sim->d.P < 2u) return fail(RG_EINVAL, "epsilon_pure_new needs at least 2 products");
-    if (!d_cdf) return fail(RG_EINVAL, "the explore table is NULL");
-    DevSim& d = sim->d;
-    d.eg_on = 1u; d.eg_pure_new = pure_new ? 1u : 0u; d.eg_seed = eg_seed;
-    d.eg_eps = epsilon; d.eg_ps_explore = ps_explore; d.eg_one_minus = one_minus_eps; d.eg_cdf = d_cdf;
-    sim->walk = sim->walk2 = false;            // the overlay lives in the lock-step kernels only (as time_mode / RECOGYM_WALK=0)
-    return RG_OK;
+    return set_eg_overlay(sim, epsilon, eg_seed, pure_new, d_cdf, ps_explore, one_minus_eps);
 }
 
 int rg_sim_set_epsilon_greedy_model(rg_sim* sim, double epsilon, uint64_t eg_seed, uint32_t pure_new, const double* d_cdf,
@@ -1694,14 +1729,7 @@ int rg_sim_set_epsilon_greedy_model(rg_sim* sim, double epsilon, uint64_t eg_see
     if (sim->d.lr_sample)
         return fail(RG_EINVAL, "rg_sim_set_epsilon_greedy_model: a LogReg with lr_select_randomly samples its act (propensity != 1): host path");
     if (sim->wh.wt.tab) return fail(RG_EINVAL, "EpsilonGreedy round a time-weighted likelihood agent: host path");
-    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(RG_EINVAL, "epsilon %g outside [0, 1]", epsilon);
-    if (pure_new && sim->d.P < 2u) return fail(RG_EINVAL, "epsilon_pure_new needs at least 2 products");
-    if (!d_cdf) return fail(RG_EINVAL, "the explore table is NULL");
-    DevSim& d = sim->d;
-    d.eg_on = 1u; d.eg_pure_new = pure_new ? 1u : 0u; d.eg_seed = eg_seed;
-    d.eg_eps = epsilon; d.eg_ps_explore = ps_explore; d.eg_one_minus = one_minus_eps; d.eg_cdf = d_cdf;
-    sim->walk = sim->walk2 = false;            // (as rg_sim_set_epsilon_greedy)
-    return RG_OK;
+    return set_eg_overlay(sim, epsilon, eg_seed, pure_new, d_cdf, ps_explore, one_minus_eps);
 }
 
 int rg_sim_set_epsilon_greedy_model_ps(rg_sim* sim, double epsilon, uint64_t eg_seed, uint32_t pure_new, const double* d_cdf,
@@ -1710,14 +1738,7 @@ int rg_sim_set_epsilon_greedy_model_ps(rg_sim* sim, double epsilon, uint64_t eg_
     if (sim->users_reset) return fail(RG_ESTATE, "rg_sim_set_epsilon_greedy_model_ps must be called before rg_sim_reset_users");
     if (sim->cfg.policy != RG_POLICY_NN_IPS && sim->cfg.policy != RG_POLICY_BAYES_VB)
         return fail(RG_EINVAL, "rg_sim_set_epsilon_greedy_model_ps wraps NnIpsAgent or BayesianAgentVB (policy %u)", sim->cfg.policy);
-    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(RG_EINVAL, "epsilon %g outside [0, 1]", epsilon);
-    if (pure_new && sim->d.P < 2u) return fail(RG_EINVAL, "epsilon_pure_new needs at least 2 products");
-    if (!d_cdf) return fail(RG_EINVAL, "the explore table is NULL");
-    DevSim& d = sim->d;
-    d.eg_on = 1u; d.eg_pure_new = pure_new ? 1u : 0u; d.eg_seed = eg_seed;
-    d.eg_eps = epsilon; d.eg_ps_explore = ps_explore; d.eg_one_minus = one_minus_eps; d.eg_cdf = d_cdf;
-    sim->walk = sim->walk2 = false;            // (as rg_sim_set_epsilon_greedy)
-    return RG_OK;
+    return set_eg_overlay(sim, epsilon, eg_seed, pure_new, d_cdf, ps_explore, one_minus_eps);
 }
 
 int rg_eg_explore_actions(uint32_t num_products, uint32_t pure_new, const double* d_cdf, const double* d_u1, const int32_t* d_greedy,
@@ -2181,51 +2202,32 @@ int rg_sim_debug_ouc_acts(rg_sim* sim, const double* d_u1, int32_t* d_action, do
     return RG_OK;
 }
 
+// (the launch ledger counts the debug launch of the three younger agents with their step-loop kernel's, and not the likelihood
+// agent's: a test may count launches, so each stays as it was)
 int rg_sim_debug_poly_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, void* stream) {
-    if (!sim || !d_action || !d_flags) return fail(RG_EINVAL, "NULL argument");
-    if (sim->cfg.policy != RG_POLICY_LOGREG_POLY) return fail(RG_ESTATE, "policy is not RG_POLICY_LOGREG_POLY");
-    if (!sim->d.pl_wk_t) return fail(RG_ESTATE, "rg_sim_set_logreg_poly must be called first");
-    if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
-    hipLaunchKernelGGL(poly_debug_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
-                       sim->d, d_action, d_flags);
-    HIP_TRY(hipGetLastError());
-    return RG_OK;
+    if (int rc = debug_acts_ok(sim, d_action && d_flags, RG_POLICY_LOGREG_POLY, "RG_POLICY_LOGREG_POLY", sim && sim->d.pl_wk_t, "rg_sim_set_logreg_poly"))
+        return rc;
+    return launch_debug_acts(sim, poly_debug_kernel(), 0, stream, d_action, d_flags);
 }
 
 int rg_sim_debug_bayes_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, double* d_q, void* stream) {
-    if (!sim || !d_action || !d_flags || !d_q) return fail(RG_EINVAL, "NULL argument");
-    if (sim->cfg.policy != RG_POLICY_BAYES_VB) return fail(RG_ESTATE, "policy is not RG_POLICY_BAYES_VB");
-    if (!sim->d.pl_wk_t) return fail(RG_ESTATE, "rg_sim_set_bayes_vb must be called first");
-    if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
-    hipLaunchKernelGGL(bayes_debug_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
-                       sim->d, d_action, d_flags, d_q);
+    if (int rc = debug_acts_ok(sim, d_action && d_flags && d_q, RG_POLICY_BAYES_VB, "RG_POLICY_BAYES_VB", sim && sim->d.pl_wk_t, "rg_sim_set_bayes_vb"))
+        return rc;
     sim->led.bayes_vb += 1;
-    HIP_TRY(hipGetLastError());
-    return RG_OK;
+    return launch_debug_acts(sim, bayes_debug_kernel(), 0, stream, d_action, d_flags, d_q);
 }
 
 int rg_sim_debug_nn_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, double* d_z, double* d_ps, void* stream) {
-    if (!sim || !d_action || !d_flags || !d_z || !d_ps) return fail(RG_EINVAL, "NULL argument");
-    if (sim->cfg.policy != RG_POLICY_NN_IPS) return fail(RG_ESTATE, "policy is not RG_POLICY_NN_IPS");
-    if (!sim->nn.w1t) return fail(RG_ESTATE, "rg_sim_set_nn_ips must be called first");
-    if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
-    hipLaunchKernelGGL(nn_debug_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), sim->nn_smem, static_cast<hipStream_t>(stream),
-                       sim->d, sim->nn, d_action, d_flags, d_z, d_ps);
+    if (int rc = debug_acts_ok(sim, d_action && d_flags && d_z && d_ps, RG_POLICY_NN_IPS, "RG_POLICY_NN_IPS", sim && sim->nn.w1t, "rg_sim_set_nn_ips"))
+        return rc;
     sim->led.nn_ips += 1;
-    HIP_TRY(hipGetLastError());
-    return RG_OK;
+    return launch_debug_acts(sim, nn_debug_kernel(), sim->nn_smem, stream, sim->nn, d_action, d_flags, d_z, d_ps);
 }
 
 int rg_sim_debug_mlr_acts(rg_sim* sim, int32_t* d_action, uint8_t* d_flags, double* d_z, void* stream) {
-    if (!sim || !d_action || !d_flags || !d_z) return fail(RG_EINVAL, "NULL argument");
-    if (sim->cfg.policy != RG_POLICY_MLR) return fail(RG_ESTATE, "policy is not RG_POLICY_MLR");
-    if (!sim->mlr.wt) return fail(RG_ESTATE, "rg_sim_set_mlr must be called first");
-    if (!sim->users_reset || sim->t != 0) return fail(RG_ESTATE, "only right after rg_sim_reset_users (slot == user index)");
-    hipLaunchKernelGGL(mlr_debug_kernel(), dim3(grid_for(sim->d.n_users, kBlock / 64)), dim3(kBlock), sim->mlr_smem, static_cast<hipStream_t>(stream),
-                       sim->d, sim->mlr, d_action, d_flags, d_z);
+    if (int rc = debug_acts_ok(sim, d_action && d_flags && d_z, RG_POLICY_MLR, "RG_POLICY_MLR", sim && sim->mlr.wt, "rg_sim_set_mlr")) return rc;
     sim->led.mlr += 1;
-    HIP_TRY(hipGetLastError());
-    return RG_OK;
+    return launch_debug_acts(sim, mlr_debug_kernel(), sim->mlr_smem, stream, sim->mlr, d_action, d_flags, d_z);
 }
 
 int rg_sim_debug_logreg_acts(rg_sim* sim, int32_t* d_action, void* stream) {

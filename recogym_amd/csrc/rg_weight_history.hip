@@ -12,6 +12,7 @@
 // The cached act of the count form (lr_dirty, k_logreg_select, k_poly_acts) is not used: an act is stale as soon as the clock moves.
 
 #include "rg_wh_common.hpp"
+#include "rg_act_common.hpp"
 #include "rg_ope_common.hpp"
 
 namespace rgk {
@@ -54,7 +55,7 @@ __global__ void __launch_bounds__(kBlock) k_poly_acts_w(DevSim d, WhRun r, uint3
     const uint32_t waves_total = gridDim.x * (kBlock / 64), gw = blockIdx.x * (kBlock / 64) + wave;
     uint32_t* g_prod = r.spill ? r.spill + static_cast<size_t>(gw) * 2 * r.spill_cap : nullptr;      // this wave's, beyond kPolyHist products
     uint32_t* g_bits = r.spill ? g_prod + r.spill_cap : nullptr;
-    unsigned long long c_acts = 0, c_rows = 0, c_table = 0, c_range = 0;
+    unsigned long long c[4] = {};             // acts, list entries, acts decided on the table, acts with a clock value out of range
     for (uint32_t w = gw; w < n; w += waves_total) {
         const uint32_t slot = phase ? (w < n_o ? cur_o[w] : cur_b[w - n_o]) : cur_b[w];
         const uint32_t uidx = d.uid[slot];
@@ -67,33 +68,14 @@ __global__ void __launch_bounds__(kBlock) k_poly_acts_w(DevSim d, WhRun r, uint3
         bool range = false;
         const uint32_t action = wh_act(d, r.wt, hr + 1, ne, now, lane, s_th, s_w[wave], s_ep[wave], s_val[wave], s_prod[wave], g_prod, g_bits,
                                        r.spill_cap, &fl, &ln, &range);
-        c_acts += 1; c_rows += ln; c_table += fl & 1u; c_range += range ? 1u : 0u;
+        c[0] += 1; c[1] += ln; c[2] += fl & 1u; c[3] += range ? 1u : 0u;
         if (lane == 0) {
             if (phase) d.phantom[uidx].code = RG_EV_BANDIT | RG_EV_PHANTOM | action;
             else d.lr_action[uidx] = action;
-            if (fl & 2u) {       // (user id, the event index of the act's row, the action taken) for the host
-                const unsigned long long pos = atomicAdd(&d.counters[RG_CNT_POLY_UNRESOLVED], 1ull);
-                if (pos < kPolyListCap) {
-                    uint32_t* e = d.pl_list + 3 * static_cast<size_t>(pos);
-                    e[0] = static_cast<uint32_t>(d.first_user + uidx); e[1] = t_act; e[2] = action;
-                }
-            }
+            if (fl & 2u) act_list_add<false>(d, uidx, t_act, action);      // (the event index of the act's own row)
         }
     }
-    // the counters once per block (as k_poly_acts)
-    if (lane == 0 && c_acts) {
-        atomicAdd(&s_sum[0], c_acts);
-        atomicAdd(&s_sum[1], c_rows);
-        if (c_table) atomicAdd(&s_sum[2], c_table);
-        if (c_range) atomicAdd(&s_sum[3], c_range);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum[0]) {
-        atomicAdd(&d.counters[RG_CNT_LR_ACTS], s_sum[0]);
-        atomicAdd(&d.counters[RG_CNT_LR_ROWS], s_sum[1]);
-        if (s_sum[2]) atomicAdd(&d.counters[RG_CNT_POLY_TABLE], s_sum[2]);
-        if (s_sum[3]) atomicAdd(&d.counters[RG_CNT_WH_CLOCK_RANGE], s_sum[3]);
-    }
+    act_count(d, s_sum, lane, c, {RG_CNT_LR_ACTS, RG_CNT_LR_ROWS, RG_CNT_POLY_TABLE, RG_CNT_WH_CLOCK_RANGE});
 }
 
 // rg_sim_debug_set_timed_history: the timed rows of the reset range, a thread per user index.  The views go in one at a time, in

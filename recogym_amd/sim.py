@@ -357,8 +357,13 @@ class Simulator:
                         self.logreg16 = self.logreg[0].to(torch.float16).contiguous()
                         _abi.check(self.lib.rg_sim_set_logreg_fp16(self._h, self.logreg16.data_ptr()), 'rg_sim_set_logreg_fp16')
             self.weight_history = None
+            # _host_act(views) -> the attached model's act on a user's views, by the host's arithmetic (poly_verify; the
+            # time-weighted likelihood agent's takes clock values too and is called there).  The model is bound as a default
+            # argument, not through self: a Simulator that is dropped unclosed is still released by its reference count.
+            self._host_act = None
             if policy == _abi.RG_POLICY_LOGREG_POLY:
                 self.logreg_poly_host, self.logreg_poly = poly_device_model(logreg_poly, int(config.num_products), self.device)
+                self._host_act = lambda views, model=self.logreg_poly_host: poly_host_act(views, model)
                 _abi.check(self.lib.rg_sim_set_logreg_poly(self._h, *[t.data_ptr() for t in self.logreg_poly[:3]],
                                                            C.c_double(self.logreg_poly_host[3]), self.logreg_poly[3].data_ptr(),
                                                            int(self.logreg_poly[3].numel())), 'rg_sim_set_logreg_poly')
@@ -376,15 +381,18 @@ class Simulator:
                 self.bayes_vb_host, self.bayes_vb = bayes_device_model(bayes_vb, int(config.num_products), self.device)
                 _abi.check(self.lib.rg_sim_set_bayes_vb(self._h, self.bayes_vb.data_ptr(), int(self.bayes_vb.shape[2])),
                            'rg_sim_set_bayes_vb')
+                self._host_act = lambda views, P=config.num_products, model=self.bayes_vb_host: bayes_host_act(views, P, model)
             self.nn_ips_host = None
             if policy == _abi.RG_POLICY_NN_IPS:
                 self.nn_ips_host, self.nn_ips_model, self.nn_ips = nn_device_model(nn_ips, self.device)
                 _abi.check(self.lib.rg_sim_set_nn_ips(self._h, *[x.data_ptr() for x in self.nn_ips], int(self.nn_ips_model.H)),
                            'rg_sim_set_nn_ips')
+                self._host_act = lambda views, P=config.num_products, model=self.nn_ips_host: nn_host_act(views, P, model)
             self.mlr_host = None
             if policy == _abi.RG_POLICY_MLR:
                 self.mlr_host, self.mlr = mlr_device_model(mlr, self.device)
                 _abi.check(self.lib.rg_sim_set_mlr(self._h, self.mlr.data_ptr()), 'rg_sim_set_mlr')
+                self._host_act = lambda views, P=config.num_products, model=self.mlr_host: mlr_host_act(views, P, model)
             self.poly_unresolved = self.poly_refuted = None
             self.poly_overflow = False
             if log_capacity is None:
@@ -521,45 +529,32 @@ class Simulator:
                                                          int(products.shape[1]), self._stream()), 'rg_sim_debug_set_history')
             torch.cuda.synchronize(self.device)
 
-    def debug_bayes_acts(self):
-        """rg_sim_debug_bayes_acts -> (actions, flags, q (n, P)): BayesianAgentVB's act of every user index on its current history
-        and the device's means."""
-        n, P = self.n_active, int(self.config.num_products)
+    def _debug_model_acts(self, what, extras):
+        """The debug entry point `what` of a model agent -> (actions, flags, *extras): the act of every user index on its current
+        history, into poisoned tensors.  extras: the trailing shape of each float64 output beyond actions and flags."""
+        n = self.n_active
         with torch.cuda.device(self.device):
             act = torch.full((n,), -1, dtype=torch.int32, device=self.device)
             fl = torch.full((n,), 255, dtype=torch.uint8, device=self.device)
-            q = torch.full((n, P), float('nan'), dtype=torch.float64, device=self.device)
-            _abi.check(self.lib.rg_sim_debug_bayes_acts(self._h, act.data_ptr(), fl.data_ptr(), q.data_ptr(), self._stream()),
-                       'rg_sim_debug_bayes_acts')
+            out = [torch.full((n, *shape), float('nan'), dtype=torch.float64, device=self.device) for shape in extras]
+            _abi.check(getattr(self.lib, what)(self._h, act.data_ptr(), fl.data_ptr(), *[x.data_ptr() for x in out], self._stream()), what)
             torch.cuda.synchronize(self.device)
-        return act.cpu().numpy().astype(np.int64), fl.cpu().numpy().astype(np.int64), q.cpu().numpy()
+        return (act.cpu().numpy().astype(np.int64), fl.cpu().numpy().astype(np.int64), *[x.cpu().numpy() for x in out])
+
+    def debug_bayes_acts(self):
+        """rg_sim_debug_bayes_acts -> (actions, flags, q (n, P)): BayesianAgentVB's act of every user index on its current history
+        and the device's means."""
+        return self._debug_model_acts('rg_sim_debug_bayes_acts', [(int(self.config.num_products),)])
 
     def debug_nn_acts(self):
         """rg_sim_debug_nn_acts -> (actions, flags, z (n, P), ps (n,)): NnIpsAgent's act of every user index on its current history,
         the device's logits and propensity."""
-        n, P = self.n_active, int(self.config.num_products)
-        with torch.cuda.device(self.device):
-            act = torch.full((n,), -1, dtype=torch.int32, device=self.device)
-            fl = torch.full((n,), 255, dtype=torch.uint8, device=self.device)
-            z = torch.full((n, P), float('nan'), dtype=torch.float64, device=self.device)
-            ps = torch.full((n,), float('nan'), dtype=torch.float64, device=self.device)
-            _abi.check(self.lib.rg_sim_debug_nn_acts(self._h, act.data_ptr(), fl.data_ptr(), z.data_ptr(), ps.data_ptr(), self._stream()),
-                       'rg_sim_debug_nn_acts')
-            torch.cuda.synchronize(self.device)
-        return act.cpu().numpy().astype(np.int64), fl.cpu().numpy().astype(np.int64), z.cpu().numpy(), ps.cpu().numpy()
+        return self._debug_model_acts('rg_sim_debug_nn_acts', [(int(self.config.num_products),), ()])
 
     def debug_mlr_acts(self):
         """rg_sim_debug_mlr_acts -> (actions, flags, z (n, P)): PyTorchMLRAgent's act of every user index on its current history, the
         device's scores."""
-        n, P = self.n_active, int(self.config.num_products)
-        with torch.cuda.device(self.device):
-            act = torch.full((n,), -1, dtype=torch.int32, device=self.device)
-            fl = torch.full((n,), 255, dtype=torch.uint8, device=self.device)
-            z = torch.full((n, P), float('nan'), dtype=torch.float64, device=self.device)
-            _abi.check(self.lib.rg_sim_debug_mlr_acts(self._h, act.data_ptr(), fl.data_ptr(), z.data_ptr(), self._stream()),
-                       'rg_sim_debug_mlr_acts')
-            torch.cuda.synchronize(self.device)
-        return act.cpu().numpy().astype(np.int64), fl.cpu().numpy().astype(np.int64), z.cpu().numpy()
+        return self._debug_model_acts('rg_sim_debug_mlr_acts', [(int(self.config.num_products),)])
 
     def debug_logreg_acts(self):
         """rg_sim_debug_logreg_acts -> actions: the frozen LogReg's act of every user index on its current history, by the step loop's
@@ -640,14 +635,8 @@ class Simulator:
                     mine = u == user
                     host = weighted_host_act(v[mine & organic & (t < t_act)], clock[mine & organic & (t < t_act)],
                                              clock[mine & (t == t_act)], self.weight_history, self.logreg_poly_host)
-                elif self.nn_ips_host is not None:
-                    host = nn_host_act(v[organic & (u == user) & (t <= t_act)], self.config.num_products, self.nn_ips_host)
-                elif self.mlr_host is not None:
-                    host = mlr_host_act(v[organic & (u == user) & (t <= t_act)], self.config.num_products, self.mlr_host)
-                elif self.bayes_vb_host is not None:
-                    host = bayes_host_act(v[organic & (u == user) & (t <= t_act)], self.config.num_products, self.bayes_vb_host)
                 else:
-                    host = poly_host_act(v[organic & (u == user) & (t <= t_act)], self.logreg_poly_host)
+                    host = self._host_act(v[organic & (u == user) & (t <= t_act)])
                 if host != int(a):
                     bad.append((user, t_act, a))
             self.poly_refuted = np.asarray(bad, dtype=np.uint32).reshape(-1, 3)
