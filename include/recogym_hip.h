@@ -65,6 +65,8 @@ extern "C" {
  * loop) and the flag RG_MLR_UNRESOLVED; its unresolved acts share the same list, counter and reader; and rg_ope_mlr_workspace_bytes /
  * rg_ope_replay_mlr / rg_ope_replay_mlr_eg (its off-policy replay). */
 /* v15: rg_sim_debug_logreg_acts (the frozen LogReg's act kernels on placed histories). */
+/* v15, additive since: rg_ope_poly_w_workspace_bytes / rg_ope_replay_poly_w (the off-policy replay of the likelihood agent on a
+ * time-weighted view history).  New symbols only: the version stays 15. */
 #define RG_ABI_VERSION 15
 
 /* error codes */
@@ -760,6 +762,38 @@ size_t rg_ope_poly_workspace_bytes(const rg_ope_poly* model, uint64_t n_users, u
 int rg_ope_replay_poly(const rg_ope_poly* model, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
                        uint32_t max_user_rows, uint32_t ps_mode, const double* d_ps, double ps_const, double* d_ratio,
                        uint8_t* d_click, double* d_sums, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Off-policy evaluation of the likelihood agent on a TIME-WEIGHTED view history (a weight_history_function, with_ps_all = True):
+ * rg_ope_replay_poly's replay with the act of rg_sim_set_weight_history — at every bandit row the user's organic rows before it,
+ * each weighted by table[now - t] at the row's own clock value `now`, summed per product by that function's rule (table, n,
+ * accumulate_f32 as it and rg_weighted_feed take them), then the likelihood agent's act on that feature list.  d_t16[row] is the
+ * row's clock value after the int16 cast, 0xFFFF where it lies outside [0, 32767] (rg_weighted_feed's convention).  Nothing is
+ * dropped from a user's views, and no act is shared between bandit rows.
+ */
+typedef struct rg_ope_poly_w {
+    rg_ope_poly model;              /* the likelihood agent's model, as rg_ope_replay_poly takes it */
+    const double* table;            /* device: the weight table over clock differences */
+    uint32_t n;                     /* 1 .. 32768 entries */
+    uint32_t accumulate_f32;        /* the table's dtype rule: every add rounds to float32 */
+} rg_ope_poly_w;
+
+/* rg_ope_poly_w_workspace_bytes: device workspace rg_ope_replay_poly_w needs (0 = error, see rg_last_error).
+ * rg_ope_replay_poly_w: rows, offsets, the ps source, d_ratio / d_click / d_sums and the validation of the log as
+ * rg_ope_replay_poly; d_act (optional, int32 per row) receives the act at every bandit row, organic rows are not written.
+ * RG_EINVAL for a null model, model array or table, n outside 1 .. 32768, null d_t16 with n_users > 0 and rows that are not 16-byte
+ * aligned; RG_ENOMEM for a workspace too small — all before a device is looked for.  Afterwards the workspace's first int64 words
+ * hold rg_ope_replay_poly's in their places — [0] error bits, [1] acts computed (here: every bandit row), [2] decided on the step
+ * table, [3] a lower index won, [4] unresolved acts, [5] non-zero when more than 4096 of them, [6] feature-list entries read — and
+ * [7] the rows whose d_t16 lies outside [0, 32767] plus the acts at a row inside the range whose feature list met a clamped table
+ * index (a view outside the range or AFTER the act — a clock that runs backwards inside a user — or a difference >= n): where it
+ * is not 0 the ratios are not the reference's and the caller takes its host loop.  The unresolved acts follow from byte 256 as rg_ope_replay_poly's do, one entry per unresolved bandit row; the host
+ * confirms them with recogym_amd.sim.weighted_replay_verify.  d_sums holds the same bits on every run.  Synchronises `stream` once. */
+size_t rg_ope_poly_w_workspace_bytes(const rg_ope_poly_w* model, uint64_t n_users, uint32_t max_user_rows);
+int rg_ope_replay_poly_w(const rg_ope_poly_w* model, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
+                         uint32_t max_user_rows, const uint16_t* d_t16, uint32_t ps_mode, const double* d_ps, double ps_const,
+                         double* d_ratio, uint8_t* d_click, double* d_sums, int32_t* d_act, void* d_workspace, size_t workspace_bytes,
+                         void* stream);
 
 /*
  * Off-policy evaluation of an EpsilonGreedy target (agents/epsilon_greedy.py:30-71 with with_ps_all = True on the wrapper and the

@@ -102,6 +102,11 @@ class RgOpePoly(C.Structure):
                 ('th', C.c_void_p), ('intercept', C.c_double)]
 
 
+class RgOpePolyW(C.Structure):
+    """struct rg_ope_poly_w: the likelihood agent's model plus the weight table of rg_ope_replay_poly_w (device arrays)."""
+    _fields_ = [('model', RgOpePoly), ('table', C.c_void_p), ('n', C.c_uint32), ('accumulate_f32', C.c_uint32)]
+
+
 class RgOpeNn(C.Structure):
     """struct rg_ope_nn: NnIpsAgent's net of rg_ope_replay_nn (device arrays, rg_sim_set_nn_ips's layout)."""
     _fields_ = [('num_products', C.c_uint32), ('num_hidden', C.c_uint32), ('w1t', C.c_void_p), ('b1', C.c_void_p), ('w2t', C.c_void_p),
@@ -131,6 +136,7 @@ class RgOpeEg(C.Structure):
 OPE_HEAD_BYTES = 256
 OPE_HEADS = {'logreg': ('error', 'acts', 'exact', 'rows_read'),
              'poly': ('error', 'acts', 'table', 'lower', 'unresolved', 'overflow', 'rows_read'),
+             'poly_w': ('error', 'acts', 'table', 'lower', 'unresolved', 'overflow', 'rows_read', 'range'),
              'nn': ('error', 'acts', 'unresolved', 'overflow', 'rows_read'),
              'mlr': ('error', 'acts', 'unresolved', 'overflow', 'rows_read'),
              'bayes': ('error', 'acts', 'saturated', 'unresolved', 'overflow', 'rows_read')}
@@ -233,6 +239,11 @@ SYMBOLS = {
     'rg_ope_replay_poly': (C.c_int, [C.POINTER(RgOpePoly), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                      C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
+    'rg_ope_poly_w_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpePolyW), C.c_uint64, C.c_uint32]),
+    # (rg_ope_replay_poly's arguments with d_t16 ahead of ps_mode and d_act ahead of the workspace)
+    'rg_ope_replay_poly_w': (C.c_int, [C.POINTER(RgOpePolyW), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]),
     'rg_ope_eg_workspace_bytes': (C.c_size_t, [C.POINTER(RgOpePolicy), C.c_uint64, C.c_uint32]),
     'rg_ope_replay_eg': (C.c_int, [C.POINTER(RgOpePolicy), C.POINTER(RgOpeEg), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
                                    C.c_uint32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -155,6 +155,8 @@ class EpsilonGreedy(Agent):
         pol = ope_checked_policy_of(self.agent)
         if pol is None or pol.get('kind') not in _CHECKED_INNER or pol.get('epsilon_greedy') is not None:
             return None
+        if (pol.get('logreg_poly') or {}).get('weight_history') is not None:          # a time-weighted likelihood agent: host loop
+            return None
         if int(pol['num_products']) < 2 and c.epsilon_pure_new:
             return None
         return dict(pol, epsilon_greedy=self._overlay())

@@ -147,6 +147,14 @@ def device_log_columns(dl):
     return {k: x.cpu().numpy() for k, x in cols.items()}
 
 
+def device_clock16(t):
+    """A tensor of clock values (any real dtype) -> the int16 tensor rg_weighted_feed and rg_ope_replay_poly_w take as d_t16: the
+    reference's int16 cast (truncation) inside [0, 32767], -1 = 0xFFFF outside (NaN included)."""
+    import torch
+    inside = (t >= 0) & (t < 32768)                                       # (NaN: outside)
+    return torch.where(inside, t, torch.full_like(t, -1)).to(torch.int32).to(torch.int16).contiguous()      # -1 = 0xFFFF: outside
+
+
 def weighted_train_data_device(dl, num_products, table, is_f32, is_sparse=True):
     """train_data_weighted on a DeviceLog, by rg_weighted_feed -> the same (features, actions, deltas, pss) tuple — features CSR
     float32 with sorted indices — or None where a row's clock value lies outside [0, 32767] (the caller takes the host loop).
@@ -167,8 +175,7 @@ def weighted_train_data_device(dl, num_products, table, is_f32, is_sparse=True):
     if nb == 0 or n_users <= 0:
         feats = sparse.csr_matrix((nb, P), dtype=np.float32)
         return (feats if is_sparse else np.asarray(feats.todense(), dtype=float)), actions, deltas, pss
-    inside = (t32 >= 0) & (t32 < 32768)                                   # (NaN: outside)
-    t16 = torch.where(inside, t32, torch.full_like(t32, -1.0)).to(torch.int32).to(torch.int16).contiguous()      # -1 = 0xFFFF: outside
+    t16 = device_clock16(t32)
     brow = (torch.cumsum(is_b.to(torch.int64), 0) - is_b.to(torch.int64)).contiguous()
     offsets = dl.offsets.contiguous()
     max_rows = int((offsets[1:] - offsets[:-1]).max().item())

@@ -204,12 +204,16 @@ class LogregPolyFrozenAgent(Agent):
 
     def ope_policy_checked(self):
         """The replay form of rg_ope_replay_poly, or None where only the host loop is exact (no `ps-a` without with_ps_all; the
-        time-weighted features of a weight_history_function).  "Checked": the device lists the acts its rule cannot resolve and
-        the caller confirms them on the host (sim.poly_replay_verify) before it lets the result stand."""
-        if not getattr(self.config, 'with_ps_all', False) or self.history is not None:
+        time-weighted features of a weight_history_function that has no device form).  With `device_weight_history` and a function
+        that stands for a table the dict's `logreg_poly` carries `weight_history` (table, f32), the form of rg_ope_replay_poly_w.
+        "Checked": the device lists the acts its rule cannot resolve and the caller confirms them on the host
+        (sim.poly_replay_verify, sim.weighted_replay_verify) before it lets the result stand."""
+        if not getattr(self.config, 'with_ps_all', False) or (self.history is not None and self.weight_history is None):
             return None
-        return dict(kind=_abi.RG_POLICY_LOGREG_POLY, num_products=int(self.config.num_products), policy_seed=0,
-                    logreg_poly=dict(wf=self.wf, wa=self.wa, wk=self.wk, intercept=self.b))
+        model = dict(wf=self.wf, wa=self.wa, wk=self.wk, intercept=self.b)
+        if self.weight_history is not None:
+            model['weight_history'] = self.weight_history
+        return dict(kind=_abi.RG_POLICY_LOGREG_POLY, num_products=int(self.config.num_products), policy_seed=0, logreg_poly=model)
 
     def reset(self):
         self.views = np.zeros(self.config.num_products, dtype=np.int64)

@@ -143,14 +143,6 @@ __global__ __launch_bounds__(64 * kOpeWaves, 4) void k_ope_poly(
     }
 }
 
-int pl_model_ok(const rg_ope_poly* m, const char* who) {
-    if (!m) return fail(RG_EINVAL, "%s: null model", who);
-    if (m->num_products == 0 || m->num_products > RG_EV_INDEX_MASK) return fail(RG_EINVAL, "%s: bad num_products %u", who, m->num_products);
-    if (m->n_steps == 0 || m->n_steps > kPolySteps) return fail(RG_EINVAL, "%s: n_steps %u outside 1 .. %u", who, m->n_steps, kPolySteps);
-    if (!m->wf || !m->wa || !m->wk_t || !m->th) return fail(RG_EINVAL, "%s: null wf / wa / wk_t / th", who);
-    return RG_OK;
-}
-
 }  // namespace
 
 extern "C" size_t rg_ope_poly_workspace_bytes(const rg_ope_poly* m, uint64_t n_users, uint32_t max_user_rows) {

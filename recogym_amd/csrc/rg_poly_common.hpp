@@ -45,6 +45,15 @@ struct PolyModel {
     double pl_b;
 };
 
+// the model's own argument checks (the replay entry points of rg_ope_poly.hip and rg_ope_poly_w.hip)
+inline int pl_model_ok(const rg_ope_poly* m, const char* who) {
+    if (!m) return fail(RG_EINVAL, "%s: null model", who);
+    if (m->num_products == 0 || m->num_products > RG_EV_INDEX_MASK) return fail(RG_EINVAL, "%s: bad num_products %u", who, m->num_products);
+    if (m->n_steps == 0 || m->n_steps > kPolySteps) return fail(RG_EINVAL, "%s: n_steps %u outside 1 .. %u", who, m->n_steps, kPolySteps);
+    if (!m->wf || !m->wa || !m->wk_t || !m->th) return fail(RG_EINVAL, "%s: null wf / wa / wk_t / th", who);
+    return RG_OK;
+}
+
 // the entries of a step-loop history row after its header
 struct PolyRowHist {
     typedef uint32_t val_t;

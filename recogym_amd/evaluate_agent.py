@@ -157,7 +157,8 @@ def ope_checked_policy_of(agent):
     """-> the policy dict of an agent whose replay form needs a host step before its result stands (`ope_policy_checked()`: the
     likelihood agent and, behind the configuration key `device_replay`, NnIpsAgent and BayesianAgentVB, whose device rules list the
     acts they cannot resolve — ope_replay confirms them with sim.replay_verify and the unit's host act), else None.  Kept apart from ope_policy_of, whose forms are exact as the device leaves them.  The dict's `logreg_poly` entry
-    holds wf, wa, wk, intercept (host arrays) and may carry two optional keys: `expit_steps` (a step table other than
+    holds wf, wa, wk, intercept (host arrays), `weight_history` (dict(table, f32)) where the agent acts on a time-weighted view history
+    (rg_ope_replay_poly_w instead of rg_ope_replay_poly), and may carry two optional keys: `expit_steps` (a step table other than
     expit_steps()) and `device_model` (sim.poly_device_model's result for the log's device: a caller that replays several logs
     under one model keeps it there instead of moving it per call; ope_replay asserts the device)."""
     hook = getattr(agent, 'ope_policy_checked', None)
@@ -169,6 +170,11 @@ def _draws(pol):
         return True                            # an EpsilonGreedy target always flips its coin, keyed by the event index
     o = pol.get('ouc')
     return bool(o and o['exploit_explore'] and o['epsilon'] != 0.0)
+
+
+def _weighted(pol):
+    """The policy dict is the likelihood agent's on a time-weighted view history (rg_ope_replay_poly_w, never rg_ope_replay_poly)."""
+    return (pol.get('logreg_poly') or {}).get('weight_history') is not None
 
 
 def _device_present():
@@ -206,8 +212,11 @@ def _frame_to_device(reco_log, pol, device):
     raw[:, 3] = ps[order].astype(np.float32).view(np.uint32)
     rows = torch.from_numpy(raw.view(np.int32)).to(device)
     offsets = torch.from_numpy(start.astype(np.int64)).to(device)
+    # a time-weighted target reads the clock: the truncation of the frame's own `t` values (what the reference's int16 cast makes of
+    # them inside the clock range), in float64 — whole numbers up to 32767 pass ope_replay's float32 cast unchanged
+    time = torch.from_numpy(np.trunc(tt)).to(device) if _weighted(pol) else None
     return DeviceLog(rows, offsets, torch.from_numpy(np.ascontiguousarray(ps[order])).to(device), 0,
-                     pol['num_products'], None)
+                     pol['num_products'], time)
 
 
 def _as_device_log(reco_log):
@@ -269,6 +278,7 @@ _REPLAY_ENTRY = {
     ('logreg', True): ('rg_ope_logreg_workspace_bytes', 'rg_ope_replay_logreg_eg'),       # (the wrapper round a model: the plain
     ('poly', False): ('rg_ope_poly_workspace_bytes', 'rg_ope_replay_poly'),               # unit's workspace, list and head words)
     ('poly', True): ('rg_ope_poly_workspace_bytes', 'rg_ope_replay_poly_eg'),
+    ('poly_w', False): ('rg_ope_poly_w_workspace_bytes', 'rg_ope_replay_poly_w'),        # (time-weighted: no wrapper form)
     ('nn', False): ('rg_ope_nn_workspace_bytes', 'rg_ope_replay_nn'),
     ('nn', True): ('rg_ope_nn_workspace_bytes', 'rg_ope_replay_nn_eg'),
     ('mlr', False): ('rg_ope_mlr_workspace_bytes', 'rg_ope_replay_mlr'),
@@ -280,6 +290,8 @@ _REPLAY_ENTRY = {
 _REFUTED = {
     'poly': 'the likelihood agent\'s replay has acts the host does not confirm (or more unresolved acts than the '
             'device lists): the off-policy evaluation takes the host loop',
+    'poly_w': 'the time-weighted likelihood agent\'s replay has acts the host does not confirm (or more unresolved acts than the '
+              'device lists): the off-policy evaluation takes the host loop',
     'nn': 'the replay of NnIpsAgent has acts that torch\'s forward on the host does not confirm (or more unresolved acts than the '
           'device lists): the off-policy evaluation takes the host loop',
     'mlr': 'the replay of PyTorchMLRAgent has acts that the reference\'s fp32 dot on the host does not confirm (or more unresolved acts '
@@ -287,10 +299,14 @@ _REFUTED = {
     'bayes': 'the replay of BayesianAgentVB has acts that the reference\'s expression on the host does not confirm (or more unresolved '
              'acts than the device lists): the off-policy evaluation takes the host loop',
 }
+# the one warning of a time-weighted replay whose log leaves the clock differences the device's table covers (head word `range`)
+_CLOCK_RANGE = ('the time-weighted likelihood agent\'s replay met clock values outside [0, 32767], where the reference\'s int16 cast '
+                'wraps, or a view after its act (a clock that runs backwards inside a user): the off-policy evaluation takes the host loop')
 # structs: what leads the argument list (the policy or model, then the wrapper); keep: the tensors they point into; size_fn / replay_fn /
 # what: the entry point and its name; unit / head: the unit and the word names of its workspace's head or None; host_act: where the unit
-# lists unresolved acts, the agent's act on the host, host_act(views) -> action (sim.replay_verify), else None
-_ReplayTarget = namedtuple('_ReplayTarget', 'structs keep size_fn replay_fn what unit head host_act')
+# lists unresolved acts, the agent's act on the host, host_act(views) -> action (sim.replay_verify), else None; weighted: (weight_history,
+# host model) of the time-weighted unit, whose entry point takes d_t16 and d_act and whose acts sim.weighted_replay_verify judges
+_ReplayTarget = namedtuple('_ReplayTarget', 'structs keep size_fn replay_fn what unit head host_act weighted', defaults=(None,))
 
 
 def _replay_target(pol, device):
@@ -298,9 +314,10 @@ def _replay_target(pol, device):
     what it wraps (an inner policy that samples its act)."""
     import torch
     P = int(pol['num_products'])
-    eg, host_act = pol.get('epsilon_greedy'), None
+    eg, host_act, weighted = pol.get('epsilon_greedy'), None, None
     if eg is not None and (pol.get('kind') not in (_abi.RG_POLICY_RANDOM_AGENT, _abi.RG_POLICY_LAST_VIEW_TABLE, _abi.RG_POLICY_LOGREG_FROZEN,
-                                                    _abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_BAYES_VB, _abi.RG_POLICY_MLR) or (pol.get('logreg') or {}).get('select_randomly')):
+                                                    _abi.RG_POLICY_LOGREG_POLY, _abi.RG_POLICY_NN_IPS, _abi.RG_POLICY_BAYES_VB, _abi.RG_POLICY_MLR) or (pol.get('logreg') or {}).get('select_randomly')
+                           or _weighted(pol)):          # (the time-weighted likelihood agent has no wrapper form either)
         return None
     if pol.get('logreg_poly') is not None:
         # the likelihood agent: the model and the step table move to the log's device as the step loop's do (sim.poly_device_model)
@@ -312,6 +329,13 @@ def _replay_target(pol, device):
         cp = _abi.RgOpePoly(num_products=P, n_steps=int(keep[3].numel()), wf=keep[0].data_ptr(), wa=keep[1].data_ptr(),
                             wk_t=keep[2].data_ptr(), th=keep[3].data_ptr(), intercept=poly_host[3])
         host_act = lambda views: sim.poly_host_act(views, poly_host)                    # noqa: E731
+        wh = poly.get('weight_history')
+        if wh is not None:
+            # the time-weighted form: its own unit, with the table beside the model (a float32 table widens exactly)
+            unit, host_act, weighted = 'poly_w', None, (wh, poly_host)
+            wtab = torch.from_numpy(np.ascontiguousarray(wh['table']).astype(np.float64)).to(device)
+            cp = _abi.RgOpePolyW(model=cp, table=wtab.data_ptr(), n=int(wtab.numel()), accumulate_f32=int(bool(wh['f32'])))
+            keep = [*keep, wtab]
     elif pol.get('nn_ips') is not None:
         # NnIpsAgent's argmax form: the six arrays move to the log's device as the step loop's do (sim.nn_device_model)
         from . import sim
@@ -357,7 +381,7 @@ def _replay_target(pol, device):
                                     reserved=0, prob_explore=explore_table(P, pure_new)[1]))
     lib = _abi.load()
     size_name, what = _REPLAY_ENTRY[unit, eg is not None]
-    return _ReplayTarget(structs, keep, getattr(lib, size_name), getattr(lib, what), what, unit, _abi.OPE_HEADS.get(unit), host_act)
+    return _ReplayTarget(structs, keep, getattr(lib, size_name), getattr(lib, what), what, unit, _abi.OPE_HEADS.get(unit), host_act, weighted)
 
 
 def _replay_users(dl, pol, n_users):
@@ -381,7 +405,7 @@ def _replay_head(ws, names):
     return {name: bool(words[i]) if name == 'overflow' else int(words[i]) for i, name in enumerate(names)}
 
 
-def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
+def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None, act_out=None):
     """Replay a DeviceLog under `agent` on the device -> (ratio r = pi[a] / ps, click c as float64, sums) for the bandit rows of
     the log's first `n_users` users (default: all but the last, whose id is max(u)), in log order (device tensors);
     sums = float64 tensor (n, sum c r, sum r).  None where the agent has no replay form or the log does not qualify (a user
@@ -392,7 +416,10 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
     is None, after one RuntimeWarning, also where the host refutes an unresolved act or the device's list of them overflowed (under an
     EpsilonGreedy wrapper the listed acts are the GREEDY ones; with pure_new a wrong one changes pi on explored rows too).  `eg_out` (a
     dict, EpsilonGreedy targets only) receives `greedy` (uint8) and `h0` (int32) of the same bandit rows (device tensors); where it
-    comes in with `per_row=True` also `greedy_rows` / `h0_rows`, one entry per row of the evaluated users (0 on organic rows)."""
+    comes in with `per_row=True` also `greedy_rows` / `h0_rows`, one entry per row of the evaluated users (0 on organic rows).
+    The time-weighted likelihood agent (rg_ope_replay_poly_w) reads the rows' clock — dl.time where the log has one, else the event
+    index — and is None, after one RuntimeWarning, also where a clock value leaves [0, 32767] or a view lies after its act (`stats['range']`); `act_out` (a dict,
+    that target only) receives `act_rows` (int32), the act at every bandit row, one entry per row of the evaluated users."""
     import torch
     pol = _replay_policy_of(agent) if pol is None else pol
     if pol is None or int(pol['num_products']) != int(dl.num_products):
@@ -426,29 +453,47 @@ def ope_replay(agent, dl, pol=None, n_users=None, stats=None, eg_out=None):
         greedy = torch.zeros(max(total, 1), dtype=torch.uint8, device=device) if want else None
         h0 = torch.zeros(max(total, 1), dtype=torch.int32, device=device) if want else None
         eg_ptrs = [greedy.data_ptr() if want else None, h0.data_ptr() if want else None] if wrapped else []
-        _abi.check(target.replay_fn(*[C.byref(x) for x in target.structs], dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows, mode,
-                                    ps_ptr, ps_const, ratio.data_ptr(), None, sums.data_ptr(), *eg_ptrs, ws.data_ptr(), need,
+        # the time-weighted unit's two: the int16 clock ahead of the ps source, the optional acts ahead of the workspace
+        t16_ptrs, act_ptrs = [], []
+        if target.weighted is not None:
+            from .agents.feature_feed import device_clock16
+            # (the `t` column of the log's frame, float32: log_columns' and _device_log_to_frame's — the host loop casts that)
+            clock = (dl.time if dl.time is not None else dl.rows[:, 1]).to(torch.float32)
+            t16 = device_clock16(clock)
+            acts = torch.zeros(max(total, 1), dtype=torch.int32, device=device) if act_out is not None else None
+            t16_ptrs, act_ptrs = [t16.data_ptr()], [None if acts is None else acts.data_ptr()]
+        _abi.check(target.replay_fn(*[C.byref(x) for x in target.structs], dl.rows.data_ptr(), offsets.data_ptr(), n_eval, max_rows, *t16_ptrs,
+                                    mode, ps_ptr, ps_const, ratio.data_ptr(), None, sums.data_ptr(), *eg_ptrs, *act_ptrs, ws.data_ptr(), need,
                                     C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), target.what)
         if target.head is not None:
             head = _replay_head(ws, target.head)
             if stats is not None:
                 stats.update(head)
+            if head.get('range'):
+                warnings.warn(_CLOCK_RANGE, RuntimeWarning, stacklevel=2)
+                return None
             if head['error']:
                 # error bits after the validation passed: a history list overflowed — the ratios are not to be trusted
                 raise _abi.RecoGymHipError(f'{target.what}: the replay reported error bits {head["error"]:#x} (a view history outgrew its list)')
             if head.get('unresolved'):
                 # the acts the device's rule could not resolve: confirmed on the host, or the whole replay is given up (no patching)
-                from .sim import replay_verify
+                from .sim import replay_verify, weighted_replay_verify
                 n_listed = min(head['unresolved'], _abi.OPE_POLY_LIST_CAP)
                 listed = ws[_abi.OPE_HEAD_BYTES:_abi.OPE_HEAD_BYTES + _abi.OPE_POLY_LIST_ENTRY_BYTES * n_listed]
                 listed = listed.view(torch.int32).cpu().numpy().view(np.uint32).reshape(-1, 3)
-                if not replay_verify(dl, listed, head['overflow'], target.host_act):
+                if target.weighted is not None:
+                    stands = weighted_replay_verify(dl, clock, listed, head['overflow'], *target.weighted)
+                else:
+                    stands = replay_verify(dl, listed, head['overflow'], target.host_act)
+                if not stands:
                     warnings.warn(_REFUTED[target.unit], RuntimeWarning, stacklevel=2)
                     return None
         code = dl.rows[:total, 2]
         is_b = (code & _abi.RG_EV_BANDIT) != 0
         r = _masked(ratio[:total], is_b)
         c = _masked(((code & _abi.RG_EV_CLICK) != 0).to(torch.float64), is_b)
+        if target.weighted is not None and act_out is not None:
+            act_out.update(act_rows=acts[:total])
         if want:
             eg_out.update(greedy=_masked(greedy[:total], is_b), h0=_masked(h0[:total], is_b))
             if eg_out.pop('per_row', False):   # (recall_replay: the two arrays as the device wrote them, one entry per row of the log)
@@ -647,7 +692,8 @@ def recall_replay(agent, dl, k=5, n_users=None, list_cap=None, stats=None):
                   (ope_policy_checked), and
                   EpsilonGreedy round any of them where ope_replay accepts it: the rg_ope_replay_*_eg entry points write the
                   act at every bandit row (`h0`) and the flip (`greedy`) — a bare target goes through them with epsilon = 0 —
-                  recall_sets builds the set of every key that occurs and rg_ope_recall_hits tests membership.
+                  recall_sets builds the set of every key that occurs and rg_ope_recall_hits tests membership.  The time-weighted
+                  likelihood agent has no wrapper form: its act of every row is the plain entry point's d_act (key 2 act).
       rank form   the sampling LogReg: rg_ope_recall_logreg; the rows inside its margin are decided on the host, and a list
                   that overflowed gives the call up after one RuntimeWarning.  `list_cap`: the list's entries (default
                   _abi.OPE_RECALL_LIST_CAP); `stats` (a dict) receives the head words (_abi.OPE_RECALL_HEAD).
@@ -703,11 +749,18 @@ def recall_replay(agent, dl, k=5, n_users=None, list_cap=None, stats=None):
                 key = torch.zeros(max(total, 1), dtype=torch.int32, device=device)          # one constant vector: one key
                 present, sets_pol = np.zeros(1, dtype=np.int64), pol
             else:
-                sets_pol = pol if pol.get('epsilon_greedy') is not None else dict(pol, epsilon_greedy=_NO_FLIP)
-                out = dict(per_row=True)
-                if ope_replay(agent, dl, sets_pol, n_users=n_eval, eg_out=out) is None:
-                    return None
-                raw = out['h0_rows'] * 2 + (1 - out['greedy_rows'].to(torch.int32))
+                if _weighted(pol):
+                    # the time-weighted likelihood agent has no wrapper form: the act of every row from the plain entry point's d_act
+                    sets_pol, out = pol, {}
+                    if ope_replay(agent, dl, pol, n_users=n_eval, act_out=out) is None:
+                        return None
+                    raw = out['act_rows'] * 2
+                else:
+                    sets_pol = pol if pol.get('epsilon_greedy') is not None else dict(pol, epsilon_greedy=_NO_FLIP)
+                    out = dict(per_row=True)
+                    if ope_replay(agent, dl, sets_pol, n_users=n_eval, eg_out=out) is None:
+                        return None
+                    raw = out['h0_rows'] * 2 + (1 - out['greedy_rows'].to(torch.int32))
                 is_b = (dl.rows[:total, 2] & _abi.RG_EV_BANDIT) != 0
                 uniq = torch.unique(_masked(raw, is_b))                                       # ascending; only this leaves the device
                 present = uniq.cpu().numpy().astype(np.int64)

@@ -219,6 +219,34 @@ def replay_verify(dl, acts, overflow, host_act):
     return True
 
 
+def weighted_replay_verify(dl, t, acts, overflow, weight_history, model):
+    """replay_verify for the likelihood agent on a time-weighted history (rg_ope_replay_poly_w).  `t`: the clock value of every row
+    of `dl` (a tensor beside dl.rows: dl.time, or the rows' event index); `acts`: (n, 3) array of (user index, position of the bandit
+    row within the user's rows, action taken); `weight_history`: dict(table, f32); `model`: (wf, wa, wk, b) on the host.  The act of
+    a listed row is judged by weighted_host_act on the user's organic rows BEFORE that position, with their clock values, at the
+    clock value of the row itself; -1 from it (a clock value outside [0, 32767]) refutes like any other action than the listed one.
+    Only the listed users' rows leave the device.  -> True when the replay stands: every listed act confirmed, no overflow."""
+    if overflow:
+        return False
+    acts = np.asarray(acts, dtype=np.int64).reshape(-1, 3)
+    if not len(acts):
+        return True
+    users = np.unique(acts[:, 0])
+    at = torch.as_tensor(users, device=dl.offsets.device)
+    begin, end = dl.offsets[at].cpu().numpy(), dl.offsets[at + 1].cpu().numpy()
+    code = {int(u): dl.rows[int(b):int(e), 2].contiguous().cpu().numpy().view(np.uint32) for u, b, e in zip(users, begin, end)}
+    clock = {int(u): t[int(b):int(e)].cpu().numpy().astype(np.float64) for u, b, e in zip(users, begin, end)}
+    for user, pos, a in acts:
+        c, tt = code[int(user)], clock[int(user)]
+        if int(pos) >= len(c):
+            return False
+        organic = (c[:int(pos)] & _abi.RG_EV_BANDIT) == 0
+        got = weighted_host_act(c[:int(pos)][organic] & _abi.RG_EV_INDEX_MASK, tt[:int(pos)][organic], tt[int(pos)], weight_history, model)
+        if got < 0 or got != int(a):
+            return False
+    return True
+
+
 class Simulator:
     """N concurrent users of one reco-gym-v1 environment on one GPU.
 
