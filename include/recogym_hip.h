@@ -67,6 +67,9 @@ extern "C" {
 /* v15: rg_sim_debug_logreg_acts (the frozen LogReg's act kernels on placed histories). */
 /* v15, additive since: rg_ope_poly_w_workspace_bytes / rg_ope_replay_poly_w (the off-policy replay of the likelihood agent on a
  * time-weighted view history).  New symbols only: the version stays 15. */
+/* v15, additive since: rg_omf_pairs_workspace_bytes / rg_omf_pairs / rg_omf_limits / rg_omf_steps_workspace_bytes / rg_omf_steps
+ * (OrganicMFSquare's training from a sorted device log: the pair list of every optimiser step, and the chain of RMSprop steps in
+ * one launch).  New symbols only: the version stays 15. */
 #define RG_ABI_VERSION 15
 
 /* error codes */
@@ -1044,6 +1047,64 @@ int rg_evolution_stats(const rg_ope_eg* eg, const rg_event* d_rows, const int64_
 size_t rg_count_online_workspace_bytes(uint32_t num_products, uint64_t n_users);
 int rg_count_train_online(const rg_count_tables* tables, const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users,
                           const uint8_t* d_mask, int64_t* d_carry, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * OrganicMFSquare's training (reference agents/organic_mf.py:80-116 under the offline protocol of bench_agents.py:168-190) from a
+ * sorted device log; rows / offsets as rg_count_train, stateless.
+ *
+ * The train CALLS of a log: one per organic-only user (users 0 .. n_organic_users-1, the session = the user's organic rows), then
+ * one per bandit row of every other user, the phantom row included (the session = the organic rows of that user since its previous
+ * bandit row); a user's trailing organic rows belong to no call.  Call number k = first_call + 1 + (calls in front of it).  A call
+ * with k % mini_batch == 0 is a TRIGGER: one optimiser step over the sessions stored since the previous trigger, its own session
+ * is dropped.  A session [v0 .. vm] stands for the PAIRS (v0, v1) .. (v(m-1), vm).
+ *
+ * rg_omf_pairs writes, in log order: d_pairs = the (i, j) int32 pairs of every stored session, the n_pending pairs of d_pending
+ * (carried in from an earlier log: they belong to the first step) in front; d_step_offsets[0 .. n_steps] = the CSR rows of the
+ * n_steps triggers of the log (a step without pairs is an empty row), and d_step_offsets[n_steps + 1] = all pairs: the row
+ * n_steps is what lies behind the last trigger, the caller's new pending set.  d_out (8 int64, device): [0] error bits (0), [1]
+ * calls, [2] n_steps, [3] pairs written, [4] pairs of the pending row.  pairs_capacity >= n_pending + n_rows pairs (2 int32 each),
+ * step_capacity >= (first_call % mini_batch + n_rows) / mini_batch + 2; d_workspace: what the workspace function answers for
+ * (n_rows, n_pending), 8-byte aligned.  Integer work only: the same bytes on every run.  Synchronises `stream` once: the log is
+ * validated before any output is written — RG_EINVAL for a user whose first row is a bandit row, an index >= num_products, an
+ * organic-only user without rows or with a bandit row, offsets that descend or leave the n_rows rows, and more than 2^32 - 16 rows; RG_ENOMEM for
+ * a capacity or a workspace too small.  d_out is read after the stream's work is done.
+ */
+size_t rg_omf_pairs_workspace_bytes(uint64_t n_rows, uint64_t n_pending);
+int rg_omf_pairs(const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users, uint64_t n_organic_users, uint64_t n_rows,
+                 uint32_t num_products, uint64_t first_call, uint32_t mini_batch, const int32_t* d_pending, uint64_t n_pending,
+                 int32_t* d_pairs, uint64_t pairs_capacity, int64_t* d_step_offsets, uint64_t step_capacity, int64_t* d_out,
+                 void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* The model of rg_omf_steps: float64 device arrays, read and written in place. */
+typedef struct rg_omf_model {
+    uint32_t num_products;          /* P <= 2048 */
+    uint32_t embed_dim;             /* E <= 64 */
+    double* emb;                    /* [P][E] nn.Embedding.weight */
+    double* w;                      /* [P][E] nn.Linear.weight */
+    double* bias;                   /* [P]    nn.Linear.bias */
+    double* sq_emb;                 /* RMSprop's square averages of the three */
+    double* sq_w;
+    double* sq_bias;
+} rg_omf_model;
+
+/*
+ * rg_omf_steps: every optimiser step of a pair list (d_pairs, d_step_offsets[0 .. n_steps] as rg_omf_pairs writes them) in one
+ * launch of one workgroup.  A step with pairs: per distinct input i, logits = w emb[i] + bias, a max-shifted softmax,
+ * G[i] = n_i softmax - N[i][.] (N[i][j] = how often the step holds the pair (i, j)); g_emb[i] = G[i] w, g_w = sum_i G[i]^T emb[i],
+ * g_bias = sum_i G[i], the sums over i in ascending order; then torch's RMSprop step (no momentum, not centred) on all
+ * 2 P E + P parameters: sq = alpha sq + (1 - alpha) g g, p -= lr g / (sqrt(sq) + eps) — a row of emb the step did not see has
+ * g = 0.  A step without pairs changes nothing.  float64, no floating-point atomics: the same bits on every run.  The model lives
+ * in LDS while P <= lds_max_products of the limits function (228 at E = 5), else in global memory (force_global != 0: there in any
+ * case), up to max_products; the global form needs d_workspace of the workspace function's size, 8-byte aligned.  d_out (4 int64,
+ * device): [0] error bits, [1] steps taken, [2] steps skipped as empty, [3] pairs consumed.  The list is validated on the device
+ * before the model is touched: a pair with an index >= P (bit 2) or offsets that descend or leave n_pairs (bit 4) leave the model
+ * as it was.  No synchronisation.  RG_EINVAL: P or E out of range, a null array, alpha outside [0, 1], eps < 0; RG_ENOMEM.
+ */
+int rg_omf_limits(uint32_t embed_dim, uint32_t* lds_max_products, uint32_t* max_products);
+size_t rg_omf_steps_workspace_bytes(uint32_t num_products, uint32_t embed_dim);
+int rg_omf_steps(const rg_omf_model* model, double lr, double alpha, double eps, const int32_t* d_pairs, uint64_t n_pairs,
+                 const int64_t* d_step_offsets, uint64_t n_steps, uint32_t force_global, int64_t* d_out, void* d_workspace,
+                 size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

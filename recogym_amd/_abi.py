@@ -159,6 +159,12 @@ class RgCountTables(C.Structure):
                 ('clicks', C.c_void_p)]
 
 
+class RgOmfModel(C.Structure):
+    """struct rg_omf_model: OrganicMFSquare's float64 device arrays (the model and RMSprop's square averages) of rg_omf_steps."""
+    _fields_ = [('num_products', C.c_uint32), ('embed_dim', C.c_uint32), ('emb', C.c_void_p), ('w', C.c_void_p), ('bias', C.c_void_p),
+                ('sq_emb', C.c_void_p), ('sq_w', C.c_void_p), ('sq_bias', C.c_void_p)]
+
+
 # every symbol include/recogym_hip.h declares, with its ctypes signature
 _SIM = C.c_void_p
 SYMBOLS = {
@@ -285,6 +291,13 @@ SYMBOLS = {
     'rg_count_online_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint64]),
     'rg_count_train_online': (C.c_int, [C.POINTER(RgCountTables), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rg_omf_pairs_workspace_bytes': (C.c_size_t, [C.c_uint64, C.c_uint64]),
+    'rg_omf_pairs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p,
+                               C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rg_omf_limits': (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    'rg_omf_steps_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    'rg_omf_steps': (C.c_int, [C.POINTER(RgOmfModel), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 LIB_NAME = 'librecogym_hip.so'

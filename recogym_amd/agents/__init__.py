@@ -13,3 +13,4 @@ from .bandit_mf import BanditMFSquareAgent, bandit_mf_square_args
 from .organic_count import OrganicCount, organic_count_args
 from .bandit_count import BanditCount, bandit_count_args
 from .epsilon_greedy import EpsilonGreedy, epsilon_greedy_args
+from .organic_mf import OrganicMFSquare, organic_mf_square_args

@@ -41,6 +41,22 @@ class LastViewTableAgent(Agent):
             win[lo:lo + rows] = logits[np.arange(logits.shape[0]), table[lo:lo + rows]]
         return cls(config, table, win)
 
+    @classmethod
+    def from_organic_mf(cls, config, embedding, weight, bias):
+        """embedding (P, E), weight (P, E), bias (P): the nn.Embedding and nn.Linear weights of a trained OrganicMFSquare
+        (organic_mf.py:49-64): table[l] = argmax_a (W emb[l] + b)[a], `ps` = 1."""
+        emb = np.asarray(embedding, dtype=np.float32)
+        W = np.asarray(weight, dtype=np.float32)
+        b = np.asarray(bias, dtype=np.float32)
+        P, E = emb.shape
+        assert W.shape == (P, E) and b.shape == (P,)
+        table = np.empty(P, dtype=np.int64)
+        rows = max(1, min(P, (64 << 20) // max(1, P * E * 4)))      # a block of rows at a time, as from_bandit_mf
+        for lo in range(0, P, rows):
+            logits = (emb[lo:lo + rows, None, :] * W[None, :, :]).sum(axis=2) + b[None, :]
+            table[lo:lo + rows] = logits.argmax(axis=1)
+        return cls(config, table, None)
+
     def device_policy(self):
         if getattr(self.config, 'with_ps_all', False):
             return None
