@@ -70,6 +70,8 @@ extern "C" {
 /* v15, additive since: rg_omf_pairs_workspace_bytes / rg_omf_pairs / rg_omf_limits / rg_omf_steps_workspace_bytes / rg_omf_steps
  * (OrganicMFSquare's training from a sorted device log: the pair list of every optimiser step, and the chain of RMSprop steps in
  * one launch).  New symbols only: the version stays 15. */
+/* v15, additive since: rg_bmf_samples_workspace_bytes / rg_bmf_samples / rg_bmf_limits / rg_bmf_steps_workspace_bytes / rg_bmf_steps
+ * and struct rg_bmf_model (BanditMFSquare's training from a sorted device log). */
 #define RG_ABI_VERSION 15
 
 /* error codes */
@@ -1103,6 +1105,64 @@ typedef struct rg_omf_model {
 int rg_omf_limits(uint32_t embed_dim, uint32_t* lds_max_products, uint32_t* max_products);
 size_t rg_omf_steps_workspace_bytes(uint32_t num_products, uint32_t embed_dim);
 int rg_omf_steps(const rg_omf_model* model, double lr, double alpha, double eps, const int32_t* d_pairs, uint64_t n_pairs,
+                 const int64_t* d_step_offsets, uint64_t n_steps, uint32_t force_global, int64_t* d_out, void* d_workspace,
+                 size_t workspace_bytes, void* stream);
+
+/*
+ * BanditMFSquare's training (reference agents/bandit_mf.py:89-126 under the offline protocol of bench_agents.py:168-190) from a
+ * sorted device log; rows / offsets as rg_count_train, stateless.
+ *
+ * The train CALLS and their numbers k are rg_omf_pairs'.  Every call sets the last product viewed to the last view of its
+ * session when the session is not empty; a user opens with an organic row (anything else is refused), so at a bandit row it is
+ * the nearest organic row in front of it in the same user.  A call with k % mini_batch == 0 is a TRIGGER: one optimiser step over
+ * the samples stored since the previous trigger, and it stores nothing itself; every other call with an action (a bandit row)
+ * stores the TRIPLE (last product viewed, action, reward 0 / 1).
+ *
+ * rg_bmf_samples writes, in log order: d_triples = the int32 triples, the n_pending triples of d_pending (carried in from an
+ * earlier log: they belong to the first step) in front; d_step_offsets as rg_omf_pairs writes them (rows 0 .. n_steps-1 the steps,
+ * row n_steps what lies behind the last trigger).  d_out (8 int64, device): [0] error bits (0), [1] calls, [2] n_steps, [3]
+ * triples written, [4] triples of the pending row, [5] the last view at the last call (-1: the log has no call).
+ * triples_capacity >= n_pending + n_rows triples (3 int32 each), step_capacity >= (first_call % mini_batch + n_rows) / mini_batch
+ * + 2; d_workspace: what the workspace function answers for (n_rows, n_pending), 8-byte aligned.  Integer work only: the same
+ * bytes on every run.  Synchronises `stream` once: the log is validated before any output is written — RG_EINVAL for a user whose
+ * first row is a bandit row, an index >= num_products (a view or an action), an organic-only user without rows or with a bandit
+ * row, offsets that descend or leave the n_rows rows, and more than 2^32 - 16 rows; RG_ENOMEM for a capacity or a workspace too
+ * small.  d_out is read after the stream's work is done.
+ */
+size_t rg_bmf_samples_workspace_bytes(uint64_t n_rows, uint64_t n_pending);
+int rg_bmf_samples(const rg_event* d_rows, const int64_t* d_offsets, uint64_t n_users, uint64_t n_organic_users, uint64_t n_rows,
+                   uint32_t num_products, uint64_t first_call, uint32_t mini_batch, const int32_t* d_pending, uint64_t n_pending,
+                   int32_t* d_triples, uint64_t triples_capacity, int64_t* d_step_offsets, uint64_t step_capacity, int64_t* d_out,
+                   void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* The model of rg_bmf_steps: float64 device arrays, read and written in place. */
+typedef struct rg_bmf_model {
+    uint32_t num_products;          /* P <= 16384 */
+    uint32_t embed_dim;             /* E <= 64 */
+    double* ep;                     /* [P][E] product_embedding.weight (indexed by the action) */
+    double* eu;                     /* [P][E] user_embedding.weight (indexed by the last product viewed) */
+    double* sq_ep;                  /* RMSprop's square averages of the two */
+    double* sq_eu;
+} rg_bmf_model;
+
+/*
+ * rg_bmf_steps: every optimiser step of a triple list (d_triples, d_step_offsets[0 .. n_steps] as rg_bmf_samples writes them) in
+ * one launch of one workgroup.  A step with n > 0 samples (l_s, a_s, r_s): z_s = <ep[a_s], eu[l_s]>, the loss is the mean of
+ * BCEWithLogits(z, r), so d_s = (sigmoid(z_s) - r_s) / n, computed from t = exp(-|z|) without cancellation: sigmoid(|z|) = 1 / (1 + t),
+ * sigmoid(-|z|) = t / (1 + t), and sigmoid(z) - 1 = -sigmoid(-z); g_ep[a] = sum_{a_s = a} d_s eu[l_s], g_eu[l] = sum_{l_s = l} d_s ep[a_s], the sums in sample order; then torch's
+ * RMSprop step (no momentum, not centred) on all 2 P E parameters: sq = alpha sq + (1 - alpha) g g, p -= lr g / (sqrt(sq) + eps) —
+ * a row the step did not touch has g = 0.  A step without samples changes nothing.  float64, no floating-point atomics: the same
+ * bits on every run.  The model lives in LDS while P <= lds_max_products of the limits function (245 at E = 5), else in global
+ * memory (force_global != 0: there in any case), up to max_products; the global form needs d_workspace of the workspace function's
+ * size, 8-byte aligned.  A step holds at most max_step samples (256).  d_out (4 int64, device): [0] error bits, [1] steps taken,
+ * [2] steps skipped as empty, [3] samples consumed.  The list is validated on the device before the model is touched: an index
+ * >= P (bit 2), offsets that descend or leave n_triples (bit 4), a reward that is not 0 / 1 (bit 64) or a step longer than
+ * max_step (bit 128) leave the model as it was.  No synchronisation.  RG_EINVAL: P or E out of range, a null array, alpha outside
+ * [0, 1], eps < 0; RG_ENOMEM.
+ */
+int rg_bmf_limits(uint32_t embed_dim, uint32_t* lds_max_products, uint32_t* max_products, uint32_t* max_step);
+size_t rg_bmf_steps_workspace_bytes(uint32_t num_products, uint32_t embed_dim);
+int rg_bmf_steps(const rg_bmf_model* model, double lr, double alpha, double eps, const int32_t* d_triples, uint64_t n_triples,
                  const int64_t* d_step_offsets, uint64_t n_steps, uint32_t force_global, int64_t* d_out, void* d_workspace,
                  size_t workspace_bytes, void* stream);
 

@@ -164,6 +164,11 @@ class RgOmfModel(C.Structure):
     _fields_ = [('num_products', C.c_uint32), ('embed_dim', C.c_uint32), ('emb', C.c_void_p), ('w', C.c_void_p), ('bias', C.c_void_p),
                 ('sq_emb', C.c_void_p), ('sq_w', C.c_void_p), ('sq_bias', C.c_void_p)]
 
+class RgBmfModel(C.Structure):
+    """struct rg_bmf_model: BanditMFSquare's float64 device arrays (the two embeddings and RMSprop's square averages) of rg_bmf_steps."""
+    _fields_ = [('num_products', C.c_uint32), ('embed_dim', C.c_uint32), ('ep', C.c_void_p), ('eu', C.c_void_p), ('sq_ep', C.c_void_p),
+                ('sq_eu', C.c_void_p)]
+
 
 # every symbol include/recogym_hip.h declares, with its ctypes signature
 _SIM = C.c_void_p
@@ -297,6 +302,13 @@ SYMBOLS = {
     'rg_omf_limits': (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     'rg_omf_steps_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32]),
     'rg_omf_steps': (C.c_int, [C.POINTER(RgOmfModel), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rg_bmf_samples_workspace_bytes': (C.c_size_t, [C.c_uint64, C.c_uint64]),
+    'rg_bmf_samples': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p,
+                                 C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'rg_bmf_limits': (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    'rg_bmf_steps_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    'rg_bmf_steps': (C.c_int, [C.POINTER(RgBmfModel), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
